@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """Headline benchmark: query-correspondences/sec of the COTR forward path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|batch256|train]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|batch256|dense|train] [--dump-outputs DIR]
+
+``--dump-outputs DIR`` writes what the last timed step computed - pred_corrs (all pairs / queries of the job); for train the
+loss, pred_corrs and a seeded sample of the updated weights - as DIR/<name>.npy.  Inputs, weights and dropout seeds are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 Workloads
   headline (default)  BASELINE.json configs[1], SURVEY.md 8d "primary": one 256x512 side-by-side pair, 1000 queries, zoom
@@ -63,6 +67,29 @@ def apply_knobs(model):
     for name, val in KNOBS:
         model.set_knob(name, val)
     return model
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+WEIGHT_SAMPLE = 1 << 20       # --workload train: updated weights dumped, a fixed seeded sample of the ~18.5 M parameters
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: what the timed path computed in its last step, one DIR/<name>.npy per array (float32 / float64, at most
+    DUMP_LIMIT_BYTES in all), so that two builds run with the same arguments can be compared output for output.  -> {name: shape}"""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a))
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        host[name] = a
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the limit of {DUMP_LIMIT_BYTES}')
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in host.items()}
 
 
 def flop(b, q):
@@ -437,13 +464,14 @@ def cpu_baseline(budget_s=12.0):
 # ---- training step -----------------------------------------------------------------------------------------------------
 def run_train(args, dev, world, rank):
     import cotr_amd
-    from cotr_amd import training
+    from cotr_amd import train_ops, training
     from cotr_amd.models import build_model
     from cotr_amd.utils.synth import synth_state_dict
     pairs, nq = 16, 200                       # BASELINE.json configs[4]: bs=16 per GPU, 200 queries, cycle + bidirectional
     # stage 2 of the reference recipe (readme.md:50, train_cotr.py --lr_backbone=1e-5): layer2 / layer3 of the backbone train
     # (backbone.py:64-69) - what BASELINE.json configs[4] names; --stage 1 = the frozen-backbone first stage (lr_backbone 0)
     lr_backbone = 1e-5 if args.stage == 2 else 0.0
+    train_ops.reseed(5 + rank)       # the dropout masks, like the inputs, are the same from run to run
     model = apply_knobs(build_model(cotr_amd.default_args(dropout=0.1, lr_backbone=lr_backbone)).to(dev))
     model.load_state_dict(synth_state_dict(0))
     model.train()
@@ -470,7 +498,7 @@ def run_train(args, dev, world, rank):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        result = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -480,6 +508,14 @@ def run_train(args, dev, world, rank):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what train_batch / GraphedTrainStep return (loss, prediction) and the weights the step left behind (a seeded sample)
+        loss, pred = result
+        flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).float().cpu()
+        pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:WEIGHT_SAMPLE].sort().values
+        dumped = dump_outputs(args.dump_outputs, {'loss': torch.tensor([float(loss)], dtype=torch.float64),
+                                                  'pred_corrs': pred.float(), 'weights_sample': flat[pick]})
     ident = rank_identity(world, dev)
     # FLOP of one step (DESIGN.md "Training step"): forward = backbone once (the cycle pass sees the same image) + input_proj, encoder and
     # decoder K/V projection on 2 x pairs (prediction and cycle pass, each with its own dropout) + two decodes; backward = 2 x the forward
@@ -513,6 +549,7 @@ def run_train(args, dev, world, rank):
                        'gradients': ('GradSink: flat buffer, one deferred reduction launch' + (' per third of the buffer, each third\'s reduce-scatter / all-gather started right behind it' if world > 1 and not graphed else '')) if use_sink else 'per-weight reductions + autograd accumulation',
                        'optimizer': 'FusedAdam (torch.optim.Adam update, one launch)' if fused_adam else 'torch.optim.Adam',
                        'parallelism': f'data parallel x{world}, reduce-scatter + all-gather of the gradients' if world > 1 else 'single GPU'},
+            **({'dumped_outputs': dumped} if dumped else {}),
         }), flush=True)
 
 
@@ -603,6 +640,7 @@ def dry_run(args, world, rank):
     rank_ms = [elapsed / args.steps * 1e3]
     if world > 1:
         elapsed, rank_ms = reduce_elapsed(elapsed, args.steps, dev, world)
+    dumped = dump_outputs(args.dump_outputs, {'pred_corrs': gathered}) if args.dump_outputs and rank == 0 else None
     ident = rank_identity(world, dev)
     if rank == 0:
         line = {'metric': 'DRY RUN (CPU stand-in model, gloo): plumbing only, not a measurement', 'value': total_pairs * 10 * args.steps / elapsed,
@@ -611,6 +649,8 @@ def dry_run(args, world, rank):
                 'higher_is_better': True, 'scaling': 'strong' if (batch256 or dense) else 'weak', 'vs_baseline': None, 'dtype': 'f32',
                 'data': 'synthetic', 'dry_run': True, 'gathered_rows': int(gathered.shape[0]),
                 'config': {'workload': f'dry run of --workload {args.workload}', 'pairs_per_gpu': pairs}}
+        if dumped:
+            line['dumped_outputs'] = dumped
         line.update(ident)
         # what each rank of the REAL run would execute per step, and where that point sits on the measured 1-GPU batch curve
         real_pairs = {'headline': 1, 'batch256': -(-256 // world), 'dense': 1, 'train': 16}[args.workload]
@@ -655,6 +695,9 @@ def main():
                     help='--workload train: 2 (default, BASELINE.json configs[4]) = lr_backbone 1e-5, layer2/3 train; 1 = frozen backbone')
     ap.add_argument('--set', action='append', default=[], metavar='KNOB=INT',
                     help='experiments: cotr_set_knob(h, KNOB, INT) on every model handle (and the process-wide set) first, e.g. --set attention_fusion_max_rows=0')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (pred_corrs; --workload train: loss, pred_corrs and a '
+                         'seeded sample of the updated weights) as DIR/<name>.npy; the inputs are seeded, the same from run to run')
     args = ap.parse_args()
     if args.traffic_child:
         return traffic_child(args.traffic_child)
@@ -664,6 +707,8 @@ def main():
         args.steps = {'headline': 200, 'batch256': 5, 'dense': 10, 'train': 10}[args.workload]
     if args.warmup is None:
         args.warmup = {'headline': 20, 'batch256': 2, 'dense': 2, 'train': 3}[args.workload]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` as the driver calls it: start one rank per GPU ourselves (torch.distributed.run on this node,
@@ -734,16 +779,17 @@ def main():
     torch.cuda.synchronize()
 
     def step():
+        """-> (work to wait for or None, this step's pred_corrs as the caller receives it: a tensor, or a callable that returns it)"""
         if dense and world > 1:                                 # encode the pair, decode this rank's query slice, all-gather: all timed
-            sharded(img, qs)
-            return None
+            return None, sharded(img, qs)['pred_corrs']
         out = model(img, qs)['pred_corrs']
         if world > 1:  # RCCL all-gather of the predicted (x,y), asynchronous w.r.t. the next step's kernels
-            return all_gather_rows(out, counts, async_op=True)[1]
-        return None
+            finish, work = all_gather_rows(out, counts, async_op=True)
+            return work, finish
+        return None, out
 
     for _ in range(args.warmup):
-        w = step()
+        w, _ = step()
         if w is not None:
             w.wait()
     torch.cuda.synchronize()
@@ -755,7 +801,8 @@ def main():
     ev[0].record()
     works = []
     for i in range(args.steps):
-        works.append(step())
+        w, result = step()
+        works.append(w)
         ev[i + 1].record()
     for w in works:
         if w is not None:
@@ -769,6 +816,9 @@ def main():
     if world > 1:
         elapsed, rank_ms = reduce_elapsed(elapsed, args.steps, dev, world)
     kernel_ms = sum(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps)) / args.steps  # HIP events, launch stream
+    dumped = None
+    if args.dump_outputs and rank == 0:    # the last timed step's prediction (all pairs / queries of the job), before any extra forward
+        dumped = dump_outputs(args.dump_outputs, {'pred_corrs': result() if callable(result) else result})
     ident = rank_identity(world, dev)
 
     if rank == 0:
@@ -826,6 +876,8 @@ def main():
                                                      'peak and is not a fraction of any roofline of the kernels that ran')
             line['roofline']['bound'] = 'none (research path)'
         extras = world == 1 and not args.no_extras and not batch256 and not dense and not research
+        if dumped:
+            line['dumped_outputs'] = dumped
         line.update(ident)
         roof = line['roofline']
         mode = args.traffic

@@ -12,9 +12,7 @@ reference's model code runs untouched on torch CPU:
 * ``cv2`` / ``imageio`` / ``tables``: empty modules (only touched by
   visualisation / dataset helpers that the forward path never calls).
 
-Used by ``tests/golden/make_golden.py`` to generate the committed golden vectors
-and by ``tests/test_oracle_golden.py::test_restatement_matches_live_reference``
-(skipped when ``/root/reference`` is absent).
+Used by ``tests/golden/make_golden.py`` to generate the committed golden vectors.
 
 TEST INFRASTRUCTURE ONLY (see ``oracle/__init__.py``).
 """

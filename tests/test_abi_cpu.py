@@ -189,23 +189,21 @@ def test_research_sources_are_derived_from_the_current_product_sources(tmp_path)
 
 
 def test_first_run_kit_applies_the_one_line_switch(tmp_path):
-    """tools/first_run_check.py --patch on a copy of the reference's COTR/models/__init__.py (authoring container only: the
-    reference is not on the GPU box): the switch of INTEGRATION.md section 1 goes in, the original is kept, a second run is a
+    """tools/first_run_check.py --patch on a stand-in for the reference's COTR/models/__init__.py (a docstring and the build_model
+    definition the switch replaces): the switch of INTEGRATION.md section 1 goes in, the original is kept, a second run is a
     no-op, and the patched module resolves build_model to the cotr_amd binding."""
     import importlib.util
-    import shutil
     import subprocess
     import sys
-    src = '/root/reference/COTR/models/__init__.py'
-    if not os.path.exists(src):
-        pytest.skip('no reference checkout here')
+    original = ('"""COTR model package (stand-in)."""\n'
+                'from .cotr_model import build\n\n\ndef build_model(args):\n    return build(args)\n')
     pkg = tmp_path / 'COTR' / 'models'
     pkg.mkdir(parents=True)
-    shutil.copy(src, pkg / '__init__.py')
+    (pkg / '__init__.py').write_text(original)
     tool = os.path.join(ROOT, 'tools', 'first_run_check.py')
     for _ in range(2):
         subprocess.run([sys.executable, tool, '--patch', str(pkg / '__init__.py')], check=True, cwd=ROOT)
-    assert (pkg / '__init__.py.orig').read_text() == open(src).read()
+    assert (pkg / '__init__.py.orig').read_text() == original
     patched = (pkg / '__init__.py').read_text()
     assert 'from cotr_amd.models import build_model' in patched and 'from .cotr_model import build' in patched
     spec = importlib.util.spec_from_file_location('patched_models', pkg / '__init__.py')

@@ -72,3 +72,25 @@ def test_dense_workload_on_eight_ranks_shards_the_full_query_grid():
     assert line['dense_check'] == {'equals_unsharded': True, 'queries_this_rank': 16384, 'queries_total': 131072}
     assert line['gathered_rows'] == 131072
     assert [r['rank'] for r in line['ranks']] == list(range(8)) and len({r['pid'] for r in line['ranks']}) == 8
+
+
+def test_dump_outputs_writes_the_last_step_and_is_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the prediction of the last timed step (all ranks' pairs, gathered) as DIR/pred_corrs.npy in float32;
+    two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for run in ('a', 'b'):
+        out = tmp_path / run
+        line = _run(['--gpus', '2', '--steps', '2', '--warmup', '1', '--backend', 'gloo', '--dry-run', '--dump-outputs', str(out)],
+                    _clean_env())
+        assert line['dumped_outputs'] == {'pred_corrs': [2, 10, 2]}
+        assert sorted(os.listdir(out)) == ['pred_corrs.npy']
+        dumps.append(np.load(out / 'pred_corrs.npy'))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (2, 10, 2)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_steps_below_one_are_refused():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-run', '--backend', 'gloo', '--steps', '0'], cwd=ROOT,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=_clean_env())
+    assert r.returncode != 0 and '--steps' in r.stderr

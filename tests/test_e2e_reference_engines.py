@@ -82,41 +82,3 @@ def test_engines_on_the_binding_reproduce_the_reference_engines_on_the_reference
     err = check(g, corrs, idx, 'engines + HIP binding')
     print(f'{name}: {len(corrs)} correspondences, max {err:.2e} px from the reference')
 
-
-@pytest.mark.parametrize('name', ['e2e_sparse_known', 'e2e_faster_known'])
-def test_reference_engine_classes_drive_the_binding_object_unchanged(name, golden_dir, monkeypatch):
-    """The REFERENCE's own SparseEngine / FasterSparseEngine classes (imported unchanged from /root/reference: authoring container
-    only) constructed on the cotr_amd BINDING object, as INTEGRATION.md section 1's one-line switch would hand it to them: device
-    discovery through next(model.parameters()).device (sparse_engine.py:49,278), model(img_batch, query_batch)['pred_corrs']
-    .clone().detach().cpu() (:52-53,281), eval mode, the NaN check.  There is no GPU here, so the ONE thing replaced is the C-ABI call
-    inside the binding's forward, answered by the CPU oracle; everything the reference's engine touches of the binding's Python surface
-    is the real object.  Their output must be the goldens (reference engines on the reference model)."""
-    from oracle import ref_import
-    if not ref_import.reference_available():
-        pytest.skip('the reference checkout is only present in the authoring container')
-    ref_import.import_reference_models()
-    from COTR.inference.sparse_engine import SparseEngine as RefSparse, FasterSparseEngine as RefFaster
-    from cotr_amd.models.cotr_model import COTR
-    sd = synth_state_dict(0)
-    model = build_model(cotr_amd.default_args()).eval()
-    model.load_state_dict(sd)
-    calls = []
-
-    def forward_on_the_oracle(self, samples, queries):
-        img = COTR._as_batch(samples)                      # the binding's own input contract (backbone.py:80's assertion included)
-        calls.append((tuple(img.shape), tuple(queries.shape)))
-        return {'pred_corrs': cotr_oracle.cotr_forward(sd, img.float(), queries.float())}
-
-    monkeypatch.setattr(COTR, '_forward_eval', forward_on_the_oracle)
-    g = np.load(os.path.join(golden_dir, name + '.npz'))
-    seed, nq, conv, cycle, bs, load = (int(v) for v in g['meta'])
-    img_a, img_b = synthetic_pair(seed)
-    engine = RefSparse(model, bs, mode='tile') if load < 0 else RefFaster(model, bs, mode='tile', max_load=load)
-    np.random.seed(seed)
-    import contextlib
-    import io
-    with torch.no_grad(), contextlib.redirect_stdout(io.StringIO()):
-        corrs, idx = engine.cotr_corr_multiscale(img_a, img_b, ZOOMS, conv, max_corrs=nq, queries_a=g['queries'].copy(),
-                                                 return_idx=True, force=True, areas=[1.0, 1.0])
-    assert calls and all(s[0][1:] == (3, 256, 512) and s[0][0] <= bs for s in calls)
-    check(g, np.asarray(corrs, dtype=np.float64).reshape(-1, 4), ids(idx), 'reference engine class + binding object (oracle compute)')
