@@ -310,8 +310,20 @@ int linear(cotr_ctx* h, const float* x, const float* x2, int x2_row_mod, int a2_
   p.bias = bias; p.residual = residual; p.ldr = ldr ? ldr : N; p.res_row_mod = res_row_mod; p.relu = relu;
   p.colscale = colscale; p.colscale_n = colscale_n;
   KCHK(h, launch_gemm(GEMM_DENSE, p, s), "linear");
-  if (h->prof >= 2) { char nm[96]; snprintf(nm, sizeof nm, "linear %dx%dx%d cfg%d", M, N, K, gemm_pick_config(GEMM_DENSE, p)); prof_mark(h, nm, s, 2); }
+  if (h->prof >= 2) {   // (+pos: the x + pos prologue; +table: the row-periodic residual of a pos table)
+    char nm[96];
+    snprintf(nm, sizeof nm, "linear %dx%dx%d cfg%d%s%s", M, N, K, gemm_pick_config(GEMM_DENSE, p), x2 ? " +pos" : "", res_row_mod ? " +table" : "");
+    prof_mark(h, nm, s, 2);
+  }
   return COTR_OK;
+}
+
+// a launch of the attention kernels, named with the variant launch_attention / launch_attention_fused picked
+void prof_attention(cotr_ctx* h, const char* name, hipStream_t s) {
+  if (h->prof < 2) return;
+  char nm[64];
+  snprintf(nm, sizeof nm, "%s %s", name, attention_last_variant());
+  prof_mark(h, nm, s, 2);
 }
 
 int layernorm(cotr_ctx* h, const float* x, const float* w, const float* b, float* y, int M, hipStream_t s) {
@@ -466,7 +478,12 @@ int conv(cotr_ctx* h, const ConvW& c, const float* x, const float* residual, int
          int Hin, int Win, hipStream_t s) {
   const GemmParams p = conv_params(c, x, residual, relu, y, B, Hin, Win);
   KCHK(h, launch_gemm(GEMM_CONV, p, s), "conv");
-  if (h->prof >= 2) { char nm[96]; snprintf(nm, sizeof nm, "conv%dx%d/%d %dx%dx%d cfg%d", c.k, c.k, c.stride, p.M, p.N, p.K, gemm_pick_config(GEMM_CONV, p)); prof_mark(h, nm, s, 2); }
+  if (h->prof >= 2) {
+    char nm[96];
+    snprintf(nm, sizeof nm, "conv%dx%d/%d %dx%dx%d cfg%d%s", c.k, c.k, c.stride, p.M, p.N, p.K, gemm_pick_config(GEMM_CONV, p),
+             gemm_conv_as_dense(p) ? " dense" : "");
+    prof_mark(h, nm, s, 2);
+  }
   return COTR_OK;
 }
 
@@ -810,6 +827,9 @@ static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream strea
   float* t_hid = p; p += (size_t)TOK * 4 * FFN * Bc_max;  // hidden activations, or up to 16 partial outputs of the fused FFN
   float* t_part = p; p += n_part;
 
+  // side_stream bit 1 (K / V of decoder layers 1-5 on the second stream) needs the pos table and one pass; where it does not apply,
+  // the bit is cleared for the rest of the call, so that decode_chunk does not wait on an event this call never recorded
+  if (B > ENC_CHUNK || knob(KN_POS_TABLE_MIN_ROWS) >= (1 << 30)) h->side_mode &= ~2;
   if (h->prof) prof_reset(h);
   prof_mark(h, "begin", s);
   for (int b0 = 0, Bc = 0; b0 < B; b0 += Bc) {
@@ -920,7 +940,7 @@ static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream strea
         // few rows: out_proj inside the attention kernel (8 per-head partial outputs), summed + bias + residual + norm1 by ln_reduce
         KCHK(h, launch_attention_fused(t_qkv, 3 * D, nullptr, nullptr, nullptr, nullptr, 0.f, t_qkv + D, t_qkv + 2 * D, 3 * D,
                                        nullptr, 0, e.out_w, t_part, Bc, TOK, s), "attention+out_proj");
-        prof_mark(h, "attention+oproj enc", s, 2);
+        prof_attention(h, "attention+oproj enc", s);
         KCHK(h, launch_ln_reduce(t_part, 8, e.out_b, xin, e.n1w, e.n1b, t_x1, M, s), "ln_reduce");
         prof_mark(h, "ln_reduce heads", s, 2);
       } else if (att_rows_applies(Bc, TOK)) {
@@ -930,7 +950,7 @@ static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream strea
         prof_mark(h, "att_rows enc", s, 2);
       } else {
         KCHK(h, launch_attention(t_qkv, 3 * D, t_qkv + D, t_qkv + 2 * D, 3 * D, t_ao, D, Bc, TOK, s), "attention");
-        prof_mark(h, "attention enc", s, 2);
+        prof_attention(h, "attention enc", s);
         if ((r = linear(h, t_ao, nullptr, 0, 1, 0, e.out_w, e.out_b, xin, 0, 1.f, 0, t_tmp, M, D, D, s))) return r;
         if ((r = layernorm(h, t_tmp, e.n1w, e.n1b, t_x1, M, s))) return r;
       }
@@ -943,7 +963,7 @@ static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream strea
     float* kv_c = kv + (size_t)b0 * TOK * KVLD;
     // (the hoisted K/V projection takes the table at any row count: 3072 columns fill the chip with large tiles even at one pair -
     // 18 -> 14 us there; the encoder in-projections only from knob pos_table_min_rows on)
-    if ((h->side_mode & 2) && B <= ENC_CHUNK && knob(KN_POS_TABLE_MIN_ROWS) < (1 << 30)) {
+    if (h->side_mode & 2) {
       // cotr_forward with few rows (knob side_stream bit 1): decoder layer 0 needs its own K / V columns only - the other layers'
       // 5/6 of this product run on the handle's second stream beside decoder layer 0 (decode_chunk waits for them before layer 1)
       const int n0 = 2 * D, n1 = (int)KVLD - n0;
@@ -1060,7 +1080,7 @@ int decode_chunk(cotr_ctx* h, const DecPlan& d0, size_t row0, const float* qsrc,
       // in the FFN block's ln_reduce launch (its input has no other consumer); pre2 = the normed 'hs'
       KCHK(h, launch_attention_fused(nullptr, 0, tgt_in, d.qpos, w.q_w, w.q_b, QSCALE, kl, kl + D, KVLD, nullptr, 0, w.out_w, d.part,
                                      nb, nq, s), "q_proj+attention+out_proj");
-      prof_mark(h, "qproj+attention+oproj dec", s, 2);
+      prof_attention(h, "qproj+attention+oproj dec", s);
       KCHK(h, launch_ln_reduce(d.part, 8, w.out_b, tgt_in, w.n2w, w.n2b, d.t2, R, s), "ln_reduce");
       prof_mark(h, "ln_reduce heads", s, 2);
       const bool post = li + 1 == L;
@@ -1076,7 +1096,7 @@ int decode_chunk(cotr_ctx* h, const DecPlan& d0, size_t row0, const float* qsrc,
         // q = Wq(tgt + query_pos) * 32^-0.5 (layer 0: computed by dec_prologue)
         if (li > 0 && (r = linear(h, d.tgt, d.qpos, 0, 1, 1, w.q_w, w.q_b, nullptr, 0, QSCALE, D, d.q, R, D, D, s))) return r;
         KCHK(h, launch_attention(d.q, D, kl, kl + D, KVLD, d.ao, D, nb, nq, s), "attention");
-        prof_mark(h, "attention dec", s, 2);
+        prof_attention(h, "attention dec", s);
         if ((r = linear(h, d.ao, nullptr, 0, 1, 0, w.out_w, w.out_b, tgt_in, 0, 1.f, 0, d.pre2, R, D, D, s))) return r;
         if ((r = layernorm(h, d.pre2, w.n2w, w.n2b, d.t2, R, s))) return r;
       }
@@ -1154,7 +1174,12 @@ static int forward_impl(cotr_ctx* h, const float* img, const float* queries, int
     // cotr_forward returns: the caller sees one stream.
     side = knob(KN_SIDE_STREAM);
     if (h->dec.size() < 2) side &= ~2;
-    if (h->prof || h->keep_taps || B > knob(KN_ENCODE_CHUNK) || (long)B * Q > 8192 || enc_next_chunk(B, knob(KN_ENCODE_CHUNK)) != B) side = 0;
+    // One encode pass and one decode pass only: the query encoding below is written once for all B x Q rows, and every decode pass
+    // reads its rows from the start of d.qpos (decode_impl: row0 = 0).  Below 8192 rows the decode has one chunk of queries and
+    // nb_max = B, so dec_next_pairs(B, B, Q) is the first decode pass cotr_batch_chunks reports.
+    if (h->prof || h->keep_taps || B > knob(KN_ENCODE_CHUNK) || (long)B * Q > 8192 || enc_next_chunk(B, knob(KN_ENCODE_CHUNK)) != B ||
+        dec_next_pairs(B, B, Q) != B)
+      side = 0;
     if (side) {
       if (!h->side) {   // the handle's second stream and its events, created at first use
         HIPCHK(h, hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));

@@ -582,6 +582,10 @@ static const int g_att_wide_head_major = 1;
 
 static thread_local unsigned long long* g_att_dbg = nullptr;   // set_attention_debug_times
 void set_attention_debug_times(unsigned long long* p) { g_att_dbg = p; }
+// the kernel the last launch_attention / launch_attention_fused call on this thread picked: "res", "wide3" / "wide2" (occupancy) or
+// "s<key splits>" - what the per-launch profile names carry (api.hip, cotr_set_profiling level 2)
+static thread_local const char* g_att_variant = "";
+const char* attention_last_variant() { return g_att_variant; }
 // knobs: KN_ATTENTION_SPLITS (0 = automatic), KN_ATTENTION_FUSED_SPLITS (0 = 4; 48 / 84: encoder (q given) / decoder (q projected)
 // separately), KN_XCD_MAPPING bit 3 = heads over XCDs (measured: -88 MB of fabric traffic per forward, +0.4 % time -> off)
 static const int g_att_part_wt = 1;  // write-through stores for the out-projection partials
@@ -611,6 +615,7 @@ int launch_attention(const float* q, int ldq, const float* k, const float* v, in
       attr_set.set();
     }
     const int chunks = (res_tiles + res_tpc - 1) / res_tpc;
+    g_att_variant = "res";
     hipLaunchKernelGGL(attention_res_kernel, dim3(chunks * 8, 1, nb), dim3(512), ATT_RES_SMEM, s, q, ldq, k, v, ldkv, o, ldo, nq, res_tpc);
     return hipGetLastError() == hipSuccess ? 0 : -2;
   }
@@ -618,6 +623,7 @@ int launch_attention(const float* q, int ldq, const float* k, const float* v, in
     dim3 wgrid(((nq + 63) / 64) * 8, 1, nb);
     // head-major workgroup order here (head = XCD): with many pairs in flight every XCD then keeps one head's K/V slice of each
     // pair in its L2 instead of all eight (32 pairs x 1000 queries: 176 -> 163 us; one pair: no difference)
+    g_att_variant = g_att_wide_occ == 3 ? "wide3" : "wide2";
     if (g_att_wide_occ == 3)
       hipLaunchKernelGGL((attention_wide_kernel<4, 3>), wgrid, dim3(256), 0, s, q, ldq, k, v, ldkv, o, ldo, nq, g_att_wide_head_major);
     else
@@ -629,18 +635,23 @@ int launch_attention(const float* q, int ldq, const float* k, const float* v, in
   if (ns == 0) ns = 4;
   switch (ns) {
     case 1:
+      g_att_variant = "s1";
       hipLaunchKernelGGL((attention_kernel<1, 0, false>), grid, dim3(64), 0, s, q, ldq, k, v, ldkv, o, ldo, nq, g_att_head_major, fz);
       break;
     case 2:
+      g_att_variant = "s2";
       hipLaunchKernelGGL((attention_kernel<2, 0, false>), grid, dim3(128), 0, s, q, ldq, k, v, ldkv, o, ldo, nq, g_att_head_major, fz);
       break;
     case 4:
+      g_att_variant = "s4";
       hipLaunchKernelGGL((attention_kernel<4, 0, false>), grid, dim3(256), 0, s, q, ldq, k, v, ldkv, o, ldo, nq, g_att_head_major, fz);
       break;
     case 8:
+      g_att_variant = "s8";
       hipLaunchKernelGGL((attention_kernel<8, 0, false>), grid, dim3(512), 0, s, q, ldq, k, v, ldkv, o, ldo, nq, g_att_head_major, fz);
       break;
     case 16:
+      g_att_variant = "s16";
       hipLaunchKernelGGL((attention_kernel<16, 0, false>), grid, dim3(1024), 0, s, q, ldq, k, v, ldkv, o, ldo, nq, g_att_head_major, fz);
       break;
     default:
@@ -684,6 +695,7 @@ static int attention_fused_impl(const float* q, int ldq, const float* x, const f
     else if (op) ATT_LAUNCH(NSV, 0, true);            \
     else ATT_LAUNCH(NSV, 0, false);                   \
   } while (0)
+  g_att_variant = ns == 8 ? "s8" : "s4";
   if (ns == 8) ATT_PICK(8);
   else ATT_PICK(4);
 #undef ATT_PICK

@@ -259,6 +259,7 @@ static inline bool gemm_fill_divs(GemmParams& p, int mode, int bm, int bn) {
 int launch_gemm(int mode, const GemmParams& p, hipStream_t s);            // tuned / modelled config
 int launch_gemm_cfg(int mode, int cfg, const GemmParams& p, hipStream_t s);  // explicit config (tuning, tests)
 int gemm_pick_config(int mode, const GemmParams& p);
+bool gemm_conv_as_dense(const GemmParams& p);   // a 1x1 stride-1 convolution launched as the dense product (knob conv1x1_dense)
 int launch_gemm_big(int mode, int variant, const GemmParams& p, hipStream_t s);  // gemm_big.hip: 0 = 128x128, 1 = 128x64
 int launch_gemm_wp(int mode, int variant, const GemmParams& p, hipStream_t s);   // gemm_wp.hip: wave-private K chunks
 int launch_gemm_wp_dual(int mode, int variant, const GemmParams& p0, const GemmParams& p1, hipStream_t s);
@@ -280,6 +281,8 @@ int launch_attention(const float* q, int ldq, const float* k, const float* v, in
 int launch_attention_fused(const float* q, int ldq, const float* x, const float* x2, const float* wq, const float* bq,
                            float qscale, const float* k, const float* v, int ldkv, float* o, int ldo, const float* wo,
                            float* part, int nb, int nq, hipStream_t s);
+// the kernel the last of those two calls picked on this thread ("res", "wide3", "wide2", "s<key splits>"): per-launch profile names
+const char* attention_last_variant();
 
 int launch_layernorm(const float* x, const float* w, const float* b, float* y, int rows, hipStream_t s);
 // lin_sine encoding; point (bi, qi) read from pts[((bi*q_total) + qi)*2], written to row bi*nq+qi

@@ -1005,6 +1005,11 @@ static void set_xcd_split(int mode, int cfg, GemmParams& p) {
   p.xcd_msplit = mode != GEMM_STEM && fits && ((knob(KN_XCD_MAPPING) & 3) == 2 || ((knob(KN_XCD_MAPPING) & 3) == 1 && a_bytes >= 2.0 * w_bytes));
 }
 
+// knob KN_CONV1X1_DENSE: a 1x1 stride-1 convolution goes out on the dense instantiation (launch_gemm_cfg)
+bool gemm_conv_as_dense(const GemmParams& p) {
+  return knob(KN_CONV1X1_DENSE) && p.ksize == 1 && p.stride == 1 && p.pad == 0 && p.lda == p.Cin && p.lda % 4 == 0;
+}
+
 int launch_gemm_dual_cfg(int mode, int cfg, const GemmParams& a, const GemmParams& b, hipStream_t s) {
   if (mode != GEMM_CONV || cfg < 0 || cfg >= kNumCfgs || !gemm_cfg_supports_dual(cfg)) return -1;
   if (!cfg_fits(cfg, a) || !cfg_fits(cfg, b)) return -1;
@@ -1033,8 +1038,7 @@ int launch_gemm_cfg(int mode, int cfg, const GemmParams& p0, hipStream_t s) {
       // a 1x1 stride-1 convolution IS the dense product of the pixel rows (row m = pixel m, lda = Cin, no padding): the
       // dense instantiation of the same configuration computes the same sums in the same order without the per-row pixel
       // decomposition - ~640 fewer instructions between workgroup entry and the first load (profiles/r3_prologue_*.txt)
-      if (knob(KN_CONV1X1_DENSE) && p.ksize == 1 && p.stride == 1 && p.pad == 0 && p.lda == p.Cin && p.lda % 4 == 0)
-        return launch_cfg<GEMM_DENSE>(cfg, p, s);
+      if (gemm_conv_as_dense(p)) return launch_cfg<GEMM_DENSE>(cfg, p, s);
       return launch_cfg<GEMM_CONV>(cfg, p, s);
     case GEMM_STEM:
       if (p.N != 64 || p.K != 160) return -1;

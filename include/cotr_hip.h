@@ -411,9 +411,10 @@ int cotr_resize_f32(const float* src, int Hs, int Ws, int C, float* dst, int Hd,
  *                              passes from a measured table (csrc/enc_split.inc, tools/batch_cost.py: 17 pairs = 16 + 1, 33 = 32 + 1),
  *                              decode passes where a prefix of the pairs fills the one-launch rows kernels and the whole does not;
  *                              0: passes of encode_chunk pairs / 32768 query rows only (cotr_batch_chunks reports the passes)
- *   side_stream                cotr_forward with few rows (B * Q <= 8192, one pass): bit 0 the query encoding, bit 1 the K/V projections of
- *                              decoder layers 1-5 run on a second stream owned by the handle, beside the chain; joined before the
- *                              call returns (default 0: measured, profiles/r6_ab_side_stream_*.txt)
+ *   side_stream                cotr_forward with few rows (B * Q <= 8192, one encode pass and one decode pass; otherwise off for that
+ *                              call): bit 0 the query encoding, bit 1 the K/V projections of decoder layers 1-5 (with the pos table
+ *                              only) run on a second stream owned by the handle, beside the chain; joined before the call returns
+ *                              (default 0: measured, profiles/r6_ab_side_stream_*.txt)
  * libcotr_hip_exp.so (the experimental build, -DCOTR_EXPERIMENTAL) adds the knobs of the measured dead ends, all off by default:
  *   head_fusion_max_rows, ffn_preln, ffn_tail, coop_tail, coop_tail_spin, gemm_ln_min_rows, l2_warm  (cotr_amd/csrc/experimental/experimental.h)
  * and the RESEARCH path of docs/LABNOTES.md 3e (not a dead end; off by default, results as close to fp64 as the fp32 path but not its bits):

@@ -152,6 +152,40 @@ def test_knob_registry_round_trip_without_a_gpu():
     assert m.knobs()['encode_chunk'] == (64, 64)
 
 
+def test_every_knob_has_a_case_in_the_gpu_sweep():
+    """tests/knob_cases.py KNOB_CASES (run by tests/test_knobs_gpu.py): every product knob has a case or a written exclusion, every value a
+    case runs is one the library accepts, and a knob with a value set lists every value of it - a new knob, or a new value, without a
+    case fails here, without a GPU."""
+    from tests.knob_cases import KNOB_CASES, KNOB_EXCLUDED, case_values
+    lib = _lib.load_library()
+    names = list(_lib.knobs())
+    assert not set(KNOB_CASES) & set(KNOB_EXCLUDED)
+    assert sorted(names) == sorted(set(KNOB_CASES) | set(KNOB_EXCLUDED)), set(names) ^ (set(KNOB_CASES) | set(KNOB_EXCLUDED))
+    assert all(reason for reason in KNOB_EXCLUDED.values())
+    for name, case in KNOB_CASES.items():
+        assert case['kind'] in ('set', 'threshold', 'fields') and case['bits'] in ('same', 'noise') and case['note'], name
+        values = case_values(name)
+        assert values, name
+        for v in values:
+            assert lib.cotr_check_knob(name.encode(), v) == 0, (name, v)
+        for run in case['runs']:
+            reach = run[2]
+            assert reach in ('changes', 'default', 'side') or (reach[0] == 'has' and reach[1]), (name, reach)
+            for base_name, base_value in (run[3] if len(run) > 3 else {}).items():
+                assert base_name in names and base_name != name and lib.cotr_check_knob(base_name.encode(), base_value) == 0
+        if case['kind'] == 'set':
+            assert lib.cotr_check_knob(name.encode(), 1 << 20) != 0, f'{name}: not a bounded value set'
+            legal = [v for v in range(-1, 1025) if lib.cotr_check_knob(name.encode(), v) == 0]
+            assert sorted(values) == legal, (name, legal)
+        elif case['kind'] == 'threshold':
+            assert min(values) <= 1 and (max(values) >= 1 << 30 or lib.cotr_check_knob(name.encode(), max(values) + 1) != 0), (name, values)
+    # xcd_mapping: bits 0-1 = 0, 1, 2 and each of bits 2-5 on its own (on top of the default bits 0-1)
+    xcd = case_values('xcd_mapping')
+    assert {0, 1, 2} <= set(xcd) and all(any(v & ~3 == 1 << bit for v in xcd) for bit in range(2, 6)), xcd
+    assert all(v & ~3 == 0 or (v & ~3) & ((v & ~3) - 1) == 0 for v in xcd), xcd
+    assert {1, 7, 128} <= set(case_values('encode_chunk'))
+
+
 def test_experimental_library_has_the_dead_ends_and_their_knobs():
     """libcotr_hip_exp.so (python -m cotr_amd.build --experimental): same ABI version, cotr_is_experimental() = 1, six more knobs
     (all at 'off'), two more op-level entry points.  Opened next to the product library with plain ctypes (RTLD_LOCAL)."""
@@ -215,8 +249,8 @@ def test_first_run_kit_applies_the_one_line_switch(tmp_path):
 
 def test_encode_split_table_is_well_formed():
     """csrc/enc_split.inc (knob batch_split; written by tools/batch_cost.py from measured encode times): kEncFirst[n] is the first
-    pass of n pairs - between 1 and n, and following it to the end covers n pairs in passes that are themselves unsplit first
-    passes (what api.hip enc_next_chunk walks); the recorded times it was derived from are there for the reader."""
+    pass of n pairs - between 1 and n, and following it to the end covers n pairs in passes that are EACH themselves unsplit first
+    passes (what api.hip enc_next_chunk walks: a later pass must not be cut again); the recorded times it was derived from are there for the reader."""
     import re
     src = open(os.path.join(os.path.dirname(LIB), 'enc_split.inc')).read()
     body = re.search(r'kEncFirst\[65\] = \{([^}]*)\}', src).group(1)
@@ -228,5 +262,5 @@ def test_encode_split_table_is_well_formed():
         while r:
             passes.append(first[r])
             r -= first[r]
-        assert sum(passes) == n and all(first[c] == c for c in passes[:1]), (n, passes)
+        assert sum(passes) == n and all(first[c] == c for c in passes), (n, passes)   # every pass, not only the first
     assert first[1] == 1 and first[16] == 16 and first[32] == 32 and first[64] == 64
