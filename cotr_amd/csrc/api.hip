@@ -405,6 +405,105 @@ int dec_next_pairs(int remaining, int cap, int nq) {
   return n;
 }
 
+// ---- the shape of a call: pass geometry and scratch layouts, read by the passes, the carves, the size queries and cotr_batch_chunks
+// alike (a workspace sized by a query fits the carve by construction) -------------------------------------------------------------
+// floats per pair of an encode pass: stem output, pooled stem, 5 backbone activations, 6 token activations of the encoder, q|k|v
+constexpr size_t ENC_STEM = (size_t)128 * 256 * 64, ENC_POOL = (size_t)64 * 128 * 64, ENC_ACT = (size_t)64 * 128 * 256,
+                 ENC_TOK = (size_t)TOK * D, ENC_QKV = (size_t)TOK * 3 * D, ENC_HID = (size_t)TOK * 4 * FFN;
+// floats per query row of a decode pass: 7 activations; the FFN hidden activations, or the fused FFN's up to 16 partial outputs.  And
+// per row of either pass: the 8 per-head partial outputs of the fused attention + out_proj launch
+constexpr size_t DEC_ACT_ROW = (size_t)7 * D, DEC_HID_ROW = FFN, DEC_HID_FUSED_ROW = (size_t)4 * FFN, PART_ROW = (size_t)8 * D;
+
+// the encode cache of B pairs: memory [B*512*256] then K / V of every decoder layer [B*512*L*512]
+size_t enc_cache_floats(const cotr_ctx* h, int B) {
+  const size_t L = h->dec.empty() ? 6 : h->dec.size();
+  return (size_t)B * TOK * (D + L * 2 * D);
+}
+
+// most pairs of an encode pass (enc_next_chunk never takes more)
+int enc_chunk_max(int B, const KnobSet& kn) { return B < kn.v[KN_ENCODE_CHUNK] ? B : kn.v[KN_ENCODE_CHUNK]; }
+
+struct EncBufs {
+  float *b_stem, *b_pool, *b_x, *b_y, *b_t1, *b_t2, *b_d, *t_src, *t_alt, *t_tmp, *t_x1, *t_pre2, *t_ao, *t_qkv, *t_hid, *t_part;
+  size_t hid_cap;   // floats behind t_hid
+};
+
+// the encoder scratch for passes of up to Bc_max pairs: returns its floats; with base != nullptr also carves [base, base + floats)
+// into *out.  t_hid holds the hidden activations or up to 16 partial outputs of the fused FFN; t_part the per-head partial outputs
+// of the fused attention + out_proj launch (small-row regime only), a buffer of their own because the fused FFN's partials are
+// written with write-through stores right after these were read - sized for the largest pass that can take that path (with
+// batch_split a small remainder follows a large first pass)
+size_t enc_layout(int Bc_max, const KnobSet& kn, float* base, EncBufs* out) {
+  EncBufs e;
+  size_t off = 0;
+  auto take = [&](float*& p, size_t n) { p = base ? base + off : nullptr; off += n; };
+  const size_t n = Bc_max;
+  const size_t part_cap = kn.v[KN_ATTENTION_FUSION_MAX_ROWS] > 1024 ? kn.v[KN_ATTENTION_FUSION_MAX_ROWS] : 1024;
+  const size_t part_rows = n * TOK < part_cap ? n * TOK : part_cap;
+  take(e.b_stem, ENC_STEM * n);
+  take(e.b_pool, ENC_POOL * n);
+  for (float** p : {&e.b_x, &e.b_y, &e.b_t1, &e.b_t2, &e.b_d}) take(*p, ENC_ACT * n);
+  for (float** p : {&e.t_src, &e.t_alt, &e.t_tmp, &e.t_x1, &e.t_pre2, &e.t_ao}) take(*p, ENC_TOK * n);
+  take(e.t_qkv, ENC_QKV * n);
+  e.hid_cap = ENC_HID * n;
+  take(e.t_hid, e.hid_cap);
+  take(e.t_part, PART_ROW * part_rows);
+  if (out) *out = e;
+  return off;
+}
+
+// a decode pass takes up to nb_max pairs x q_chunk queries, Rmax rows (a pair's queries are split over passes above DEC_ROWS only)
+struct DecGeom { int q_chunk = 0, nb_max = 0; size_t Rmax = 0; };
+DecGeom dec_geom(int B, int Q) {
+  DecGeom g;
+  g.q_chunk = Q < DEC_ROWS ? Q : DEC_ROWS;
+  const int pairs_per = (Q > 0 && Q < DEC_ROWS) ? DEC_ROWS / Q : 1;
+  g.nb_max = B < pairs_per ? B : pairs_per;
+  g.Rmax = (size_t)g.nb_max * g.q_chunk;
+  return g;
+}
+
+struct DecBufs {
+  size_t hid_cap = 0;   // floats behind `hid`
+  float *qpos = nullptr, *tgt = nullptr, *q = nullptr, *ao = nullptr, *pre2 = nullptr, *t2 = nullptr, *pre3 = nullptr,
+        *hid = nullptr, *part = nullptr;
+};
+struct DecPlan : DecGeom, DecBufs {};
+
+// the decoder scratch for passes of up to Rmax rows, in the form of enc_layout.  With batch_split a small remainder follows a large
+// first pass: `hid` and `part` are sized for the largest pass of EITHER kind that the fusion thresholds admit (part: none where the
+// attention fusion admits no rows)
+size_t dec_layout(size_t Rmax, const KnobSet& kn, float* base, DecBufs* out) {
+  DecBufs d;
+  size_t off = 0;
+  auto take = [&](float*& p, size_t n) { p = base ? base + off : nullptr; off += n; };
+  const size_t fr = Rmax < (size_t)kn.v[KN_FFN_FUSION_MAX_ROWS] ? Rmax : (size_t)kn.v[KN_FFN_FUSION_MAX_ROWS];
+  const size_t ar = Rmax < (size_t)kn.v[KN_ATTENTION_FUSION_MAX_ROWS] ? Rmax : (size_t)kn.v[KN_ATTENTION_FUSION_MAX_ROWS];
+  d.hid_cap = Rmax * DEC_HID_ROW > fr * DEC_HID_FUSED_ROW ? Rmax * DEC_HID_ROW : fr * DEC_HID_FUSED_ROW;
+  for (float** p : {&d.qpos, &d.tgt, &d.q, &d.ao, &d.pre2, &d.t2, &d.pre3}) take(*p, Rmax * D);
+  take(d.hid, d.hid_cap);
+  take(d.part, ar * PART_ROW);
+  if (!ar) d.part = nullptr;
+  if (out) *out = d;
+  return off;
+}
+
+int dec_plan(cotr_ctx* h, int B, int Q, DecPlan& d) {
+  static_cast<DecGeom&>(d) = dec_geom(B, Q);
+  if (int r = ensure(h, h->dec_scr, dec_layout(d.Rmax, h->knobs, nullptr, nullptr))) return r;
+  dec_layout(d.Rmax, h->knobs, h->dec_scr.ptr, &d);
+  return COTR_OK;
+}
+
+// knob side_stream applies to a cotr_forward of (B, Q > 0): the query encoding is written once for all B x Q rows and every decode pass
+// reads its rows from the start of d.qpos (decode_impl: row0 = 0) - so one encode pass and one decode pass of one query chunk; few rows
+// (B x Q <= 8192); no profiling, no debug taps
+bool side_stream_ok(const cotr_ctx* h, int B, int Q) {
+  const DecGeom g = dec_geom(B, Q);
+  return !h->prof && !h->keep_taps && (long)B * Q <= 8192 && enc_next_chunk(B, knob(KN_ENCODE_CHUNK)) == B && g.q_chunk >= Q &&
+         dec_next_pairs(B, g.nb_max, g.q_chunk) == B;
+}
+
 // y = LayerNorm(x + linear2(relu(linear1(x))))  (transformer.py:156-158 / 199-201; x is already normalised).
 // Where ffn_fused_applies: ONE fused launch that keeps the hidden activations on the CU and writes per-chunk
 // partial outputs + ln_reduce (sum, bias, residual, norm [, a second norm: decoder.norm after the last layer]); above: linear1,
@@ -787,49 +886,17 @@ static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream strea
   h->enc_B = 0;
   h->taps.clear();
   if (!feat_out) {
-    int r = ensure(h, h->memkv, (size_t)B * TOK * (D + KVLD));
+    int r = ensure(h, h->memkv, enc_cache_floats(h, B));
     if (r) return r;
   }
   float* memory = h->memkv.ptr;
   float* kv = h->memkv.ptr + (size_t)B * TOK * D;
 
-  const int ENC_CHUNK = knob(KN_ENCODE_CHUNK);
-  const int Bc_max = B < ENC_CHUNK ? B : ENC_CHUNK;
-  // scratch carve (floats per pair)
-  const size_t n_stem = (size_t)128 * 256 * 64, n_pool = (size_t)64 * 128 * 64, n_act = (size_t)64 * 128 * 256;
-  const size_t n_tok = (size_t)TOK * D;
-  const size_t per_pair = n_stem + n_pool + 5 * n_act + 6 * n_tok + (size_t)TOK * 3 * D + (size_t)TOK * 4 * FFN;
-  // per-head partial outputs of the fused attention + out_proj launch (small-row regime only); a buffer of their own: the
-  // fused FFN's partials (t_hid) are written with write-through stores right after these were read
-  // (sized for the largest pass that can take that path: with batch_split a small remainder follows a large first pass)
-  const size_t part_rows_cap = knob(KN_ATTENTION_FUSION_MAX_ROWS) > 1024 ? knob(KN_ATTENTION_FUSION_MAX_ROWS) : 1024;
-  const size_t part_rows = (size_t)Bc_max * TOK < part_rows_cap ? (size_t)Bc_max * TOK : part_rows_cap;
-  const size_t n_part = (size_t)8 * part_rows * D;
-  {
-    int r = ensure(h, h->enc_scr, per_pair * Bc_max + n_part);
-    if (r) return r;
-  }
-  float* p = h->enc_scr.ptr;
-  float* b_stem = p; p += n_stem * Bc_max;
-  float* b_pool = p; p += n_pool * Bc_max;
-  float* b_x = p; p += n_act * Bc_max;
-  float* b_y = p; p += n_act * Bc_max;
-  float* b_t1 = p; p += n_act * Bc_max;
-  float* b_t2 = p; p += n_act * Bc_max;
-  float* b_d = p; p += n_act * Bc_max;
-  float* t_src = p; p += n_tok * Bc_max;
-  float* t_alt = p; p += n_tok * Bc_max;
-  float* t_tmp = p; p += n_tok * Bc_max;
-  float* t_x1 = p; p += n_tok * Bc_max;
-  float* t_pre2 = p; p += n_tok * Bc_max;
-  float* t_ao = p; p += n_tok * Bc_max;
-  float* t_qkv = p; p += (size_t)TOK * 3 * D * Bc_max;
-  float* t_hid = p; p += (size_t)TOK * 4 * FFN * Bc_max;  // hidden activations, or up to 16 partial outputs of the fused FFN
-  float* t_part = p; p += n_part;
+  const int ENC_CHUNK = knob(KN_ENCODE_CHUNK), Bc_max = enc_chunk_max(B, h->knobs);
+  if (int r = ensure(h, h->enc_scr, enc_layout(Bc_max, h->knobs, nullptr, nullptr))) return r;
+  EncBufs eb;
+  enc_layout(Bc_max, h->knobs, h->enc_scr.ptr, &eb);
 
-  // side_stream bit 1 (K / V of decoder layers 1-5 on the second stream) needs the pos table and one pass; where it does not apply,
-  // the bit is cleared for the rest of the call, so that decode_chunk does not wait on an event this call never recorded
-  if (B > ENC_CHUNK || knob(KN_POS_TABLE_MIN_ROWS) >= (1 << 30)) h->side_mode &= ~2;
   if (h->prof) prof_reset(h);
   prof_mark(h, "begin", s);
   for (int b0 = 0, Bc = 0; b0 < B; b0 += Bc) {
@@ -839,18 +906,18 @@ static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream strea
     int ci = 0;
     if (knob(KN_FUSED_STEM) && !h->keep_taps) {  // conv1 + bn1 + relu + maxpool in one launch; the 'stem' tap needs the unfused pair
       const ConvW& c0 = h->convs[ci++];
-      KCHK(h, launch_stem_pool(img_c, c0.w, 160, c0.scale, c0.bias, b_pool, Bc, s), "stem_pool");
+      KCHK(h, launch_stem_pool(img_c, c0.w, 160, c0.scale, c0.bias, eb.b_pool, Bc, s), "stem_pool");
       prof_mark(h, "stem_pool conv7x7+bn+relu+maxpool", s, 2);
     } else {
-      { int r = stem(h, h->convs[ci++], img_c, b_stem, Bc, s); if (r) return r; }
-      KCHK(h, launch_maxpool(b_stem, b_pool, Bc, 128, 128, 64, s), "maxpool");
+      { int r = stem(h, h->convs[ci++], img_c, eb.b_stem, Bc, s); if (r) return r; }
+      KCHK(h, launch_maxpool(eb.b_stem, eb.b_pool, Bc, 128, 128, 64, s), "maxpool");
       prof_mark(h, "maxpool", s, 2);
     }
     prof_mark(h, "stem+pool", s);
-    if (int r = tap_save(h, "stem", b_stem, n_stem * Bc, s)) return r;
-    if (int r = tap_save(h, "pool", b_pool, n_pool * Bc, s)) return r;
-    const float* x = b_pool;
-    float* outbuf[2] = {b_x, b_y};
+    if (int r = tap_save(h, "stem", eb.b_stem, ENC_STEM * Bc, s)) return r;
+    if (int r = tap_save(h, "pool", eb.b_pool, ENC_POOL * Bc, s)) return r;
+    const float* x = eb.b_pool;
+    float* outbuf[2] = {eb.b_x, eb.b_y};
     int flip = 0, H = 64, W = 64;
     for (int st = 0; st < 3; ++st) {
       for (int b = 0; b < kStages[st].blocks; ++b) {
@@ -879,30 +946,30 @@ static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream strea
           const ConvW& cd = h->convs[ci++];
           if (st == 0 && cd.stride == 1 && c1.cin == 64 && Bc * H * 2 * W >= knob(KN_EXPAND_MIN_ROWS)) {
             // many pairs: downsample branch and conv1 read the pooled stem output once, in one launch (expand.hip)
-            KCHK(h, launch_expand(x, Bc * H * 2 * W, cd.w, cd.scale, cd.bias, 0, b_d, cd.cout, c1.w, c1.scale, c1.bias, 1, b_t1, c1.cout, s),
+            KCHK(h, launch_expand(x, Bc * H * 2 * W, cd.w, cd.scale, cd.bias, 0, eb.b_d, cd.cout, c1.w, c1.scale, c1.bias, 1, eb.b_t1, c1.cout, s),
                  "expand");
             if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "expand ds+conv1 layer1.0 %d pairs", Bc); prof_mark(h, nm, s, 2); }
             c1_done = true;
           } else {
-            const int pr = conv_pair(h, cd, c1, x, b_d, b_t1, Bc, H, W, s);
+            const int pr = conv_pair(h, cd, c1, x, eb.b_d, eb.b_t1, Bc, H, W, s);
             if (pr < 0) return pr;
             c1_done = pr == 1;
-            if (!c1_done && (r = conv(h, cd, x, nullptr, 0, b_d, Bc, H, W, s))) return r;
+            if (!c1_done && (r = conv(h, cd, x, nullptr, 0, eb.b_d, Bc, H, W, s))) return r;
           }
-          idt = b_d;
+          idt = eb.b_d;
         }
-        if (!c1_done && (r = conv(h, c1, x, nullptr, 1, b_t1, Bc, H, W, s))) return r;
+        if (!c1_done && (r = conv(h, c1, x, nullptr, 1, eb.b_t1, Bc, H, W, s))) return r;
         if (st == 0 && H == 64 && W == 64 && Bc >= knob(KN_CONV23_MIN_PAIRS)) {
           // many pairs: conv2 -> conv3 + identity + ReLU in one launch, t2 never leaves the CU (conv23.hip)
-          KCHK(h, launch_conv23(b_t1, c2.w, c2.scale, c2.bias, c3.w, c3.scale, c3.bias, idt, y, Bc, s), "conv23");
+          KCHK(h, launch_conv23(eb.b_t1, c2.w, c2.scale, c2.bias, c3.w, c3.scale, c3.bias, idt, y, Bc, s), "conv23");
           if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "conv23 layer1.%d %d pairs", b, Bc); prof_mark(h, nm, s, 2); }
         } else if (st == 1 && Ho == 32 && Wo == 32 && Bc >= knob(KN_CONV23M_MIN_PAIRS) && conv23m_fill_ok(Bc)) {
           // many pairs: the same fusion for layer2 (conv23m.hip)
-          KCHK(h, launch_conv23m(b_t1, c2.w, c2.scale, c2.bias, c3.w, c3.scale, c3.bias, idt, y, Bc, stride, s), "conv23m");
+          KCHK(h, launch_conv23m(eb.b_t1, c2.w, c2.scale, c2.bias, c3.w, c3.scale, c3.bias, idt, y, Bc, stride, s), "conv23m");
           if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "conv23m layer2.%d %d pairs", b, Bc); prof_mark(h, nm, s, 2); }
         } else {
-          if ((r = conv(h, c2, b_t1, nullptr, 1, b_t2, Bc, H, W, s))) return r;
-          if ((r = conv(h, c3, b_t2, idt, 1, y, Bc, Ho, Wo, s))) return r;
+          if ((r = conv(h, c2, eb.b_t1, nullptr, 1, eb.b_t2, Bc, H, W, s))) return r;
+          if ((r = conv(h, c3, eb.b_t2, idt, 1, y, Bc, Ho, Wo, s))) return r;
         }
         x = y;
         H = Ho; W = Wo;
@@ -921,40 +988,40 @@ static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream strea
     // ---- input_proj: x is [Bc*512, 1024] --------------------------------------------------
     const int M = Bc * TOK;
     int r;
-    if ((r = linear(h, x, nullptr, 0, 1, 0, h->ip_w, h->ip_b, nullptr, 0, 1.f, 0, t_src, M, D, CFEAT, s))) return r;
-    if ((r = tap_save(h, "src", t_src, (size_t)M * D, s))) return r;
+    if ((r = linear(h, x, nullptr, 0, 1, 0, h->ip_w, h->ip_b, nullptr, 0, 1.f, 0, eb.t_src, M, D, CFEAT, s))) return r;
+    if ((r = tap_save(h, "src", eb.t_src, (size_t)M * D, s))) return r;
     prof_mark(h, "input_proj", s);
     // ---- encoder (transformer.py:143-159, post-norm) ----------------------------------------
     float* mem_c = memory + (size_t)b0 * TOK * D;
-    const float* xin = t_src;
+    const float* xin = eb.t_src;
     for (size_t li = 0; li < h->enc.size(); ++li) {
       const EncW& e = h->enc[li];
       // q|k use src+pos, v uses src; q scaled by 32^-0.5 (transformer.py:147-153)
       if (M >= knob(KN_POS_TABLE_MIN_ROWS)) {
-        if ((r = linear(h, xin, nullptr, 0, 1, 0, e.in_w, e.in_b, h->tab_qkv + li * TOK * 3 * D, 0, QSCALE, D, t_qkv, M, 3 * D, D, s, 0, TOK)))
+        if ((r = linear(h, xin, nullptr, 0, 1, 0, e.in_w, e.in_b, h->tab_qkv + li * TOK * 3 * D, 0, QSCALE, D, eb.t_qkv, M, 3 * D, D, s, 0, TOK)))
           return r;
-      } else if ((r = linear(h, xin, h->pos, TOK, 3 * D, 2 * D, e.in_w, e.in_b, nullptr, 0, QSCALE, D, t_qkv, M, 3 * D, D, s))) return r;
-      float* y = (li + 1 == h->enc.size()) ? mem_c : (xin == t_alt ? t_pre2 : t_alt);
-      bool fused = n_part != 0 && att_fused_applies(M);   // (the FFN block decides for itself: ffn_block)
+      } else if ((r = linear(h, xin, h->pos, TOK, 3 * D, 2 * D, e.in_w, e.in_b, nullptr, 0, QSCALE, D, eb.t_qkv, M, 3 * D, D, s))) return r;
+      float* y = (li + 1 == h->enc.size()) ? mem_c : (xin == eb.t_alt ? eb.t_pre2 : eb.t_alt);
+      bool fused = att_fused_applies(M);   // (the FFN block decides for itself: ffn_block)
       if (fused) {
         // few rows: out_proj inside the attention kernel (8 per-head partial outputs), summed + bias + residual + norm1 by ln_reduce
-        KCHK(h, launch_attention_fused(t_qkv, 3 * D, nullptr, nullptr, nullptr, nullptr, 0.f, t_qkv + D, t_qkv + 2 * D, 3 * D,
-                                       nullptr, 0, e.out_w, t_part, Bc, TOK, s), "attention+out_proj");
+        KCHK(h, launch_attention_fused(eb.t_qkv, 3 * D, nullptr, nullptr, nullptr, nullptr, 0.f, eb.t_qkv + D, eb.t_qkv + 2 * D, 3 * D,
+                                       nullptr, 0, e.out_w, eb.t_part, Bc, TOK, s), "attention+out_proj");
         prof_attention(h, "attention+oproj enc", s);
-        KCHK(h, launch_ln_reduce(t_part, 8, e.out_b, xin, e.n1w, e.n1b, t_x1, M, s), "ln_reduce");
+        KCHK(h, launch_ln_reduce(eb.t_part, 8, e.out_b, xin, e.n1w, e.n1b, eb.t_x1, M, s), "ln_reduce");
         prof_mark(h, "ln_reduce heads", s, 2);
       } else if (att_rows_applies(Bc, TOK)) {
         // many rows: attention, out_proj, residual and norm1 in one launch (att_rows.hip)
-        KCHK(h, launch_att_rows(t_qkv, 3 * D, nullptr, nullptr, nullptr, nullptr, 0.f, t_qkv + D, t_qkv + 2 * D, 3 * D, e.out_w, e.out_b,
-                                xin, e.n1w, e.n1b, t_x1, Bc, TOK, s), "att_rows");
+        KCHK(h, launch_att_rows(eb.t_qkv, 3 * D, nullptr, nullptr, nullptr, nullptr, 0.f, eb.t_qkv + D, eb.t_qkv + 2 * D, 3 * D, e.out_w, e.out_b,
+                                xin, e.n1w, e.n1b, eb.t_x1, Bc, TOK, s), "att_rows");
         prof_mark(h, "att_rows enc", s, 2);
       } else {
-        KCHK(h, launch_attention(t_qkv, 3 * D, t_qkv + D, t_qkv + 2 * D, 3 * D, t_ao, D, Bc, TOK, s), "attention");
+        KCHK(h, launch_attention(eb.t_qkv, 3 * D, eb.t_qkv + D, eb.t_qkv + 2 * D, 3 * D, eb.t_ao, D, Bc, TOK, s), "attention");
         prof_attention(h, "attention enc", s);
-        if ((r = linear(h, t_ao, nullptr, 0, 1, 0, e.out_w, e.out_b, xin, 0, 1.f, 0, t_tmp, M, D, D, s))) return r;
-        if ((r = layernorm(h, t_tmp, e.n1w, e.n1b, t_x1, M, s))) return r;
+        if ((r = linear(h, eb.t_ao, nullptr, 0, 1, 0, e.out_w, e.out_b, xin, 0, 1.f, 0, eb.t_tmp, M, D, D, s))) return r;
+        if ((r = layernorm(h, eb.t_tmp, e.n1w, e.n1b, eb.t_x1, M, s))) return r;
       }
-      if ((r = ffn_block(h, t_x1, e.l1w, e.l1b, e.l2w, e.l2b, e.n2w, e.n2b, t_hid, (size_t)TOK * 4 * FFN * Bc_max, fused ? t_tmp : t_ao, y, M, s)))
+      if ((r = ffn_block(h, eb.t_x1, e.l1w, e.l1b, e.l2w, e.l2b, e.n2w, e.n2b, eb.t_hid, eb.hid_cap, fused ? eb.t_tmp : eb.t_ao, y, M, s)))
         return r;
       xin = y;
     }
@@ -1001,42 +1068,6 @@ int cotr_backbone_upto(cotr_handle h, const float* img, int B, int stage, float*
 }  // extern "C"
 
 namespace {
-
-struct DecPlan {
-  int q_chunk = 0, nb_max = 0;
-  size_t Rmax = 0, hid_cap = 0;   // most rows of a pass; floats behind `hid`
-  float *qpos = nullptr, *tgt = nullptr, *q = nullptr, *ao = nullptr, *pre2 = nullptr, *t2 = nullptr, *pre3 = nullptr,
-        *hid = nullptr, *part = nullptr;
-  bool single_chunk = false;
-};
-
-int dec_plan(cotr_ctx* h, int B, int Q, DecPlan& d) {
-  d.q_chunk = Q < DEC_ROWS ? Q : DEC_ROWS;
-  const int pairs_per = Q < DEC_ROWS ? (DEC_ROWS / Q) : 1;
-  d.nb_max = B < pairs_per ? B : pairs_per;
-  d.Rmax = (size_t)d.nb_max * d.q_chunk;
-  d.single_chunk = d.nb_max >= B && d.q_chunk >= Q;
-  // A pass has at most Rmax rows - and with batch_split a small remainder follows a large first pass: `hid` (FFN hidden activations, FFN
-  // floats per row; or the fused FFN's up to 16 partial outputs, 4 * FFN per row) and `part` (per-head partials of attention + out_proj,
-  // 8 * D per row) are sized for the largest pass of EITHER kind that the fusion thresholds admit
-  const size_t fr = d.Rmax < (size_t)knob(KN_FFN_FUSION_MAX_ROWS) ? d.Rmax : (size_t)knob(KN_FFN_FUSION_MAX_ROWS);
-  const size_t ar = d.Rmax < (size_t)knob(KN_ATTENTION_FUSION_MAX_ROWS) ? d.Rmax : (size_t)knob(KN_ATTENTION_FUSION_MAX_ROWS);
-  d.hid_cap = d.Rmax * FFN > fr * 4 * FFN ? d.Rmax * FFN : fr * 4 * FFN;
-  const size_t part_cap = ar * 8 * D;
-  int r = ensure(h, h->dec_scr, d.Rmax * 7 * D + d.hid_cap + part_cap);
-  if (r) return r;
-  float* p = h->dec_scr.ptr;
-  d.qpos = p; p += d.Rmax * D;
-  d.tgt = p; p += d.Rmax * D;
-  d.q = p; p += d.Rmax * D;
-  d.ao = p; p += d.Rmax * D;
-  d.pre2 = p; p += d.Rmax * D;
-  d.t2 = p; p += d.Rmax * D;
-  d.pre3 = p; p += d.Rmax * D;
-  d.hid = p; p += d.hid_cap;
-  d.part = part_cap ? p : nullptr; p += part_cap;
-  return COTR_OK;
-}
 
 // query-side prologue of one chunk: lin_sine encoding of the queries (cotr_model.py:34-36) and layer 0's
 // q = Wq(0 + query_pos) * 32^-0.5 (tgt == 0 at layer 0, transformer.py:54).  Depends on the queries only.
@@ -1172,14 +1203,9 @@ static int forward_impl(cotr_ctx* h, const float* img, const float* queries, int
     // launches, not by the chip - work that depends on the queries only (their lin_sine encoding, cotr_model.py:34-36) or on the memory
     // only (K / V of decoder layers 1-5, transformer.py:192-195) leaves the chain for a second stream.  Both streams join before
     // cotr_forward returns: the caller sees one stream.
-    side = knob(KN_SIDE_STREAM);
-    if (h->dec.size() < 2) side &= ~2;
-    // One encode pass and one decode pass only: the query encoding below is written once for all B x Q rows, and every decode pass
-    // reads its rows from the start of d.qpos (decode_impl: row0 = 0).  Below 8192 rows the decode has one chunk of queries and
-    // nb_max = B, so dec_next_pairs(B, B, Q) is the first decode pass cotr_batch_chunks reports.
-    if (h->prof || h->keep_taps || B > knob(KN_ENCODE_CHUNK) || (long)B * Q > 8192 || enc_next_chunk(B, knob(KN_ENCODE_CHUNK)) != B ||
-        dec_next_pairs(B, B, Q) != B)
-      side = 0;
+    side = side_stream_ok(h, B, Q) ? knob(KN_SIDE_STREAM) : 0;
+    // bit 1 (K / V of decoder layers 1-5 on the second stream) needs those layers and the pos table
+    if (h->dec.size() < 2 || knob(KN_POS_TABLE_MIN_ROWS) >= (1 << 30)) side &= ~2;
     if (side) {
       if (!h->side) {   // the handle's second stream and its events, created at first use
         HIPCHK(h, hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
@@ -1213,24 +1239,13 @@ int cotr_forward(cotr_handle h, const float* img, const float* queries, int B, i
 // the passes a (B, Q) call is cut into under the handle's knobs (tests, tools): which = 0 encode passes, 1 decode passes; pairs per pass
 int cotr_batch_chunks(cotr_handle h, int B, int Q, int which, int* sizes, int cap) {
   if (!h || B <= 0 || Q < 0 || (which != 0 && which != 1) || (cap > 0 && !sizes)) return COTR_ERR_ARG;
-  KnobScope knob_scope_(&h->knobs);
+  DEVICE_SCOPE(h);
+  if (which == 1 && Q == 0) return 0;
+  const DecGeom g = dec_geom(B, Q);
   int n = 0;
-  if (which == 0) {
-    for (int b0 = 0, c = 0; b0 < B; b0 += c) {
-      c = enc_next_chunk(B - b0, knob(KN_ENCODE_CHUNK));
-      if (n < cap) sizes[n] = c;
-      ++n;
-    }
-  } else {
-    if (Q == 0) return 0;
-    const int q_chunk = Q < DEC_ROWS ? Q : DEC_ROWS;
-    const int pairs_per = Q < DEC_ROWS ? (DEC_ROWS / Q) : 1;
-    const int nb_max = B < pairs_per ? B : pairs_per;
-    for (int b0 = 0, c = 0; b0 < B; b0 += c) {
-      c = dec_next_pairs(B - b0, nb_max, q_chunk);
-      if (n < cap) sizes[n] = c;
-      ++n;
-    }
+  for (int b0 = 0, c = 0; b0 < B; b0 += c, ++n) {
+    c = which == 0 ? enc_next_chunk(B - b0, knob(KN_ENCODE_CHUNK)) : dec_next_pairs(B - b0, g.nb_max, g.q_chunk);
+    if (n < cap) sizes[n] = c;
   }
   return n;
 }
@@ -1238,23 +1253,18 @@ int cotr_batch_chunks(cotr_handle h, int B, int Q, int which, int* sizes, int ca
 // bytes of the three arenas a call of that size carves (each rounded up to 256 B): what cotr_set_workspace must be given
 int cotr_scratch_bytes(cotr_handle h, int B, int Q, size_t* bytes) {
   if (!h || !bytes || B <= 0 || Q < 0) return COTR_ERR_ARG;
-  const size_t L = h->dec.empty() ? 6 : h->dec.size();
   const int* kn = h->knobs.v;
-  const size_t Bc = B < kn[KN_ENCODE_CHUNK] ? B : kn[KN_ENCODE_CHUNK];
-  const size_t per_pair = (size_t)128 * 256 * 64 + (size_t)64 * 128 * 64 + 5 * (size_t)64 * 128 * 256 +
-                          6 * (size_t)TOK * D + (size_t)TOK * 3 * D + (size_t)TOK * 4 * FFN;
-  // Monotone in B and in Q, and an upper bound over the fusion thresholds' settings: a workspace sized for (B, Q) must serve
-  // every (B' <= B, Q' <= Q) - whose decoder passes can have MORE rows than (B, Q)'s own (2 x 16000 rows against 1 x 20000)
-  // and, below the thresholds, more scratch per row - and flipping a tuning knob must not make a sized workspace too small.
+  // The decoder term is a bound, not dec_layout: a workspace sized for (B, Q) must serve every (B' <= B, Q' <= Q) - whose decoder passes
+  // can have MORE rows than (B, Q)'s own (2 x 16000 rows against 1 x 20000) and, below the fusion thresholds, more scratch per row - and
+  // flipping a tuning knob must not make a sized workspace too small: the most rows of any pass, each at the most any threshold asks.
   const size_t R = (size_t)B * Q < (size_t)DEC_ROWS ? (size_t)B * Q : (size_t)DEC_ROWS;
   const size_t thr_a = kn[KN_ATTENTION_FUSION_MAX_ROWS] > 1024 ? kn[KN_ATTENTION_FUSION_MAX_ROWS] : 1024;
   const size_t thr_f = kn[KN_FFN_FUSION_MAX_ROWS] > 1024 ? kn[KN_FFN_FUSION_MAX_ROWS] : 1024;
-  const size_t f_memkv = (size_t)B * TOK * (D + L * 2 * D);
-  const size_t enc_rows = Bc * TOK;
-  const size_t f_enc = per_pair * Bc + 8 * (enc_rows < thr_a ? enc_rows : thr_a) * D;
-  const size_t f_dec = R * (7 * D + FFN) + (R < thr_f ? R : thr_f) * 3 * FFN + (R < thr_a ? R : thr_a) * 8 * D;
+  const size_t f_dec = R * (DEC_ACT_ROW + DEC_HID_ROW) + (R < thr_f ? R : thr_f) * (DEC_HID_FUSED_ROW - DEC_HID_ROW) +
+                       (R < thr_a ? R : thr_a) * PART_ROW;
   size_t total = 0;
-  for (size_t f : {f_memkv, f_enc, f_dec}) total = ((total + 255) & ~size_t(255)) + f * sizeof(float);
+  for (size_t f : {enc_cache_floats(h, B), enc_layout(enc_chunk_max(B, h->knobs), h->knobs, nullptr, nullptr), f_dec})
+    total = ((total + 255) & ~size_t(255)) + f * sizeof(float);
   *bytes = total + 256;
   return COTR_OK;
 }
@@ -1272,7 +1282,7 @@ int cotr_set_workspace(cotr_handle h, void* ws, size_t bytes, int keep_encode, c
   // a cached encode moves with the workspace (copied on `stream`, ordered after the work that produced it): a caller that
   // encodes once and then decodes a larger query set than ever before keeps its encode
   const size_t L = h->dec.size();
-  const size_t keep = (ws != nullptr && keep_encode && h->enc_B > 0 && h->memkv.ptr) ? (size_t)h->enc_B * TOK * (D + L * 2 * D) : 0;
+  const size_t keep = (ws != nullptr && keep_encode && h->enc_B > 0 && h->memkv.ptr) ? enc_cache_floats(h, h->enc_B) : 0;
   if (keep * sizeof(float) > bytes) { h->err = "cotr_set_workspace: smaller than the cached encode"; return COTR_ERR_ARG; }
   if (keep) HIPCHK(h, hipMemcpyAsync(ws, h->memkv.ptr, keep * sizeof(float), hipMemcpyDeviceToDevice, s));
   bool synced = false;
@@ -1304,21 +1314,8 @@ int cotr_set_workspace(cotr_handle h, void* ws, size_t bytes, int keep_encode, c
 
 int cotr_workspace_bytes(cotr_handle h, int B, int Q, size_t* bytes) {
   if (!h || !bytes || B <= 0 || Q < 0) return COTR_ERR_ARG;
-  const size_t L = h->dec.empty() ? 6 : h->dec.size();
-  const int* kn = h->knobs.v;
-  const size_t Bc = B < kn[KN_ENCODE_CHUNK] ? B : kn[KN_ENCODE_CHUNK];
-  const size_t per_pair = (size_t)128 * 256 * 64 + (size_t)64 * 128 * 64 + 5 * (size_t)64 * 128 * 256 +
-                          6 * (size_t)TOK * D + (size_t)TOK * 3 * D + (size_t)TOK * 4 * FFN;
-  const size_t q_chunk = Q < DEC_ROWS ? Q : DEC_ROWS;
-  const size_t pairs_per = (Q > 0 && Q < DEC_ROWS) ? (DEC_ROWS / Q) : 1;
-  const size_t nb = (size_t)B < pairs_per ? B : pairs_per;
-  const size_t thr_a = kn[KN_ATTENTION_FUSION_MAX_ROWS] > 1024 ? kn[KN_ATTENTION_FUSION_MAX_ROWS] : 1024;
-  const size_t R = nb * q_chunk;
-  const size_t fr = R < (size_t)kn[KN_FFN_FUSION_MAX_ROWS] ? R : (size_t)kn[KN_FFN_FUSION_MAX_ROWS];
-  const size_t ar = R < (size_t)kn[KN_ATTENTION_FUSION_MAX_ROWS] ? R : (size_t)kn[KN_ATTENTION_FUSION_MAX_ROWS];
-  size_t fl = h->wfloats + (size_t)TOK * D + (size_t)B * TOK * (D + L * 2 * D) + per_pair * Bc +
-              8 * (Bc * TOK < thr_a ? Bc * TOK : thr_a) * D +
-              R * 7 * D + (R * FFN > fr * 4 * FFN ? R * FFN : fr * 4 * FFN) + ar * 8 * D;
+  const size_t fl = h->wfloats + (size_t)TOK * D + enc_cache_floats(h, B) +
+                    enc_layout(enc_chunk_max(B, h->knobs), h->knobs, nullptr, nullptr) + dec_layout(dec_geom(B, Q).Rmax, h->knobs, nullptr, nullptr);
   *bytes = fl * sizeof(float);
   return COTR_OK;
 }
