@@ -10,7 +10,8 @@
 // Work decomposition (v2, "split keys"): one workgroup = 32 queries x 1 head x 1 pair; its NS
 // wavefronts each take 512/NS keys, so a wavefront runs 512/NS/32 key blocks instead of 16 and
 // the grid is (nq/32) x 8 x pairs workgroups (128 for the encoder of one pair, 256 for 1000
-// queries) - the 128-query, whole-K-in-LDS tiling of v1 left 7/8 of the CUs idle at one pair.
+// queries) - the 128-query, whole-K-in-LDS tiling of v1 left 7/8 of the CUs idle at one pair.  (The encoder of one pair now runs
+// attention_q16_kernel below: 16-query tiles, 256 workgroups.)
 // K and V fragments go global -> registers directly in MFMA operand layout (each element is used
 // by exactly one wavefront once, so LDS staging would be pure overhead; K_h/V_h of a pair are
 // 128 KB and L2-resident).  Per 32-key block, per wavefront:
@@ -280,6 +281,207 @@ __global__ __launch_bounds__(NS * 64) void attention_kernel(const float* __restr
   for (int i = t; i < 256; i += NS * 64) {  // 32 rows x 128 B, one float4 per thread: coalesced row stores
     const int row = i >> 3, c4 = (i & 7) * 4;
     const int qo = qtile * 32 + row;
+    if (qo < nq)
+      *reinterpret_cast<f32x4*>(o + ((size_t)pair * nq + qo) * ldo + head * ATT_HD + c4) =
+          *reinterpret_cast<const f32x4*>(&lds_out[row][c4]);
+  }
+}
+
+
+// ---- q given, 16-query tiles (the encoder self-attention of one pair) -----------------------------------------------------------
+// attention_kernel's 32-query tiles give the encoder of one pair 16 x 8 = 128 workgroups: half the CUs idle while each busy one runs
+// 160 dependent 64-cycle MFMAs per wavefront.  Here one workgroup = 16 queries x 1 head x 1 pair, so the same launch is 256
+// workgroups (one per CU) with half the matrix and softmax work each; every workgroup still takes in its K_h / V_h (and W_out,h) once.
+// 4 wavefronts x 128 keys, in 2 blocks of 64 keys, on v_mfma_f32_16x16x4_f32 (lane: l15 = lane & 15, g = lane >> 4):
+//   S^T = K . Q^T     4 tiles of 16 keys x 8 MFMAs        D: s[t][i] = score(key t*16 + 4g + i, query l15)
+//   online softmax    running max / sum per query (the 4 lane groups of a query agree through two shuffles)
+//   O^T += V^T . P^T  2 halves of 16 head dims x 16 MFMAs (s[t][i] is the B operand as it stands: k = g <-> key t*16 + 4g + i)
+// The accumulators of the 4 tiles / 2 halves are independent chains (the 16x16x4 form has 40 cycles of dependent latency for a
+// 32-cycle issue).  With only 2 key blocks per wavefront, every K and V fragment of the wavefront is requested up front.  The 4 key
+// splits are merged through LDS in a fixed order (bit-repeatable); the out projection (OP) writes the same [8][rows][256] per-head
+// partials as attention_kernel<4, 0, true>, so ln_reduce is unchanged.
+template <bool OP>
+__global__ __launch_bounds__(256) void attention_q16_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k,
+                                                            const float* __restrict__ v, int ldkv, float* __restrict__ o, int ldo,
+                                                            int nq, int head_major, const AttnFuse fz) {
+  constexpr int NS = 4, KPW = ATT_KEYS / NS, NBLK = KPW / 64;
+  constexpr int SLD = 64 + 4;   // OP: padded row of a wave-private staging tile [16][64 columns]
+  constexpr int LDS_BUF = (OP && NS * 16 * SLD > NS * 8 * 64) ? NS * 16 * SLD : NS * 8 * 64;
+  __shared__ __attribute__((aligned(16))) float lds_buf[LDS_BUF];
+  float (*lds_o)[8][64] = reinterpret_cast<float (*)[8][64]>(lds_buf);   // key-split merge [NS][8 accumulator registers][64 lanes]
+  __shared__ float lds_m[NS][16];
+  __shared__ float lds_l[NS][16];
+  __shared__ __attribute__((aligned(16))) float lds_out[16][36];   // merged O tile [query][d]
+
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int qtiles = gridDim.x >> 3;
+  const int head = head_major ? (blockIdx.x & 7) : (blockIdx.x / qtiles);
+  const int qtile = head_major ? (blockIdx.x >> 3) : (blockIdx.x % qtiles);
+  const int pair = blockIdx.z;
+  const int qi = qtile * 16 + l15;
+  const bool q_ok = qi < nq;
+  const size_t qrow = (size_t)pair * nq + (q_ok ? qi : 0);
+  const size_t key0 = (size_t)pair * ATT_KEYS + (size_t)wave * KPW;
+
+  // Q^T fragment (B operand: k = head dim g*8 + 4j + e, column = query l15); K fragment (A operand: row = key l15, the same k)
+  // (unconditional loads: rows past nq re-read row 0 of the pair and are zeroed after the load, never stored)
+  f32x4 qf[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) qf[j] = *reinterpret_cast<const f32x4*>(q + qrow * ldq + head * ATT_HD + g * 8 + j * 4);
+  // V fragment (A operand of O^T: row = head dim dh*16 + l15, k = g): vf[kb][dh][tt*4 + i] = v[key kb*64 + tt*16 + 4g + i][d].
+  // Requested in the order of use (loads retire in order): K and V of block 0, then of block 1
+  f32x4 kf[NBLK][4][2];
+  float vf[NBLK][2][16];
+#pragma unroll
+  for (int kb = 0; kb < NBLK; ++kb) {
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt) {
+      const float* kg = k + (key0 + kb * 64 + tt * 16 + l15) * ldkv + head * ATT_HD + g * 8;
+      kf[kb][tt][0] = *reinterpret_cast<const f32x4*>(kg);
+      kf[kb][tt][1] = *reinterpret_cast<const f32x4*>(kg + 4);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float* vg = v + (key0 + kb * 64 + (r >> 2) * 16 + 4 * g + (r & 3)) * ldkv + head * ATT_HD + l15;
+      vf[kb][0][r] = vg[0];
+      vf[kb][1][r] = vg[16];
+    }
+  }
+  f32x4 wof[4][2];   // OP: W_out fragment (B operand: k = head dim g*8 + 4j + e, column n = 64*wave + 16*nt + l15)
+  if constexpr (OP) {
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const float* worow = fz.wo + (size_t)(wave * 64 + nt * 16 + l15) * 256 + head * ATT_HD + g * 8;
+      wof[nt][0] = *reinterpret_cast<const f32x4*>(worow);
+      wof[nt][1] = *reinterpret_cast<const f32x4*>(worow + 4);
+    }
+  }
+  // keep every request above in flight together: the scheduler would otherwise sink each load next to its first use (occupancy
+  // heuristics), which leaves a wavefront with a few L2 round trips outstanding at a time
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    qf[j] = q_ok ? qf[j] * 1.44269504088896340736f : z;   // scores in the log2 domain, as attention_kernel
+  }
+
+  f32x4 oacc[2];
+#pragma unroll
+  for (int dh = 0; dh < 2; ++dh)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) oacc[dh][i] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+#pragma unroll
+  for (int kb = 0; kb < NBLK; ++kb) {
+    f32x4 s[4];
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s[tt][i] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) s[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kb][tt][j][e], qf[j][e], s[tt], 0, 0, 0);
+    float mx = s[0][0];
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[tt][i]);
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float m_new = fmaxf(m_run, mx);
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // first block: 2^(-inf) = 0
+    float psum = 0.f;
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        s[tt][i] = __builtin_amdgcn_exp2f(s[tt][i] - m_new);
+        psum += s[tt][i];
+      }
+    l_run = l_run * alpha + psum;   // this lane's 16 keys of the block; the 4 lane groups of a query are summed after the loop
+    m_run = m_new;
+#pragma unroll
+    for (int dh = 0; dh < 2; ++dh) oacc[dh] *= alpha;
+    // O^T[d][q] += sum_key V[key][d] * P[q][key]
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+#pragma unroll
+      for (int dh = 0; dh < 2; ++dh) oacc[dh] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[kb][dh][r], s[r >> 2][r & 3], oacc[dh], 0, 0, 0);
+  }
+  l_run += __shfl_xor(l_run, 16);
+  l_run += __shfl_xor(l_run, 32);
+
+  // ---- merge the 4 key splits: oacc[dh][i] = O^T[d = dh*16 + 4g + i][query l15] ---------------------------------------------
+#pragma unroll
+  for (int dh = 0; dh < 2; ++dh)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) lds_o[wave][dh * 4 + i][lane] = oacc[dh][i];
+  if (g == 0) {
+    lds_m[wave][l15] = m_run;
+    lds_l[wave][l15] = l_run;
+  }
+  __syncthreads();
+  float m_all = lds_m[0][l15];
+#pragma unroll
+  for (int w = 1; w < NS; ++w) m_all = fmaxf(m_all, lds_m[w][l15]);
+  float f[NS];
+  float l_all = 0.f;
+#pragma unroll
+  for (int w = 0; w < NS; ++w) {
+    f[w] = __builtin_amdgcn_exp2f(lds_m[w][l15] - m_all);
+    l_all += f[w] * lds_l[w][l15];
+  }
+  const float inv = 1.f / l_all;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {   // wave w finishes accumulator registers 2w and 2w + 1
+    const int r = wave * 2 + i;
+    float acc = 0.f;
+#pragma unroll
+    for (int w = 0; w < NS; ++w) acc += f[w] * lds_o[w][r][lane];
+    lds_out[l15][(r >> 2) * 16 + 4 * g + (r & 3)] = acc * inv;
+  }
+  __syncthreads();
+  if constexpr (OP) {
+    // partial[head][row][n] = sum_d O[row][d] * Wo[n][head*32 + d]: wave w -> output columns [64w, 64w + 64) as 4 tiles of 16, staged
+    // through a wave-private LDS tile so that the rows leave as float4 (one instruction = 4 rows x 256 B)
+    float* stage = lds_buf + wave * (16 * SLD);   // aliases lds_o: every wave is past the merge (barrier above)
+    f32x4 af[2];   // A operand: row = query l15, k = head dim g*8 + 4j + e
+#pragma unroll
+    for (int j = 0; j < 2; ++j) af[j] = *reinterpret_cast<const f32x4*>(&lds_out[l15][g * 8 + j * 4]);
+    f32x4 pacc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) pacc[nt][i] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) pacc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j][e], wof[nt][j][e], pacc[nt], 0, 0, 0);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) stage[(4 * g + i) * SLD + nt * 16 + l15] = pacc[nt][i];
+    float* pbase = fz.part + ((size_t)head * fz.rows_total + (size_t)pair * nq) * 256 + wave * 64;
+    const int sr = lane >> 4, sc = (lane & 15) * 4;   // 16 lanes (float4) per staged row, 4 rows per instruction
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int row = it * 4 + sr;
+      const int qo = qtile * 16 + row;
+      const f32x4 val = *reinterpret_cast<const f32x4*>(&stage[row * SLD + sc]);
+      if (qo < nq) store_f32x4(pbase + (size_t)qo * 256 + sc, val, fz.wt != 0);
+    }
+    if (o == nullptr) return;
+  }
+  if (t < 128) {   // 16 rows x 128 B, one float4 per thread
+    const int row = t >> 3, c4 = (t & 7) * 4;
+    const int qo = qtile * 16 + row;
     if (qo < nq)
       *reinterpret_cast<f32x4*>(o + ((size_t)pair * nq + qo) * ldo + head * ATT_HD + c4) =
           *reinterpret_cast<const f32x4*>(&lds_out[row][c4]);
@@ -583,7 +785,7 @@ static const int g_att_wide_head_major = 1;
 static thread_local unsigned long long* g_att_dbg = nullptr;   // set_attention_debug_times
 void set_attention_debug_times(unsigned long long* p) { g_att_dbg = p; }
 // the kernel the last launch_attention / launch_attention_fused call on this thread picked: "res", "wide3" / "wide2" (occupancy) or
-// "s<key splits>" - what the per-launch profile names carry (api.hip, cotr_set_profiling level 2)
+// "s<key splits>", "q16" (16-query tiles) - what the per-launch profile names carry (api.hip, cotr_set_profiling level 2)
 static thread_local const char* g_att_variant = "";
 const char* attention_last_variant() { return g_att_variant; }
 // knobs: KN_ATTENTION_SPLITS (0 = automatic), KN_ATTENTION_FUSED_SPLITS (0 = 4; 48 / 84: encoder (q given) / decoder (q projected)
@@ -684,6 +886,16 @@ static int attention_fused_impl(const float* q, int ldq, const float* x, const f
   // 16 query tiles x 8 heads = 128 workgroups on 256 CUs): measured 0.978 vs 0.973 ms per forward, the merge of 8 partial
   // softmaxes and the narrower out-projection blocks cost more than the idle CUs -- kept as a knob only
   const int ns = g_att_fused_splits == 48 ? (qp ? 8 : 4) : g_att_fused_splits == 84 ? (qp ? 4 : 8) : g_att_fused_splits ? g_att_fused_splits : 4;
+  // q given and 32-query tiles that leave CUs without a workgroup (the encoder of one pair): 16-query tiles, twice the workgroups
+  if (!qp && ns == 4 && (long)grid.x * nb < cotr_num_cus()) {
+    dim3 grid16(((nq + 15) / 16) * 8, 1, nb);
+    g_att_variant = "q16";
+    if (op)
+      hipLaunchKernelGGL((attention_q16_kernel<true>), grid16, dim3(256), 0, s, q, ldq, k, v, ldkv, o, ldo, nq, g_att_head_major, fz);
+    else
+      hipLaunchKernelGGL((attention_q16_kernel<false>), grid16, dim3(256), 0, s, q, ldq, k, v, ldkv, o, ldo, nq, g_att_head_major, fz);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+  }
 #define ATT_LAUNCH(NSV, QPV, OPV)                                                                                         \
   hipLaunchKernelGGL((attention_kernel<NSV, QPV, OPV>), grid, dim3(NSV * 64), 0, s, q, ldq, k, v, ldkv, o, ldo, nq, g_att_head_major, fz)
 #define ATT_PICK(NSV)                              \

@@ -55,6 +55,8 @@ def describe(name):
         return 2.0 * 8192 * (64 * 64 + 576 * 64 + 64 * 256 + 64 * 256), 256, 64 * 4 * (64 + 576 + 256 + 256) + 60 * 64 * 4
     if name.startswith('bottleneck'):
         return 2.0 * 8192 * (256 * 64 + 576 * 64 + 64 * 256), 256, 64 * 4 * (256 + 576 + 256) + 60 * 256 * 4
+    if name.startswith('attention+oproj enc q16'):        # 16 queries x 1 head (attention_q16_kernel): K_h, V_h, q rows, Wo_h
+        return 512 * (2 * 2 * 512 * 256 + 2 * 256 * 256), 256, 2 * 512 * 32 * 4 + 16 * 32 * 4 + 256 * 32 * 4
     if name.startswith('attention+oproj enc'):            # 32 queries x 1 head: K_h, V_h, q rows, Wo_h
         return 512 * (2 * 2 * 512 * 256 + 2 * 256 * 256), 128, 2 * 512 * 32 * 4 + 32 * 32 * 4 + 256 * 32 * 4
     if name.startswith('qproj+attention+oproj dec'):      # + the rows to project (tgt, query_pos) and Wq_h
@@ -76,7 +78,7 @@ def main():
     a = ap.parse_args()
     names = [re.match(r'\s*\d+ (.*?)\s+[\d.]+ us', l).group(1) for l in open(a.names) if re.match(r'\s*\d+ \S.* us$', l)]
     trace = [(re.search(r'grid (\d+)x(\d+)x', l), float(re.search(r'([\d.]+) us$', l).group(1)), l) for l in open(a.trace)
-             if re.match(r'\s*\d+ _Z', l)]
+             if re.match(r'\s*\d+ \S.* grid \d+x\d+x\d+ ', l)]
     start = next(i for i, t in enumerate(trace) if 'stem_pool' in t[2])       # the rocprofv3 list starts in the middle of a forward
     trace = trace[start:] + trace[:start]
     assert len(names) == len(trace) == 94, (len(names), len(trace))
