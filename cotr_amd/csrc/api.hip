@@ -18,6 +18,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -168,6 +169,12 @@ struct cotr_ctx {
   int prof = 0;  // 0 off, 1 per stage, 2 per kernel launch
   std::vector<std::string> prof_names;
   std::vector<hipEvent_t> prof_ev;
+  // varlen calls (cotr_decode_varlen): their tile tables are staged in pinned host memory and copied into the decoder scratch on the
+  // call's stream; a ring of slots, each reused only after the event of its last copy (the caller's offsets are not read after the
+  // call returns, and back-to-back calls do not overwrite a table that is still being copied)
+  struct VlStage { int4* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool pending = false; };
+  VlStage vl_stage[4];
+  unsigned vl_next = 0;
 };
 
 namespace {
@@ -658,6 +665,10 @@ void cotr_destroy(cotr_handle h) {
     if (a->ptr && !a->external) (void)hipFree(a->ptr);
   for (auto& kv : h->tap_store)
     if (kv.second.ptr) (void)hipFree(kv.second.ptr);
+  for (auto& st : h->vl_stage) {
+    if (st.host) (void)hipHostFree(st.host);
+    if (st.ev) (void)hipEventDestroy(st.ev);
+  }
   delete h;
 }
 
@@ -1266,6 +1277,256 @@ int cotr_scratch_bytes(cotr_handle h, int B, int Q, size_t* bytes) {
   for (size_t f : {enc_cache_floats(h, B), enc_layout(enc_chunk_max(B, h->knobs), h->knobs, nullptr, nullptr), f_dec})
     total = ((total + 255) & ~size_t(255)) + f * sizeof(float);
   *bytes = total + 256;
+  return COTR_OK;
+}
+
+}  // extern "C"
+
+// ---- varlen decode: B pairs, pair b owns rows offsets[b] .. offsets[b+1] of a packed [N][2] query array (cotr_decode_varlen) ---------
+// A pass is a range [r0, r1) of the packed rows: up to DEC_ROWS of them, cut at any row (a pair's rows continue in the next pass, as a
+// uniform call's queries do above DEC_ROWS; a pair with no rows takes no tile).  With knob batch_split, dec_next_pairs' prefix rule
+// holds at the pair boundaries inside a pass: where att_rows + ffn_rows do not take the whole pass but take a prefix of whole pairs, that
+// prefix is a pass of its own.  A pass's attention form follows decode_chunk's fill rules on the pass's row and tile counts:
+//   fused  att_fused_applies(R) && ffn_fused_applies(R) (and the partials fit)    attention_kernel<4|8, QP, OP, VL>, 32-row tiles
+//   rows   att_rows_min_rows rows, 64-row tiles that fill the last round of the CUs to rows_min_fill percent and are at least 7/8
+//          full on average (att_rows_applies' per-pair padding rule, over the pass)  att_rows_kernel<true, ., ., VL>, 64-row tiles
+//   plain  otherwise: attention_kernel<knob attention_splits, 0, false, VL> (the wide / resident many-row kernels have no varlen mode)
+// Every other stage is row-wise and runs on the pass's R packed rows as on one "pair" of R queries.  Each pass's tile table - entry
+// (pair, first row in the pass, valid rows, 0) per workgroup tile - is built on the host, staged in a pinned slot of the handle's ring
+// and copied into the decoder scratch right before the pass on the call's stream.  The second stream (knob side_stream) is not used.
+namespace {
+
+constexpr int VL_TILE = 32, VL_TILE_ROWS = 64;   // rows per tile: attention_kernel, att_rows_kernel
+enum { VL_PLAIN = 0, VL_FUSED = 1, VL_ROWS = 2 };
+
+struct VlPass { long r0 = 0, r1 = 0; int b0 = 0, b1 = 0; };   // packed rows [r0, r1), of pairs [b0, b1)
+
+// rows of pair b inside [r0, r1)
+long vl_lo(const int* off, int b, long r0) { return off[b] > r0 ? off[b] : r0; }
+long vl_hi(const int* off, int b, long r1) { return off[b + 1] < r1 ? off[b + 1] : r1; }
+
+long vl_tiles(const int* off, const VlPass& p, int rows_per_tile) {
+  long n = 0;
+  for (int b = p.b0; b < p.b1; ++b) {
+    const long r = vl_hi(off, b, p.r1) - vl_lo(off, b, p.r0);
+    if (r > 0) n += (r + rows_per_tile - 1) / rows_per_tile;
+  }
+  return n;
+}
+
+// tile-table entries a pass of up to R rows of up to B pairs can need (every pair's last 32-row tile may be partial)
+size_t vl_tile_cap(size_t R, int B) { return R / VL_TILE + (R < (size_t)B ? R : (size_t)B) + 1; }
+
+// att_rows_applies on a pass of R rows in `tiles` 64-row tiles
+bool vl_att_rows_applies(long R, long tiles) {
+  if (R < knob(KN_ATT_ROWS_MIN_ROWS)) return false;
+  const long cus = cotr_num_cus(), rounds = (tiles + cus - 1) / cus;
+  return tiles * 100 >= rounds * cus * knob(KN_ROWS_MIN_FILL) && R * 8 >= tiles * VL_TILE_ROWS * 7;
+}
+bool vl_rows_kernels_apply(const int* off, const VlPass& p) {
+  const long R = p.r1 - p.r0;
+  return vl_att_rows_applies(R, vl_tiles(off, p, VL_TILE_ROWS)) && ffn_rows_applies((int)R);
+}
+
+VlPass vl_next_pass(const int* off, int B, long r0) {
+  VlPass p;
+  const long N = off[B];
+  p.r0 = r0;
+  p.r1 = N - r0 < DEC_ROWS ? N : r0 + DEC_ROWS;
+  p.b0 = (int)(std::upper_bound(off + 1, off + B + 1, (int)r0) - off) - 1;   // the pair that holds row r0
+  p.b1 = (int)(std::lower_bound(off, off + B + 1, (int)p.r1) - off);        // pairs that start below r1
+  if (!knob(KN_BATCH_SPLIT) || p.b1 - p.b0 < 2 || vl_rows_kernels_apply(off, p)) return p;
+  const long min_rows = knob(KN_ATT_ROWS_MIN_ROWS) > knob(KN_FFN_ROWS_MIN_ROWS) ? knob(KN_ATT_ROWS_MIN_ROWS) : knob(KN_FFN_ROWS_MIN_ROWS);
+  for (int b = p.b1 - 1; b > p.b0 && off[b] - r0 >= min_rows; --b) {   // the longest prefix of whole pairs [b0, b) the rows kernels take
+    VlPass q = p;
+    q.r1 = off[b];
+    q.b1 = b;
+    if (vl_rows_kernels_apply(off, q)) return q;
+  }
+  return p;
+}
+
+int vl_form(const DecBufs& d, long R, long tiles64) {
+  if (d.part != nullptr && att_fused_applies(R) && ffn_fused_applies(R) && (size_t)ffn_fused_chunks((int)R) * R * D <= d.hid_cap)
+    return VL_FUSED;
+  return vl_att_rows_applies(R, tiles64) ? VL_ROWS : VL_PLAIN;
+}
+
+long vl_fill(const int* off, const VlPass& p, int rows_per_tile, int4* out) {
+  long n = 0;
+  for (int b = p.b0; b < p.b1; ++b)
+    for (long r = vl_lo(off, b, p.r0), hi = vl_hi(off, b, p.r1); r < hi; r += rows_per_tile)
+      out[n++] = make_int4(b, (int)(r - p.r0), (int)(hi - r < rows_per_tile ? hi - r : rows_per_tile), 0);
+  return n;
+}
+
+// the decoder scratch of dec_layout for passes of up to min(N, DEC_ROWS) rows, then the tile table
+int vl_plan(cotr_ctx* h, long N, int B, DecPlan& d, int4** tab, size_t* tab_cap) {
+  d.Rmax = N < DEC_ROWS ? (size_t)N : (size_t)DEC_ROWS;
+  const size_t main = dec_layout(d.Rmax, h->knobs, nullptr, nullptr);
+  *tab_cap = vl_tile_cap(d.Rmax, B);
+  if (int r = ensure(h, h->dec_scr, main + *tab_cap * 4)) return r;
+  dec_layout(d.Rmax, h->knobs, h->dec_scr.ptr, &d);
+  *tab = reinterpret_cast<int4*>(h->dec_scr.ptr + main);
+  return COTR_OK;
+}
+
+// one pass of R packed rows through the decoder (decode_chunk's schedule with the varlen attention launches)
+int vl_decode_pass(cotr_ctx* h, const DecPlan& d, const float* qsrc, float* odst, const float* kv, const int4* tab, int ntab, int form,
+                   int R, hipStream_t s) {
+  const int L = (int)h->dec.size();
+  const int KVLD = L * 2 * D;
+  const bool fused = form == VL_FUSED, rows = form == VL_ROWS;
+  int r;
+  if ((r = dec_prologue(h, d, qsrc, 1, R, R, s, fused || rows))) return r;
+  bool hs_normed = false;
+  for (int li = 0; li < L; ++li) {
+    const DecW& w = h->dec[li];
+    const float* kl = kv + (size_t)li * 2 * D;
+    const float* tgt_in = li == 0 ? nullptr : d.tgt;
+    bool post;
+    if (fused) {
+      KCHK(h, launch_attention_varlen(nullptr, 0, tgt_in, d.qpos, w.q_w, w.q_b, QSCALE, kl, kl + D, KVLD, nullptr, 0, w.out_w, d.part, R,
+                                      tab, ntab, s), "q_proj+attention+out_proj (varlen)");
+      prof_attention(h, "qproj+attention+oproj dec", s);
+      KCHK(h, launch_ln_reduce(d.part, 8, w.out_b, tgt_in, w.n2w, w.n2b, d.t2, R, s), "ln_reduce");
+      prof_mark(h, "ln_reduce heads", s, 2);
+      post = li + 1 == L;
+    } else {
+      if (rows) {
+        KCHK(h, launch_att_rows_varlen(tgt_in, d.qpos, w.q_w, w.q_b, QSCALE, kl, kl + D, KVLD, w.out_w, w.out_b, tgt_in, w.n2w, w.n2b,
+                                       d.t2, tab, ntab, s), "att_rows (varlen)");
+        prof_mark(h, "att_rows dec", s, 2);
+      } else {
+        if (li > 0 && (r = linear(h, d.tgt, d.qpos, 0, 1, 1, w.q_w, w.q_b, nullptr, 0, QSCALE, D, d.q, R, D, D, s))) return r;
+        KCHK(h, launch_attention_varlen(d.q, D, nullptr, nullptr, nullptr, nullptr, 0.f, kl, kl + D, KVLD, d.ao, D, nullptr, nullptr, R,
+                                        tab, ntab, s), "attention (varlen)");
+        prof_attention(h, "attention dec", s);
+        if ((r = linear(h, d.ao, nullptr, 0, 1, 0, w.out_w, w.out_b, tgt_in, 0, 1.f, 0, d.pre2, R, D, D, s))) return r;
+        if ((r = layernorm(h, d.pre2, w.n2w, w.n2b, d.t2, R, s))) return r;
+      }
+      post = li + 1 == L && ffn_rows_applies(R);
+    }
+    if ((r = ffn_block(h, d.t2, w.l1w, w.l1b, w.l2w, w.l2b, w.n3w, w.n3b, d.hid, d.hid_cap, d.pre3, post ? d.pre2 : d.tgt, R, s,
+                       post ? h->dn_w : nullptr, post ? h->dn_b : nullptr))) return r;
+    hs_normed = post;
+  }
+  if (!hs_normed && (r = layernorm(h, d.tgt, h->dn_w, h->dn_b, d.pre2, R, s))) return r;
+  if ((r = linear(h, d.pre2, nullptr, 0, 1, 0, h->mlp_w[0], h->mlp_b[0], nullptr, 1, 1.f, 0, d.ao, R, D, D, s))) return r;
+  if ((r = linear(h, d.ao, nullptr, 0, 1, 0, h->mlp_w[1], h->mlp_b[1], nullptr, 1, 1.f, 0, d.q, R, D, D, s))) return r;
+  KCHK(h, launch_head2(d.q, h->mlp_w[2], h->mlp_b[2], odst, 1, R, R, s), "head2");
+  prof_mark(h, "head2", s, 2);
+  return COTR_OK;
+}
+
+int vl_decode(cotr_ctx* h, const float* queries, const int* off, int B, float* out, hipStream_t s) {
+  const long N = off[B];
+  DecPlan d;
+  int4* tab = nullptr;
+  size_t tab_cap = 0;
+  if (int r = vl_plan(h, N, B, d, &tab, &tab_cap)) return r;
+  // the whole walk on the host first: every pass's rows, form and tile table (read from the caller's offsets now, never later)
+  struct Pass { VlPass p; int form; long ntab; size_t at; };
+  std::vector<Pass> passes;
+  size_t total = 0;
+  for (long r0 = 0; r0 < N;) {
+    Pass ps;
+    ps.p = vl_next_pass(off, B, r0);
+    ps.form = vl_form(d, ps.p.r1 - ps.p.r0, vl_tiles(off, ps.p, VL_TILE_ROWS));
+    ps.ntab = vl_tiles(off, ps.p, ps.form == VL_ROWS ? VL_TILE_ROWS : VL_TILE);
+    if (ps.ntab <= 0 || (size_t)ps.ntab > tab_cap) { h->err = "cotr_decode_varlen: tile table overflow"; return COTR_ERR_STATE; }
+    ps.at = total;
+    total += ps.ntab;
+    passes.push_back(ps);
+    r0 = ps.p.r1;
+  }
+  cotr_ctx::VlStage& st = h->vl_stage[h->vl_next++ % 4];
+  if (!st.ev) HIPCHK(h, hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+  if (st.pending) HIPCHK(h, hipEventSynchronize(st.ev));   // this slot's tables of 4 calls ago have been copied
+  st.pending = false;
+  if (st.cap < total) {
+    if (st.host) HIPCHK(h, hipHostFree(st.host));
+    st.host = nullptr;
+    st.cap = 0;
+    const size_t cap = total > 4096 ? total : 4096;
+    HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&st.host), cap * sizeof(int4), hipHostMallocDefault));
+    st.cap = cap;
+  }
+  for (const Pass& ps : passes) vl_fill(off, ps.p, ps.form == VL_ROWS ? VL_TILE_ROWS : VL_TILE, st.host + ps.at);
+  const float* kv = h->memkv.ptr + (size_t)B * TOK * D;
+  prof_mark(h, "dec_begin", s);
+  int r = COTR_OK;
+  for (const Pass& ps : passes) {
+    const long R = ps.p.r1 - ps.p.r0;
+    const hipError_t e = hipMemcpyAsync(tab, st.host + ps.at, ps.ntab * sizeof(int4), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { h->err = std::string("hipMemcpyAsync (varlen tile table): ") + hipGetErrorString(e); r = COTR_ERR_HIP; break; }
+    st.pending = true;
+    if ((r = vl_decode_pass(h, d, queries + ps.p.r0 * 2, out + ps.p.r0 * 2, kv, tab, (int)ps.ntab, ps.form, (int)R, s))) break;
+    if ((r = tap_save(h, "query_pos", d.qpos, (size_t)R * D, s))) break;
+    if ((r = tap_save(h, "hs", d.pre2, (size_t)R * D, s))) break;
+  }
+  if (st.pending) HIPCHK(h, hipEventRecord(st.ev, s));
+  if (r) return r;
+  prof_mark(h, "decoder", s);
+  return COTR_OK;
+}
+
+// offsets: B + 1 ints from 0, nondecreasing
+int vl_check_offsets(cotr_ctx* h, const int* off, int B, const char* who) {
+  if (B <= 0 || !off) { h->err = std::string(who) + ": B <= 0 or null offsets"; return COTR_ERR_ARG; }
+  if (off[0] != 0) { h->err = std::string(who) + ": offsets[0] != 0"; return COTR_ERR_ARG; }
+  for (int b = 0; b < B; ++b)
+    if (off[b + 1] < off[b]) {
+      char msg[160];
+      snprintf(msg, sizeof msg, "%s: offsets decrease at pair %d (%d -> %d)", who, b, off[b], off[b + 1]);
+      h->err = msg;
+      return COTR_ERR_ARG;
+    }
+  return COTR_OK;
+}
+
+int vl_check(cotr_ctx* h, const float* queries, const int* off, int B, float* out, const char* who) {
+  if (!h->loaded) { h->err = std::string(who) + " before cotr_load_weights"; return COTR_ERR_STATE; }
+  if (int r = vl_check_offsets(h, off, B, who)) return r;
+  if (off[B] > 0 && (!queries || !out)) { h->err = std::string(who) + ": null queries/out"; return COTR_ERR_ARG; }
+  return COTR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cotr_decode_varlen(cotr_handle h, const float* queries, const int* offsets, int B, float* out, cotr_stream stream) {
+  if (!h) return COTR_ERR_ARG;
+  if (int r = vl_check(h, queries, offsets, B, out, "cotr_decode_varlen")) return r;
+  if (h->enc_B != B) {
+    h->err = "cotr_decode_varlen: no cached encode for this batch size (call cotr_encode first)";
+    return COTR_ERR_STATE;
+  }
+  if (offsets[B] == 0) return COTR_OK;
+  DEVICE_SCOPE(h);
+  return vl_decode(h, queries, offsets, B, out, static_cast<hipStream_t>(stream));
+}
+
+int cotr_forward_varlen(cotr_handle h, const float* img, const float* queries, const int* offsets, int B, float* out,
+                        cotr_stream stream) {
+  if (!h) return COTR_ERR_ARG;
+  if (int r = vl_check(h, queries, offsets, B, out, "cotr_forward_varlen")) return r;
+  DEVICE_SCOPE(h);
+  int r = encode_impl(h, img, B, stream, nullptr);
+  if (r || offsets[B] == 0) return r;
+  return vl_decode(h, queries, offsets, B, out, static_cast<hipStream_t>(stream));
+}
+
+// cotr_scratch_bytes of (B, ceil(N / B)) - whose decoder passes hold at least as many rows as this call's - plus the largest tile table
+int cotr_scratch_bytes_varlen(cotr_handle h, const int* offsets, int B, size_t* bytes) {
+  if (!h || !bytes) return COTR_ERR_ARG;
+  if (int r = vl_check_offsets(h, offsets, B, "cotr_scratch_bytes_varlen")) return r;
+  const long N = offsets[B];
+  const int Qeq = (int)((N + B - 1) / B);
+  if (int r = cotr_scratch_bytes(h, B, Qeq, bytes)) return r;
+  const size_t R = (size_t)B * Qeq < (size_t)DEC_ROWS ? (size_t)B * Qeq : (size_t)DEC_ROWS;
+  *bytes += vl_tile_cap(R, B) * sizeof(int4);
   return COTR_OK;
 }
 

@@ -66,6 +66,7 @@ struct AttRowsParams {
   int nb, tpp;           // pairs; 64-row tiles per pair
   int by_xcd;            // 1: 1-D grid, all tiles of a pair on ONE XCD (see att_rows_kernel); 0: grid (tiles per pair, pairs)
   float* dbg;            // debug instantiation only (tools/micro/att_rows_probe.hip): stage dumps of workgroup 0
+  const int4* tiles;     // VL: [workgroups] (pair, first row, valid rows, -): api.hip's varlen tile table (1-D grid, one entry per workgroup)
 };
 
 constexpr int AR_T = 8 * AR_BM * 32;                      // floats of the T tile
@@ -369,7 +370,8 @@ __device__ __forceinline__ void ar_out_steps(const AttRowsParams& p, const ArLan
   (ar_out_step<QP, S_>(p, L, wave, key0, it, cur, yacc), ...);
 }
 
-template <bool QP, bool DBG = false, int ABL = 0>
+// VL (varlen decode): workgroup b takes entry b of p.tiles - up to 64 rows of ONE pair, at a row of the pass's packed rows of its own
+template <bool QP, bool DBG = false, int ABL = 0, bool VL = false>
 __global__ __launch_bounds__(512, 2) void att_rows_kernel(const AttRowsParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* T = smem;
@@ -389,7 +391,10 @@ __global__ __launch_bounds__(512, 2) void att_rows_kernel(const AttRowsParams p)
   // bound by its softmax VALU + matrix pipe, not by the fabric.  Other pair counts keep the plain grid (a padded 1-D grid leaves
   // XCDs idle: 4 pairs on 4 of the 8 XCDs ran the dense pass 4 x slower).  Placement is for speed only: any mapping gives the same results.
   int pair, tile;
-  if (p.by_xcd) {
+  if constexpr (VL) {
+    pair = p.tiles[blockIdx.x].x;
+    tile = 0;
+  } else if (p.by_xcd) {
     const int j = blockIdx.x >> 3;
     pair = (blockIdx.x & 7) + 8 * (j / p.tpp);
     tile = j % p.tpp;
@@ -399,9 +404,9 @@ __global__ __launch_bounds__(512, 2) void att_rows_kernel(const AttRowsParams p)
     tile = blockIdx.x;
   }
   const int q0 = tile * AR_BM;                             // first query of this tile inside its pair
-  const size_t row0 = (size_t)pair * p.nq + q0;            // ... its global row
+  const size_t row0 = VL ? (size_t)p.tiles[blockIdx.x].y : (size_t)pair * p.nq + q0;   // ... its global row
   const size_t key0 = (size_t)pair * AR_KEYS;
-  const int nvalid = p.nq - q0 < AR_BM ? p.nq - q0 : AR_BM;
+  const int nvalid = VL ? p.tiles[blockIdx.x].z : (p.nq - q0 < AR_BM ? p.nq - q0 : AR_BM);
 
 #define AR_STAMP(slot)                                                                                                    \
   do {                                                                                                                    \
@@ -633,22 +638,26 @@ __global__ __launch_bounds__(512, 2) void att_rows_kernel(const AttRowsParams p)
 // Y = LN(residual + out_proj(MHA(q, K, V)) + bo) for nb pairs x nq query rows; q given (wq == nullptr: [rows][ldq], pre-scaled) or
 // projected here from x (+ x2).  Y must not alias the residual / x / x2 (a tile's rows are re-read for the residual after other tiles
 // may have written theirs - keep the contract simple: distinct buffers).
-int launch_att_rows(const float* q, int ldq, const float* x, const float* x2, const float* wq, const float* bq, float qscale,
-                    const float* k, const float* v, int ldkv, const float* wo, const float* bo, const float* residual,
-                    const float* ln_w, const float* ln_b, float* Y, int nb, int nq, hipStream_t s) {
-  if (nb <= 0 || nq <= 0) return 0;
+// tiles != nullptr: varlen - ntiles workgroups, one per entry of the tile table (nb, nq unused)
+static int att_rows_impl(const float* q, int ldq, const float* x, const float* x2, const float* wq, const float* bq, float qscale,
+                         const float* k, const float* v, int ldkv, const float* wo, const float* bo, const float* residual,
+                         const float* ln_w, const float* ln_b, float* Y, int nb, int nq, const int4* tiles, int ntiles, hipStream_t s) {
+  if (tiles ? ntiles <= 0 : (nb <= 0 || nq <= 0)) return 0;
   const bool qp = wq != nullptr;
   if (!k || !v || !wo || !bo || !ln_w || !ln_b || !Y || ldkv % 32 || nb > 65535) return -1;   // (ldkv % 32: the odd-instruction offset is an XOR)
   if (qp ? (!x2 || !bq) : (!q || ldq % 4)) return -1;
   if (Y == residual || Y == x || Y == x2 || Y == q) return -1;
   if (((uintptr_t)q | (uintptr_t)x | (uintptr_t)x2 | (uintptr_t)k | (uintptr_t)v | (uintptr_t)wo | (uintptr_t)wq | (uintptr_t)residual | (uintptr_t)Y) & 15)
     return -1;
+  if (tiles && !qp) return -1;   // the varlen mode is the decoder's (q projected here)
   static PerDeviceFlag attr_set;
   if (!attr_set.get()) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(att_rows_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)kAttRowsSmem) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(att_rows_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kAttRowsSmem) != hipSuccess)
+                            (int)kAttRowsSmem) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(att_rows_kernel<true, false, 0, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttRowsSmem) != hipSuccess)
       return -2;
     attr_set.set();
   }
@@ -656,10 +665,31 @@ int launch_att_rows(const float* q, int ldq, const float* x, const float* x2, co
   p.q = q; p.ldq = ldq; p.x = x; p.x2 = x2; p.wq = wq; p.bq = bq; p.qscale = qscale; p.k = k; p.v = v; p.ldkv = ldkv;
   p.wo = wo; p.bo = bo; p.residual = residual; p.ln_w = ln_w; p.ln_b = ln_b; p.Y = Y; p.zeros = gemm_zero_buffer(); p.nq = nq;
   p.dbg = nullptr;
+  p.tiles = tiles;
+  if (tiles) {
+    // varlen: the tiles in table order (a pair's tiles are consecutive) on a 1-D grid
+    p.nb = 0; p.tpp = 0; p.by_xcd = 0;
+    hipLaunchKernelGGL((att_rows_kernel<true, false, 0, true>), dim3(ntiles), dim3(64 * AR_NW), kAttRowsSmem, s, p);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+  }
   p.nb = nb; p.tpp = (nq + AR_BM - 1) / AR_BM;
   p.by_xcd = (knob(KN_XCD_MAPPING) & 32) == 0 && nb % 8 == 0;
   const dim3 grid = p.by_xcd ? dim3(p.tpp * nb) : dim3(p.tpp, nb);
   if (qp) hipLaunchKernelGGL(att_rows_kernel<true>, grid, dim3(64 * AR_NW), kAttRowsSmem, s, p);
   else hipLaunchKernelGGL(att_rows_kernel<false>, grid, dim3(64 * AR_NW), kAttRowsSmem, s, p);
   return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_att_rows(const float* q, int ldq, const float* x, const float* x2, const float* wq, const float* bq, float qscale,
+                    const float* k, const float* v, int ldkv, const float* wo, const float* bo, const float* residual,
+                    const float* ln_w, const float* ln_b, float* Y, int nb, int nq, hipStream_t s) {
+  return att_rows_impl(q, ldq, x, x2, wq, bq, qscale, k, v, ldkv, wo, bo, residual, ln_w, ln_b, Y, nb, nq, nullptr, 0, s);
+}
+
+// the decoder form over a varlen tile table (api.hip cotr_decode_varlen): ntiles workgroups, entry i = up to 64 rows of one pair
+int launch_att_rows_varlen(const float* x, const float* x2, const float* wq, const float* bq, float qscale, const float* k,
+                           const float* v, int ldkv, const float* wo, const float* bo, const float* residual, const float* ln_w,
+                           const float* ln_b, float* Y, const int4* tiles, int ntiles, hipStream_t s) {
+  if (!tiles) return -1;
+  return att_rows_impl(nullptr, 0, x, x2, wq, bq, qscale, k, v, ldkv, wo, bo, residual, ln_w, ln_b, Y, 0, 0, tiles, ntiles, s);
 }

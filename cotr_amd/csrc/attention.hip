@@ -45,9 +45,12 @@ struct AttnFuse {
   int rows_total;      // OP: rows of one partial
   int wt;              // OP: write-through (sc1) stores for the partials (read once, by every XCD)
   unsigned long long* dbg;  // nullptr, or [workgroups][8] phase timestamps (100 MHz wall clock): cotr_debug_attention_times
+  const int4* tiles;   // VL: [query tiles] (pair, first row, valid rows, -): api.hip's varlen tile table
 };
 
-template <int NS, int QP, bool OP>   // QP: 0 = q given, 1 = project x, 2 = project x + x2
+// VL (varlen decode): query tile i of the grid is entry i of fz.tiles - rows [first row, + valid rows) of the pass's packed rows, all of
+// ONE pair (K / V at that pair's slot); gridDim.z == 1.  Otherwise tile qtile of pair blockIdx.z: rows pair * nq + qtile * 32 ...
+template <int NS, int QP, bool OP, bool VL = false>   // QP: 0 = q given, 1 = project x, 2 = project x + x2
 __global__ __launch_bounds__(NS * 64) void attention_kernel(const float* __restrict__ q, int ldq,
                                                             const float* __restrict__ k,
                                                             const float* __restrict__ v, int ldkv,
@@ -80,10 +83,18 @@ __global__ __launch_bounds__(NS * 64) void attention_kernel(const float* __restr
   const int qtiles = gridDim.x >> 3;
   const int head = head_major ? (blockIdx.x & 7) : (blockIdx.x / qtiles);
   const int qtile = head_major ? (blockIdx.x >> 3) : (blockIdx.x % qtiles);
-  const int pair = blockIdx.z;
-  const int qi = qtile * 32 + l31;
-  const bool q_ok = qi < nq;
-  const size_t qrow = (size_t)pair * nq + (q_ok ? qi : 0);
+  int pair = blockIdx.z, q_first = qtile * 32, q_end = nq;   // this tile: queries [q_first, q_first + 32) of rows row_base + ..., valid below q_end
+  size_t row_base = (size_t)pair * nq;
+  if constexpr (VL) {
+    const int4 e = fz.tiles[qtile];
+    pair = e.x;
+    row_base = (size_t)e.y;
+    q_first = 0;
+    q_end = e.z;
+  }
+  const int qi = q_first + l31;
+  const bool q_ok = qi < q_end;
+  const size_t qrow = row_base + (q_ok ? qi : 0);
 
   const size_t key0 = (size_t)pair * ATT_KEYS + (size_t)wave * (ATT_KEYS / NS);
   // K fragment (A operand of S^T): lane (key l31, half hh) reads k[key][j*8 + hh*4 .. +3]
@@ -264,25 +275,25 @@ __global__ __launch_bounds__(NS * 64) void attention_kernel(const float* __restr
       for (int r = 0; r < 16; ++r) stage[((r & 3) + 8 * (r >> 2) + 4 * hh) * SLD + nb * 32 + l31] = pacc[r];
     }
     ATT_STAMP(4);
-    float* pbase = fz.part + ((size_t)head * fz.rows_total + (size_t)pair * nq) * 256 + wave * (32 * NBO);
+    float* pbase = fz.part + ((size_t)head * fz.rows_total + row_base) * 256 + wave * (32 * NBO);
     constexpr int LPR = 8 * NBO;                  // lanes (float4) per staged row
     constexpr int RPI = 64 / LPR;                 // rows per wave instruction
     const int sr = lane / LPR, sc = (lane % LPR) * 4;
 #pragma unroll
     for (int it = 0; it < 32 / RPI; ++it) {
       const int row = it * RPI + sr;
-      const int qo = qtile * 32 + row;
+      const int qo = q_first + row;
       const f32x4 val = *reinterpret_cast<const f32x4*>(&stage[row * SLD + sc]);
-      if (qo < nq) store_f32x4(pbase + (size_t)qo * 256 + sc, val, fz.wt != 0);
+      if (qo < q_end) store_f32x4(pbase + (size_t)qo * 256 + sc, val, fz.wt != 0);
     }
     ATT_STAMP(5);
     if (o == nullptr) return;
   }
   for (int i = t; i < 256; i += NS * 64) {  // 32 rows x 128 B, one float4 per thread: coalesced row stores
     const int row = i >> 3, c4 = (i & 7) * 4;
-    const int qo = qtile * 32 + row;
-    if (qo < nq)
-      *reinterpret_cast<f32x4*>(o + ((size_t)pair * nq + qo) * ldo + head * ATT_HD + c4) =
+    const int qo = q_first + row;
+    if (qo < q_end)
+      *reinterpret_cast<f32x4*>(o + (row_base + qo) * ldo + head * ATT_HD + c4) =
           *reinterpret_cast<const f32x4*>(&lds_out[row][c4]);
   }
 }
@@ -919,4 +930,53 @@ int launch_attention_fused(const float* q, int ldq, const float* x, const float*
                            float qscale, const float* k, const float* v, int ldkv, float* o, int ldo, const float* wo,
                            float* part, int nb, int nq, hipStream_t s) {
   return attention_fused_impl(q, ldq, x, x2, wq, bq, qscale, k, v, ldkv, o, ldo, wo, part, nb, nq, s);
+}
+
+// Varlen decode (api.hip cotr_decode_varlen): the decoder cross-attention over the query tiles of `tiles` (ntiles entries of 32 rows or
+// fewer, each of one pair; device memory), rows of the pass packed back to back.  Plain form (wq == nullptr: q given [rows][ldq],
+// output o) with knob attention_splits' key splits (0 = 4), or the fused few-rows form (q projected from x (+ x2) in the prologue, the
+// out-projection's 8 per-head partials [8][rows][256] to `part`) with attention_fused_splits'.  Only attention_kernel has this mode:
+// the wide / resident many-row kernels are left to the uniform path.
+int launch_attention_varlen(const float* q, int ldq, const float* x, const float* x2, const float* wq, const float* bq, float qscale,
+                            const float* k, const float* v, int ldkv, float* o, int ldo, const float* wo, float* part, int rows,
+                            const int4* tiles, int ntiles, hipStream_t s) {
+  if (ntiles <= 0) return 0;
+  const bool qp = wq != nullptr, op = wo != nullptr;
+  if (!tiles || rows <= 0 || qp != op || ldkv % 4) return -1;     // plain: q -> o; fused: x (+ x2) -> part
+  if (qp ? (bq == nullptr || x2 == nullptr || part == nullptr) : (q == nullptr || o == nullptr || ldq % 4 || ldo % 4)) return -1;
+  const int g_att_head_major = (knob(KN_XCD_MAPPING) >> 3) & 1;
+  const dim3 grid((unsigned)ntiles * 8, 1, 1);
+  AttnFuse fz = {};
+  fz.tiles = tiles;
+  if (!qp) {
+    const int ns = knob(KN_ATTENTION_SPLITS) ? knob(KN_ATTENTION_SPLITS) : 4;
+#define ATT_VL_PLAIN(NSV)                                                                                                        \
+  hipLaunchKernelGGL((attention_kernel<NSV, 0, false, true>), grid, dim3(NSV * 64), 0, s, q, ldq, k, v, ldkv, o, ldo, 0, g_att_head_major, fz)
+    switch (ns) {
+      case 1: ATT_VL_PLAIN(1); break;
+      case 2: ATT_VL_PLAIN(2); break;
+      case 4: ATT_VL_PLAIN(4); break;
+      case 8: ATT_VL_PLAIN(8); break;
+      case 16: ATT_VL_PLAIN(16); break;
+      default: return -1;
+    }
+#undef ATT_VL_PLAIN
+    g_att_variant = ns == 1 ? "s1 vl" : ns == 2 ? "s2 vl" : ns == 4 ? "s4 vl" : ns == 8 ? "s8 vl" : "s16 vl";
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+  }
+  // the fused decoder form: x == nullptr at layer 0 (tgt == 0) -> project x2 alone, as attention_fused_impl does
+  fz.x = x ? x : x2; fz.x2 = x ? x2 : nullptr; fz.wq = wq; fz.bq = bq; fz.qscale = qscale;
+  fz.wo = wo; fz.part = part; fz.rows_total = rows; fz.wt = g_att_part_wt;
+  const int fs = knob(KN_ATTENTION_FUSED_SPLITS);
+  const int ns = fs == 48 ? 8 : fs == 84 ? 4 : fs ? fs : 4;
+#define ATT_VL_FUSED(NSV, QPV)                                                                                                   \
+  hipLaunchKernelGGL((attention_kernel<NSV, QPV, true, true>), grid, dim3(NSV * 64), 0, s, q, ldq, k, v, ldkv, nullptr, 0, 0, g_att_head_major, fz)
+  if (ns == 8) {
+    if (fz.x2) ATT_VL_FUSED(8, 2); else ATT_VL_FUSED(8, 1);
+  } else {
+    if (fz.x2) ATT_VL_FUSED(4, 2); else ATT_VL_FUSED(4, 1);
+  }
+#undef ATT_VL_FUSED
+  g_att_variant = ns == 8 ? "s8 vl" : "s4 vl";
+  return hipGetLastError() == hipSuccess ? 0 : -2;
 }

@@ -283,6 +283,16 @@ int launch_attention_fused(const float* q, int ldq, const float* x, const float*
                            float* part, int nb, int nq, hipStream_t s);
 // the kernel the last of those two calls picked on this thread ("res", "wide3", "wide2", "s<key splits>"): per-launch profile names
 const char* attention_last_variant();
+// varlen decode (api.hip cotr_decode_varlen): the decoder cross-attention forms over a tile table in device memory - entry i =
+// (pair, first row of the pass's packed rows, valid rows, unused) of workgroup tile i; 32-row tiles for launch_attention_varlen (plain
+// form: q given -> o; fused few-rows form: wq / wo given -> part [8][rows][256]), 64-row tiles for launch_att_rows_varlen (Y as
+// launch_att_rows computes it, q projected from x (+ x2))
+int launch_attention_varlen(const float* q, int ldq, const float* x, const float* x2, const float* wq, const float* bq, float qscale,
+                            const float* k, const float* v, int ldkv, float* o, int ldo, const float* wo, float* part, int rows,
+                            const int4* tiles, int ntiles, hipStream_t s);
+int launch_att_rows_varlen(const float* x, const float* x2, const float* wq, const float* bq, float qscale, const float* k,
+                           const float* v, int ldkv, const float* wo, const float* bo, const float* residual, const float* ln_w,
+                           const float* ln_b, float* Y, const int4* tiles, int ntiles, hipStream_t s);
 
 int launch_layernorm(const float* x, const float* w, const float* b, float* y, int rows, hipStream_t s);
 // lin_sine encoding; point (bi, qi) read from pts[((bi*q_total) + qi)*2], written to row bi*nq+qi

@@ -731,11 +731,17 @@ class FasterSparseEngine(SparseEngine):
     same squads, same RNG draws (:339-427) - and therefore the same correspondences.  What is MI355X-specific: all crop
     pairs of a model call are cut, resized (Pillow-exact), laid side by side and normalised by ONE launch of the device
     crop kernel instead of 2 PIL resizes + an H2D copy per pilot, and the forward is the HIP library's batched
-    encode + decode (queries of a squad share their pilot's encode)."""
+    encode + decode (queries of a squad share their pilot's encode).
 
-    def __init__(self, model, batch_size, mode='stretching', max_load=256):
+    ``varlen=True`` (opt-in; the default keeps the reference's padded call): a grouped call packs only the squads' real
+    queries and runs ``model.forward_varlen`` - the padding rows of the other squads are not decoded.  ``decoded_rows``
+    counts the query rows the model decoded, padding included, in either mode."""
+
+    def __init__(self, model, batch_size, mode='stretching', max_load=256, varlen=False):
         super().__init__(model, batch_size, mode)
         self.max_load = int(max_load)
+        self.varlen = bool(varlen)
+        self.decoded_rows = 0
 
     # -- task list --------------------------------------------------------------------------------------------
     def _make_tasks(self, img_a, img_b, zoom_ins, converge_iters, max_corrs, queries_a, force, areas):
@@ -815,9 +821,24 @@ class FasterSparseEngine(SparseEngine):
         buf = torch.empty((len(boxes), 3, 256, 512), dtype=torch.float32, device=device)
         img = cropper(boxes, buf)
         pred = self.model(img, torch.from_numpy(queries).to(device))['pred_corrs']
+        self.decoded_rows += queries.shape[0] * queries.shape[1]
         if count:
             self.total_tasks += len(boxes)                           # only infer_batch counts (:48), infer_batch_grouped not
         return pred.detach().cpu().numpy()
+
+    def _forward_varlen(self, cropper, boxes, queries, counts, device):
+        """A grouped call with only the real queries: queries [P,Qmax,2] zero-padded, counts[k] of squad k real -> float32
+        [P,Qmax,2] with the answers of the real rows (the padding rows stay zero)."""
+        buf = torch.empty((len(boxes), 3, 256, 512), dtype=torch.float32, device=device)
+        img = cropper(boxes, buf)
+        packed = np.concatenate([queries[k, :c] for k, c in enumerate(counts)])
+        pred = self.model.forward_varlen(img, torch.from_numpy(packed).to(device), counts).cpu().numpy()
+        self.decoded_rows += packed.shape[0]
+        out = np.zeros(queries.shape, dtype=np.float32)
+        ends = np.cumsum(counts)
+        for k, c in enumerate(counts):
+            out[k, :c] = pred[ends[k] - c:ends[k]]
+        return out
 
     def cotr_corr_multiscale(self, img_a, img_b, zoom_ins=(1.0,), converge_iters=1, max_corrs=1000, queries_a=None,
                              return_idx=False, force=False, return_tasks_only=False, areas=None):
@@ -837,7 +858,10 @@ class FasterSparseEngine(SparseEngine):
                 squads, boxes, queries = self._form_grouped_batch(zm, tasks)
                 if not squads or num_g >= max_corrs:                 # (a batch formed before the exit test stays submitted,
                     break                                            #  exactly as in the reference)
-                out = self._forward(cropper, boxes, queries, device, count=False)
+                if self.varlen:
+                    out = self._forward_varlen(cropper, boxes, queries, [len(m) for m in squads], device)
+                else:
+                    out = self._forward(cropper, boxes, queries, device, count=False)
                 num_steps = 0
                 for i, members in enumerate(squads):
                     for j, t in enumerate(members):

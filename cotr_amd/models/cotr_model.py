@@ -218,17 +218,25 @@ class COTR(nn.Module):
             self._encoded_batch = 0
         return lib
 
-    def _ensure_workspace(self, lib, device, b, q, keep_encode=False):
+    def _ensure_workspace(self, lib, device, b, q, keep_encode=False, varlen=False):
         """The library's encode cache + scratch come from torch's caching allocator (cotr_set_workspace): a larger batch then
         costs one torch allocation instead of hipFree + hipMalloc (device synchronisations) inside the library.  The
         workspace only grows; a cached encode is carried over into the new one (stream-ordered device copy; the old tensor
-        goes back to torch's pool, which is stream-ordered too)."""
+        goes back to torch's pool, which is stream-ordered too).  varlen: sized for varlen calls of up to b pairs and b * q
+        rows as well (cotr_scratch_bytes_varlen: the decoder scratch plus the tile tables); remembered once asked for."""
         b, q = max(b, self._ws_shape[0]), max(q, self._ws_shape[1])
         stale = self.__dict__.get('_ws_stale', False)      # a knob changed: the library's carving of the workspace is re-done
-        if (b, q) == self._ws_shape and not stale:
+        grow_varlen = varlen and not self.__dict__.get('_ws_varlen', False)
+        if (b, q) == self._ws_shape and not stale and not grow_varlen:
             return
         need = ctypes.c_size_t()
-        _lib.check(lib.cotr_scratch_bytes(self._handle, b, max(q, 1), ctypes.byref(need)), self._handle, 'cotr_scratch_bytes')
+        if varlen or self.__dict__.get('_ws_varlen', False):
+            offsets = (ctypes.c_int * (b + 1))(*[i * max(q, 1) for i in range(b + 1)])
+            _lib.check(lib.cotr_scratch_bytes_varlen(self._handle, offsets, b, ctypes.byref(need)), self._handle,
+                       'cotr_scratch_bytes_varlen')
+            self._ws_varlen = True
+        else:
+            _lib.check(lib.cotr_scratch_bytes(self._handle, b, max(q, 1), ctypes.byref(need)), self._handle, 'cotr_scratch_bytes')
         if self._ws is None or self._ws.numel() < need.value + 256:
             if self._ws is not None and self.__dict__.get('_ws_pins'):
                 raise _lib.CotrHipError(
@@ -337,6 +345,73 @@ class COTR(nn.Module):
                 raise _lib.CotrHipError(f'decode of {b} pairs: the cached encode was dropped by a workspace change')
             _lib.check(lib.cotr_decode(self._handle, qs.data_ptr(), b, q, out.data_ptr(), _lib.current_stream_ptr()),
                        self._handle, 'cotr_decode')
+        return out
+
+    @staticmethod
+    def _varlen_offsets(counts, queries, pairs):
+        """counts (host sequence of `pairs` non-negative ints summing to N, for packed queries [N, 2]) -> ctypes int[pairs + 1]
+        offsets.  Raises ValueError before anything touches a device."""
+        if queries.ndim != 2 or queries.shape[1] != 2:
+            raise ValueError(f'varlen queries are packed [N, 2]; got {tuple(queries.shape)}')
+        if isinstance(counts, torch.Tensor):
+            if counts.is_floating_point() or counts.is_complex():
+                raise ValueError('counts must be integers')
+            counts = counts.tolist()
+        counts = list(counts)
+        if len(counts) != pairs:
+            raise ValueError(f'{len(counts)} counts for {pairs} pairs')
+        offsets = [0]
+        for c in counts:
+            if isinstance(c, bool) or int(c) != c or c < 0:
+                raise ValueError(f'counts must be non-negative integers; got {c!r}')
+            offsets.append(offsets[-1] + int(c))
+        if offsets[-1] != queries.shape[0]:
+            raise ValueError(f'counts sum to {offsets[-1]} but queries hold {queries.shape[0]} rows')
+        if offsets[-1] >= 2 ** 31:
+            raise ValueError(f'{offsets[-1]} query rows: the library indexes rows with int')
+        return (ctypes.c_int * (pairs + 1))(*offsets)
+
+    @torch.no_grad()
+    def forward_varlen(self, samples, queries, counts):
+        """A different number of queries per pair in one call: pair b owns the next counts[b] rows of the packed queries
+        [N, 2] (device); returns the packed pred_corrs [N, 2] in the same order.  counts: host sequence of B non-negative
+        ints summing to N.  Eval mode only.  Each row is what ``model(img[b:b+1], q_b[None])`` gives for it."""
+        self._check_mode()
+        img = self._as_batch(samples)
+        b = img.shape[0]
+        offsets = self._varlen_offsets(counts, queries, b)
+        if img.device != queries.device:
+            raise _lib.CotrHipError(f'samples on {img.device} but queries on {queries.device}')
+        lib = self._ensure_ready(img.device)
+        img = img.contiguous().float()
+        qs = queries.contiguous().float()
+        n = qs.shape[0]
+        out = torch.empty((n, 2), dtype=torch.float32, device=img.device)
+        with torch.cuda.device(img.device):
+            self._ensure_workspace(lib, img.device, b, -(-n // b), varlen=True)
+            _lib.check(lib.cotr_forward_varlen(self._handle, img.data_ptr(), qs.data_ptr(), offsets, b, out.data_ptr(),
+                                               _lib.current_stream_ptr()), self._handle, 'cotr_forward_varlen')
+        self._encoded_batch = b
+        return out
+
+    @torch.no_grad()
+    def decode_varlen(self, queries, counts):
+        """forward_varlen's decode against the last ``encode`` (counts: one per encoded pair)."""
+        self._check_mode()
+        b = self._encoded_batch
+        if b <= 0:
+            raise _lib.CotrHipError('decode_varlen before encode')
+        offsets = self._varlen_offsets(counts, queries, b)
+        lib = self._ensure_ready(queries.device)
+        qs = queries.contiguous().float()
+        n = qs.shape[0]
+        out = torch.empty((n, 2), dtype=torch.float32, device=qs.device)
+        with torch.cuda.device(qs.device):
+            self._ensure_workspace(lib, qs.device, b, -(-n // b), keep_encode=True, varlen=True)
+            if self._encoded_batch != b:
+                raise _lib.CotrHipError(f'decode_varlen of {b} pairs: the cached encode was dropped by a workspace change')
+            _lib.check(lib.cotr_decode_varlen(self._handle, qs.data_ptr(), offsets, b, out.data_ptr(), _lib.current_stream_ptr()),
+                       self._handle, 'cotr_decode_varlen')
         return out
 
     def pin_workspace(self, owner):

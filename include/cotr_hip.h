@@ -120,6 +120,21 @@ int cotr_set_workspace(cotr_handle h, void* ws, size_t bytes, int keep_encode, c
  * pass exactly as a call on those pairs alone would (tests/test_parity_gpu.py). */
 int cotr_batch_chunks(cotr_handle h, int B, int Q, int which, int* sizes, int cap);
 
+/* ---- varlen: a different number of queries per pair in one call ------------------------------
+ * B >= 1 pairs; pair b owns rows offsets[b] .. offsets[b+1] of the packed queries [N][2] and of out [N][2], N = offsets[B].
+ * `offsets` is a HOST array of B + 1 ints: offsets[0] = 0, nondecreasing (a pair may have no rows).  It is read before the call
+ * returns and may be freed or changed right after; calls with different offsets may be enqueued back to back on one stream.
+ * The result of every row is that of a uniform call on its pair (no arithmetic couples two rows).  cotr_decode_varlen decodes
+ * against the cached encode of exactly B pairs (COTR_ERR_STATE otherwise); cotr_forward_varlen is cotr_encode + cotr_decode_varlen.
+ * Malformed offsets, B <= 0, or null queries / out with N > 0: COTR_ERR_ARG, with a message in cotr_last_error.
+ * cotr_scratch_bytes_varlen: what cotr_set_workspace must be given for such a call (it never allocates device memory then).
+ * The tile tables of a call are staged in pinned host memory of the handle (allocated at first use, grow-only) and wait on a
+ * HIP event of the call 4 varlen calls back: a varlen call can NOT be captured in a HIP graph.  Knob side_stream is not used. */
+int cotr_decode_varlen(cotr_handle h, const float* queries, const int* offsets, int B, float* out, cotr_stream stream);
+int cotr_forward_varlen(cotr_handle h, const float* img, const float* queries, const int* offsets, int B, float* out,
+                        cotr_stream stream);
+int cotr_scratch_bytes_varlen(cotr_handle h, const int* offsets, int B, size_t* bytes);
+
 /* ---- test / profiling hooks (not needed by a binding) ------------------------------------ */
 
 /* Keep copies of scratch intermediates for cotr_debug_tap (off by default: costs D2D copies). */
