@@ -36,6 +36,12 @@ _PROTOS = {
                                            ctypes.c_void_p]),
     'cotr_scratch_bytes_varlen': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                                  ctypes.POINTER(ctypes.c_size_t)]),
+    'cotr_encode_pairs': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                         ctypes.c_void_p]),
+    'cotr_forward_pairs': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), c_float_p, ctypes.c_int,
+                                          ctypes.c_int, c_float_p, ctypes.c_void_p]),
+    'cotr_scratch_bytes_pairs': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_size_t)]),
     'cotr_set_workspace': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]),
     'cotr_debug_tap': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_float_p, ctypes.c_size_t,
                                       ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]),

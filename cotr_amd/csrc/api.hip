@@ -884,6 +884,162 @@ int cotr_load_weights(cotr_handle h, const char* const* names, const float* cons
   return COTR_OK;
 }
 
+// The backbone of one encode pass of Bc side-by-side inputs (pairs, or the image slots of a pairs call) at img_c, then input_proj:
+// src [Bc*512, 256] to src_out.  feat_out (cotr_backbone): the output of stage `upto` goes to feat_out from pair b0 on instead, and
+// input_proj does not run
+static int enc_backbone_pass(cotr_ctx* h, const EncBufs& eb, const float* img_c, int Bc, int b0, float* src_out, float* feat_out,
+                             int upto, hipStream_t s) {
+  // ---- backbone -------------------------------------------------------------------------
+  int ci = 0;
+  if (knob(KN_FUSED_STEM) && !h->keep_taps) {  // conv1 + bn1 + relu + maxpool in one launch; the 'stem' tap needs the unfused pair
+    const ConvW& c0 = h->convs[ci++];
+    KCHK(h, launch_stem_pool(img_c, c0.w, 160, c0.scale, c0.bias, eb.b_pool, Bc, s), "stem_pool");
+    prof_mark(h, "stem_pool conv7x7+bn+relu+maxpool", s, 2);
+  } else {
+    { int r = stem(h, h->convs[ci++], img_c, eb.b_stem, Bc, s); if (r) return r; }
+    KCHK(h, launch_maxpool(eb.b_stem, eb.b_pool, Bc, 128, 128, 64, s), "maxpool");
+    prof_mark(h, "maxpool", s, 2);
+  }
+  prof_mark(h, "stem+pool", s);
+  if (int r = tap_save(h, "stem", eb.b_stem, ENC_STEM * Bc, s)) return r;
+  if (int r = tap_save(h, "pool", eb.b_pool, ENC_POOL * Bc, s)) return r;
+  const float* x = eb.b_pool;
+  float* outbuf[2] = {eb.b_x, eb.b_y};
+  int flip = 0, H = 64, W = 64;
+  for (int st = 0; st < 3; ++st) {
+    for (int b = 0; b < kStages[st].blocks; ++b) {
+      const int stride = (b == 0) ? kStages[st].stride : 1;
+      const int Ho = H / stride, Wo = W / stride;
+      const ConvW& c1 = h->convs[ci++];
+      const ConvW& c2 = h->convs[ci++];
+      const ConvW& c3 = h->convs[ci++];
+      float* y = outbuf[flip];
+      flip ^= 1;
+      int r;
+      bool one_launch = st == 0 && Bc <= knob(KN_BOTTLENECK_MAX_PAIRS) && H == 64 && W == 64;
+      if (one_launch) {
+        // the whole bottleneck - conv1, conv2, conv3, (downsample,) FrozenBN, identity, ReLU - in one launch (bottleneck.hip)
+        const ConvW* cd = (b == 0) ? &h->convs[ci++] : nullptr;
+        KCHK(h, launch_bottleneck(x, y, Bc, c1.cin, c1.w, h->l1_fused[b].w2p, h->l1_fused[b].w3p, h->l1_fused[b].wdp, c1.scale,
+                                  c1.bias, c2.scale, c2.bias, c3.scale, c3.bias, cd ? cd->scale : nullptr, cd ? cd->bias : nullptr, s),
+             "bottleneck");
+        if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "bottleneck layer1.%d %d pairs", b, Bc); prof_mark(h, nm, s, 2); }
+        x = y;
+        continue;
+      }
+      const float* idt = x;
+      bool c1_done = false;
+      if (b == 0) {  // downsample branch (1x1, strided)
+        const ConvW& cd = h->convs[ci++];
+        if (st == 0 && cd.stride == 1 && c1.cin == 64 && Bc * H * 2 * W >= knob(KN_EXPAND_MIN_ROWS)) {
+          // many pairs: downsample branch and conv1 read the pooled stem output once, in one launch (expand.hip)
+          KCHK(h, launch_expand(x, Bc * H * 2 * W, cd.w, cd.scale, cd.bias, 0, eb.b_d, cd.cout, c1.w, c1.scale, c1.bias, 1, eb.b_t1, c1.cout, s),
+               "expand");
+          if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "expand ds+conv1 layer1.0 %d pairs", Bc); prof_mark(h, nm, s, 2); }
+          c1_done = true;
+        } else {
+          const int pr = conv_pair(h, cd, c1, x, eb.b_d, eb.b_t1, Bc, H, W, s);
+          if (pr < 0) return pr;
+          c1_done = pr == 1;
+          if (!c1_done && (r = conv(h, cd, x, nullptr, 0, eb.b_d, Bc, H, W, s))) return r;
+        }
+        idt = eb.b_d;
+      }
+      if (!c1_done && (r = conv(h, c1, x, nullptr, 1, eb.b_t1, Bc, H, W, s))) return r;
+      if (st == 0 && H == 64 && W == 64 && Bc >= knob(KN_CONV23_MIN_PAIRS)) {
+        // many pairs: conv2 -> conv3 + identity + ReLU in one launch, t2 never leaves the CU (conv23.hip)
+        KCHK(h, launch_conv23(eb.b_t1, c2.w, c2.scale, c2.bias, c3.w, c3.scale, c3.bias, idt, y, Bc, s), "conv23");
+        if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "conv23 layer1.%d %d pairs", b, Bc); prof_mark(h, nm, s, 2); }
+      } else if (st == 1 && Ho == 32 && Wo == 32 && Bc >= knob(KN_CONV23M_MIN_PAIRS) && conv23m_fill_ok(Bc)) {
+        // many pairs: the same fusion for layer2 (conv23m.hip)
+        KCHK(h, launch_conv23m(eb.b_t1, c2.w, c2.scale, c2.bias, c3.w, c3.scale, c3.bias, idt, y, Bc, stride, s), "conv23m");
+        if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "conv23m layer2.%d %d pairs", b, Bc); prof_mark(h, nm, s, 2); }
+      } else {
+        if ((r = conv(h, c2, eb.b_t1, nullptr, 1, eb.b_t2, Bc, H, W, s))) return r;
+        if ((r = conv(h, c3, eb.b_t2, idt, 1, y, Bc, Ho, Wo, s))) return r;
+      }
+      x = y;
+      H = Ho; W = Wo;
+    }
+    const char* names[3] = {"layer1", "layer2", "layer3"};
+    if (int r = tap_save(h, names[st], x, (size_t)Bc * H * 2 * W * kStages[st].planes * 4, s)) return r;
+    prof_mark(h, names[st], s);
+    if (feat_out && st + 1 == upto) {  // cotr_backbone: [Bc, H, 2W, 4*planes] of this stage, NHWC over the pair
+      const size_t per_pair = (size_t)H * 2 * W * kStages[st].planes * 4;
+      HIPCHK(h, hipMemcpyAsync(feat_out + (size_t)b0 * per_pair, x, (size_t)Bc * per_pair * sizeof(float),
+                               hipMemcpyDeviceToDevice, s));
+      break;
+    }
+  }
+  if (feat_out) return COTR_OK;
+  // ---- input_proj: x is [Bc*512, 1024] --------------------------------------------------
+  const int M = Bc * TOK;
+  int r;
+  if ((r = linear(h, x, nullptr, 0, 1, 0, h->ip_w, h->ip_b, nullptr, 0, 1.f, 0, src_out, M, D, CFEAT, s))) return r;
+  if ((r = tap_save(h, "src", src_out, (size_t)M * D, s))) return r;
+  prof_mark(h, "input_proj", s);
+  return COTR_OK;
+}
+
+// The encoder and the decoder K/V of one encode pass of Bc pairs: src [Bc*512, 256] in eb.t_src -> memory mem_c, K / V kv_c
+static int enc_encoder_pass(cotr_ctx* h, const EncBufs& eb, int Bc, float* mem_c, float* kv_c, hipStream_t s) {
+  const size_t KVLD = h->dec.size() * 2 * D;
+  const int M = Bc * TOK;
+  int r;
+  // ---- encoder (transformer.py:143-159, post-norm) ----------------------------------------
+  const float* xin = eb.t_src;
+  for (size_t li = 0; li < h->enc.size(); ++li) {
+    const EncW& e = h->enc[li];
+    // q|k use src+pos, v uses src; q scaled by 32^-0.5 (transformer.py:147-153)
+    if (M >= knob(KN_POS_TABLE_MIN_ROWS)) {
+      if ((r = linear(h, xin, nullptr, 0, 1, 0, e.in_w, e.in_b, h->tab_qkv + li * TOK * 3 * D, 0, QSCALE, D, eb.t_qkv, M, 3 * D, D, s, 0, TOK)))
+        return r;
+    } else if ((r = linear(h, xin, h->pos, TOK, 3 * D, 2 * D, e.in_w, e.in_b, nullptr, 0, QSCALE, D, eb.t_qkv, M, 3 * D, D, s))) return r;
+    float* y = (li + 1 == h->enc.size()) ? mem_c : (xin == eb.t_alt ? eb.t_pre2 : eb.t_alt);
+    bool fused = att_fused_applies(M);   // (the FFN block decides for itself: ffn_block)
+    if (fused) {
+      // few rows: out_proj inside the attention kernel (8 per-head partial outputs), summed + bias + residual + norm1 by ln_reduce
+      KCHK(h, launch_attention_fused(eb.t_qkv, 3 * D, nullptr, nullptr, nullptr, nullptr, 0.f, eb.t_qkv + D, eb.t_qkv + 2 * D, 3 * D,
+                                     nullptr, 0, e.out_w, eb.t_part, Bc, TOK, s), "attention+out_proj");
+      prof_attention(h, "attention+oproj enc", s);
+      KCHK(h, launch_ln_reduce(eb.t_part, 8, e.out_b, xin, e.n1w, e.n1b, eb.t_x1, M, s), "ln_reduce");
+      prof_mark(h, "ln_reduce heads", s, 2);
+    } else if (att_rows_applies(Bc, TOK)) {
+      // many rows: attention, out_proj, residual and norm1 in one launch (att_rows.hip)
+      KCHK(h, launch_att_rows(eb.t_qkv, 3 * D, nullptr, nullptr, nullptr, nullptr, 0.f, eb.t_qkv + D, eb.t_qkv + 2 * D, 3 * D, e.out_w, e.out_b,
+                              xin, e.n1w, e.n1b, eb.t_x1, Bc, TOK, s), "att_rows");
+      prof_mark(h, "att_rows enc", s, 2);
+    } else {
+      KCHK(h, launch_attention(eb.t_qkv, 3 * D, eb.t_qkv + D, eb.t_qkv + 2 * D, 3 * D, eb.t_ao, D, Bc, TOK, s), "attention");
+      prof_attention(h, "attention enc", s);
+      if ((r = linear(h, eb.t_ao, nullptr, 0, 1, 0, e.out_w, e.out_b, xin, 0, 1.f, 0, eb.t_tmp, M, D, D, s))) return r;
+      if ((r = layernorm(h, eb.t_tmp, e.n1w, e.n1b, eb.t_x1, M, s))) return r;
+    }
+    if ((r = ffn_block(h, eb.t_x1, e.l1w, e.l1b, e.l2w, e.l2b, e.n2w, e.n2b, eb.t_hid, eb.hid_cap, fused ? eb.t_tmp : eb.t_ao, y, M, s)))
+      return r;
+    xin = y;
+  }
+  prof_mark(h, "encoder", s);
+  // ---- decoder K/V of every layer: k = Wk(memory+pos), v = Wv(memory) (transformer.py:192-195)
+  // (the hoisted K/V projection takes the table at any row count: 3072 columns fill the chip with large tiles even at one pair -
+  // 18 -> 14 us there; the encoder in-projections only from knob pos_table_min_rows on)
+  if (h->side_mode & 2) {
+    // cotr_forward with few rows (knob side_stream bit 1): decoder layer 0 needs its own K / V columns only - the other layers'
+    // 5/6 of this product run on the handle's second stream beside decoder layer 0 (decode_chunk waits for them before layer 1)
+    const int n0 = 2 * D, n1 = (int)KVLD - n0;
+    if ((r = linear(h, mem_c, nullptr, 0, 1, 0, h->kv_w, h->kv_b, h->tab_kv, 0, 1.f, 0, kv_c, M, n0, D, s, (int)KVLD, TOK, (int)KVLD))) return r;
+    HIPCHK(h, hipEventRecord(h->ev_mem, s));
+    HIPCHK(h, hipStreamWaitEvent(h->side, h->ev_mem, 0));
+    if ((r = linear(h, mem_c, nullptr, 0, 1, 0, h->kv_w + (size_t)n0 * D, h->kv_b + n0, h->tab_kv + n0, 0, 1.f, 0, kv_c + n0, M, n1, D, h->side,
+                    (int)KVLD, TOK, (int)KVLD))) return r;
+    HIPCHK(h, hipEventRecord(h->ev_kv, h->side));
+  } else if (knob(KN_POS_TABLE_MIN_ROWS) < (1 << 30)) {
+    if ((r = linear(h, mem_c, nullptr, 0, 1, 0, h->kv_w, h->kv_b, h->tab_kv, 0, 1.f, 0, kv_c, M, (int)KVLD, D, s, 0, TOK))) return r;
+  } else if ((r = linear(h, mem_c, h->pos, TOK, 2 * D, D, h->kv_w, h->kv_b, nullptr, 0, 1.f, 0, kv_c, M, (int)KVLD, D, s))) return r;
+  prof_mark(h, "dec_kv", s);
+  return COTR_OK;
+}
+
 // feat_out == nullptr: the whole query-independent half (cotr_encode); otherwise only the backbone, its layer3 output
 // [B,16,32,1024] (NHWC, both halves side by side = 512 token rows per pair) copied to feat_out (cotr_backbone)
 static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream stream, float* feat_out, int upto = 3) {
@@ -912,149 +1068,9 @@ static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream strea
   prof_mark(h, "begin", s);
   for (int b0 = 0, Bc = 0; b0 < B; b0 += Bc) {
     Bc = enc_next_chunk(B - b0, ENC_CHUNK);
-    const float* img_c = img + (size_t)b0 * 3 * 256 * 512;
-    // ---- backbone -------------------------------------------------------------------------
-    int ci = 0;
-    if (knob(KN_FUSED_STEM) && !h->keep_taps) {  // conv1 + bn1 + relu + maxpool in one launch; the 'stem' tap needs the unfused pair
-      const ConvW& c0 = h->convs[ci++];
-      KCHK(h, launch_stem_pool(img_c, c0.w, 160, c0.scale, c0.bias, eb.b_pool, Bc, s), "stem_pool");
-      prof_mark(h, "stem_pool conv7x7+bn+relu+maxpool", s, 2);
-    } else {
-      { int r = stem(h, h->convs[ci++], img_c, eb.b_stem, Bc, s); if (r) return r; }
-      KCHK(h, launch_maxpool(eb.b_stem, eb.b_pool, Bc, 128, 128, 64, s), "maxpool");
-      prof_mark(h, "maxpool", s, 2);
-    }
-    prof_mark(h, "stem+pool", s);
-    if (int r = tap_save(h, "stem", eb.b_stem, ENC_STEM * Bc, s)) return r;
-    if (int r = tap_save(h, "pool", eb.b_pool, ENC_POOL * Bc, s)) return r;
-    const float* x = eb.b_pool;
-    float* outbuf[2] = {eb.b_x, eb.b_y};
-    int flip = 0, H = 64, W = 64;
-    for (int st = 0; st < 3; ++st) {
-      for (int b = 0; b < kStages[st].blocks; ++b) {
-        const int stride = (b == 0) ? kStages[st].stride : 1;
-        const int Ho = H / stride, Wo = W / stride;
-        const ConvW& c1 = h->convs[ci++];
-        const ConvW& c2 = h->convs[ci++];
-        const ConvW& c3 = h->convs[ci++];
-        float* y = outbuf[flip];
-        flip ^= 1;
-        int r;
-        bool one_launch = st == 0 && Bc <= knob(KN_BOTTLENECK_MAX_PAIRS) && H == 64 && W == 64;
-        if (one_launch) {
-          // the whole bottleneck - conv1, conv2, conv3, (downsample,) FrozenBN, identity, ReLU - in one launch (bottleneck.hip)
-          const ConvW* cd = (b == 0) ? &h->convs[ci++] : nullptr;
-          KCHK(h, launch_bottleneck(x, y, Bc, c1.cin, c1.w, h->l1_fused[b].w2p, h->l1_fused[b].w3p, h->l1_fused[b].wdp, c1.scale,
-                                    c1.bias, c2.scale, c2.bias, c3.scale, c3.bias, cd ? cd->scale : nullptr, cd ? cd->bias : nullptr, s),
-               "bottleneck");
-          if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "bottleneck layer1.%d %d pairs", b, Bc); prof_mark(h, nm, s, 2); }
-          x = y;
-          continue;
-        }
-        const float* idt = x;
-        bool c1_done = false;
-        if (b == 0) {  // downsample branch (1x1, strided)
-          const ConvW& cd = h->convs[ci++];
-          if (st == 0 && cd.stride == 1 && c1.cin == 64 && Bc * H * 2 * W >= knob(KN_EXPAND_MIN_ROWS)) {
-            // many pairs: downsample branch and conv1 read the pooled stem output once, in one launch (expand.hip)
-            KCHK(h, launch_expand(x, Bc * H * 2 * W, cd.w, cd.scale, cd.bias, 0, eb.b_d, cd.cout, c1.w, c1.scale, c1.bias, 1, eb.b_t1, c1.cout, s),
-                 "expand");
-            if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "expand ds+conv1 layer1.0 %d pairs", Bc); prof_mark(h, nm, s, 2); }
-            c1_done = true;
-          } else {
-            const int pr = conv_pair(h, cd, c1, x, eb.b_d, eb.b_t1, Bc, H, W, s);
-            if (pr < 0) return pr;
-            c1_done = pr == 1;
-            if (!c1_done && (r = conv(h, cd, x, nullptr, 0, eb.b_d, Bc, H, W, s))) return r;
-          }
-          idt = eb.b_d;
-        }
-        if (!c1_done && (r = conv(h, c1, x, nullptr, 1, eb.b_t1, Bc, H, W, s))) return r;
-        if (st == 0 && H == 64 && W == 64 && Bc >= knob(KN_CONV23_MIN_PAIRS)) {
-          // many pairs: conv2 -> conv3 + identity + ReLU in one launch, t2 never leaves the CU (conv23.hip)
-          KCHK(h, launch_conv23(eb.b_t1, c2.w, c2.scale, c2.bias, c3.w, c3.scale, c3.bias, idt, y, Bc, s), "conv23");
-          if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "conv23 layer1.%d %d pairs", b, Bc); prof_mark(h, nm, s, 2); }
-        } else if (st == 1 && Ho == 32 && Wo == 32 && Bc >= knob(KN_CONV23M_MIN_PAIRS) && conv23m_fill_ok(Bc)) {
-          // many pairs: the same fusion for layer2 (conv23m.hip)
-          KCHK(h, launch_conv23m(eb.b_t1, c2.w, c2.scale, c2.bias, c3.w, c3.scale, c3.bias, idt, y, Bc, stride, s), "conv23m");
-          if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "conv23m layer2.%d %d pairs", b, Bc); prof_mark(h, nm, s, 2); }
-        } else {
-          if ((r = conv(h, c2, eb.b_t1, nullptr, 1, eb.b_t2, Bc, H, W, s))) return r;
-          if ((r = conv(h, c3, eb.b_t2, idt, 1, y, Bc, Ho, Wo, s))) return r;
-        }
-        x = y;
-        H = Ho; W = Wo;
-      }
-      const char* names[3] = {"layer1", "layer2", "layer3"};
-      if (int r = tap_save(h, names[st], x, (size_t)Bc * H * 2 * W * kStages[st].planes * 4, s)) return r;
-      prof_mark(h, names[st], s);
-      if (feat_out && st + 1 == upto) {  // cotr_backbone: [Bc, H, 2W, 4*planes] of this stage, NHWC over the pair
-        const size_t per_pair = (size_t)H * 2 * W * kStages[st].planes * 4;
-        HIPCHK(h, hipMemcpyAsync(feat_out + (size_t)b0 * per_pair, x, (size_t)Bc * per_pair * sizeof(float),
-                                 hipMemcpyDeviceToDevice, s));
-        break;
-      }
-    }
+    if (int r = enc_backbone_pass(h, eb, img + (size_t)b0 * 3 * 256 * 512, Bc, b0, eb.t_src, feat_out, upto, s)) return r;
     if (feat_out) continue;
-    // ---- input_proj: x is [Bc*512, 1024] --------------------------------------------------
-    const int M = Bc * TOK;
-    int r;
-    if ((r = linear(h, x, nullptr, 0, 1, 0, h->ip_w, h->ip_b, nullptr, 0, 1.f, 0, eb.t_src, M, D, CFEAT, s))) return r;
-    if ((r = tap_save(h, "src", eb.t_src, (size_t)M * D, s))) return r;
-    prof_mark(h, "input_proj", s);
-    // ---- encoder (transformer.py:143-159, post-norm) ----------------------------------------
-    float* mem_c = memory + (size_t)b0 * TOK * D;
-    const float* xin = eb.t_src;
-    for (size_t li = 0; li < h->enc.size(); ++li) {
-      const EncW& e = h->enc[li];
-      // q|k use src+pos, v uses src; q scaled by 32^-0.5 (transformer.py:147-153)
-      if (M >= knob(KN_POS_TABLE_MIN_ROWS)) {
-        if ((r = linear(h, xin, nullptr, 0, 1, 0, e.in_w, e.in_b, h->tab_qkv + li * TOK * 3 * D, 0, QSCALE, D, eb.t_qkv, M, 3 * D, D, s, 0, TOK)))
-          return r;
-      } else if ((r = linear(h, xin, h->pos, TOK, 3 * D, 2 * D, e.in_w, e.in_b, nullptr, 0, QSCALE, D, eb.t_qkv, M, 3 * D, D, s))) return r;
-      float* y = (li + 1 == h->enc.size()) ? mem_c : (xin == eb.t_alt ? eb.t_pre2 : eb.t_alt);
-      bool fused = att_fused_applies(M);   // (the FFN block decides for itself: ffn_block)
-      if (fused) {
-        // few rows: out_proj inside the attention kernel (8 per-head partial outputs), summed + bias + residual + norm1 by ln_reduce
-        KCHK(h, launch_attention_fused(eb.t_qkv, 3 * D, nullptr, nullptr, nullptr, nullptr, 0.f, eb.t_qkv + D, eb.t_qkv + 2 * D, 3 * D,
-                                       nullptr, 0, e.out_w, eb.t_part, Bc, TOK, s), "attention+out_proj");
-        prof_attention(h, "attention+oproj enc", s);
-        KCHK(h, launch_ln_reduce(eb.t_part, 8, e.out_b, xin, e.n1w, e.n1b, eb.t_x1, M, s), "ln_reduce");
-        prof_mark(h, "ln_reduce heads", s, 2);
-      } else if (att_rows_applies(Bc, TOK)) {
-        // many rows: attention, out_proj, residual and norm1 in one launch (att_rows.hip)
-        KCHK(h, launch_att_rows(eb.t_qkv, 3 * D, nullptr, nullptr, nullptr, nullptr, 0.f, eb.t_qkv + D, eb.t_qkv + 2 * D, 3 * D, e.out_w, e.out_b,
-                                xin, e.n1w, e.n1b, eb.t_x1, Bc, TOK, s), "att_rows");
-        prof_mark(h, "att_rows enc", s, 2);
-      } else {
-        KCHK(h, launch_attention(eb.t_qkv, 3 * D, eb.t_qkv + D, eb.t_qkv + 2 * D, 3 * D, eb.t_ao, D, Bc, TOK, s), "attention");
-        prof_attention(h, "attention enc", s);
-        if ((r = linear(h, eb.t_ao, nullptr, 0, 1, 0, e.out_w, e.out_b, xin, 0, 1.f, 0, eb.t_tmp, M, D, D, s))) return r;
-        if ((r = layernorm(h, eb.t_tmp, e.n1w, e.n1b, eb.t_x1, M, s))) return r;
-      }
-      if ((r = ffn_block(h, eb.t_x1, e.l1w, e.l1b, e.l2w, e.l2b, e.n2w, e.n2b, eb.t_hid, eb.hid_cap, fused ? eb.t_tmp : eb.t_ao, y, M, s)))
-        return r;
-      xin = y;
-    }
-    prof_mark(h, "encoder", s);
-    // ---- decoder K/V of every layer: k = Wk(memory+pos), v = Wv(memory) (transformer.py:192-195)
-    float* kv_c = kv + (size_t)b0 * TOK * KVLD;
-    // (the hoisted K/V projection takes the table at any row count: 3072 columns fill the chip with large tiles even at one pair -
-    // 18 -> 14 us there; the encoder in-projections only from knob pos_table_min_rows on)
-    if (h->side_mode & 2) {
-      // cotr_forward with few rows (knob side_stream bit 1): decoder layer 0 needs its own K / V columns only - the other layers'
-      // 5/6 of this product run on the handle's second stream beside decoder layer 0 (decode_chunk waits for them before layer 1)
-      const int n0 = 2 * D, n1 = (int)KVLD - n0;
-      if ((r = linear(h, mem_c, nullptr, 0, 1, 0, h->kv_w, h->kv_b, h->tab_kv, 0, 1.f, 0, kv_c, M, n0, D, s, (int)KVLD, TOK, (int)KVLD))) return r;
-      HIPCHK(h, hipEventRecord(h->ev_mem, s));
-      HIPCHK(h, hipStreamWaitEvent(h->side, h->ev_mem, 0));
-      if ((r = linear(h, mem_c, nullptr, 0, 1, 0, h->kv_w + (size_t)n0 * D, h->kv_b + n0, h->tab_kv + n0, 0, 1.f, 0, kv_c + n0, M, n1, D, h->side,
-                      (int)KVLD, TOK, (int)KVLD))) return r;
-      HIPCHK(h, hipEventRecord(h->ev_kv, h->side));
-    } else if (knob(KN_POS_TABLE_MIN_ROWS) < (1 << 30)) {
-      if ((r = linear(h, mem_c, nullptr, 0, 1, 0, h->kv_w, h->kv_b, h->tab_kv, 0, 1.f, 0, kv_c, M, (int)KVLD, D, s, 0, TOK))) return r;
-    } else if ((r = linear(h, mem_c, h->pos, TOK, 2 * D, D, h->kv_w, h->kv_b, nullptr, 0, 1.f, 0, kv_c, M, (int)KVLD, D, s))) return r;
-    prof_mark(h, "dec_kv", s);
+    if (int r = enc_encoder_pass(h, eb, Bc, memory + (size_t)b0 * TOK * D, kv + (size_t)b0 * TOK * KVLD, s)) return r;
   }
   if (feat_out) return COTR_OK;
   h->taps["memory"] = {memory, (size_t)B * TOK * D};
@@ -1262,21 +1278,130 @@ int cotr_batch_chunks(cotr_handle h, int B, int Q, int which, int* sizes, int ca
 }
 
 // bytes of the three arenas a call of that size carves (each rounded up to 256 B): what cotr_set_workspace must be given
-int cotr_scratch_bytes(cotr_handle h, int B, int Q, size_t* bytes) {
-  if (!h || !bytes || B <= 0 || Q < 0) return COTR_ERR_ARG;
+// The decoder term is a bound, not dec_layout: a workspace sized for (B, Q) must serve every (B' <= B, Q' <= Q) - whose decoder passes
+// can have MORE rows than (B, Q)'s own (2 x 16000 rows against 1 x 20000) and, below the fusion thresholds, more scratch per row - and
+// flipping a tuning knob must not make a sized workspace too small: the most rows of any pass, each at the most any threshold asks.
+static size_t dec_bound_floats(const cotr_ctx* h, int B, int Q) {
   const int* kn = h->knobs.v;
-  // The decoder term is a bound, not dec_layout: a workspace sized for (B, Q) must serve every (B' <= B, Q' <= Q) - whose decoder passes
-  // can have MORE rows than (B, Q)'s own (2 x 16000 rows against 1 x 20000) and, below the fusion thresholds, more scratch per row - and
-  // flipping a tuning knob must not make a sized workspace too small: the most rows of any pass, each at the most any threshold asks.
   const size_t R = (size_t)B * Q < (size_t)DEC_ROWS ? (size_t)B * Q : (size_t)DEC_ROWS;
   const size_t thr_a = kn[KN_ATTENTION_FUSION_MAX_ROWS] > 1024 ? kn[KN_ATTENTION_FUSION_MAX_ROWS] : 1024;
   const size_t thr_f = kn[KN_FFN_FUSION_MAX_ROWS] > 1024 ? kn[KN_FFN_FUSION_MAX_ROWS] : 1024;
-  const size_t f_dec = R * (DEC_ACT_ROW + DEC_HID_ROW) + (R < thr_f ? R : thr_f) * (DEC_HID_FUSED_ROW - DEC_HID_ROW) +
-                       (R < thr_a ? R : thr_a) * PART_ROW;
+  return R * (DEC_ACT_ROW + DEC_HID_ROW) + (R < thr_f ? R : thr_f) * (DEC_HID_FUSED_ROW - DEC_HID_ROW) + (R < thr_a ? R : thr_a) * PART_ROW;
+}
+
+// the three arenas [encode cache | encoder scratch | decoder scratch], each from a 256-byte boundary, plus 256 B
+static size_t arenas_bytes(size_t f_cache, size_t f_enc, size_t f_dec) {
   size_t total = 0;
-  for (size_t f : {enc_cache_floats(h, B), enc_layout(enc_chunk_max(B, h->knobs), h->knobs, nullptr, nullptr), f_dec})
-    total = ((total + 255) & ~size_t(255)) + f * sizeof(float);
-  *bytes = total + 256;
+  for (size_t f : {f_cache, f_enc, f_dec}) total = ((total + 255) & ~size_t(255)) + f * sizeof(float);
+  return total + 256;
+}
+
+int cotr_scratch_bytes(cotr_handle h, int B, int Q, size_t* bytes) {
+  if (!h || !bytes || B <= 0 || Q < 0) return COTR_ERR_ARG;
+  *bytes = arenas_bytes(enc_cache_floats(h, B), enc_layout(enc_chunk_max(B, h->knobs), h->knobs, nullptr, nullptr), dec_bound_floats(h, B, Q));
+  return COTR_OK;
+}
+
+// ---- pairs calls: M distinct images [M,3,256,256], B index pairs (cotr_encode_pairs) -----------------------------------------------
+// The backbone runs on each half of a side-by-side input on its own (per-half padding) and input_proj is per token, so an image's src
+// rows do not depend on the image it is paired with.  Two phases:
+//  * images: ceil(M/2) side-by-side SLOTS (images 2i, 2i + 1; an odd M leaves the last right half zero), walked in enc_next_chunk passes:
+//    pack_pairs (pairs.hip) -> enc_backbone_pass, whose input_proj writes the slot's 512 rows into the image region behind the encoder
+//    scratch: [slots*512, 256], image m = half m & 1 of slot m >> 1.
+//  * pairs: B pairs in enc_next_chunk passes: gather_pairs builds the pass's src [Bc*512, 256] (token (y, x) from image
+//    pairs[b][x >= 16], column x mod 16), then enc_encoder_pass as cotr_encode runs it.  The pass's indices go in the launch's kernel
+//    arguments (PairIdx): no host staging, no event - a pairs call can be captured in a HIP graph.
+// With pairs (2i, 2i + 1) the slots and the pairs are cotr_encode's passes on the side-by-side batch: the same launches on the same
+// rows, plus one copy each side - bit for bit the same memory and K / V.  Knob side_stream is not used.
+// floats of the image region
+static size_t pairs_img_floats(int M) { return (size_t)((M - 1) / 2 + 1) * TOK * D; }
+// the encoder scratch serves passes of either phase
+static int pairs_chunk_max(int M, int B, const KnobSet& kn) {
+  const int a = enc_chunk_max((M - 1) / 2 + 1, kn), b = enc_chunk_max(B, kn);
+  return a > b ? a : b;
+}
+
+static int pairs_check(cotr_ctx* h, const float* images, int M, const int* pairs, int B, const char* who) {
+  if (!h->loaded) { h->err = std::string(who) + " before cotr_load_weights"; return COTR_ERR_STATE; }
+  if (!images || !pairs || M <= 0 || B <= 0) { h->err = std::string(who) + ": null images / pairs, M <= 0 or B <= 0"; return COTR_ERR_ARG; }
+  for (int i = 0; i < 2 * B; ++i)
+    if (pairs[i] < 0 || pairs[i] >= M) {
+      char msg[160];
+      snprintf(msg, sizeof msg, "%s: pair %d names image %d, outside [0, %d)", who, i / 2, pairs[i], M);
+      h->err = msg;
+      return COTR_ERR_ARG;
+    }
+  return COTR_OK;
+}
+
+static int encode_pairs_impl(cotr_ctx* h, const float* images, int M, const int* pairs, int B, hipStream_t s) {
+  const size_t KVLD = h->dec.size() * 2 * D;
+  h->enc_B = 0;
+  h->taps.clear();
+  if (int r = ensure(h, h->memkv, enc_cache_floats(h, B))) return r;
+  float* memory = h->memkv.ptr;
+  float* kv = h->memkv.ptr + (size_t)B * TOK * D;
+  const int S = (M - 1) / 2 + 1, ENC_CHUNK = knob(KN_ENCODE_CHUNK), Bc_max = pairs_chunk_max(M, B, h->knobs);
+  const size_t f_enc = enc_layout(Bc_max, h->knobs, nullptr, nullptr);
+  if (int r = ensure(h, h->enc_scr, f_enc + pairs_img_floats(M))) return r;
+  EncBufs eb;
+  enc_layout(Bc_max, h->knobs, h->enc_scr.ptr, &eb);
+  float* img_rows = h->enc_scr.ptr + f_enc;
+
+  if (h->prof) prof_reset(h);
+  prof_mark(h, "begin", s);
+  for (int s0 = 0, Sc = 0; s0 < S; s0 += Sc) {
+    Sc = enc_next_chunk(S - s0, ENC_CHUNK);
+    // the slots' side-by-side input in b_y: 3*256*512 of its ENC_ACT floats per pair, first written by layer1.1 - after the stem read it
+    KCHK(h, launch_pack_pairs(images, M, 2 * s0, Sc, eb.b_y, s), "pack_pairs");
+    prof_mark(h, "pack_pairs", s, 2);
+    if (int r = enc_backbone_pass(h, eb, eb.b_y, Sc, s0, img_rows + (size_t)s0 * TOK * D, nullptr, 3, s)) return r;
+  }
+  for (int b0 = 0, Bc = 0; b0 < B; b0 += Bc) {
+    Bc = enc_next_chunk(B - b0, ENC_CHUNK);
+    PairIdx idx = {};
+    for (int i = 0; i < Bc; ++i) {
+      idx.left[i] = pairs[2 * (b0 + i)];
+      idx.right[i] = pairs[2 * (b0 + i) + 1];
+    }
+    KCHK(h, launch_gather_pairs(img_rows, idx, Bc, eb.t_src, s), "gather_pairs");
+    prof_mark(h, "gather_pairs", s);
+    if (int r = tap_save(h, "src", eb.t_src, (size_t)Bc * TOK * D, s)) return r;
+    if (int r = enc_encoder_pass(h, eb, Bc, memory + (size_t)b0 * TOK * D, kv + (size_t)b0 * TOK * KVLD, s)) return r;
+  }
+  h->taps["memory"] = {memory, (size_t)B * TOK * D};
+  h->taps["kv"] = {kv, (size_t)B * TOK * KVLD};
+  h->taps["pos"] = {h->pos, (size_t)TOK * D};
+  h->enc_B = B;
+  return COTR_OK;
+}
+
+int cotr_encode_pairs(cotr_handle h, const float* images, int M, const int* pairs, int B, cotr_stream stream) {
+  if (!h) return COTR_ERR_ARG;
+  if (int r = pairs_check(h, images, M, pairs, B, "cotr_encode_pairs")) return r;
+  DEVICE_SCOPE(h);
+  return encode_pairs_impl(h, images, M, pairs, B, static_cast<hipStream_t>(stream));
+}
+
+int cotr_forward_pairs(cotr_handle h, const float* images, int M, const int* pairs, const float* queries, int B, int Q, float* out,
+                       cotr_stream stream) {
+  if (!h) return COTR_ERR_ARG;
+  if (int r = decode_check(h, queries, B, Q, out)) return r;
+  if (int r = pairs_check(h, images, M, pairs, B, "cotr_forward_pairs")) return r;
+  DEVICE_SCOPE(h);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  int r = encode_pairs_impl(h, images, M, pairs, B, s);
+  if (r || Q == 0) return r;
+  DecPlan d;
+  if ((r = dec_plan(h, B, Q, d))) return r;
+  return decode_impl(h, queries, B, Q, out, s, d);
+}
+
+// cotr_scratch_bytes with the encoder scratch of either phase plus the image region
+int cotr_scratch_bytes_pairs(cotr_handle h, int M, int B, int Q, size_t* bytes) {
+  if (!h || !bytes || M <= 0 || B <= 0 || Q < 0) return COTR_ERR_ARG;
+  *bytes = arenas_bytes(enc_cache_floats(h, B), enc_layout(pairs_chunk_max(M, B, h->knobs), h->knobs, nullptr, nullptr) + pairs_img_floats(M),
+                        dec_bound_floats(h, B, Q));
   return COTR_OK;
 }
 

@@ -303,6 +303,16 @@ int launch_maxpool(const float* x, float* y, int B, int Hin, int Win, int C, hip
 int launch_head2(const float* x, const float* w, const float* b, float* y, int nb, int nq, int q_total,
                  hipStream_t s);
 
+// pairs calls (pairs.hip, api.hip cotr_encode_pairs): the (left, right) image of each pair of one encode pass, passed BY VALUE in the
+// kernel arguments - sized for the largest settable encode pass (ENC_CHUNK_MAX in api.hip, 1 KB)
+constexpr int PAIR_IDX_MAX = 128;
+struct PairIdx { int left[PAIR_IDX_MAX], right[PAIR_IDX_MAX]; };
+// images [M,3,256,256] NCHW: images m0 + 2i, m0 + 2i + 1 -> side-by-side slot i of out [slots,3,256,512] (a missing right image: zeros)
+int launch_pack_pairs(const float* images, int M, int m0, int slots, float* out, hipStream_t s);
+// out [nb*512, 256]: token (y, x) of pair b = token (y, x mod 16) of image (x < 16 ? left[b] : right[b]) of the slot-major
+// image rows src [ceil(M/2)*512, 256] (image m = half m & 1 of slot m >> 1); indices are checked by the caller
+int launch_gather_pairs(const float* src, const PairIdx& idx, int nb, float* out, hipStream_t s);
+
 // conv1 7x7/2 + FrozenBN + ReLU + maxpool 3x3/2 in one launch (stem_pool.hip): img NCHW [B,3,256,512] -> [B,64,128,64]
 int launch_stem_pool(const float* img, const float* w, int wk, const float* scale, const float* bias, float* out, int B,
                      hipStream_t s);

@@ -14,6 +14,7 @@ tensors, or without the built library, raises.
 """
 import ctypes
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -218,16 +219,19 @@ class COTR(nn.Module):
             self._encoded_batch = 0
         return lib
 
-    def _ensure_workspace(self, lib, device, b, q, keep_encode=False, varlen=False):
+    def _ensure_workspace(self, lib, device, b, q, keep_encode=False, varlen=False, images=0):
         """The library's encode cache + scratch come from torch's caching allocator (cotr_set_workspace): a larger batch then
         costs one torch allocation instead of hipFree + hipMalloc (device synchronisations) inside the library.  The
         workspace only grows; a cached encode is carried over into the new one (stream-ordered device copy; the old tensor
         goes back to torch's pool, which is stream-ordered too).  varlen: sized for varlen calls of up to b pairs and b * q
-        rows as well (cotr_scratch_bytes_varlen: the decoder scratch plus the tile tables); remembered once asked for."""
+        rows as well (cotr_scratch_bytes_varlen: the decoder scratch plus the tile tables); remembered once asked for.  images: sized
+        for pairs calls of up to that many distinct images as well (cotr_scratch_bytes_pairs); the largest count asked for is kept."""
         b, q = max(b, self._ws_shape[0]), max(q, self._ws_shape[1])
         stale = self.__dict__.get('_ws_stale', False)      # a knob changed: the library's carving of the workspace is re-done
         grow_varlen = varlen and not self.__dict__.get('_ws_varlen', False)
-        if (b, q) == self._ws_shape and not stale and not grow_varlen:
+        m = max(images, self.__dict__.get('_ws_images', 0))
+        grow_pairs = m > self.__dict__.get('_ws_images', 0)
+        if (b, q) == self._ws_shape and not stale and not grow_varlen and not grow_pairs:
             return
         need = ctypes.c_size_t()
         if varlen or self.__dict__.get('_ws_varlen', False):
@@ -237,6 +241,12 @@ class COTR(nn.Module):
             self._ws_varlen = True
         else:
             _lib.check(lib.cotr_scratch_bytes(self._handle, b, max(q, 1), ctypes.byref(need)), self._handle, 'cotr_scratch_bytes')
+        if m:
+            need_p = ctypes.c_size_t()
+            _lib.check(lib.cotr_scratch_bytes_pairs(self._handle, m, b, max(q, 1), ctypes.byref(need_p)), self._handle,
+                       'cotr_scratch_bytes_pairs')
+            need.value = max(need.value, need_p.value)
+            self._ws_images = m
         if self._ws is None or self._ws.numel() < need.value + 256:
             if self._ws is not None and self.__dict__.get('_ws_pins'):
                 raise _lib.CotrHipError(
@@ -413,6 +423,74 @@ class COTR(nn.Module):
             _lib.check(lib.cotr_decode_varlen(self._handle, qs.data_ptr(), offsets, b, out.data_ptr(), _lib.current_stream_ptr()),
                        self._handle, 'cotr_decode_varlen')
         return out
+
+    @staticmethod
+    def _pairs_args(images, pairs):
+        """images [M, 3, 256, 256], pairs (host sequence of B (left, right) image indices, or an int tensor [B, 2]) -> (M, B, ctypes
+        int[2B]).  Raises ValueError before anything touches a device.  A CUDA `pairs` tensor is copied to the host first: that copy
+        waits for the work queued on its stream."""
+        if not isinstance(images, torch.Tensor) or images.ndim != 4 or tuple(images.shape[1:]) != (3, MAX_SIZE, MAX_SIZE):
+            raise ValueError(f'images must be [M, 3, {MAX_SIZE}, {MAX_SIZE}]; got {tuple(getattr(images, "shape", ()))}')
+        m = images.shape[0]
+        if m < 1:
+            raise ValueError('images holds no image')
+        if isinstance(pairs, torch.Tensor):
+            if pairs.is_floating_point() or pairs.is_complex() or pairs.dtype == torch.bool:
+                raise ValueError(f'pairs must be integers; got {pairs.dtype}')
+            pairs = pairs.detach().cpu().tolist()
+        try:
+            rows = [list(p) for p in pairs]
+        except TypeError:
+            raise ValueError('pairs must be a sequence of (left, right) image indices') from None
+        if not rows:
+            raise ValueError('pairs holds no pair')
+        flat = []
+        for i, p in enumerate(rows):
+            if len(p) != 2:
+                raise ValueError(f'pair {i} has {len(p)} entries, not 2 (left, right)')
+            for v in p:
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < m:
+                    raise ValueError(f'pair {i}: {v!r} is not an image index in [0, {m})')
+                flat.append(int(v))
+        return m, len(rows), (ctypes.c_int * len(flat))(*flat)
+
+    @torch.no_grad()
+    def encode_pairs(self, images, pairs):
+        """encode() for B pairs drawn from M distinct images [M, 3, 256, 256] (each one half of a side-by-side input, normalised as
+        for encode): pair b is (images[pairs[b][0]] | images[pairs[b][1]]).  Each image's backbone runs once.  Eval mode only;
+        follow with decode(q) [B, Q, 2] or decode_varlen(q, counts).  Returns self."""
+        self._check_mode()
+        m, b, idx = self._pairs_args(images, pairs)
+        lib = self._ensure_ready(images.device)
+        imgs = images.contiguous().float()
+        with torch.cuda.device(imgs.device):
+            self._ensure_workspace(lib, imgs.device, b, self._ws_shape[1], images=m)
+            _lib.check(lib.cotr_encode_pairs(self._handle, imgs.data_ptr(), m, idx, b, _lib.current_stream_ptr()),
+                       self._handle, 'cotr_encode_pairs')
+        self._encoded_batch = b
+        return self
+
+    @torch.no_grad()
+    def forward_pairs(self, images, pairs, queries):
+        """forward() for B pairs drawn from M distinct images (see encode_pairs): queries [B, Q, 2] -> {'pred_corrs': [B, Q, 2]}, pair
+        b's rows as ``model(torch.cat([images[l], images[r]], -1)[None], queries[b:b+1])`` gives them."""
+        self._check_mode()
+        m, b, idx = self._pairs_args(images, pairs)
+        if queries.ndim != 3 or queries.shape[0] != b or queries.shape[2] != 2:
+            raise ValueError(f'queries must be [{b}, Q, 2] for {b} pairs; got {tuple(queries.shape)}')
+        if images.device != queries.device:
+            raise _lib.CotrHipError(f'images on {images.device} but queries on {queries.device}')
+        lib = self._ensure_ready(images.device)
+        imgs = images.contiguous().float()
+        qs = queries.contiguous().float()
+        q = qs.shape[1]
+        out = torch.empty((b, q, 2), dtype=torch.float32, device=imgs.device)
+        with torch.cuda.device(imgs.device):
+            self._ensure_workspace(lib, imgs.device, b, q, images=m)
+            _lib.check(lib.cotr_forward_pairs(self._handle, imgs.data_ptr(), m, idx, qs.data_ptr(), b, q, out.data_ptr(),
+                                              _lib.current_stream_ptr()), self._handle, 'cotr_forward_pairs')
+        self._encoded_batch = b
+        return {'pred_corrs': out}
 
     def pin_workspace(self, owner):
         """A captured HIP graph (training.GraphedTrainStep) holds the workspace's addresses: until unpin_workspace(owner) the

@@ -135,6 +135,22 @@ int cotr_forward_varlen(cotr_handle h, const float* img, const float* queries, c
                         cotr_stream stream);
 int cotr_scratch_bytes_varlen(cotr_handle h, const int* offsets, int B, size_t* bytes);
 
+/* ---- pairs: B pairs drawn from M distinct images, each image's backbone run once ----------------
+ * images: device [M,3,256,256] fp32 NCHW, normalised as the reference does (one half of a side-by-side input).
+ * pairs:  HOST int32 [B][2], (left image, right image) of pair b; read before the call returns; repeats, self-pairs (a, a) and
+ *         unused images are allowed.
+ * Each image's backbone and input_proj run once; each pair's encoder input is then assembled from its two images and the encoder
+ * and decoder K/V run per pair.  Afterwards the encode cache holds B pairs: cotr_decode / cotr_decode_varlen follow as after
+ * cotr_encode.  cotr_forward_pairs is cotr_encode_pairs + cotr_decode (queries, out [B,Q,2]).  Pair b's result is that of
+ * cotr_forward on the side-by-side input [images[pairs[b][0]] | images[pairs[b][1]]].  An index outside [0, M), M <= 0, B <= 0
+ * or a null pointer: COTR_ERR_ARG with a message in cotr_last_error, nothing enqueued.  cotr_scratch_bytes_pairs: what
+ * cotr_set_workspace must be given for such a call.  The indices travel in kernel arguments: a pairs call has no host wait and
+ * can be captured in a HIP graph.  Knob side_stream is not used. */
+int cotr_encode_pairs(cotr_handle h, const float* images, int M, const int* pairs, int B, cotr_stream stream);
+int cotr_forward_pairs(cotr_handle h, const float* images, int M, const int* pairs, const float* queries, int B, int Q, float* out,
+                       cotr_stream stream);
+int cotr_scratch_bytes_pairs(cotr_handle h, int M, int B, int Q, size_t* bytes);
+
 /* ---- test / profiling hooks (not needed by a binding) ------------------------------------ */
 
 /* Keep copies of scratch intermediates for cotr_debug_tap (off by default: costs D2D copies). */
