@@ -118,6 +118,10 @@ _PROTOS = {
                                         c_float_p, c_float_p, ctypes.c_void_p]),
     'cotr_resize_f32': (ctypes.c_int, [c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_void_p]),
+    'cotr_raster_mesh_scratch_bytes': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'cotr_raster_mesh': (ctypes.c_int, [c_float_p, ctypes.c_int, c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'cotr_raster_last_error': (ctypes.c_char_p, []),
     'cotr_gemm_num_configs': (ctypes.c_int, []),
     'cotr_op_conv_dual_cfg': (ctypes.c_int, [c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, c_float_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, c_float_p, c_float_p, c_float_p, ctypes.c_int, c_float_p,

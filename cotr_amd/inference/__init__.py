@@ -4,7 +4,9 @@ The reference's own engines (``COTR/inference/sparse_engine.py``) keep working u
 ``cotr_amd.models.build_model`` (same call contract).  ``ZoomEngine`` is the MI355X-native way to run the
 same recursive zoom-in: it stays host-side Python as the reference's is, but every zoom level is ONE
 device-side crop+resize launch and one batched encode/decode instead of one PIL resize, one H2D copy and
-one backbone pass per query per level."""
+one backbone pass per query per level.  ``triangulate_corr`` densifies the sparse correspondences they return (one
+rasterisation launch sequence on the device)."""
+from .triangulate import triangulate_corr
 from .zoom_engine import FasterSparseEngine, RefineResult, SparseEngine, ZoomEngine, patch_boxes
 
-__all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'RefineResult']
+__all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'RefineResult', 'triangulate_corr']

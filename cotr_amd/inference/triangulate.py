@@ -1,0 +1,78 @@
+"""``triangulate_corr`` (COTR/inference/inference_helper.py:293-308): sparse correspondences -> a dense per-pixel map of A.
+
+The reference triangulates the correspondences' A points (normalised by A's size) with scipy's Delaunay and renders the
+triangles with vispy/OpenGL, B's normalised coordinates as vertex colours, into a float framebuffer of A's size.  Here the
+triangulation stays on the host (scipy, imported when called) and the rasterisation is one ``cotr_raster_mesh`` call on
+the current device (cotr_amd/csrc/triangulate.hip; semantics and tie rule in DESIGN.md 3g).  No CPU fallback."""
+import ctypes
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+
+def _check(rc, what):
+    if rc != 0:
+        msg = _lib.load_library().cotr_raster_last_error()
+        raise _lib.CotrHipError(f'{what} failed (code {rc}): {msg.decode() if msg else "?"}')
+
+
+def raster_mesh(verts, attrs, tris, H, W, device=None):
+    """Rasterise the triangles ``tris`` [T,3] over ``verts`` [N,2] (normalised A points) carrying ``attrs`` [N,2] into an
+    H x W canvas on ``device`` (default: the current one), on the current stream.  Returns (out float32 [H,W,2],
+    mask bool [H,W]) device tensors."""
+    lib = _lib.load_library()
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    verts = torch.as_tensor(verts, dtype=torch.float32).to(device).contiguous()
+    attrs = torch.as_tensor(attrs, dtype=torch.float32).to(device).contiguous()
+    tris = torch.as_tensor(np.asarray(tris, dtype=np.int32) if not torch.is_tensor(tris) else tris,
+                           dtype=torch.int32).to(device).contiguous()
+    n_tris = tris.numel() // 3
+    nbytes = ctypes.c_size_t()
+    _check(lib.cotr_raster_mesh_scratch_bytes(n_tris, H, W, ctypes.byref(nbytes)), 'cotr_raster_mesh_scratch_bytes')
+    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    out = torch.empty((H, W, 2), dtype=torch.float32, device=device)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _check(lib.cotr_raster_mesh(ctypes.c_void_p(verts.data_ptr()), verts.shape[0], ctypes.c_void_p(attrs.data_ptr()),
+                                    ctypes.c_void_p(tris.data_ptr()), n_tris, H, W, ctypes.c_void_p(out.data_ptr()),
+                                    ctypes.c_void_p(mask.data_ptr()), ctypes.c_void_p(scratch.data_ptr()), nbytes.value,
+                                    _lib.current_stream_ptr()), 'cotr_raster_mesh')
+    return out, mask.bool()
+
+
+def triangulate_corr(corr, from_shape, to_shape, simplices=None, return_mask=False, as_tensor=False):
+    """``corr`` [N,4] = (x_a, y_a, x_b, y_b) px -> float64 [H_a, W_a, 2]: at every pixel centre of A, B's position by linear
+    interpolation over the Delaunay triangle of the normalised A points that covers it, 0 outside their hull (the
+    reference's return value).  ``from_shape`` / ``to_shape``: A's and B's image shapes (H, W, ...).
+
+    simplices: triangles [T,3] of indices into ``corr`` to use instead of scipy's Delaunay.
+    return_mask: also return the bool [H_a, W_a] coverage mask.
+    as_tensor: return device tensors (float64 map, bool mask) instead of numpy arrays: no copy back to the host."""
+    corr = np.array(corr, dtype=np.float64)
+    if corr.ndim != 2 or corr.shape[1] != 4:
+        raise ValueError(f'corr must be [N, 4] (x_a, y_a, x_b, y_b), got shape {corr.shape}')
+    to_shape, from_shape = tuple(to_shape[:2]), tuple(from_shape[:2])
+    corr = corr / np.concatenate([from_shape[::-1], to_shape[::-1]])
+    if simplices is None:
+        try:
+            from scipy.spatial import Delaunay
+        except ImportError as e:
+            raise ImportError('triangulate_corr needs scipy (scipy.spatial.Delaunay) to triangulate the correspondences; '
+                              'install scipy or pass simplices=') from e
+        simplices = Delaunay(corr[:, :2]).simplices
+    else:
+        simplices = np.asarray(simplices)
+        if simplices.ndim != 2 or simplices.shape[1] != 3 or not np.issubdtype(simplices.dtype, np.integer):
+            raise ValueError(f'simplices must be an integer array [T, 3], got {simplices.dtype} {simplices.shape}')
+        if simplices.size and (simplices.min() < 0 or simplices.max() >= len(corr)):
+            raise ValueError(f'simplices index outside [0, {len(corr)})')
+    out, mask = raster_mesh(corr[:, :2].astype(np.float32), corr[:, 2:].astype(np.float32), simplices.astype(np.int32),
+                            int(from_shape[0]), int(from_shape[1]))
+    scale = np.array(to_shape[::-1])
+    if as_tensor:
+        render = out.double() * torch.as_tensor(scale, dtype=torch.float64, device=out.device)
+        return (render, mask) if return_mask else render
+    render = out.cpu().numpy() * scale          # float32 * int64 -> float64 [H_a, W_a, 2]
+    return (render, mask.cpu().numpy()) if return_mask else render

@@ -392,6 +392,27 @@ int cotr_dense_merge(const float* maps, const int32_t* boxes, int n_pairs, int s
  * of the squared images back to the image shape (sparse_engine.py:124-129). */
 int cotr_resize_f32(const float* src, int Hs, int Ws, int C, float* dst, int Hd, int Wd, cotr_stream stream);
 
+/* ---- triangulate_corr: rasterise a triangle mesh into a dense map (cotr_amd/csrc/triangulate.hip) --------------------
+ * Replaces the vispy/OpenGL render of COTR/inference/inference_helper.py:293-308 (the Delaunay triangles of the
+ * correspondences drawn into an H x W float framebuffer, B's normalised coordinates as vertex colours).
+ *
+ * cotr_raster_mesh: verts [n_verts,2] normalised A points (u, v), attrs [n_verts,2] float values, tris [n_tris,3] int32
+ *   vertex indices, all DEVICE pointers -> out [H,W,2] (DEVICE, 8-byte aligned) = at the centre (j + 0.5, i + 0.5) px of
+ *   pixel (i, j) the barycentric interpolation of attrs over the covering triangle, 0 where no triangle covers it;
+ *   mask [H,W] (DEVICE, may be NULL) = 1 where covered.  Vertices are snapped to 1/256 px (X = rint(u*W*256),
+ *   Y = rint(v*H*256)); coverage uses exact int64 edge functions with a tie rule that covers every sample of a proper
+ *   triangulation exactly once; where triangles overlap the highest index wins (bit-identical from run to run).
+ *   A triangle with an index outside [0, n_verts), a non-finite vertex, a snapped coordinate of magnitude >= 2^30
+ *   (2^22 px) or zero snapped area is skipped.  1 <= H, W <= 16384; n_tris == 0 writes zeros.
+ *   scratch: DEVICE, 16-byte aligned, at least cotr_raster_mesh_scratch_bytes(n_tris, H, W) bytes.  Stream-ordered,
+ *   no host waits, capturable.
+ * Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error() (these
+ * calls have no handle; the message is per thread). */
+int cotr_raster_mesh_scratch_bytes(int n_tris, int H, int W, size_t* bytes);
+int cotr_raster_mesh(const float* verts, int n_verts, const float* attrs, const int32_t* tris, int n_tris, int H, int W,
+                     float* out, uint8_t* mask, void* scratch, size_t scratch_bytes, cotr_stream stream);
+const char* cotr_raster_last_error(void);
+
 /* ---- tuning knobs -------------------------------------------------------------------------------------------
  * Named integer switches that choose between launch schedules / kernel variants with the SAME results (bit-identical unless a
  * knob's line says otherwise).  They are not part of the drop-in boundary: a binding never needs them.  ONE SET PER HANDLE:
