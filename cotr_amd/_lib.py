@@ -122,6 +122,12 @@ _PROTOS = {
     'cotr_raster_mesh': (ctypes.c_int, [c_float_p, ctypes.c_int, c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'cotr_raster_last_error': (ctypes.c_char_p, []),
+    'cotr_nearest_mutual_scratch_bytes': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'cotr_nearest_mutual': (ctypes.c_int, [c_float_p] * 4 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_size_t,
+                                                                                                               ctypes.c_void_p]),
+    'cotr_ransac_fundamental_scratch_bytes': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'cotr_ransac_fundamental': (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                               ctypes.c_uint64] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]),
     'cotr_gemm_num_configs': (ctypes.c_int, []),
     'cotr_op_conv_dual_cfg': (ctypes.c_int, [c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, c_float_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, c_float_p, c_float_p, c_float_p, ctypes.c_int, c_float_p,

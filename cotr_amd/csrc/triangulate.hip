@@ -237,13 +237,19 @@ __global__ __launch_bounds__(256) void tri_resolve_kernel(const TriRec* __restri
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 namespace {
+thread_local char g_raster_error[256];   // the message of the last failed handle-less call on this thread (raster and guided.hip)
+}  // namespace
 
-thread_local char g_raster_error[256];
-
-int raster_fail(int code, const char* msg) {
+namespace cotr_detail {
+int handleless_fail(int code, const char* msg) {
   snprintf(g_raster_error, sizeof g_raster_error, "%s", msg);
   return code;
 }
+}  // namespace cotr_detail
+
+namespace {
+
+int raster_fail(int code, const char* msg) { return cotr_detail::handleless_fail(code, msg); }
 
 size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
 

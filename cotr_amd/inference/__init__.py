@@ -5,8 +5,12 @@ The reference's own engines (``COTR/inference/sparse_engine.py``) keep working u
 same recursive zoom-in: it stays host-side Python as the reference's is, but every zoom level is ONE
 device-side crop+resize launch and one batched encode/decode instead of one PIL resize, one H2D copy and
 one backbone pass per query per level.  ``triangulate_corr`` densifies the sparse correspondences they return (one
-rasterisation launch sequence on the device)."""
+rasterisation launch sequence on the device).  ``mutual_matches``, ``find_fundamental_mat`` and ``filter_guided_matches``
+are the guided-matching post-processing of demo_guided_matching.py (nearest keypoints, mutual check, F-matrix RANSAC) as
+device calls; ``ZoomEngine.guided_match`` runs the whole demo."""
+from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .triangulate import triangulate_corr
 from .zoom_engine import FasterSparseEngine, RefineResult, SparseEngine, ZoomEngine, patch_boxes
 
-__all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'RefineResult', 'triangulate_corr']
+__all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'RefineResult', 'triangulate_corr',
+           'mutual_matches', 'find_fundamental_mat', 'filter_guided_matches']

@@ -663,6 +663,19 @@ class ZoomEngine:
             idx = np.array([None if i < 0 else int(i) for i in idx], dtype=object)
         return (corrs, idx) if return_idx else corrs
 
+    def guided_match(self, img_a, img_b, kp_a, kp_b, zoom_ins=np.linspace(0.5, 0.0625, 4), converge_iters=1, **filter_kw):
+        """demo_guided_matching.py:44-65 on this engine: ``cotr_corr_multiscale`` from every keypoint of A into B and from
+        every keypoint of B into A (max_corrs = number of keypoints, force=True), then ``filter_guided_matches``: the mutual
+        nearest keypoints that the fundamental-matrix RANSAC keeps, rows (x_a, y_a, x_b, y_b).  ``filter_kw``:
+        ransac_threshold (5), confidence (0.999999), seed (0)."""
+        from .guided import filter_guided_matches
+        kp_a, kp_b = np.asarray(kp_a), np.asarray(kp_b)
+        corrs_a_b = self.cotr_corr_multiscale(img_a, img_b, zoom_ins, converge_iters, max_corrs=kp_a.shape[0], queries_a=kp_a,
+                                              force=True)
+        corrs_b_a = self.cotr_corr_multiscale(img_b, img_a, zoom_ins, converge_iters, max_corrs=kp_b.shape[0], queries_a=kp_b,
+                                              force=True)
+        return filter_guided_matches(corrs_a_b, corrs_b_a, kp_a, kp_b, **filter_kw)
+
     @staticmethod
     def _task_objects(shape_a, shape_b, loc_from, loc_to, ident, area_a, area_b, zoom_ins, converge_iters, results, executed,
                       with_ident):

@@ -413,6 +413,38 @@ int cotr_raster_mesh(const float* verts, int n_verts, const float* attrs, const 
                      float* out, uint8_t* mask, void* scratch, size_t scratch_bytes, cotr_stream stream);
 const char* cotr_raster_last_error(void);
 
+/* ---- guided matching: nearest / mutual keypoints and fundamental-matrix RANSAC (cotr_amd/csrc/guided.hip) --------------
+ * The host post-processing of demo_guided_matching.py:48-63 (scipy distance matrices + argmin, the mutual double loop,
+ * cv2.findFundamentalMat(FM_RANSAC)) on the device.  Rules in DESIGN.md 3h.
+ *
+ * cotr_nearest_mutual: pred_ab [na,2], kp_b [nb,2], pred_ba [nb,2], kp_a [na,2], float64 DEVICE pointers (callers widen
+ *   float32 keypoints exactly) -> idx_ab [na] int32 = argmin_j d(pred_ab[i], kp_b[j]), idx_ba [nb] int32 likewise, and
+ *   mutual [na] uint8 = 1 iff idx_ba[idx_ab[i]] == i.  d = sqrt(dx*dx + dy*dy) with dx = k.x - p.x, dy = k.y - p.y in
+ *   float64, no contraction, correctly rounded sqrt (bit-equal to scipy.spatial.distance_matrix); the lowest j wins ties
+ *   and a NaN distance counts as the minimum (numpy's argmin).  1 <= na, nb <= 2^24.
+ *   scratch: DEVICE, 16-byte aligned, at least cotr_nearest_mutual_scratch_bytes(na, nb) bytes.
+ * cotr_ransac_fundamental: pts1 [n,2], pts2 [n,2] float64 DEVICE pointers (rounded to float32 first) -> F_out [9]
+ *   (float64, row-major, p2^T F p1 = 0), mask_out [n] uint8 inliers of F_out, info_out [4] int32 = {found, best inlier
+ *   count, sequential iterations run, chosen hypothesis slot (-1: none)}; F_out = 0 and mask_out = 0 when nothing is
+ *   found.  Iteration it draws 7 distinct indices from splitmix64 counters of (seed, it, draw), solves the 7-point
+ *   problem (up to 3 candidates, slots 3*it + k) and the candidates are counted in parallel; the sequential FM_RANSAC
+ *   loop (adaptive iteration count with confidence) is then replayed on the counts.  An inlier has
+ *   float(max(e1, e2)) <= float(threshold^2), e1 / e2 the squared distances to the epipolar lines.  15 <= n <= 2^24,
+ *   1 <= max_iters <= 65536, threshold > 0 finite, 0 < confidence < 1.
+ *   hyp_F [3*max_iters][9] float64, hyp_count [3*max_iters] int32 (-1: no candidate in the slot; its F is NaN),
+ *   hyp_samples [max_iters][7] int32 (-1 past the indices drawn): optional DEVICE outputs (NULL: not written).
+ *   scratch: DEVICE, 16-byte aligned, at least cotr_ransac_fundamental_scratch_bytes(n, max_iters) bytes.
+ * Both calls are stream-ordered, with no host waits and no allocation (capturable).  Bad arguments are checked before
+ * any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error() (the per-thread message slot of every
+ * handle-less call). */
+int cotr_nearest_mutual_scratch_bytes(int na, int nb, size_t* bytes);
+int cotr_nearest_mutual(const double* pred_ab, const double* kp_b, const double* pred_ba, const double* kp_a, int na, int nb,
+                        int32_t* idx_ab, int32_t* idx_ba, uint8_t* mutual, void* scratch, size_t scratch_bytes, cotr_stream stream);
+int cotr_ransac_fundamental_scratch_bytes(int n, int max_iters, size_t* bytes);
+int cotr_ransac_fundamental(const double* pts1, const double* pts2, int n, double threshold, double confidence, int max_iters,
+                            uint64_t seed, double* F_out, uint8_t* mask_out, int32_t* info_out, double* hyp_F, int32_t* hyp_count,
+                            int32_t* hyp_samples, void* scratch, size_t scratch_bytes, cotr_stream stream);
+
 /* ---- tuning knobs -------------------------------------------------------------------------------------------
  * Named integer switches that choose between launch schedules / kernel variants with the SAME results (bit-identical unless a
  * knob's line says otherwise).  They are not part of the drop-in boundary: a binding never needs them.  ONE SET PER HANDLE:
