@@ -367,14 +367,15 @@ bool ffn_rows_applies(int M) {
   return tiles * 100 >= rounds * cus * knob(KN_ROWS_MIN_FILL);
 }
 
-// The attention sub-layer as ONE launch (att_rows.hip): from knob att_rows_min_rows query rows on, where its 64-query tiles (per
-// pair) fill the last round of the 256 CUs to at least rows_min_fill percent and a pair's last tile is not mostly padding
-bool att_rows_applies(int nb, int nq) {
-  const long R = (long)nb * nq;
+// The attention sub-layer as ONE launch (att_rows.hip) on R query rows in `tiles` 64-query tiles (each pair's rows tiled on their
+// own): from knob att_rows_min_rows rows on, where the tiles fill the last round of the 256 CUs to at least rows_min_fill percent and
+// are at least 7/8 full on average (a pair's last tile is not mostly padding)
+bool att_rows_fill(long R, long tiles) {
   if (R < knob(KN_ATT_ROWS_MIN_ROWS)) return false;
-  const long cus = cotr_num_cus(), tpp = (nq + 63) / 64, tiles = tpp * nb, rounds = (tiles + cus - 1) / cus;
-  return tiles * 100 >= rounds * cus * knob(KN_ROWS_MIN_FILL) && (long)nq * 8 >= tpp * 64 * 7;
+  const long cus = cotr_num_cus(), rounds = (tiles + cus - 1) / cus;
+  return tiles * 100 >= rounds * cus * knob(KN_ROWS_MIN_FILL) && R * 8 >= tiles * 64 * 7;
 }
+bool att_rows_applies(int nb, int nq) { return att_rows_fill((long)nb * nq, (long)nb * ((nq + 63) / 64)); }
 
 // conv23m (layer2's conv2 -> conv3 in one launch) runs TWO workgroups per CU, 16 per pair: where its grid is a single round that fills
 // the chip unevenly - more than one workgroup per CU, fewer than 7/8 of two (17 ... 27 pairs on 256 CUs) - the CUs that hold two set the
@@ -402,13 +403,15 @@ int enc_next_chunk(int remaining, int cap) {
   const int c = kEncFirst[n];
   return (c >= 1 && c <= n) ? c : n;
 }
+// both rows kernels (att_rows, ffn_rows) take a decode pass of R rows in tiles64 64-row tiles: the prefix a batch_split pass stops at
+bool rows_kernels_take(long R, long tiles64) { return att_rows_fill(R, tiles64) && ffn_rows_applies((int)R); }
 int dec_next_pairs(int remaining, int cap, int nq) {
   const int n = remaining < cap ? remaining : cap;
-  if (!knob(KN_BATCH_SPLIT) || n < 2) return n;
-  if (att_rows_applies(n, nq) && ffn_rows_applies(n * nq)) return n;
+  const long tpp = (nq + 63) / 64;   // 64-row tiles per pair
+  if (!knob(KN_BATCH_SPLIT) || n < 2 || rows_kernels_take((long)n * nq, n * tpp)) return n;
   const long min_rows = knob(KN_ATT_ROWS_MIN_ROWS) > knob(KN_FFN_ROWS_MIN_ROWS) ? knob(KN_ATT_ROWS_MIN_ROWS) : knob(KN_FFN_ROWS_MIN_ROWS);
   for (int k = n - 1; k >= 1 && (long)k * nq >= min_rows; --k)   // (below either threshold no prefix can take both rows kernels)
-    if (att_rows_applies(k, nq) && ffn_rows_applies(k * nq)) return k;
+    if (rows_kernels_take((long)k * nq, k * tpp)) return k;
   return n;
 }
 
@@ -503,7 +506,7 @@ int dec_plan(cotr_ctx* h, int B, int Q, DecPlan& d) {
 }
 
 // knob side_stream applies to a cotr_forward of (B, Q > 0): the query encoding is written once for all B x Q rows and every decode pass
-// reads its rows from the start of d.qpos (decode_impl: row0 = 0) - so one encode pass and one decode pass of one query chunk; few rows
+// reads its rows from the start of d.qpos (dec_pass) - so one encode pass and one decode pass of one query chunk; few rows
 // (B x Q <= 8192); no profiling, no debug taps
 bool side_stream_ok(const cotr_ctx* h, int B, int Q) {
   const DecGeom g = dec_geom(B, Q);
@@ -1025,7 +1028,7 @@ static int enc_encoder_pass(cotr_ctx* h, const EncBufs& eb, int Bc, float* mem_c
   // 18 -> 14 us there; the encoder in-projections only from knob pos_table_min_rows on)
   if (h->side_mode & 2) {
     // cotr_forward with few rows (knob side_stream bit 1): decoder layer 0 needs its own K / V columns only - the other layers'
-    // 5/6 of this product run on the handle's second stream beside decoder layer 0 (decode_chunk waits for them before layer 1)
+    // 5/6 of this product run on the handle's second stream beside decoder layer 0 (dec_pass waits for them before layer 1)
     const int n0 = 2 * D, n1 = (int)KVLD - n0;
     if ((r = linear(h, mem_c, nullptr, 0, 1, 0, h->kv_w, h->kv_b, h->tab_kv, 0, 1.f, 0, kv_c, M, n0, D, s, (int)KVLD, TOK, (int)KVLD))) return r;
     HIPCHK(h, hipEventRecord(h->ev_mem, s));
@@ -1040,6 +1043,25 @@ static int enc_encoder_pass(cotr_ctx* h, const EncBufs& eb, int Bc, float* mem_c
   return COTR_OK;
 }
 
+// An encode's bookkeeping around its passes: before them the cache holds no pairs, the taps are cleared and the cache is sized for B
+// pairs (0: cotr_backbone, which writes none) - memory [B*512*256], then every decoder layer's K / V; after them (enc_cache_done) it
+// holds B pairs
+static int enc_cache_begin(cotr_ctx* h, int B, float** memory, float** kv) {
+  h->enc_B = 0;
+  h->taps.clear();
+  if (int r = ensure(h, h->memkv, enc_cache_floats(h, B))) return r;
+  *memory = h->memkv.ptr;
+  *kv = h->memkv.ptr + (size_t)B * TOK * D;
+  return COTR_OK;
+}
+static void enc_cache_done(cotr_ctx* h, int B) {
+  const size_t KVLD = h->dec.size() * 2 * D;
+  h->taps["memory"] = {h->memkv.ptr, (size_t)B * TOK * D};
+  h->taps["kv"] = {h->memkv.ptr + (size_t)B * TOK * D, (size_t)B * TOK * KVLD};
+  h->taps["pos"] = {h->pos, (size_t)TOK * D};
+  h->enc_B = B;
+}
+
 // feat_out == nullptr: the whole query-independent half (cotr_encode); otherwise only the backbone, its layer3 output
 // [B,16,32,1024] (NHWC, both halves side by side = 512 token rows per pair) copied to feat_out (cotr_backbone)
 static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream stream, float* feat_out, int upto = 3) {
@@ -1050,14 +1072,8 @@ static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream strea
   DEVICE_SCOPE(h);
   const int L = (int)h->dec.size();
   const size_t KVLD = (size_t)L * 2 * D;
-  h->enc_B = 0;
-  h->taps.clear();
-  if (!feat_out) {
-    int r = ensure(h, h->memkv, enc_cache_floats(h, B));
-    if (r) return r;
-  }
-  float* memory = h->memkv.ptr;
-  float* kv = h->memkv.ptr + (size_t)B * TOK * D;
+  float *memory, *kv;
+  if (int r = enc_cache_begin(h, feat_out ? 0 : B, &memory, &kv)) return r;
 
   const int ENC_CHUNK = knob(KN_ENCODE_CHUNK), Bc_max = enc_chunk_max(B, h->knobs);
   if (int r = ensure(h, h->enc_scr, enc_layout(Bc_max, h->knobs, nullptr, nullptr))) return r;
@@ -1072,11 +1088,7 @@ static int encode_impl(cotr_handle h, const float* img, int B, cotr_stream strea
     if (feat_out) continue;
     if (int r = enc_encoder_pass(h, eb, Bc, memory + (size_t)b0 * TOK * D, kv + (size_t)b0 * TOK * KVLD, s)) return r;
   }
-  if (feat_out) return COTR_OK;
-  h->taps["memory"] = {memory, (size_t)B * TOK * D};
-  h->taps["kv"] = {kv, (size_t)B * TOK * KVLD};
-  h->taps["pos"] = {h->pos, (size_t)TOK * D};
-  h->enc_B = B;
+  if (!feat_out) enc_cache_done(h, B);
   return COTR_OK;
 }
 
@@ -1096,101 +1108,117 @@ int cotr_backbone_upto(cotr_handle h, const float* img, int B, int stage, float*
 
 namespace {
 
-// query-side prologue of one chunk: lin_sine encoding of the queries (cotr_model.py:34-36) and layer 0's
-// q = Wq(0 + query_pos) * 32^-0.5 (tgt == 0 at layer 0, transformer.py:54).  Depends on the queries only.
-int dec_prologue(cotr_ctx* h, const DecPlan& d, const float* qsrc, int nb, int nq, int Q, hipStream_t s, bool fused) {
-  if (h->side_mode & 1) {
-    // (knob side_stream bit 0) cotr_forward already ran the query encoding on the second stream, beside the backbone
-    HIPCHK(h, hipStreamWaitEvent(s, h->ev_q, 0));
-  } else {
-    KCHK(h, launch_posenc(qsrc, d.qpos, nb, nq, Q, s), "posenc");
-    prof_mark(h, "posenc", s, 2);
-  }
-  if (fused) return COTR_OK;   // the attention kernel projects its own queries
-  const DecW& w = h->dec[0];
-  return linear(h, d.qpos, nullptr, 0, 1, 0, w.q_w, w.q_b, nullptr, 0, QSCALE, D, d.q, nb * nq, D, D, s);
+// The attention form of a decode pass of R rows in tiles64 64-row tiles (the FFN block decides for itself: ffn_block):
+//   fused  few rows (att_fused_applies, ffn_fused_applies, the fused FFN's partials fit): q projection, attention and out_proj in one
+//          launch, then ln_reduce
+//   rows   att_rows_fill: q projection, attention, out_proj, residual and norm2 in one launch
+//   plain  otherwise, launch by launch
+enum { FORM_PLAIN = 0, FORM_FUSED = 1, FORM_ROWS = 2 };
+int dec_form(const DecBufs& d, long R, long tiles64) {
+  if (d.part != nullptr && att_fused_applies(R) && ffn_fused_applies(R) && (size_t)ffn_fused_chunks((int)R) * R * D <= d.hid_cap)
+    return FORM_FUSED;
+  return att_rows_fill(R, tiles64) ? FORM_ROWS : FORM_PLAIN;
 }
 
-// one chunk of query rows through the decoder: rows [row0, row0 + nb*nq) of the scratch buffers
-int decode_chunk(cotr_ctx* h, const DecPlan& d0, size_t row0, const float* qsrc, float* odst, const float* kv_c, int nb, int nq,
-                 int Q, hipStream_t s) {
-  DecPlan d = d0;
-  d.qpos += row0 * D; d.tgt += row0 * D; d.q += row0 * D; d.ao += row0 * D; d.pre2 += row0 * D; d.t2 += row0 * D;
-  d.pre3 += row0 * D; d.hid += row0 * FFN;   // (row0 is 0 in every caller; d.part is only valid for row0 == 0)
-  const int L = (int)h->dec.size();
-  const int KVLD = L * 2 * D;
-  const int R = nb * nq;
+// One decoder pass: nb pairs x nq queries, a pair's query / output rows Q apart (launch_posenc, launch_head2), in attention form `form`.
+// A varlen pass is one "pair" of R packed rows (nb = 1, nq = Q = R) whose attention launches take the tile table tab[0, ntab) (device).
+struct DecPass { int nb, nq, Q, form; const int4* tab = nullptr; int ntab = 0; };
+
+// decoder.norm + corr_embed on the last layer only (the reference computes all 6 and keeps [-1])
+int dec_head(cotr_ctx* h, const DecPlan& d, const DecPass& v, bool hs_normed, float* odst, hipStream_t s) {
+  const int R = v.nb * v.nq;
   int r;
-  const size_t hid_cap = d0.hid_cap;
-  bool fused = d.part != nullptr && att_fused_applies(R) && ffn_fused_applies(R) && (size_t)ffn_fused_chunks(R) * R * D <= hid_cap;
-  bool hs_normed = false;
-  const bool rows = !fused && att_rows_applies(nb, nq);   // many rows: q projection, attention, out_proj, residual, norm2 in one launch
-  if ((r = dec_prologue(h, d, qsrc, nb, nq, Q, s, fused || rows))) return r;
-  // transformer.py:185-201 per layer (cross-attention only, post-norm)
-  for (int li = 0; li < L; ++li) {
-    const DecW& w = h->dec[li];
-    const float* kl = kv_c + (size_t)li * 2 * D;          // this layer's K (then V) columns of the hoisted projection
-    const float* tgt_in = li == 0 ? nullptr : d.tgt;      // tgt == 0 at layer 0 (transformer.py:54)
-    if (li == 1 && (h->side_mode & 2)) HIPCHK(h, hipStreamWaitEvent(s, h->ev_kv, 0));   // K / V of layers 1-5 from the second stream
-    if (fused) {
-      // few rows: q = Wq(tgt + query_pos) * 32^-0.5 in the attention kernel's prologue, out_proj in its epilogue (8 per-head
-      // partials), then ln_reduce: sum + bias + residual + norm2; FFN block; 4 launches per layer.  Last layer: decoder.norm rides
-      // in the FFN block's ln_reduce launch (its input has no other consumer); pre2 = the normed 'hs'
-      KCHK(h, launch_attention_fused(nullptr, 0, tgt_in, d.qpos, w.q_w, w.q_b, QSCALE, kl, kl + D, KVLD, nullptr, 0, w.out_w, d.part,
-                                     nb, nq, s), "q_proj+attention+out_proj");
-      prof_attention(h, "qproj+attention+oproj dec", s);
-      KCHK(h, launch_ln_reduce(d.part, 8, w.out_b, tgt_in, w.n2w, w.n2b, d.t2, R, s), "ln_reduce");
-      prof_mark(h, "ln_reduce heads", s, 2);
-      const bool post = li + 1 == L;
-      if ((r = ffn_block(h, d.t2, w.l1w, w.l1b, w.l2w, w.l2b, w.n3w, w.n3b, d.hid, hid_cap, d.pre3, post ? d.pre2 : d.tgt, R, s,
-                         post ? h->dn_w : nullptr, post ? h->dn_b : nullptr))) return r;
-      hs_normed = post;
-    } else {
-      if (rows) {
-        KCHK(h, launch_att_rows(nullptr, 0, tgt_in, d.qpos, w.q_w, w.q_b, QSCALE, kl, kl + D, KVLD, w.out_w, w.out_b, tgt_in, w.n2w, w.n2b,
-                                d.t2, nb, nq, s), "att_rows");
-        prof_mark(h, "att_rows dec", s, 2);
-      } else {
-        // q = Wq(tgt + query_pos) * 32^-0.5 (layer 0: computed by dec_prologue)
-        if (li > 0 && (r = linear(h, d.tgt, d.qpos, 0, 1, 1, w.q_w, w.q_b, nullptr, 0, QSCALE, D, d.q, R, D, D, s))) return r;
-        KCHK(h, launch_attention(d.q, D, kl, kl + D, KVLD, d.ao, D, nb, nq, s), "attention");
-        prof_attention(h, "attention dec", s);
-        if ((r = linear(h, d.ao, nullptr, 0, 1, 0, w.out_w, w.out_b, tgt_in, 0, 1.f, 0, d.pre2, R, D, D, s))) return r;
-        if ((r = layernorm(h, d.pre2, w.n2w, w.n2b, d.t2, R, s))) return r;
-      }
-      // (many rows, last layer: decoder.norm rides in the one-launch FFN block's epilogue; pre2 = the normed 'hs')
-      const bool post = li + 1 == L && ffn_rows_applies(R);
-      if ((r = ffn_block(h, d.t2, w.l1w, w.l1b, w.l2w, w.l2b, w.n3w, w.n3b, d.hid, hid_cap, d.pre3, post ? d.pre2 : d.tgt, R, s,
-                         post ? h->dn_w : nullptr, post ? h->dn_b : nullptr))) return r;
-      hs_normed = post;
-    }
-  }
-  // decoder.norm + corr_embed on the last layer only (the reference computes all 6 and keeps [-1])
   if (!hs_normed && (r = layernorm(h, d.tgt, h->dn_w, h->dn_b, d.pre2, R, s))) return r;
   if ((r = linear(h, d.pre2, nullptr, 0, 1, 0, h->mlp_w[0], h->mlp_b[0], nullptr, 1, 1.f, 0, d.ao, R, D, D, s))) return r;
   if ((r = linear(h, d.ao, nullptr, 0, 1, 0, h->mlp_w[1], h->mlp_b[1], nullptr, 1, 1.f, 0, d.q, R, D, D, s))) return r;
-  KCHK(h, launch_head2(d.q, h->mlp_w[2], h->mlp_b[2], odst, nb, nq, Q, s), "head2");
+  KCHK(h, launch_head2(d.q, h->mlp_w[2], h->mlp_b[2], odst, v.nb, v.nq, v.Q, s), "head2");
   prof_mark(h, "head2", s, 2);
   return COTR_OK;
 }
 
-int decode_impl(cotr_ctx* h, const float* queries, int B, int Q, float* out, hipStream_t s, const DecPlan& d) {
+// the pass's queries at qsrc through the decoder to its correspondences at odst, K / V from kv (the hoisted projection of its first
+// pair; a varlen pass: of pair 0); the scratch rows [0, R) of d, the taps 'query_pos' and 'hs'
+int dec_pass(cotr_ctx* h, const DecPlan& d, const float* qsrc, float* odst, const float* kv, const DecPass& v, hipStream_t s) {
   const int L = (int)h->dec.size();
   const int KVLD = L * 2 * D;
+  const int nb = v.nb, nq = v.nq, R = nb * nq;
+  const bool fused = v.form == FORM_FUSED, rows = v.form == FORM_ROWS;
+  int r;
+  // query-side prologue: lin_sine encoding of the queries (cotr_model.py:34-36) and layer 0's q = Wq(0 + query_pos) * 32^-0.5
+  // (tgt == 0 at layer 0, transformer.py:54), unless the attention launch projects its own queries.  Depends on the queries only.
+  if (h->side_mode & 1) {
+    // (knob side_stream bit 0) cotr_forward already ran the query encoding on the second stream, beside the backbone
+    HIPCHK(h, hipStreamWaitEvent(s, h->ev_q, 0));
+  } else {
+    KCHK(h, launch_posenc(qsrc, d.qpos, nb, nq, v.Q, s), "posenc");
+    prof_mark(h, "posenc", s, 2);
+  }
+  if (!fused && !rows && (r = linear(h, d.qpos, nullptr, 0, 1, 0, h->dec[0].q_w, h->dec[0].q_b, nullptr, 0, QSCALE, D, d.q, R, D, D, s)))
+    return r;
+  bool hs_normed = false;
+  // transformer.py:185-201 per layer (cross-attention only, post-norm)
+  for (int li = 0; li < L; ++li) {
+    const DecW& w = h->dec[li];
+    const float* kl = kv + (size_t)li * 2 * D;            // this layer's K (then V) columns of the hoisted projection
+    const float* tgt_in = li == 0 ? nullptr : d.tgt;      // tgt == 0 at layer 0 (transformer.py:54)
+    if (li == 1 && (h->side_mode & 2)) HIPCHK(h, hipStreamWaitEvent(s, h->ev_kv, 0));   // K / V of layers 1-5 from the second stream
+    bool post;   // last layer: decoder.norm rides in the FFN block's last launch (its input has no other consumer); pre2 = the normed 'hs'
+    if (fused) {
+      // few rows: q = Wq(tgt + query_pos) * 32^-0.5 in the attention kernel's prologue, out_proj in its epilogue (8 per-head
+      // partials), then ln_reduce: sum + bias + residual + norm2; FFN block; 4 launches per layer
+      if (v.tab)
+        KCHK(h, launch_attention_varlen(nullptr, 0, tgt_in, d.qpos, w.q_w, w.q_b, QSCALE, kl, kl + D, KVLD, nullptr, 0, w.out_w, d.part, R,
+                                        v.tab, v.ntab, s), "q_proj+attention+out_proj (varlen)");
+      else
+        KCHK(h, launch_attention_fused(nullptr, 0, tgt_in, d.qpos, w.q_w, w.q_b, QSCALE, kl, kl + D, KVLD, nullptr, 0, w.out_w, d.part,
+                                       nb, nq, s), "q_proj+attention+out_proj");
+      prof_attention(h, "qproj+attention+oproj dec", s);
+      KCHK(h, launch_ln_reduce(d.part, 8, w.out_b, tgt_in, w.n2w, w.n2b, d.t2, R, s), "ln_reduce");
+      prof_mark(h, "ln_reduce heads", s, 2);
+      post = li + 1 == L;
+    } else {
+      if (rows) {
+        if (v.tab)
+          KCHK(h, launch_att_rows_varlen(tgt_in, d.qpos, w.q_w, w.q_b, QSCALE, kl, kl + D, KVLD, w.out_w, w.out_b, tgt_in, w.n2w, w.n2b,
+                                         d.t2, v.tab, v.ntab, s), "att_rows (varlen)");
+        else
+          KCHK(h, launch_att_rows(nullptr, 0, tgt_in, d.qpos, w.q_w, w.q_b, QSCALE, kl, kl + D, KVLD, w.out_w, w.out_b, tgt_in, w.n2w, w.n2b,
+                                  d.t2, nb, nq, s), "att_rows");
+        prof_mark(h, "att_rows dec", s, 2);
+      } else {
+        // q = Wq(tgt + query_pos) * 32^-0.5 (layer 0: the prologue's)
+        if (li > 0 && (r = linear(h, d.tgt, d.qpos, 0, 1, 1, w.q_w, w.q_b, nullptr, 0, QSCALE, D, d.q, R, D, D, s))) return r;
+        if (v.tab)
+          KCHK(h, launch_attention_varlen(d.q, D, nullptr, nullptr, nullptr, nullptr, 0.f, kl, kl + D, KVLD, d.ao, D, nullptr, nullptr, R,
+                                          v.tab, v.ntab, s), "attention (varlen)");
+        else
+          KCHK(h, launch_attention(d.q, D, kl, kl + D, KVLD, d.ao, D, nb, nq, s), "attention");
+        prof_attention(h, "attention dec", s);
+        if ((r = linear(h, d.ao, nullptr, 0, 1, 0, w.out_w, w.out_b, tgt_in, 0, 1.f, 0, d.pre2, R, D, D, s))) return r;
+        if ((r = layernorm(h, d.pre2, w.n2w, w.n2b, d.t2, R, s))) return r;
+      }
+      post = li + 1 == L && ffn_rows_applies(R);   // (many rows: the one-launch FFN block's epilogue)
+    }
+    if ((r = ffn_block(h, d.t2, w.l1w, w.l1b, w.l2w, w.l2b, w.n3w, w.n3b, d.hid, d.hid_cap, d.pre3, post ? d.pre2 : d.tgt, R, s,
+                       post ? h->dn_w : nullptr, post ? h->dn_b : nullptr))) return r;
+    hs_normed = post;
+  }
+  if ((r = dec_head(h, d, v, hs_normed, odst, s))) return r;
+  if ((r = tap_save(h, "query_pos", d.qpos, (size_t)R * D, s))) return r;
+  return tap_save(h, "hs", d.pre2, (size_t)R * D, s);
+}
+
+int decode_impl(cotr_ctx* h, const float* queries, int B, int Q, float* out, hipStream_t s, const DecPlan& d) {
+  const size_t KVLD = h->dec.size() * 2 * D;
   const float* kv = h->memkv.ptr + (size_t)B * TOK * D;
   prof_mark(h, "dec_begin", s);
   for (int b0 = 0, nb = 0; b0 < B; b0 += nb) {
     nb = dec_next_pairs(B - b0, d.nb_max, d.q_chunk);
     for (int q0 = 0; q0 < Q; q0 += d.q_chunk) {
       const int nq = (Q - q0) < d.q_chunk ? (Q - q0) : d.q_chunk;
-      const int R = nb * nq;
-      const float* qsrc = queries + ((size_t)b0 * Q + q0) * 2;
-      float* odst = out + ((size_t)b0 * Q + q0) * 2;
-      const float* kv_c = kv + (size_t)b0 * TOK * KVLD;
-      int r;
-      if ((r = decode_chunk(h, d, 0, qsrc, odst, kv_c, nb, nq, Q, s))) return r;
-      if ((r = tap_save(h, "query_pos", d.qpos, (size_t)R * D, s))) return r;
-      if ((r = tap_save(h, "hs", d.pre2, (size_t)R * D, s))) return r;
+      const int form = dec_form(d, (long)nb * nq, (long)nb * ((nq + 63) / 64));
+      const size_t at = ((size_t)b0 * Q + q0) * 2;
+      if (int r = dec_pass(h, d, queries + at, out + at, kv + (size_t)b0 * TOK * KVLD, {nb, nq, Q, form}, s)) return r;
     }
   }
   prof_mark(h, "decoder", s);
@@ -1336,11 +1364,8 @@ static int pairs_check(cotr_ctx* h, const float* images, int M, const int* pairs
 
 static int encode_pairs_impl(cotr_ctx* h, const float* images, int M, const int* pairs, int B, hipStream_t s) {
   const size_t KVLD = h->dec.size() * 2 * D;
-  h->enc_B = 0;
-  h->taps.clear();
-  if (int r = ensure(h, h->memkv, enc_cache_floats(h, B))) return r;
-  float* memory = h->memkv.ptr;
-  float* kv = h->memkv.ptr + (size_t)B * TOK * D;
+  float *memory, *kv;
+  if (int r = enc_cache_begin(h, B, &memory, &kv)) return r;
   const int S = (M - 1) / 2 + 1, ENC_CHUNK = knob(KN_ENCODE_CHUNK), Bc_max = pairs_chunk_max(M, B, h->knobs);
   const size_t f_enc = enc_layout(Bc_max, h->knobs, nullptr, nullptr);
   if (int r = ensure(h, h->enc_scr, f_enc + pairs_img_floats(M))) return r;
@@ -1369,10 +1394,7 @@ static int encode_pairs_impl(cotr_ctx* h, const float* images, int M, const int*
     if (int r = tap_save(h, "src", eb.t_src, (size_t)Bc * TOK * D, s)) return r;
     if (int r = enc_encoder_pass(h, eb, Bc, memory + (size_t)b0 * TOK * D, kv + (size_t)b0 * TOK * KVLD, s)) return r;
   }
-  h->taps["memory"] = {memory, (size_t)B * TOK * D};
-  h->taps["kv"] = {kv, (size_t)B * TOK * KVLD};
-  h->taps["pos"] = {h->pos, (size_t)TOK * D};
-  h->enc_B = B;
+  enc_cache_done(h, B);
   return COTR_OK;
 }
 
@@ -1411,18 +1433,17 @@ int cotr_scratch_bytes_pairs(cotr_handle h, int M, int B, int Q, size_t* bytes) 
 // A pass is a range [r0, r1) of the packed rows: up to DEC_ROWS of them, cut at any row (a pair's rows continue in the next pass, as a
 // uniform call's queries do above DEC_ROWS; a pair with no rows takes no tile).  With knob batch_split, dec_next_pairs' prefix rule
 // holds at the pair boundaries inside a pass: where att_rows + ffn_rows do not take the whole pass but take a prefix of whole pairs, that
-// prefix is a pass of its own.  A pass's attention form follows decode_chunk's fill rules on the pass's row and tile counts:
-//   fused  att_fused_applies(R) && ffn_fused_applies(R) (and the partials fit)    attention_kernel<4|8, QP, OP, VL>, 32-row tiles
-//   rows   att_rows_min_rows rows, 64-row tiles that fill the last round of the CUs to rows_min_fill percent and are at least 7/8
-//          full on average (att_rows_applies' per-pair padding rule, over the pass)  att_rows_kernel<true, ., ., VL>, 64-row tiles
-//   plain  otherwise: attention_kernel<knob attention_splits, 0, false, VL> (the wide / resident many-row kernels have no varlen mode)
-// Every other stage is row-wise and runs on the pass's R packed rows as on one "pair" of R queries.  Each pass's tile table - entry
-// (pair, first row in the pass, valid rows, 0) per workgroup tile - is built on the host, staged in a pinned slot of the handle's ring
-// and copied into the decoder scratch right before the pass on the call's stream.  The second stream (knob side_stream) is not used.
+// prefix is a pass of its own.  A pass's attention form is dec_form's on the pass's row count and 64-row tile count:
+//   fused  attention_kernel<4|8, QP, OP, VL>, 32-row tiles
+//   rows   att_rows_kernel<true, ., ., VL>, 64-row tiles
+//   plain  attention_kernel<knob attention_splits, 0, false, VL> (the wide / resident many-row kernels have no varlen mode)
+// dec_pass runs it; every other stage is row-wise and runs on the pass's R packed rows as on one "pair" of R queries.  Each pass's
+// tile table - entry (pair, first row in the pass, valid rows, 0) per workgroup tile - is built on the host, staged in a pinned slot of
+// the handle's ring and copied into the decoder scratch right before the pass on the call's stream.  The second stream (knob
+// side_stream) is not used.
 namespace {
 
 constexpr int VL_TILE = 32, VL_TILE_ROWS = 64;   // rows per tile: attention_kernel, att_rows_kernel
-enum { VL_PLAIN = 0, VL_FUSED = 1, VL_ROWS = 2 };
 
 struct VlPass { long r0 = 0, r1 = 0; int b0 = 0, b1 = 0; };   // packed rows [r0, r1), of pairs [b0, b1)
 
@@ -1442,16 +1463,7 @@ long vl_tiles(const int* off, const VlPass& p, int rows_per_tile) {
 // tile-table entries a pass of up to R rows of up to B pairs can need (every pair's last 32-row tile may be partial)
 size_t vl_tile_cap(size_t R, int B) { return R / VL_TILE + (R < (size_t)B ? R : (size_t)B) + 1; }
 
-// att_rows_applies on a pass of R rows in `tiles` 64-row tiles
-bool vl_att_rows_applies(long R, long tiles) {
-  if (R < knob(KN_ATT_ROWS_MIN_ROWS)) return false;
-  const long cus = cotr_num_cus(), rounds = (tiles + cus - 1) / cus;
-  return tiles * 100 >= rounds * cus * knob(KN_ROWS_MIN_FILL) && R * 8 >= tiles * VL_TILE_ROWS * 7;
-}
-bool vl_rows_kernels_apply(const int* off, const VlPass& p) {
-  const long R = p.r1 - p.r0;
-  return vl_att_rows_applies(R, vl_tiles(off, p, VL_TILE_ROWS)) && ffn_rows_applies((int)R);
-}
+bool vl_rows_kernels_take(const int* off, const VlPass& p) { return rows_kernels_take(p.r1 - p.r0, vl_tiles(off, p, VL_TILE_ROWS)); }
 
 VlPass vl_next_pass(const int* off, int B, long r0) {
   VlPass p;
@@ -1460,21 +1472,15 @@ VlPass vl_next_pass(const int* off, int B, long r0) {
   p.r1 = N - r0 < DEC_ROWS ? N : r0 + DEC_ROWS;
   p.b0 = (int)(std::upper_bound(off + 1, off + B + 1, (int)r0) - off) - 1;   // the pair that holds row r0
   p.b1 = (int)(std::lower_bound(off, off + B + 1, (int)p.r1) - off);        // pairs that start below r1
-  if (!knob(KN_BATCH_SPLIT) || p.b1 - p.b0 < 2 || vl_rows_kernels_apply(off, p)) return p;
+  if (!knob(KN_BATCH_SPLIT) || p.b1 - p.b0 < 2 || vl_rows_kernels_take(off, p)) return p;
   const long min_rows = knob(KN_ATT_ROWS_MIN_ROWS) > knob(KN_FFN_ROWS_MIN_ROWS) ? knob(KN_ATT_ROWS_MIN_ROWS) : knob(KN_FFN_ROWS_MIN_ROWS);
   for (int b = p.b1 - 1; b > p.b0 && off[b] - r0 >= min_rows; --b) {   // the longest prefix of whole pairs [b0, b) the rows kernels take
     VlPass q = p;
     q.r1 = off[b];
     q.b1 = b;
-    if (vl_rows_kernels_apply(off, q)) return q;
+    if (vl_rows_kernels_take(off, q)) return q;
   }
   return p;
-}
-
-int vl_form(const DecBufs& d, long R, long tiles64) {
-  if (d.part != nullptr && att_fused_applies(R) && ffn_fused_applies(R) && (size_t)ffn_fused_chunks((int)R) * R * D <= d.hid_cap)
-    return VL_FUSED;
-  return vl_att_rows_applies(R, tiles64) ? VL_ROWS : VL_PLAIN;
 }
 
 long vl_fill(const int* off, const VlPass& p, int rows_per_tile, int4* out) {
@@ -1496,54 +1502,6 @@ int vl_plan(cotr_ctx* h, long N, int B, DecPlan& d, int4** tab, size_t* tab_cap)
   return COTR_OK;
 }
 
-// one pass of R packed rows through the decoder (decode_chunk's schedule with the varlen attention launches)
-int vl_decode_pass(cotr_ctx* h, const DecPlan& d, const float* qsrc, float* odst, const float* kv, const int4* tab, int ntab, int form,
-                   int R, hipStream_t s) {
-  const int L = (int)h->dec.size();
-  const int KVLD = L * 2 * D;
-  const bool fused = form == VL_FUSED, rows = form == VL_ROWS;
-  int r;
-  if ((r = dec_prologue(h, d, qsrc, 1, R, R, s, fused || rows))) return r;
-  bool hs_normed = false;
-  for (int li = 0; li < L; ++li) {
-    const DecW& w = h->dec[li];
-    const float* kl = kv + (size_t)li * 2 * D;
-    const float* tgt_in = li == 0 ? nullptr : d.tgt;
-    bool post;
-    if (fused) {
-      KCHK(h, launch_attention_varlen(nullptr, 0, tgt_in, d.qpos, w.q_w, w.q_b, QSCALE, kl, kl + D, KVLD, nullptr, 0, w.out_w, d.part, R,
-                                      tab, ntab, s), "q_proj+attention+out_proj (varlen)");
-      prof_attention(h, "qproj+attention+oproj dec", s);
-      KCHK(h, launch_ln_reduce(d.part, 8, w.out_b, tgt_in, w.n2w, w.n2b, d.t2, R, s), "ln_reduce");
-      prof_mark(h, "ln_reduce heads", s, 2);
-      post = li + 1 == L;
-    } else {
-      if (rows) {
-        KCHK(h, launch_att_rows_varlen(tgt_in, d.qpos, w.q_w, w.q_b, QSCALE, kl, kl + D, KVLD, w.out_w, w.out_b, tgt_in, w.n2w, w.n2b,
-                                       d.t2, tab, ntab, s), "att_rows (varlen)");
-        prof_mark(h, "att_rows dec", s, 2);
-      } else {
-        if (li > 0 && (r = linear(h, d.tgt, d.qpos, 0, 1, 1, w.q_w, w.q_b, nullptr, 0, QSCALE, D, d.q, R, D, D, s))) return r;
-        KCHK(h, launch_attention_varlen(d.q, D, nullptr, nullptr, nullptr, nullptr, 0.f, kl, kl + D, KVLD, d.ao, D, nullptr, nullptr, R,
-                                        tab, ntab, s), "attention (varlen)");
-        prof_attention(h, "attention dec", s);
-        if ((r = linear(h, d.ao, nullptr, 0, 1, 0, w.out_w, w.out_b, tgt_in, 0, 1.f, 0, d.pre2, R, D, D, s))) return r;
-        if ((r = layernorm(h, d.pre2, w.n2w, w.n2b, d.t2, R, s))) return r;
-      }
-      post = li + 1 == L && ffn_rows_applies(R);
-    }
-    if ((r = ffn_block(h, d.t2, w.l1w, w.l1b, w.l2w, w.l2b, w.n3w, w.n3b, d.hid, d.hid_cap, d.pre3, post ? d.pre2 : d.tgt, R, s,
-                       post ? h->dn_w : nullptr, post ? h->dn_b : nullptr))) return r;
-    hs_normed = post;
-  }
-  if (!hs_normed && (r = layernorm(h, d.tgt, h->dn_w, h->dn_b, d.pre2, R, s))) return r;
-  if ((r = linear(h, d.pre2, nullptr, 0, 1, 0, h->mlp_w[0], h->mlp_b[0], nullptr, 1, 1.f, 0, d.ao, R, D, D, s))) return r;
-  if ((r = linear(h, d.ao, nullptr, 0, 1, 0, h->mlp_w[1], h->mlp_b[1], nullptr, 1, 1.f, 0, d.q, R, D, D, s))) return r;
-  KCHK(h, launch_head2(d.q, h->mlp_w[2], h->mlp_b[2], odst, 1, R, R, s), "head2");
-  prof_mark(h, "head2", s, 2);
-  return COTR_OK;
-}
-
 int vl_decode(cotr_ctx* h, const float* queries, const int* off, int B, float* out, hipStream_t s) {
   const long N = off[B];
   DecPlan d;
@@ -1557,8 +1515,8 @@ int vl_decode(cotr_ctx* h, const float* queries, const int* off, int B, float* o
   for (long r0 = 0; r0 < N;) {
     Pass ps;
     ps.p = vl_next_pass(off, B, r0);
-    ps.form = vl_form(d, ps.p.r1 - ps.p.r0, vl_tiles(off, ps.p, VL_TILE_ROWS));
-    ps.ntab = vl_tiles(off, ps.p, ps.form == VL_ROWS ? VL_TILE_ROWS : VL_TILE);
+    ps.form = dec_form(d, ps.p.r1 - ps.p.r0, vl_tiles(off, ps.p, VL_TILE_ROWS));
+    ps.ntab = vl_tiles(off, ps.p, ps.form == FORM_ROWS ? VL_TILE_ROWS : VL_TILE);
     if (ps.ntab <= 0 || (size_t)ps.ntab > tab_cap) { h->err = "cotr_decode_varlen: tile table overflow"; return COTR_ERR_STATE; }
     ps.at = total;
     total += ps.ntab;
@@ -1577,18 +1535,16 @@ int vl_decode(cotr_ctx* h, const float* queries, const int* off, int B, float* o
     HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&st.host), cap * sizeof(int4), hipHostMallocDefault));
     st.cap = cap;
   }
-  for (const Pass& ps : passes) vl_fill(off, ps.p, ps.form == VL_ROWS ? VL_TILE_ROWS : VL_TILE, st.host + ps.at);
+  for (const Pass& ps : passes) vl_fill(off, ps.p, ps.form == FORM_ROWS ? VL_TILE_ROWS : VL_TILE, st.host + ps.at);
   const float* kv = h->memkv.ptr + (size_t)B * TOK * D;
   prof_mark(h, "dec_begin", s);
   int r = COTR_OK;
   for (const Pass& ps : passes) {
-    const long R = ps.p.r1 - ps.p.r0;
+    const int R = (int)(ps.p.r1 - ps.p.r0);
     const hipError_t e = hipMemcpyAsync(tab, st.host + ps.at, ps.ntab * sizeof(int4), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) { h->err = std::string("hipMemcpyAsync (varlen tile table): ") + hipGetErrorString(e); r = COTR_ERR_HIP; break; }
     st.pending = true;
-    if ((r = vl_decode_pass(h, d, queries + ps.p.r0 * 2, out + ps.p.r0 * 2, kv, tab, (int)ps.ntab, ps.form, (int)R, s))) break;
-    if ((r = tap_save(h, "query_pos", d.qpos, (size_t)R * D, s))) break;
-    if ((r = tap_save(h, "hs", d.pre2, (size_t)R * D, s))) break;
+    if ((r = dec_pass(h, d, queries + ps.p.r0 * 2, out + ps.p.r0 * 2, kv, {1, R, R, ps.form, tab, (int)ps.ntab}, s))) break;
   }
   if (st.pending) HIPCHK(h, hipEventRecord(st.ev, s));
   if (r) return r;
