@@ -2107,6 +2107,7 @@ int cotr_crop_resize_pairs(const uint8_t* img_a, int ha, int wa, const uint8_t* 
                            const int32_t* boxes, int n, float* out, int max_size, cotr_stream stream) {
   if (n < 0 || (n > 0 && (!img_a || !img_b || !boxes || !out))) return COTR_ERR_ARG;
   if (ha <= 0 || wa <= 0 || hb <= 0 || wb <= 0) return COTR_ERR_ARG;
+  if (n > 0 && (max_size < 2 || max_size > COTR_CROP_MAX_SIZE)) return COTR_ERR_ARG;   // launch_crop_resize's LDS budget ends there
   return op_ret(launch_crop_resize(img_a, ha, wa, img_b, hb, wb, boxes, n, out, max_size, static_cast<hipStream_t>(stream)));
 }
 

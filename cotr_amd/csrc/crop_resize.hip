@@ -147,11 +147,13 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const CropParams p) {
   }
 }
 
-// Host launcher.  max_size = largest crop edge among the boxes (host knows it: it computed the boxes).
+// Host launcher.  max_size = largest crop edge among the boxes (host knows it: it computed the boxes) or an upper bound of it.
+// The 160 KB budget below fits R = 8 up to max_size 3296, R = 4 up to 4864, R = 2 up to 6528, R = 1 up to 7936 and nothing
+// beyond: that is COTR_CROP_MAX_SIZE of include/cotr_hip.h (tests/test_image_kernel_cases_cpu.py holds the two together).
 int launch_crop_resize(const uint8_t* img_a, int ha, int wa, const uint8_t* img_b, int hb, int wb,
                        const int32_t* boxes, int n, float* out, int max_size, hipStream_t s) {
   if (n <= 0) return 0;
-  if (max_size < 2 || max_size > 16384) return -1;
+  if (max_size < 2) return -1;
   const double scale = max_size > OUT ? (double)max_size / OUT : 1.0;
   const int sup = (int)ceil(scale);
   const int ksize = sup * 2 + 1;

@@ -368,7 +368,10 @@ size_t cotr_train_attention_bwd_scratch(int nb, int nq);
  * and ImageNet-normalise: out float32 [n,3,256,512], directly consumable by cotr_encode.
  * Replaces per task: PIL resize x2 + two_images_side_by_side + to_tensor + normalize
  * (COTR/inference/refinement_task.py:105-120) and the H2D copy of sparse_engine.py:50.
- * max_size: largest crop edge among the boxes (sizes LDS; <= 16384). */
+ * max_size: the largest crop edge among the boxes, or any upper bound of it (the result does not depend on which); it sizes
+ * the workgroup's LDS row window, whose 160 KB hold crops up to COTR_CROP_MAX_SIZE.  2 <= max_size <= COTR_CROP_MAX_SIZE,
+ * otherwise COTR_ERR_ARG with nothing launched and `out` untouched; n == 0 returns COTR_OK and does nothing. */
+#define COTR_CROP_MAX_SIZE 7936
 int cotr_crop_resize_pairs(const uint8_t* img_a, int ha, int wa, const uint8_t* img_b, int hb, int wb,
                            const int32_t* boxes, int n, float* out, int max_size, cotr_stream stream);
 
