@@ -7,10 +7,15 @@ device-side crop+resize launch and one batched encode/decode instead of one PIL 
 one backbone pass per query per level.  ``triangulate_corr`` densifies the sparse correspondences they return (one
 rasterisation launch sequence on the device).  ``mutual_matches``, ``find_fundamental_mat`` and ``filter_guided_matches``
 are the guided-matching post-processing of demo_guided_matching.py (nearest keypoints, mutual check, F-matrix RANSAC) as
-device calls; ``ZoomEngine.guided_match`` runs the whole demo."""
+device calls; ``ZoomEngine.guided_match`` runs the whole demo.  ``warp_by_map``, ``warp_perspective`` and
+``get_perspective_transform`` are the demos' ``cv2.remap`` / ``cv2.warpPerspective`` / ``cv2.getPerspectiveTransform`` (8-bit
+bilinear, one launch each); ``warp_by_corr`` and ``paste_by_corners`` are the last lines of demo_single_pair.py and
+demo_homography.py."""
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .triangulate import triangulate_corr
+from .warp import get_perspective_transform, paste_by_corners, warp_by_corr, warp_by_map, warp_perspective
 from .zoom_engine import FasterSparseEngine, RefineResult, SparseEngine, ZoomEngine, patch_boxes
 
 __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'RefineResult', 'triangulate_corr',
-           'mutual_matches', 'find_fundamental_mat', 'filter_guided_matches']
+           'mutual_matches', 'find_fundamental_mat', 'filter_guided_matches', 'warp_by_map', 'warp_perspective',
+           'get_perspective_transform', 'warp_by_corr', 'paste_by_corners']

@@ -49,7 +49,8 @@ def triangulate_corr(corr, from_shape, to_shape, simplices=None, return_mask=Fal
 
     simplices: triangles [T,3] of indices into ``corr`` to use instead of scipy's Delaunay.
     return_mask: also return the bool [H_a, W_a] coverage mask.
-    as_tensor: return device tensors (float64 map, bool mask) instead of numpy arrays: no copy back to the host."""
+    as_tensor: return device tensors (float64 map, bool mask) instead of numpy arrays: no copy back to the host, for
+        callers that warp with ``warp_by_map``."""
     corr = np.array(corr, dtype=np.float64)
     if corr.ndim != 2 or corr.shape[1] != 4:
         raise ValueError(f'corr must be [N, 4] (x_a, y_a, x_b, y_b), got shape {corr.shape}')

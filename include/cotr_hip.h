@@ -448,6 +448,30 @@ int cotr_ransac_fundamental(const double* pts1, const double* pts2, int n, doubl
                             uint64_t seed, double* F_out, uint8_t* mask_out, int32_t* info_out, double* hyp_F, int32_t* hyp_count,
                             int32_t* hyp_samples, void* scratch, size_t scratch_bytes, cotr_stream stream);
 
+/* ---- warps of 8-bit images: cv2.remap / cv2.warpPerspective, INTER_LINEAR, BORDER_CONSTANT 0 (cotr_amd/csrc/warp.hip) ----
+ * The last host step of demo_single_pair.py:43 (image B warped by triangulate_corr's dense map) and of
+ * demo_homography.py:46-49 (a picture pasted through four corners).  Rule in DESIGN.md 3i: OpenCV's 8-bit bilinear remap.
+ *
+ * cotr_warp_map: src [Hs,Ws,C] uint8, C in {1, 3, 4}; map [Hd,Wd,2] = (x, y) source positions in pixel INDICES (sample
+ *   (j, i) is the centre of src[i, j]), float32 (8-byte aligned) or, with map_is_f64 != 0, float64 (16-byte aligned,
+ *   rounded to float32 first) -> dst [Hd,Wd,C] uint8.  X = rint(x * 32) (ties to even), ix = X >> 5, fx = X & 31, Y alike;
+ *   taps (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1), weights (32-fx)(32-fy), fx(32-fy), (32-fx)fy, fx fy; a tap outside
+ *   the source reads 0; dst = (sum w p + 512) >> 10.  A non-finite coordinate or one of magnitude >= 2^26 puts all four
+ *   taps outside.
+ *   cover [Hd,Wd] uint8 (may be NULL) = 1 where a tap with a non-zero weight lies inside the source.
+ *   background [Hd,Wd,C] uint8 (may be NULL): an uncovered pixel of dst takes the background's pixel instead of 0.
+ * cotr_warp_perspective: the same with the positions from M, a HOST double[9] (row-major 3x3, destination -> source; read
+ *   before the call returns): per destination pixel (x, y) in double, W = (m6 x + m7 y) + m8, W = W != 0 ? 32 / W : 0,
+ *   X = rint(clamp(((m0 x + m1 y) + m2) W, INT_MIN, INT_MAX)), Y alike, products and sums in this order, not contracted.
+ *   W == 0 or a NaN position puts all four taps outside.  M must be finite.
+ * All image pointers are DEVICE pointers; 1 <= Hs, Ws, Hd, Wd <= 16384; dst must not overlap src or background.  One launch
+ * each, stream-ordered, no host waits, no allocation (capturable).  Bad arguments are checked before any HIP call:
+ * COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_warp_map(const uint8_t* src, int Hs, int Ws, int C, const void* map, int map_is_f64, int Hd, int Wd, uint8_t* dst,
+                  uint8_t* cover, const uint8_t* background, cotr_stream stream);
+int cotr_warp_perspective(const uint8_t* src, int Hs, int Ws, int C, const double* M, int Hd, int Wd, uint8_t* dst,
+                          uint8_t* cover, const uint8_t* background, cotr_stream stream);
+
 /* ---- tuning knobs -------------------------------------------------------------------------------------------
  * Named integer switches that choose between launch schedules / kernel variants with the SAME results (bit-identical unless a
  * knob's line says otherwise).  They are not part of the drop-in boundary: a binding never needs them.  ONE SET PER HANDLE:
