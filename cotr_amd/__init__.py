@@ -15,3 +15,15 @@ def default_args(**over):
     for k, v in over.items():
         setattr(a, k, v)
     return a
+
+
+_DATA_NAMES = ('Capture', 'depth_corrs', 'crop_capture', 'make_batch', 'make_zoom_batch', 'draw_rand')
+__all__ = ['default_args'] + list(_DATA_NAMES)
+
+
+def __getattr__(name):
+    """the batch builders of cotr_amd/data.py, imported on first use (they bring torch and the library binding with them)"""
+    if name in _DATA_NAMES:
+        from . import data
+        return getattr(data, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

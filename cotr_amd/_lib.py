@@ -131,6 +131,12 @@ _PROTOS = {
     'cotr_warp_map': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4),
     'cotr_warp_perspective': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                              ctypes.c_int] + [ctypes.c_void_p] * 4),
+    'cotr_depth_corrs_scratch': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    'cotr_depth_corrs': (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] +
+                         [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
+    'cotr_depth_valid': (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] +
+                         [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
+    'cotr_crop_depth_nearest': (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     'cotr_gemm_num_configs': (ctypes.c_int, []),
     'cotr_op_conv_dual_cfg': (ctypes.c_int, [c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, c_float_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, c_float_p, c_float_p, c_float_p, ctypes.c_int, c_float_p,

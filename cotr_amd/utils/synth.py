@@ -70,6 +70,66 @@ def synth_inputs(batch, queries, seed=1, as_torch=True):
     return img, q
 
 
+def _ray_plane_depth(H, W, K, c2w, normal, offset):
+    """(depth along the camera's z of the plane normal . X = offset seen through every pixel centre (x, y), world hit points):
+    analytic ray-plane intersection in float64; pixel (x, y) looks along Kinv (x, y, 1), whose z is 1, so the ray parameter
+    IS the depth"""
+    xs, ys = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    rays = np.stack([xs, ys, np.ones_like(xs)], -1) @ np.linalg.inv(K).T @ c2w[:3, :3].T
+    origin = c2w[:3, 3]
+    t = (offset - normal @ origin) / (rays @ normal)
+    return t, origin + rays * t[..., None]
+
+
+def synth_captures(seed, H, W):
+    """A seeded two-view RGB-D scene -> (query, nn), each a ``cotr_amd.data.Capture`` of numpy arrays (image uint8 [H, W, 3],
+    depth float32 [H, W], K, c2w float64): a tilted background plane, a nearer plane patch that occludes part of it, holes
+    in the depth (rectangles and single pixels, 0 as in MegaDepth), two poses a few degrees and a fraction of the depth
+    apart, and an image textured by the world position of what each pixel sees.  Depth is exact ray-plane intersection in
+    float64, cast to float32."""
+    from ..data import Capture
+    rng = np.random.Generator(np.random.PCG64(seed))
+    f = 0.9 * max(H, W)
+    K = np.array([[f, 0.0, W / 2.0], [0.0, f * 1.02, H / 2.0], [0.0, 0.0, 1.0]])
+    planes = [(np.array([0.18, -0.12, 1.0]), 8.0 + rng.uniform(-0.5, 0.5), None),
+              (np.array([-0.25, 0.1, 1.0]), 5.0 + rng.uniform(-0.3, 0.3), (rng.uniform(-0.6, 0.2), rng.uniform(-0.4, 0.2), 1.4, 1.1))]
+
+    def pose(angles, t):
+        ax, ay, az = np.deg2rad(angles)
+        rx = np.array([[1, 0, 0], [0, np.cos(ax), -np.sin(ax)], [0, np.sin(ax), np.cos(ax)]])
+        ry = np.array([[np.cos(ay), 0, np.sin(ay)], [0, 1, 0], [-np.sin(ay), 0, np.cos(ay)]])
+        rz = np.array([[np.cos(az), -np.sin(az), 0], [np.sin(az), np.cos(az), 0], [0, 0, 1]])
+        m = np.eye(4)
+        m[:3, :3] = rz @ ry @ rx
+        m[:3, 3] = t
+        return m
+
+    poses = [pose(rng.uniform(-1, 1, 3), rng.uniform(-0.05, 0.05, 3)),
+             pose(np.array([2.0, -5.0, 1.5]) + rng.uniform(-1, 1, 3), np.array([0.9, 0.15, 0.4]) + rng.uniform(-0.1, 0.1, 3))]
+    caps = []
+    for c2w in poses:
+        depth = np.full((H, W), np.inf)
+        hit = np.zeros((H, W, 3))
+        for normal, offset, rect in planes:
+            normal = normal / np.linalg.norm(normal)
+            t, pts = _ray_plane_depth(H, W, K, c2w, normal, offset)
+            ok = (t > 0) & (t < depth)
+            if rect is not None:
+                ok &= (np.abs(pts[..., 0] - rect[0]) < rect[2]) & (np.abs(pts[..., 1] - rect[1]) < rect[3])
+            depth = np.where(ok, t, depth)
+            hit = np.where(ok[..., None], pts, hit)
+        depth = np.where(np.isfinite(depth), depth, 0.0)
+        for _ in range(3):                                             # holes: rectangles ...
+            h0, w0 = int(rng.integers(0, H)), int(rng.integers(0, W))
+            depth[h0:h0 + max(1, H // 9), w0:w0 + max(1, W // 7)] = 0.0
+        depth[rng.random((H, W)) < 0.02] = 0.0                         # ... and single pixels
+        tex = np.stack([np.sin(hit[..., 0] * 5.0) * np.cos(hit[..., 1] * 4.0), np.sin(hit[..., 1] * 7.0 + hit[..., 2]),
+                        np.cos(hit[..., 0] * 3.0 - hit[..., 1] * 2.0)], -1)
+        image = np.clip(127.5 + 100.0 * tex + rng.normal(0.0, 8.0, (H, W, 3)), 0, 255).astype(np.uint8)
+        caps.append(Capture(image, depth.astype(np.float32), K.copy(), c2w))
+    return caps[0], caps[1]
+
+
 def state_checksum(sd):
     """float64 (sum, sum of squares) over all tensors, to detect generator drift."""
     s = s2 = 0.0

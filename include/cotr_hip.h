@@ -472,6 +472,43 @@ int cotr_warp_map(const uint8_t* src, int Hs, int Ws, int C, const void* map, in
 int cotr_warp_perspective(const uint8_t* src, int Hs, int Ws, int C, const double* M, int Hd, int Wd, uint8_t* dst,
                           uint8_t* cover, const uint8_t* background, cotr_stream stream);
 
+/* ---- training batches from depth and camera poses (cotr_amd/csrc/reproject.hip, cotr_amd/data.py) ------------------------
+ * The geometry of COTR/datasets/cotr_dataset.py (get_corrs) and COTR/projector/pcd_projector.py on the device.  Rules in DESIGN.md 3j.
+ *
+ * cotr_depth_corrs: n items, each described by one row of three DEVICE tables (so items may differ in size):
+ *   ptrs   [n][3] uint64: from_depth [Hf,Wf] float32, to_depth [Ht,Wt] float32, subset (int32 source pixel indices y * Wf + x,
+ *          or 0: every pixel in row-major order) - DEVICE addresses
+ *   shapes [n][5] int32:  Hf, Wf, Ht, Wt, n_src (the subset's length, or Hf * Wf)
+ *   cams   [n][37] float64: Kinv_from 3x3 | c2w_from 4x4 | P_to = K_to . w2c_to[0:3] 3x4, row-major
+ *   Per source pixel (x, y), z = from_depth[y, x], in double, products and sums in this order, not contracted:
+ *     c = (Kinv . (x, y, 1)) z with a row (k0 x + k1 y) + k2; reject unless z > 0 and c.z > 0
+ *     w = c2w . (c, 1) with a row ((m0 c.x + m1 c.y) + m2 c.z) + m3; reject if w.w == 0, then w.xyz /= w.w
+ *     p = P_to . (w.xyz, 1), rows alike; reject unless p.z > 0
+ *     u = p.x / p.z, v = p.y / p.z; reject unless 0 <= u < Wt - 1 and 0 <= v < Ht - 1
+ *     keep iff |to_depth[floor(v), floor(u)] - p.z| < 0.5
+ *   -> counts [n] int32 (DEVICE) and rows [n][cap][4] float64 (DEVICE, 16-byte aligned) = (x, y, u, v) of the kept pixels in
+ *   SOURCE order (row-major, or the subset's order; a subset index outside the map is rejected).  Rows beyond cap are counted
+ *   but not written; rows past the count are left alone.  max_src: a host upper bound of every n_src (it sizes the grid; an
+ *   item's n_src is clamped to it).  The compaction is a scan (wave ballots, block totals, their scan, scatter): two runs
+ *   return the same bytes.
+ * cotr_depth_valid: the same compaction with the predicate from_depth > 0 (to_depth and cams are not read) ->
+ *   indices [n][cap] int32 = y * Wf + x of the valid pixels in source order, counts [n].
+ *   scratch for both: DEVICE, 16-byte aligned, at least cotr_depth_corrs_scratch(n, max_src) bytes (0 for arguments out of range).
+ * cotr_crop_depth_nearest: for each of n items crop the box boxes[i] = (x, y, size) (int32 [n][3], DEVICE, inside the map) of the
+ *   float32 depth map srcs[i] (uint64 [n] DEVICE addresses) of shapes[i] = (H, W) (int32 [n][2], DEVICE) and resize it to
+ *   out x out -> dst [n][out][out] float32, bit-identical to PIL.Image.fromarray(depth[y:y+s, x:x+s]).resize((out, out), NEAREST)
+ *   in mode 'F': source column of output column j is int(xo_j), xo_0 = a / 2, xo_(j+1) = xo_j + a, a = size / out in double (the
+ *   accumulated sum of Pillow's ImagingScaleAffine), rows alike.  One launch.  1 <= out <= 4096.
+ * 0 <= n <= 65535 (n == 0 does nothing), 1 <= max_src <= 2^28, n * cap <= 2^31.  Stream-ordered, no host waits, no allocation
+ * (capturable).  Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+size_t cotr_depth_corrs_scratch(int n, int max_src);
+int cotr_depth_corrs(const uint64_t* ptrs, const int32_t* shapes, const double* cams, int n, int max_src, double* rows, int cap,
+                     int32_t* counts, void* scratch, size_t scratch_bytes, cotr_stream stream);
+int cotr_depth_valid(const uint64_t* ptrs, const int32_t* shapes, int n, int max_src, int32_t* indices, int cap, int32_t* counts,
+                     void* scratch, size_t scratch_bytes, cotr_stream stream);
+int cotr_crop_depth_nearest(const uint64_t* srcs, const int32_t* shapes, const int32_t* boxes, int n, float* dst, int out,
+                            cotr_stream stream);
+
 /* ---- tuning knobs -------------------------------------------------------------------------------------------
  * Named integer switches that choose between launch schedules / kernel variants with the SAME results (bit-identical unless a
  * knob's line says otherwise).  They are not part of the drop-in boundary: a binding never needs them.  ONE SET PER HANDLE:
