@@ -18,12 +18,17 @@ def default_args(**over):
 
 
 _DATA_NAMES = ('Capture', 'depth_corrs', 'crop_capture', 'make_batch', 'make_zoom_batch', 'draw_rand')
-__all__ = ['default_args'] + list(_DATA_NAMES)
+_SCENE_NAMES = ('world_points', 'overlap_pairs', 'overlap_matrix', 'knn_pool', 'draw_pairs')
+__all__ = ['default_args'] + list(_DATA_NAMES) + list(_SCENE_NAMES)
 
 
 def __getattr__(name):
-    """the batch builders of cotr_amd/data.py, imported on first use (they bring torch and the library binding with them)"""
+    """the batch builders of cotr_amd/data.py and the pair selection of cotr_amd/scene.py, imported on first use (they bring
+    torch and the library binding with them)"""
     if name in _DATA_NAMES:
         from . import data
         return getattr(data, name)
+    if name in _SCENE_NAMES:
+        from . import scene
+        return getattr(scene, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -509,6 +509,39 @@ int cotr_depth_valid(const uint64_t* ptrs, const int32_t* shapes, int n, int max
 int cotr_crop_depth_nearest(const uint64_t* srcs, const int32_t* shapes, const int32_t* boxes, int n, float* dst, int out,
                             cotr_stream stream);
 
+/* ---- overlap of the captures of a scene (cotr_amd/csrc/overlap.hip, cotr_amd/scene.py) ------------------------------------
+ * The per-scene "distance matrix" of scripts/prepare_nn_distance_mat.py (distance_between_two_caps) on the device: the world
+ * points of capture d projected into capture q, and the intersection over union of the two depth supports.  Rule in DESIGN.md 3k.
+ *
+ * Captures are described by DEVICE tables, so the captures of one call may differ in size:
+ *   caps   [n][2] uint64: depth [H,W] float32, xyz [H*W][3] float32 (the capture's world points; 0 where none are needed) -
+ *          DEVICE addresses
+ *   shapes [n][2] int32: H, W
+ * cotr_world_points: cams [n][25] float64 = Kinv 3x3 | c2w 4x4, row-major.  Per pixel (x, y) in row-major order,
+ *   z = depth[y, x], in double, products and sums in this order, not contracted:
+ *     c = (Kinv . (x, y, 1)) z with a row (k0 x + k1 y) + k2; invalid unless z > 0 and c.z > 0
+ *     w = c2w . (c, 1) with a row ((m0 c.x + m1 c.y) + m2 c.z) + m3; invalid if w.w == 0, then w.xyz /= w.w
+ *   -> xyz[y W + x] = w.xyz rounded to float32, or three NaNs for an invalid pixel.  One launch.
+ * cotr_overlap_pairs: proj [n_caps][12] float64 = P = K . w2c[0:3] of every capture, pairs [n_pairs][2] int32 = (q, d) capture
+ *   indices (DEVICE).  Per pair, every world point X of d (float32, widened): p = P_q . (X, 1) with rows as above; kept iff
+ *   p.z > 0 and, with u = p.x / p.z and v = p.y / p.z, 0 <= u < Wq - 1 and 0 <= v < Hq - 1; it lands on the canvas pixel
+ *   (clip(rint(v), 0, Hq - 1), clip(rint(u), 0, Wq - 1)), ties to even.  canvas = p.z of the kept point with the LARGEST source
+ *   index y Wd + x landing there (no depth test: the last writer in source order), 0 where none lands.  With qm = depth_q > 0
+ *   and rm = canvas > 0: union = #(qm | rm), good = #(qm & rm & |depth_q - canvas| < 1.0)
+ *   -> counts [n_pairs][2] int32 = (good, union) and ratio [n_pairs] float32 = float(good / union), 0 when union == 0 (DEVICE).
+ *   A pair with an index outside [0, n_caps) scores (0, 0).  Integer atomics only: two runs return the same bytes.
+ *   max_px: a host upper bound of every capture's H * W (it sizes the grid and the canvases; a larger capture counts as empty).
+ *   scratch: DEVICE, 16-byte aligned, cotr_overlap_scratch(pairs_in_flight, max_px) bytes = pairs_in_flight canvases of max_px
+ *   uint32 (each rounded up to 16 bytes); 0 for arguments out of range.  The pairs are processed in tiles of as many canvases
+ *   as scratch_bytes holds (at least one): a memset and two launches per tile, one more launch for the ratios.
+ * 0 <= n <= 65535, 1 <= n_caps <= 65535, 0 <= n_pairs <= 2^24, 1 <= max_px <= 2^28, 1 <= pairs_in_flight <= 65535.  Stream-ordered,
+ * no host waits, no allocation (capturable).  Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the message in
+ * cotr_raster_last_error(). */
+int cotr_world_points(const uint64_t* caps, const int32_t* shapes, const double* cams, int n, int max_px, cotr_stream stream);
+size_t cotr_overlap_scratch(int pairs_in_flight, int max_px);
+int cotr_overlap_pairs(const uint64_t* caps, const int32_t* shapes, const double* proj, int n_caps, const int32_t* pairs, int n_pairs,
+                       int max_px, float* ratio, int32_t* counts, void* scratch, size_t scratch_bytes, cotr_stream stream);
+
 /* ---- tuning knobs -------------------------------------------------------------------------------------------
  * Named integer switches that choose between launch schedules / kernel variants with the SAME results (bit-identical unless a
  * knob's line says otherwise).  They are not part of the drop-in boundary: a binding never needs them.  ONE SET PER HANDLE:
