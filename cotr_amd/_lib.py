@@ -8,6 +8,7 @@ the one instance in the process - stream handles from torch are then valid here.
 import ctypes
 import os
 
+import numpy as np
 import torch  # noqa: F401  (must be imported before the HIP library is opened)
 
 from .build import LIB, LIB_EXP
@@ -233,6 +234,24 @@ def check(rc, handle=None, what=''):
         lib = load_library()
         msg = lib.cotr_last_error(handle)
         raise CotrHipError(f'{what} failed (code {rc}): {msg.decode() if msg else "?"}')
+
+
+def check_op(rc, what):
+    """check() of the entry points that take no handle: their message is the calling thread's cotr_raster_last_error()"""
+    if rc != 0:
+        msg = load_library().cotr_raster_last_error()
+        raise CotrHipError(f'{what} failed (code {rc}): {msg.decode() if msg else "?"}')
+
+
+def ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def on(x, device, align=1):
+    """numpy array or tensor -> contiguous tensor on ``device``, its address a multiple of ``align``"""
+    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+    t = t.to(device).contiguous()
+    return t.clone() if t.data_ptr() % align else t
 
 
 _raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "common.h"
+#include "pillow_taps.h"
 
 #define OUT 256
 #define PRECISION_BITS 22
@@ -30,33 +31,16 @@ struct CropParams {
   int ksize_max;          // taps reserved per output column / row
 };
 
-__device__ __forceinline__ double tri(double x) {
-  if (x < 0.0) x = -x;
-  return x < 1.0 ? 1.0 - x : 0.0;
-}
-
-// Pillow precompute_coeffs + normalize_coeffs_8bpc for one output index (box = [0, in_size))
+// Pillow normalize_coeffs_8bpc on the taps of one output index (box = [0, in_size))
 __device__ void coeffs_for(int in_size, int xx, int32_t* k, int& xmin_out, int& xmax_out) {
-  const double scale = (double)in_size / (double)OUT;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 1.0 * filterscale;
-  const double ss = 1.0 / filterscale;
-  const double center = ((double)xx + 0.5) * scale;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) ww += tri(((double)(x + xmin) - center + 0.5) * ss);
-  for (int x = 0; x < xmax; ++x) {
-    double w = tri(((double)(x + xmin) - center + 0.5) * ss);
-    if (ww != 0.0) w /= ww;
+  const Taps t = taps_for(in_size, OUT, xx);
+  for (int x = 0; x < t.n; ++x) {
+    const double w = tap_weight(t, x);
     const double v = w * (double)(1 << PRECISION_BITS);
     k[x] = w < 0.0 ? (int32_t)(-0.5 + v) : (int32_t)(0.5 + v);
   }
-  xmin_out = xmin;
-  xmax_out = xmax;
+  xmin_out = t.lo;
+  xmax_out = t.n;
 }
 
 __device__ __forceinline__ int clip8(int v) {

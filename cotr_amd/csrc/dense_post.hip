@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pillow_taps.h"
+
 #define NET_H 256
 #define NET_W 512
 
@@ -82,41 +84,6 @@ __global__ __launch_bounds__(256) void dense_cycle_kernel(const float* __restric
 }
 
 // ---- step 2: Pillow mode-'F' bilinear resize of every patch + merge ------------------------------------
-__device__ __forceinline__ double tri(double x) {
-  if (x < 0.0) x = -x;
-  return x < 1.0 ? 1.0 - x : 0.0;
-}
-
-// taps of output index xx when resizing NET_H (=256) samples to `out` samples: first tap, tap count, 1/ww
-struct Taps {
-  int lo, n;
-  double center, ss, ww;
-};
-
-__device__ __forceinline__ Taps taps_for(int out, int xx) {
-  Taps t;
-  const double scale = (double)NET_H / (double)out;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 1.0 * filterscale;
-  t.ss = 1.0 / filterscale;
-  t.center = ((double)xx + 0.5) * scale;
-  int lo = (int)(t.center - support + 0.5);
-  if (lo < 0) lo = 0;
-  int hi = (int)(t.center + support + 0.5);
-  if (hi > NET_H) hi = NET_H;
-  t.lo = lo;
-  t.n = hi - lo;
-  t.ww = 0.0;
-  for (int x = 0; x < t.n; ++x) t.ww += tri(((double)(x + lo) - t.center + 0.5) * t.ss);
-  return t;
-}
-
-__device__ __forceinline__ double tap_weight(const Taps& t, int x) {
-  double w = tri(((double)(x + t.lo) - t.center + 0.5) * t.ss);
-  if (t.ww != 0.0) w /= t.ww;
-  return w;
-}
-
 // maps   [P][256][512][3] from step 1;  side 0: left halves (image a), 1: right halves (image b)
 // boxes  [P][3] (x, y, size) of the patch each entry covers in this image
 // flow   [H][W][2], conf [H][W]
@@ -138,7 +105,7 @@ __global__ __launch_bounds__(256) void dense_merge_kernel(const float* __restric
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = src[((size_t)yy * NET_W + xx) * 3 + c];
       } else {
-        const Taps tx = taps_for(size, xx), ty = taps_for(size, yy);
+        const Taps tx = taps_for(NET_H, size, xx), ty = taps_for(NET_H, size, yy);
         double acc[3] = {0.0, 0.0, 0.0};
         for (int y = 0; y < ty.n; ++y) {
           const double ky = tap_weight(ty, y);
@@ -170,35 +137,6 @@ __global__ __launch_bounds__(256) void dense_merge_kernel(const float* __restric
 }
 
 // ---- generic Pillow mode-'F' BILINEAR resize of a [Hs,Ws,C] float map to [Hd,Wd,C] (utils.float_image_resize) ----
-struct GTaps {
-  int lo, n;
-  double center, ss, ww;
-};
-
-__device__ __forceinline__ GTaps gtaps_for(int in_size, int out_size, int xx) {
-  GTaps t;
-  const double scale = (double)in_size / (double)out_size;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 1.0 * filterscale;
-  t.ss = 1.0 / filterscale;
-  t.center = ((double)xx + 0.5) * scale;
-  int lo = (int)(t.center - support + 0.5);
-  if (lo < 0) lo = 0;
-  int hi = (int)(t.center + support + 0.5);
-  if (hi > in_size) hi = in_size;
-  t.lo = lo;
-  t.n = hi - lo;
-  t.ww = 0.0;
-  for (int x = 0; x < t.n; ++x) t.ww += tri(((double)(x + lo) - t.center + 0.5) * t.ss);
-  return t;
-}
-
-__device__ __forceinline__ double gtap_weight(const GTaps& t, int x) {
-  double w = tri(((double)(x + t.lo) - t.center + 0.5) * t.ss);
-  if (t.ww != 0.0) w /= t.ww;
-  return w;
-}
-
 // Pillow runs the horizontal pass only if the width changes and the vertical pass only if the height changes; the
 // intermediate image is float, so rounding the row sums to float in between reproduces it in every case.
 __global__ __launch_bounds__(256) void resize_f32_kernel(const float* __restrict__ src, int Hs, int Ws, int C,
@@ -207,9 +145,9 @@ __global__ __launch_bounds__(256) void resize_f32_kernel(const float* __restrict
   if (idx >= Hd * Wd) return;
   const int px = idx % Wd, py = idx / Wd;
   const bool horiz = Ws != Wd, vert = Hs != Hd;
-  GTaps tx, ty;
-  if (horiz) tx = gtaps_for(Ws, Wd, px);
-  if (vert) ty = gtaps_for(Hs, Hd, py);
+  Taps tx, ty;
+  if (horiz) tx = taps_for(Ws, Wd, px);
+  if (vert) ty = taps_for(Hs, Hd, py);
   const int ny = vert ? ty.n : 1, y0 = vert ? ty.lo : py;
   const int nx = horiz ? tx.n : 1, x0 = horiz ? tx.lo : px;
   for (int c = 0; c < C; ++c) {
@@ -220,12 +158,12 @@ __global__ __launch_bounds__(256) void resize_f32_kernel(const float* __restrict
       float rowv;
       if (horiz) {
         double row = 0.0;
-        for (int x = 0; x < nx; ++x) row += (double)r[(size_t)(x0 + x) * C] * gtap_weight(tx, x);
+        for (int x = 0; x < nx; ++x) row += (double)r[(size_t)(x0 + x) * C] * tap_weight(tx, x);
         rowv = (float)row;
       } else {
         rowv = r[(size_t)x0 * C];
       }
-      if (vert) acc += (double)rowv * gtap_weight(ty, y);
+      if (vert) acc += (double)rowv * tap_weight(ty, y);
       last = rowv;
     }
     dst[(size_t)idx * C + c] = vert ? (float)acc : last;

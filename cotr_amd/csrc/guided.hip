@@ -22,12 +22,9 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/cotr_hip.h"
+#include "handleless.h"
 
-namespace cotr_detail {
-int handleless_fail(int code, const char* msg);   // triangulate.hip: the per-thread message of cotr_raster_last_error()
-}
-using cotr_detail::handleless_fail;
+using namespace cotr_detail;
 
 #define NN_THREADS 256
 #define NN_KALIGN 64           // keypoint splits are multiples of this
@@ -517,8 +514,6 @@ __global__ __launch_bounds__(256) void rs_mask_kernel(const double* __restrict__
 // ---- host side ------------------------------------------------------------------------------------------------------
 namespace {
 
-size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct NnPlan {
   int qblocks[2], splits[2], chunk[2];
   size_t pd, pj, bytes;
@@ -568,8 +563,6 @@ const char* rs_check_shape(int n, int max_iters) {
   return nullptr;
 }
 
-bool aligned(const void* p, size_t a) { return (uintptr_t)p % a == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -602,9 +595,7 @@ int cotr_nearest_mutual(const double* pred_ab, const double* kp_b, const double*
   hipLaunchKernelGGL(nn_partial_kernel, dim3(l.qblocks[0] + l.qblocks[1], max(l.splits[0], l.splits[1])), dim3(NN_THREADS), 0, s, a);
   hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)(((size_t)na + nb + 255) / 256)), dim3(256), 0, s, a);
   hipLaunchKernelGGL(nn_mutual_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, idx_ab, idx_ba, na, nb, mutual);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return handleless_fail(COTR_ERR_HIP, hipGetErrorString(e));
-  return COTR_OK;
+  return launched();
 }
 
 int cotr_ransac_fundamental_scratch_bytes(int n, int max_iters, size_t* bytes) {
@@ -638,9 +629,7 @@ int cotr_ransac_fundamental(const double* pts1, const double* pts2, int n, doubl
                      s, pts1, pts2, n, F, count, thr);
   hipLaunchKernelGGL(rs_select_kernel, dim3(1), dim3(RS_SELECT_THREADS), 0, s, count, max_iters, n, confidence, info_out, hyp_count);
   hipLaunchKernelGGL(rs_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pts1, pts2, n, F, info_out, thr, F_out, mask_out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return handleless_fail(COTR_ERR_HIP, hipGetErrorString(e));
-  return COTR_OK;
+  return launched();
 }
 
 }  // extern "C"

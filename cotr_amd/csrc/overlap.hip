@@ -3,11 +3,9 @@
 //
 // overlap(q, d), everything in double unless said otherwise, products and sums in this order, not contracted:
 //   world points of d (cotr_world_points, once per capture), per pixel (x, y) in row-major order, z = depth_d[y, x]:
-//     c = (Kinv . (x, y, 1)) * z, a row being (k0 x + k1 y) + k2          invalid unless z > 0 and c.z > 0
-//     w = c2w . (c, 1), a row being ((m0 c.x + m1 c.y) + m2 c.z) + m3      invalid if w.w == 0, then w.xyz /= w.w
-//     w.xyz is stored as FLOAT32 (the reference's DEFAULT_PRECISION); an invalid pixel stores NaN
-//   splat: X = the float32 point widened, p = P_q . (X, 1), rows as above; keep iff p.z > 0 and, with u = p.x / p.z,
-//     v = p.y / p.z, 0 <= u < Wq - 1 and 0 <= v < Hq - 1; the point lands on ix = clip(rint(u)), iy = clip(rint(v))
+//     pixel_to_world of camera.h; w.xyz is stored as FLOAT32 (the reference's DEFAULT_PRECISION), an invalid pixel stores NaN
+//   splat: X = the float32 point widened, project_inside of camera.h with P_q and the size of q; a kept point lands on
+//     ix = clip(rint(u)), iy = clip(rint(v))
 //     (ties to even).  The canvas pixel belongs to the kept point with the LARGEST source index y Wd + x landing there
 //     (numpy's fancy assignment keeps the last writer; there is no depth test): atomicMax of index + 1 on a zeroed
 //     uint32 canvas, which is independent of the order of arrival, so two runs give the same bytes.
@@ -22,17 +20,13 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/cotr_hip.h"
+#include "camera.h"
+#include "handleless.h"
 
-namespace cotr_detail {
-int handleless_fail(int code, const char* msg);   // triangulate.hip: the per-thread message of cotr_raster_last_error()
-}
-using cotr_detail::handleless_fail;
+using namespace cotr_detail;
 
 #define OV_THREADS 256
 #define OV_WAVES (OV_THREADS / 64)
-#define OV_MAX_ITEMS 65535
-#define OV_MAX_PX (1 << 28)
 
 namespace {
 
@@ -53,10 +47,6 @@ __device__ __forceinline__ OvCap load_cap(const unsigned long long* __restrict__
   return o;
 }
 
-__device__ __forceinline__ double row4(const double* __restrict__ r, double x, double y, double z) {
-  return ((r[0] * x + r[1] * y) + r[2] * z) + r[3];
-}
-
 // cams = Kinv[9] | c2w[16] per capture
 __global__ __launch_bounds__(OV_THREADS) void world_points_kernel(const unsigned long long* __restrict__ caps,
                                                                   const int32_t* __restrict__ shapes, const double* __restrict__ cams,
@@ -66,24 +56,11 @@ __global__ __launch_bounds__(OV_THREADS) void world_points_kernel(const unsigned
   const int i = blockIdx.x * OV_THREADS + threadIdx.x;
   if (i >= cap.npx || !cap.xyz) return;
   const double* k = cams + 25 * (size_t)c;
-  const double* m = k + 9;
-  const double x = (double)(i % cap.w), y = (double)(i / cap.w);
-  const double z = (double)cap.depth[i];
   const float nan = __builtin_nanf("");
   float o0 = nan, o1 = nan, o2 = nan;
-  if (z > 0.0) {
-    const double c0 = ((k[0] * x + k[1] * y) + k[2]) * z;
-    const double c1 = ((k[3] * x + k[4] * y) + k[5]) * z;
-    const double c2 = ((k[6] * x + k[7] * y) + k[8]) * z;
-    if (c2 > 0.0) {
-      const double w3 = row4(m + 12, c0, c1, c2);
-      if (w3 != 0.0) {
-        o0 = (float)(row4(m, c0, c1, c2) / w3);
-        o1 = (float)(row4(m + 4, c0, c1, c2) / w3);
-        o2 = (float)(row4(m + 8, c0, c1, c2) / w3);
-      }
-    }
-  }
+  double w[3];
+  if (pixel_to_world(k, k + 9, (double)(i % cap.w), (double)(i / cap.w), (double)cap.depth[i], w))
+    o0 = (float)w[0], o1 = (float)w[1], o2 = (float)w[2];
   float* out = const_cast<float*>(cap.xyz) + 3 * (size_t)i;
   out[0] = o0, out[1] = o1, out[2] = o2;
 }
@@ -123,11 +100,9 @@ __global__ __launch_bounds__(OV_THREADS) void overlap_splat_kernel(const unsigne
   const float* X = p.d.xyz + 3 * (size_t)i;
   const float fz = X[2];
   if (fz != fz) return;                                   // an invalid pixel of d
-  const double x = (double)X[0], y = (double)X[1], z = (double)fz;
-  const double p2 = row4(p.P + 8, x, y, z);
-  if (!(p2 > 0.0)) return;
-  const double u = row4(p.P, x, y, z) / p2, v = row4(p.P + 4, x, y, z) / p2;
-  if (!(u >= 0.0 && u < (double)(p.q.w - 1) && v >= 0.0 && v < (double)(p.q.h - 1))) return;   // false for NaN
+  const double Xd[3] = {(double)X[0], (double)X[1], (double)fz};
+  double u, v, pz;
+  if (!project_inside(p.P, Xd, p.q.w, p.q.h, u, v, pz)) return;
   const int ix = min(max((int)rint(u), 0), p.q.w - 1), iy = min(max((int)rint(v), 0), p.q.h - 1);
   atomicMax(win + (size_t)blockIdx.y * max_px + (size_t)iy * p.q.w + ix, (unsigned int)i + 1u);
 }
@@ -177,29 +152,23 @@ int blocks_for(int max_px) { return (max_px + OV_THREADS - 1) / OV_THREADS; }
 
 size_t canvas_bytes(int max_px) { return ((size_t)max_px * sizeof(unsigned int) + 15) / 16 * 16; }
 
-int launched() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return handleless_fail(COTR_ERR_HIP, hipGetErrorString(e));
-  return COTR_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int cotr_world_points(const uint64_t* caps, const int32_t* shapes, const double* cams, int n, int max_px, cotr_stream stream) {
-  if (n < 0 || n > OV_MAX_ITEMS) return handleless_fail(COTR_ERR_ARG, "n must be in [0, 65535]");
+  if (n < 0 || n > MAX_ITEMS) return handleless_fail(COTR_ERR_ARG, "n must be in [0, 65535]");
   if (n == 0) return COTR_OK;
-  if (max_px < 1 || max_px > OV_MAX_PX) return handleless_fail(COTR_ERR_ARG, "max_px must be in [1, 2^28]");
+  if (max_px < 1 || max_px > MAX_PIXELS) return handleless_fail(COTR_ERR_ARG, "max_px must be in [1, 2^28]");
   if (!caps || !shapes || !cams) return handleless_fail(COTR_ERR_ARG, "the capture tables must not be NULL");
-  if ((uintptr_t)caps % 8 || (uintptr_t)cams % 8) return handleless_fail(COTR_ERR_ARG, "caps and cams must be 8-byte aligned");
+  if (!aligned(caps, 8) || !aligned(cams, 8)) return handleless_fail(COTR_ERR_ARG, "caps and cams must be 8-byte aligned");
   hipLaunchKernelGGL(world_points_kernel, dim3(blocks_for(max_px), n), dim3(OV_THREADS), 0, static_cast<hipStream_t>(stream),
                      reinterpret_cast<const unsigned long long*>(caps), shapes, cams, max_px);
   return launched();
 }
 
 size_t cotr_overlap_scratch(int pairs_in_flight, int max_px) {
-  return pairs_in_flight > 0 && pairs_in_flight <= OV_MAX_ITEMS && max_px > 0 && max_px <= OV_MAX_PX
+  return pairs_in_flight > 0 && pairs_in_flight <= MAX_ITEMS && max_px > 0 && max_px <= MAX_PIXELS
              ? (size_t)pairs_in_flight * canvas_bytes(max_px) : 0;
 }
 
@@ -207,15 +176,15 @@ int cotr_overlap_pairs(const uint64_t* caps, const int32_t* shapes, const double
                        int max_px, float* ratio, int32_t* counts, void* scratch, size_t scratch_bytes, cotr_stream stream) {
   if (n_pairs < 0 || n_pairs > (1 << 24)) return handleless_fail(COTR_ERR_ARG, "n_pairs must be in [0, 2^24]");
   if (n_pairs == 0) return COTR_OK;
-  if (n_caps < 1 || n_caps > OV_MAX_ITEMS) return handleless_fail(COTR_ERR_ARG, "n_caps must be in [1, 65535]");
-  if (max_px < 1 || max_px > OV_MAX_PX) return handleless_fail(COTR_ERR_ARG, "max_px must be in [1, 2^28]");
+  if (n_caps < 1 || n_caps > MAX_ITEMS) return handleless_fail(COTR_ERR_ARG, "n_caps must be in [1, 65535]");
+  if (max_px < 1 || max_px > MAX_PIXELS) return handleless_fail(COTR_ERR_ARG, "max_px must be in [1, 2^28]");
   if (!caps || !shapes || !proj || !pairs || !ratio || !counts)
     return handleless_fail(COTR_ERR_ARG, "the capture tables, pairs, ratio and counts must not be NULL");
-  if ((uintptr_t)caps % 8 || (uintptr_t)proj % 8 || (uintptr_t)scratch % 16)
+  if (!aligned(caps, 8) || !aligned(proj, 8) || !aligned(scratch, 16))
     return handleless_fail(COTR_ERR_ARG, "caps and proj must be 8-byte, scratch 16-byte aligned");
   const size_t per = canvas_bytes(max_px);
   if (!scratch || scratch_bytes < per) return handleless_fail(COTR_ERR_ARG, "scratch is NULL or smaller than cotr_overlap_scratch(1, max_px)");
-  const int tile = (int)(scratch_bytes / per < (size_t)OV_MAX_ITEMS ? scratch_bytes / per : (size_t)OV_MAX_ITEMS);
+  const int tile = (int)(scratch_bytes / per < (size_t)MAX_ITEMS ? scratch_bytes / per : (size_t)MAX_ITEMS);
   const int nb = blocks_for(max_px);
   const unsigned long long* c = reinterpret_cast<const unsigned long long*>(caps);
   unsigned int* win = static_cast<unsigned int*>(scratch);

@@ -2,12 +2,8 @@
 // of COTR/datasets/cotr_dataset.py (get_corrs, the seed search, the zoomed captures) and COTR/projector/pcd_projector.py.
 // Rules in DESIGN.md 3j.
 //
-// cotr_depth_corrs, per source pixel (x, y) with z = from_depth[y, x], everything in double, products and sums in this order,
-// not contracted:
-//   c = (Kinv . (x, y, 1)) * z, a row being (k0 x + k1 y) + k2          reject unless z > 0 and c.z > 0
-//   w = c2w . (c, 1), a row being ((m0 c.x + m1 c.y) + m2 c.z) + m3      reject if w.w == 0, then w.xyz /= w.w
-//   p = P_to . (w.xyz, 1), rows as above                                 reject unless p.z > 0
-//   u = p.x / p.z, v = p.y / p.z                                         reject unless 0 <= u < Wt - 1 and 0 <= v < Ht - 1
+// cotr_depth_corrs, per source pixel (x, y) with z = from_depth[y, x]: the camera rule of camera.h (pixel -> world point -> pixel
+// (u, v) of the target and its depth p.z), then
 //   zt = to_depth[floor(v), floor(u)]                                    keep iff |zt - p.z| < 0.5
 // The kept rows (x, y, u, v) leave in SOURCE order (row-major pixels, or the order of the subset list): what the reference's
 // chained boolean masks return.  The compaction is a scan, not a slot counter, so two runs give the same bytes:
@@ -22,17 +18,13 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/cotr_hip.h"
+#include "camera.h"
+#include "handleless.h"
 
-namespace cotr_detail {
-int handleless_fail(int code, const char* msg);   // triangulate.hip: the per-thread message of cotr_raster_last_error()
-}
-using cotr_detail::handleless_fail;
+using namespace cotr_detail;
 
 #define RP_THREADS 256
 #define RP_WAVES (RP_THREADS / 64)
-#define RP_MAX_ITEMS 65535
-#define RP_MAX_SRC (1 << 28)
 #define CROP_MAX_OUT 4096
 #define CROP_ROWS 8
 static_assert(RP_THREADS % 64 == 0 && RP_WAVES == 4, "four ballots per block (scan and scatter read them as a group)");
@@ -72,30 +64,11 @@ __device__ __forceinline__ int source_index(const RpItem& it, int i) {
 __device__ __forceinline__ bool reproject(const RpItem& it, const double* __restrict__ cam, int idx, double& u, double& v) {
   u = v = 0.0;
   if (idx < 0 || !it.to || it.ht < 1 || it.wt < 1) return false;
-  const double x = (double)(idx % it.wf), y = (double)(idx / it.wf);
-  const double z = (double)it.from[idx];
-  if (!(z > 0.0)) return false;
-  const double* k = cam;
-  const double* m = cam + 9;
-  const double* p = cam + 25;
-  const double c0 = ((k[0] * x + k[1] * y) + k[2]) * z;
-  const double c1 = ((k[3] * x + k[4] * y) + k[5]) * z;
-  const double c2 = ((k[6] * x + k[7] * y) + k[8]) * z;
-  if (!(c2 > 0.0)) return false;
-  double w0 = ((m[0] * c0 + m[1] * c1) + m[2] * c2) + m[3];
-  double w1 = ((m[4] * c0 + m[5] * c1) + m[6] * c2) + m[7];
-  double w2 = ((m[8] * c0 + m[9] * c1) + m[10] * c2) + m[11];
-  const double w3 = ((m[12] * c0 + m[13] * c1) + m[14] * c2) + m[15];
-  if (w3 == 0.0) return false;
-  w0 /= w3, w1 /= w3, w2 /= w3;
-  const double p0 = ((p[0] * w0 + p[1] * w1) + p[2] * w2) + p[3];
-  const double p1 = ((p[4] * w0 + p[5] * w1) + p[6] * w2) + p[7];
-  const double p2 = ((p[8] * w0 + p[9] * w1) + p[10] * w2) + p[11];
-  if (!(p2 > 0.0)) return false;
-  u = p0 / p2, v = p1 / p2;
-  if (!(u >= 0.0 && u < (double)(it.wt - 1) && v >= 0.0 && v < (double)(it.ht - 1))) return false;   // false for NaN
+  double w[3], pz;
+  if (!pixel_to_world(cam, cam + 9, (double)(idx % it.wf), (double)(idx / it.wf), (double)it.from[idx], w)) return false;
+  if (!project_inside(cam + 25, w, it.wt, it.ht, u, v, pz)) return false;
   const double zt = (double)it.to[(size_t)(int)floor(v) * it.wt + (int)floor(u)];                      // inside: 0 <= floor < size - 1
-  return fabs(zt - p2) < 0.5;
+  return fabs(zt - pz) < 0.5;
 }
 
 // VALID: the predicate is depth > 0 and no camera is read
@@ -242,22 +215,16 @@ size_t scratch_for(int n, int max_src) {
   return (blocks * (RP_WAVES * sizeof(unsigned long long) + sizeof(int32_t)) + 15) / 16 * 16;
 }
 
-int launched() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return handleless_fail(COTR_ERR_HIP, hipGetErrorString(e));
-  return COTR_OK;
-}
-
 template <bool VALID>
 int compact(const uint64_t* ptrs, const int32_t* shapes, const double* cams, int n, int max_src, void* out, int cap, int32_t* counts,
             void* scratch, size_t scratch_bytes, cotr_stream stream) {
-  if (n < 0 || n > RP_MAX_ITEMS) return handleless_fail(COTR_ERR_ARG, "n must be in [0, 65535]");
+  if (n < 0 || n > MAX_ITEMS) return handleless_fail(COTR_ERR_ARG, "n must be in [0, 65535]");
   if (n == 0) return COTR_OK;
-  if (max_src < 1 || max_src > RP_MAX_SRC) return handleless_fail(COTR_ERR_ARG, "max_src must be in [1, 2^28]");
+  if (max_src < 1 || max_src > MAX_PIXELS) return handleless_fail(COTR_ERR_ARG, "max_src must be in [1, 2^28]");
   if (cap < 0 || (size_t)n * cap > ((size_t)1 << 31)) return handleless_fail(COTR_ERR_ARG, "cap must be >= 0 and n * cap <= 2^31");
   if (!ptrs || !shapes || (!VALID && !cams) || !counts || (cap > 0 && !out))
     return handleless_fail(COTR_ERR_ARG, "the item tables, counts and the output must not be NULL");
-  if ((uintptr_t)ptrs % 8 || (uintptr_t)cams % 8 || (uintptr_t)out % 16 || (uintptr_t)scratch % 16)
+  if (!aligned(ptrs, 8) || !aligned(cams, 8) || !aligned(out, 16) || !aligned(scratch, 16))
     return handleless_fail(COTR_ERR_ARG, "ptrs and cams must be 8-byte, the output and scratch 16-byte aligned");
   if (!scratch || scratch_bytes < scratch_for(n, max_src))
     return handleless_fail(COTR_ERR_ARG, "scratch is NULL or smaller than cotr_depth_corrs_scratch(n, max_src)");
@@ -279,7 +246,7 @@ int compact(const uint64_t* ptrs, const int32_t* shapes, const double* cams, int
 extern "C" {
 
 size_t cotr_depth_corrs_scratch(int n, int max_src) {
-  return n > 0 && n <= RP_MAX_ITEMS && max_src > 0 && max_src <= RP_MAX_SRC ? scratch_for(n, max_src) : 0;
+  return n > 0 && n <= MAX_ITEMS && max_src > 0 && max_src <= MAX_PIXELS ? scratch_for(n, max_src) : 0;
 }
 
 int cotr_depth_corrs(const uint64_t* ptrs, const int32_t* shapes, const double* cams, int n, int max_src, double* rows, int cap,
@@ -294,11 +261,11 @@ int cotr_depth_valid(const uint64_t* ptrs, const int32_t* shapes, int n, int max
 
 int cotr_crop_depth_nearest(const uint64_t* srcs, const int32_t* shapes, const int32_t* boxes, int n, float* dst, int out,
                             cotr_stream stream) {
-  if (n < 0 || n > RP_MAX_ITEMS) return handleless_fail(COTR_ERR_ARG, "n must be in [0, 65535]");
+  if (n < 0 || n > MAX_ITEMS) return handleless_fail(COTR_ERR_ARG, "n must be in [0, 65535]");
   if (n == 0) return COTR_OK;
   if (out < 1 || out > CROP_MAX_OUT) return handleless_fail(COTR_ERR_ARG, "out must be in [1, 4096]");
   if (!srcs || !shapes || !boxes || !dst) return handleless_fail(COTR_ERR_ARG, "srcs, shapes, boxes and dst must not be NULL");
-  if ((uintptr_t)srcs % 8) return handleless_fail(COTR_ERR_ARG, "srcs must be 8-byte aligned");
+  if (!aligned(srcs, 8)) return handleless_fail(COTR_ERR_ARG, "srcs must be 8-byte aligned");
   hipLaunchKernelGGL(crop_depth_nearest_kernel, dim3((out + CROP_ROWS - 1) / CROP_ROWS, n), dim3(RP_THREADS), (out + CROP_ROWS) * sizeof(int),
                      static_cast<hipStream_t>(stream), reinterpret_cast<const unsigned long long*>(srcs), shapes, boxes, dst, out);
   return launched();

@@ -28,9 +28,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
-#include "../../include/cotr_hip.h"
+#include "handleless.h"
+
+using namespace cotr_detail;
 
 #define TILE 16
 #define SETUP_THREADS 256
@@ -237,21 +238,6 @@ __global__ __launch_bounds__(256) void tri_resolve_kernel(const TriRec* __restri
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 namespace {
-thread_local char g_raster_error[256];   // the message of the last failed handle-less call on this thread (raster and guided.hip)
-}  // namespace
-
-namespace cotr_detail {
-int handleless_fail(int code, const char* msg) {
-  snprintf(g_raster_error, sizeof g_raster_error, "%s", msg);
-  return code;
-}
-}  // namespace cotr_detail
-
-namespace {
-
-int raster_fail(int code, const char* msg) { return cotr_detail::handleless_fail(code, msg); }
-
-size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
 
 struct Layout {
   size_t ids, recs, local, bsum, bytes;
@@ -279,25 +265,23 @@ const char* check_shape(int n_tris, int H, int W) {
 
 extern "C" {
 
-const char* cotr_raster_last_error(void) { return g_raster_error; }
-
 int cotr_raster_mesh_scratch_bytes(int n_tris, int H, int W, size_t* bytes) {
-  if (!bytes) return raster_fail(COTR_ERR_ARG, "cotr_raster_mesh_scratch_bytes: bytes is NULL");
-  if (const char* e = check_shape(n_tris, H, W)) return raster_fail(COTR_ERR_ARG, e);
+  if (!bytes) return handleless_fail(COTR_ERR_ARG, "cotr_raster_mesh_scratch_bytes: bytes is NULL");
+  if (const char* e = check_shape(n_tris, H, W)) return handleless_fail(COTR_ERR_ARG, e);
   *bytes = layout(n_tris, H, W).bytes;
   return COTR_OK;
 }
 
 int cotr_raster_mesh(const float* verts, int n_verts, const float* attrs, const int32_t* tris, int n_tris, int H, int W,
                      float* out, uint8_t* mask, void* scratch, size_t scratch_bytes, cotr_stream stream) {
-  if (const char* e = check_shape(n_tris, H, W)) return raster_fail(COTR_ERR_ARG, e);
-  if (n_verts < 0) return raster_fail(COTR_ERR_ARG, "n_verts < 0");
-  if (!out || !scratch) return raster_fail(COTR_ERR_ARG, "out and scratch must not be NULL");
-  if (n_tris > 0 && (!verts || !attrs || !tris)) return raster_fail(COTR_ERR_ARG, "verts, attrs and tris must not be NULL");
-  if ((uintptr_t)scratch % 16 != 0 || (uintptr_t)out % 8 != 0)
-    return raster_fail(COTR_ERR_ARG, "scratch must be 16-byte and out 8-byte aligned");
+  if (const char* e = check_shape(n_tris, H, W)) return handleless_fail(COTR_ERR_ARG, e);
+  if (n_verts < 0) return handleless_fail(COTR_ERR_ARG, "n_verts < 0");
+  if (!out || !scratch) return handleless_fail(COTR_ERR_ARG, "out and scratch must not be NULL");
+  if (n_tris > 0 && (!verts || !attrs || !tris)) return handleless_fail(COTR_ERR_ARG, "verts, attrs and tris must not be NULL");
+  if (!aligned(scratch, 16) || !aligned(out, 8))
+    return handleless_fail(COTR_ERR_ARG, "scratch must be 16-byte and out 8-byte aligned");
   const Layout l = layout(n_tris, H, W);
-  if (scratch_bytes < l.bytes) return raster_fail(COTR_ERR_ARG, "scratch is smaller than cotr_raster_mesh_scratch_bytes");
+  if (scratch_bytes < l.bytes) return handleless_fail(COTR_ERR_ARG, "scratch is smaller than cotr_raster_mesh_scratch_bytes");
   hipStream_t s = static_cast<hipStream_t>(stream);
   char* base = static_cast<char*>(scratch);
   int* ids = reinterpret_cast<int*>(base + l.ids);
@@ -313,9 +297,7 @@ int cotr_raster_mesh(const float* verts, int n_verts, const float* attrs, const 
   }
   hipLaunchKernelGGL(tri_resolve_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s, recs, ids, attrs, n_tris, H, W,
                      reinterpret_cast<float2*>(out), mask);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return raster_fail(COTR_ERR_HIP, hipGetErrorString(e));
-  return COTR_OK;
+  return launched();
 }
 
 }  // extern "C"

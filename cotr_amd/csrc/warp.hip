@@ -20,12 +20,9 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "../../include/cotr_hip.h"
+#include "handleless.h"
 
-namespace cotr_detail {
-int handleless_fail(int code, const char* msg);   // triangulate.hip: the per-thread message of cotr_raster_last_error()
-}
-using cotr_detail::handleless_fail;
+using namespace cotr_detail;
 
 #ifndef WARP_TW
 #define WARP_TW 64             // tile width and height in destination pixels (what was tried)
@@ -278,12 +275,6 @@ const char* warp_check(const uint8_t* src, int Hs, int Ws, int C, int Hd, int Wd
 
 dim3 warp_grid(int Hd, int Wd) { return dim3((Wd + WARP_TW - 1) / WARP_TW, (Hd + WARP_TH - 1) / WARP_TH); }
 
-int warp_launched() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return handleless_fail(COTR_ERR_HIP, hipGetErrorString(e));
-  return COTR_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -292,11 +283,11 @@ int cotr_warp_map(const uint8_t* src, int Hs, int Ws, int C, const void* map, in
                   uint8_t* cover, const uint8_t* background, cotr_stream stream) {
   if (const char* e = warp_check(src, Hs, Ws, C, Hd, Wd, dst, background)) return handleless_fail(COTR_ERR_ARG, e);
   if (!map) return handleless_fail(COTR_ERR_ARG, "map must not be NULL");
-  if ((uintptr_t)map % (map_is_f64 ? 16 : 8) != 0)
+  if (!aligned(map, map_is_f64 ? 16 : 8))
     return handleless_fail(COTR_ERR_ARG, "a float32 map must be 8-byte and a float64 map 16-byte aligned");
   hipLaunchKernelGGL(warp_map_kernel, warp_grid(Hd, Wd), dim3(WARP_THREADS), 0, static_cast<hipStream_t>(stream), src, Hs, Ws, C,
                      map, map_is_f64 ? 1 : 0, Hd, Wd, dst, cover, background);
-  return warp_launched();
+  return launched();
 }
 
 int cotr_warp_perspective(const uint8_t* src, int Hs, int Ws, int C, const double* M, int Hd, int Wd, uint8_t* dst,
@@ -310,7 +301,7 @@ int cotr_warp_perspective(const uint8_t* src, int Hs, int Ws, int C, const doubl
   }
   hipLaunchKernelGGL(warp_perspective_kernel, warp_grid(Hd, Wd), dim3(WARP_THREADS), 0, static_cast<hipStream_t>(stream), src, Hs,
                      Ws, C, m, Hd, Wd, dst, cover, background);
-  return warp_launched();
+  return launched();
 }
 
 }  // extern "C"

@@ -10,13 +10,13 @@ builders reads a count back to the host.
 A capture is a ``Capture(image, depth, K, c2w)``: ``image`` uint8 [H, W, 3] and ``depth`` float32 [H, W] (device tensors,
 or numpy arrays that get uploaded), ``K`` 3 x 3 and ``c2w`` 4 x 4 float64 on the host.  A CPU tensor is refused: there is
 no CPU fallback."""
-import ctypes
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import check_op, on, ptr
 
 OUT = 256              # constants.MAX_SIZE of the reference
 MAX_TRY = 100          # get_seed_corr's max_try
@@ -29,16 +29,6 @@ class Capture(NamedTuple):
     depth: object      # float32 [H, W]
     K: object          # float64 3 x 3 (host)
     c2w: object        # float64 4 x 4 camera-to-world (host)
-
-
-def _check(rc, what):
-    if rc != 0:
-        msg = _lib.load_library().cotr_raster_last_error()
-        raise _lib.CotrHipError(f'{what} failed (code {rc}): {msg.decode() if msg else "?"}')
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else None)
 
 
 def _check_capture(cap, what='capture', need_image=True):
@@ -62,7 +52,7 @@ def _check_capture(cap, what='capture', need_image=True):
     if len(depth.shape) != 2 or depth.shape[0] < 1 or depth.shape[1] < 1:
         raise ValueError(f'{what}.depth must be [H, W], got shape {tuple(depth.shape)}')
     H, W = int(depth.shape[0]), int(depth.shape[1])
-    if H * W > 1 << 28:
+    if H * W > 1 << 28:   # MAX_PIXELS of csrc/handleless.h
         raise ValueError(f'{what}.depth: at most 2^28 pixels, got {H} x {W}')
     if image is not None:
         if image.dtype not in (np.uint8, torch.uint8):
@@ -84,11 +74,6 @@ def _device_of(caps):
     return devs.pop() if devs else torch.device('cuda', torch.cuda.current_device())
 
 
-def _on(x, device):
-    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-    return t.to(device).contiguous()
-
-
 def _cam_rows(from_cap, to_cap):
     """Kinv_from | c2w_from | P_to = K_to . w2c_to[0:3] as 37 float64, formed in numpy where the reference forms them
     (pcd_projector.py:74, :143)"""
@@ -107,11 +92,11 @@ def _compact(valid_only, ptrs, shapes, cams, n, max_src, cap, device, zero=True)
     scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
         if valid_only:
-            _check(lib.cotr_depth_valid(_ptr(ptrs), _ptr(shapes), n, max_src, _ptr(out), cap, _ptr(counts), _ptr(scratch), nbytes,
-                                        _lib.current_stream_ptr()), 'cotr_depth_valid')
+            check_op(lib.cotr_depth_valid(ptr(ptrs), ptr(shapes), n, max_src, ptr(out), cap, ptr(counts), ptr(scratch), nbytes,
+                                          _lib.current_stream_ptr()), 'cotr_depth_valid')
         else:
-            _check(lib.cotr_depth_corrs(_ptr(ptrs), _ptr(shapes), _ptr(cams), n, max_src, _ptr(out), cap, _ptr(counts), _ptr(scratch),
-                                        nbytes, _lib.current_stream_ptr()), 'cotr_depth_corrs')
+            check_op(lib.cotr_depth_corrs(ptr(ptrs), ptr(shapes), ptr(cams), n, max_src, ptr(out), cap, ptr(counts), ptr(scratch),
+                                          nbytes, _lib.current_stream_ptr()), 'cotr_depth_corrs')
     return out, counts
 
 
@@ -160,7 +145,7 @@ def depth_corrs(from_cap, to_cap, subset=None, cap=None):
         _check_capture(f, f'from_cap[{i}]', need_image=False)
         _check_capture(t, f'to_cap[{i}]', need_image=False)
     device = _device_of(froms + tos)
-    fd, td = [_on(f.depth, device) for f in froms], [_on(t.depth, device) for t in tos]
+    fd, td = [on(f.depth, device) for f in froms], [on(t.depth, device) for t in tos]
     sub = [None if s is None else _subset_tensor(s, d.numel(), device) for s, d in zip(subsets, fd)]
     if any(s is not None and s.numel() == 0 for s in sub):
         raise ValueError('an empty subset')
@@ -191,16 +176,16 @@ def _crop_depths(depths, boxes, out):
     shapes = torch.tensor([tuple(d.shape) for d in depths], dtype=torch.int32).to(device)
     dst = torch.empty((n, out, out), dtype=torch.float32, device=device)
     with torch.cuda.device(device):
-        _check(_lib.load_library().cotr_crop_depth_nearest(_ptr(srcs), _ptr(shapes), _ptr(boxes), n, _ptr(dst), out,
-                                                           _lib.current_stream_ptr()), 'cotr_crop_depth_nearest')
+        check_op(_lib.load_library().cotr_crop_depth_nearest(ptr(srcs), ptr(shapes), ptr(boxes), n, ptr(dst), out,
+                                                             _lib.current_stream_ptr()), 'cotr_crop_depth_nearest')
     return dst
 
 
 def _crop_images(img_a, img_b, boxes6, out_slot, max_size):
     """cotr_crop_resize_pairs for ONE pair: boxes6 int32 [1, 6] on the device -> out_slot [1, 3, 256, 512] (normalised)"""
     with torch.cuda.device(img_a.device):
-        rc = _lib.load_library().cotr_crop_resize_pairs(_ptr(img_a), img_a.shape[0], img_a.shape[1], _ptr(img_b), img_b.shape[0],
-                                                        img_b.shape[1], _ptr(boxes6), 1, _ptr(out_slot), max_size,
+        rc = _lib.load_library().cotr_crop_resize_pairs(ptr(img_a), img_a.shape[0], img_a.shape[1], ptr(img_b), img_b.shape[0],
+                                                        img_b.shape[1], ptr(boxes6), 1, ptr(out_slot), max_size,
                                                         _lib.current_stream_ptr())
     if rc != 0:
         raise _lib.CotrHipError(f'cotr_crop_resize_pairs failed (code {rc})')
@@ -232,14 +217,14 @@ def crop_capture(cap, box, out=OUT):
     if not 1 <= int(out) <= 4096:
         raise ValueError('out must be in [1, 4096]')
     device = _device_of([cap])
-    depth = _on(cap.depth, device)
+    depth = on(cap.depth, device)
     boxes = torch.tensor([[x, y, size]], dtype=torch.int32).to(device)
     zdepth = _crop_depths([depth], boxes, int(out))[0]
     image = None
     if cap.image is not None:
         if out != OUT or size < 2 or size > 7936:
             raise ValueError('the image crop resizes boxes of 2 ... 7936 pixels to 256 x 256 only')
-        img = _on(cap.image, device)
+        img = on(cap.image, device)
         sbs = torch.empty((1, 3, OUT, 2 * OUT), dtype=torch.float32, device=device)
         _crop_images(img, img, torch.cat([boxes, boxes], 1).contiguous(), sbs, size)
         mean, std = (torch.tensor(v, device=device).view(3, 1, 1) for v in (_MEAN, _STD))
@@ -265,7 +250,7 @@ def _rand_on(rand, batch, num_kp, generator, device, need):
         t = rand[k]
         if torch.is_tensor(t) and not t.is_cuda:
             raise _lib.CotrHipError(f'rand[{k!r}]: got a CPU tensor; pass a numpy array or move the tensor with .cuda()')
-        t = _on(np.asarray(t, dtype=np.float64) if not torch.is_tensor(t) else t, device).double()
+        t = on(np.asarray(t, dtype=np.float64) if not torch.is_tensor(t) else t, device).double()
         want = _RAND_SHAPES[k](batch, num_kp, t.shape[1] if k == 'seed' and t.dim() == 2 else MAX_TRY)
         if tuple(t.shape) != want:
             raise ValueError(f'rand[{k!r}] must have shape {want}, got {tuple(t.shape)}')
@@ -335,7 +320,7 @@ def _validate(query_caps, nn_caps, num_kp):
 
 def _upload(query_caps, nn_caps):
     device = _device_of(query_caps + nn_caps)
-    up = lambda c: Capture(_on(c.image, device), _on(c.depth, device), np.asarray(c.K), np.asarray(c.c2w))   # noqa: E731
+    up = lambda c: Capture(on(c.image, device), on(c.depth, device), np.asarray(c.K), np.asarray(c.c2w))   # noqa: E731
     return [up(c) for c in query_caps], [up(c) for c in nn_caps], device
 
 

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .triangulate import _check
+from .._lib import check_op, on, ptr
 
 
 def _device(device):
@@ -25,10 +25,6 @@ def _points(p, what):
     if t.dim() != 2 or t.shape[1] != 2:
         raise ValueError(f'{what} must be [N, 2], got shape {tuple(t.shape)}')
     return t.to(dtype=torch.float64)
-
-
-def _on(t, device):
-    return t.to(device=device).contiguous()
 
 
 def nearest_mutual(pred_ab, kp_b, pred_ba, kp_a, device=None):
@@ -44,18 +40,17 @@ def nearest_mutual(pred_ab, kp_b, pred_ba, kp_a, device=None):
     if na == 0 or nb == 0:
         raise ValueError('nearest keypoints need at least one keypoint on each side')
     device = _device(device)
-    pred_ab, kp_b, pred_ba, kp_a = (_on(t, device) for t in (pred_ab, kp_b, pred_ba, kp_a))
+    pred_ab, kp_b, pred_ba, kp_a = (on(t, device) for t in (pred_ab, kp_b, pred_ba, kp_a))
     lib = _lib.load_library()
     nbytes = ctypes.c_size_t()
-    _check(lib.cotr_nearest_mutual_scratch_bytes(na, nb, ctypes.byref(nbytes)), 'cotr_nearest_mutual_scratch_bytes')
+    check_op(lib.cotr_nearest_mutual_scratch_bytes(na, nb, ctypes.byref(nbytes)), 'cotr_nearest_mutual_scratch_bytes')
     scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
     idx_ab = torch.empty(na, dtype=torch.int32, device=device)
     idx_ba = torch.empty(nb, dtype=torch.int32, device=device)
     mutual = torch.empty(na, dtype=torch.uint8, device=device)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
     with torch.cuda.device(device):
-        _check(lib.cotr_nearest_mutual(ptr(pred_ab), ptr(kp_b), ptr(pred_ba), ptr(kp_a), na, nb, ptr(idx_ab), ptr(idx_ba),
-                                       ptr(mutual), ptr(scratch), nbytes.value, _lib.current_stream_ptr()), 'cotr_nearest_mutual')
+        check_op(lib.cotr_nearest_mutual(ptr(pred_ab), ptr(kp_b), ptr(pred_ba), ptr(kp_a), na, nb, ptr(idx_ab), ptr(idx_ba),
+                                         ptr(mutual), ptr(scratch), nbytes.value, _lib.current_stream_ptr()), 'cotr_nearest_mutual')
     return idx_ab, idx_ba, mutual.bool()
 
 
@@ -90,10 +85,10 @@ def ransac_fundamental(points1, points2, threshold=3.0, confidence=0.99, max_ite
     if not 0 < confidence < 1:
         raise ValueError(f'confidence must be in (0, 1), got {confidence}')
     device = _device(device)
-    p1, p2 = _on(p1, device), _on(p2, device)
+    p1, p2 = on(p1, device), on(p2, device)
     lib = _lib.load_library()
     nbytes = ctypes.c_size_t()
-    _check(lib.cotr_ransac_fundamental_scratch_bytes(n, max_iters, ctypes.byref(nbytes)), 'cotr_ransac_fundamental_scratch_bytes')
+    check_op(lib.cotr_ransac_fundamental_scratch_bytes(n, max_iters, ctypes.byref(nbytes)), 'cotr_ransac_fundamental_scratch_bytes')
     scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
     F = torch.empty(9, dtype=torch.float64, device=device)
     mask = torch.empty(n, dtype=torch.uint8, device=device)
@@ -103,12 +98,11 @@ def ransac_fundamental(points1, points2, threshold=3.0, confidence=0.99, max_ite
         out.update(samples=torch.empty((max_iters, 7), dtype=torch.int32, device=device),
                    hyp_F=torch.empty((3 * max_iters, 9), dtype=torch.float64, device=device),
                    hyp_count=torch.empty(3 * max_iters, dtype=torch.int32, device=device))
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)   # noqa: E731
     with torch.cuda.device(device):
-        _check(lib.cotr_ransac_fundamental(ptr(p1), ptr(p2), n, float(threshold), float(confidence), int(max_iters),
-                                           int(seed) & ((1 << 64) - 1), ptr(F), ptr(mask), ptr(info), ptr(out.get('hyp_F')),
-                                           ptr(out.get('hyp_count')), ptr(out.get('samples')), ptr(scratch), nbytes.value,
-                                           _lib.current_stream_ptr()), 'cotr_ransac_fundamental')
+        check_op(lib.cotr_ransac_fundamental(ptr(p1), ptr(p2), n, float(threshold), float(confidence), int(max_iters),
+                                             int(seed) & ((1 << 64) - 1), ptr(F), ptr(mask), ptr(info), ptr(out.get('hyp_F')),
+                                             ptr(out.get('hyp_count')), ptr(out.get('samples')), ptr(scratch), nbytes.value,
+                                             _lib.current_stream_ptr()), 'cotr_ransac_fundamental')
     out['F'] = F.view(3, 3)
     out['mask'] = mask.bool()
     return out

@@ -10,12 +10,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-
-
-def _check(rc, what):
-    if rc != 0:
-        msg = _lib.load_library().cotr_raster_last_error()
-        raise _lib.CotrHipError(f'{what} failed (code {rc}): {msg.decode() if msg else "?"}')
+from .._lib import check_op, ptr
 
 
 def raster_mesh(verts, attrs, tris, H, W, device=None):
@@ -30,15 +25,13 @@ def raster_mesh(verts, attrs, tris, H, W, device=None):
                            dtype=torch.int32).to(device).contiguous()
     n_tris = tris.numel() // 3
     nbytes = ctypes.c_size_t()
-    _check(lib.cotr_raster_mesh_scratch_bytes(n_tris, H, W, ctypes.byref(nbytes)), 'cotr_raster_mesh_scratch_bytes')
+    check_op(lib.cotr_raster_mesh_scratch_bytes(n_tris, H, W, ctypes.byref(nbytes)), 'cotr_raster_mesh_scratch_bytes')
     scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
     out = torch.empty((H, W, 2), dtype=torch.float32, device=device)
     mask = torch.empty((H, W), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
-        _check(lib.cotr_raster_mesh(ctypes.c_void_p(verts.data_ptr()), verts.shape[0], ctypes.c_void_p(attrs.data_ptr()),
-                                    ctypes.c_void_p(tris.data_ptr()), n_tris, H, W, ctypes.c_void_p(out.data_ptr()),
-                                    ctypes.c_void_p(mask.data_ptr()), ctypes.c_void_p(scratch.data_ptr()), nbytes.value,
-                                    _lib.current_stream_ptr()), 'cotr_raster_mesh')
+        check_op(lib.cotr_raster_mesh(ptr(verts), verts.shape[0], ptr(attrs), ptr(tris), n_tris, H, W, ptr(out), ptr(mask), ptr(scratch),
+                                      nbytes.value, _lib.current_stream_ptr()), 'cotr_raster_mesh')
     return out, mask.bool()
 
 

@@ -15,7 +15,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .triangulate import _check, triangulate_corr
+from .._lib import check_op, on, ptr
+from .triangulate import triangulate_corr
 
 MAX_SIDE = 16384
 
@@ -71,17 +72,6 @@ def _check_background(background, Hd, Wd, C, img_ndim):
                          f'got {tuple(background.shape)}')
 
 
-def _on(x, device, align=1):
-    """contiguous on ``device``, its address a multiple of ``align``"""
-    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-    t = t.to(device).contiguous()
-    return t.clone() if t.data_ptr() % align else t
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else None)
-
-
 def _finish(dst, cover, img_ndim, return_cover, as_tensor):
     if img_ndim == 2:
         dst = dst[..., 0]
@@ -107,13 +97,13 @@ def warp_by_map(img, map, background=None, return_cover=False, as_tensor=False):
     _check_background(background, Hd, Wd, C, len(img.shape))
     device = _pick_device(img, map, background)
     is_f64 = map.dtype in (np.float64, torch.float64)
-    src, m = _on(img, device), _on(map, device, 16 if is_f64 else 8)
-    bg = None if background is None else _on(background, device)
+    src, m = on(img, device), on(map, device, 16 if is_f64 else 8)
+    bg = None if background is None else on(background, device)
     dst = torch.empty((Hd, Wd, C), dtype=torch.uint8, device=device)
     cover = torch.empty((Hd, Wd), dtype=torch.uint8, device=device) if return_cover else None
     with torch.cuda.device(device):
-        _check(_lib.load_library().cotr_warp_map(_ptr(src), Hs, Ws, C, _ptr(m), int(is_f64), Hd, Wd, _ptr(dst), _ptr(cover),
-                                                 _ptr(bg), _lib.current_stream_ptr()), 'cotr_warp_map')
+        check_op(_lib.load_library().cotr_warp_map(ptr(src), Hs, Ws, C, ptr(m), int(is_f64), Hd, Wd, ptr(dst), ptr(cover),
+                                                   ptr(bg), _lib.current_stream_ptr()), 'cotr_warp_map')
     return _finish(dst, cover, len(img.shape), return_cover, as_tensor)
 
 
@@ -153,14 +143,14 @@ def warp_perspective(img, M, dsize, inverse_map=False, background=None, return_c
     _check_background(background, Hd, Wd, C, len(img.shape))
     Minv = np.ascontiguousarray(_matrix(M) if inverse_map else invert_perspective(M))
     device = _pick_device(img, background)
-    src = _on(img, device)
-    bg = None if background is None else _on(background, device)
+    src = on(img, device)
+    bg = None if background is None else on(background, device)
     dst = torch.empty((Hd, Wd, C), dtype=torch.uint8, device=device)
     cover = torch.empty((Hd, Wd), dtype=torch.uint8, device=device) if return_cover else None
     with torch.cuda.device(device):
-        _check(_lib.load_library().cotr_warp_perspective(_ptr(src), Hs, Ws, C, Minv.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                         Hd, Wd, _ptr(dst), _ptr(cover), _ptr(bg), _lib.current_stream_ptr()),
-               'cotr_warp_perspective')
+        check_op(_lib.load_library().cotr_warp_perspective(ptr(src), Hs, Ws, C, Minv.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                           Hd, Wd, ptr(dst), ptr(cover), ptr(bg), _lib.current_stream_ptr()),
+                 'cotr_warp_perspective')
     return _finish(dst, cover, len(img.shape), return_cover, as_tensor)
 
 
@@ -219,8 +209,8 @@ def warp_by_corr(img_a, img_b, corrs, alpha=0.5, as_tensor=False, simplices=None
     device = _pick_device(img_a, img_b)
     with torch.cuda.device(device):
         dense = triangulate_corr(corrs, img_a.shape, img_b.shape, simplices=simplices, as_tensor=True)
-        warped = warp_by_map(_on(img_b, device), dense, as_tensor=True)
-        a = _on(img_a, device)
+        warped = warp_by_map(on(img_b, device), dense, as_tensor=True)
+        a = on(img_a, device)
         a = a if a.dim() == 3 else a[..., None]
         w = warped if warped.dim() == 3 else warped[..., None]
         overlay = (w.double() / 255 * alpha + a.double() / 255 * (1 - alpha)).float()   # the demo's float64 expression, rounded once

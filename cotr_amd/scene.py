@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .data import _check, _check_capture, _device_of, _on, _pick, _ptr
+from ._lib import check_op, on, ptr
+from .data import _check_capture, _device_of, _pick
 
 # Canvas scratch of one overlap_pairs call: one uint32 per pixel of the largest capture per pair in flight.  256 MiB holds
 # 218 pairs of 480 x 640 captures, so a scene's matrix takes a handful of tiles and the per-tile launches do not show;
@@ -70,8 +71,8 @@ def _world_points(caps, shapes, depths, need, device):
         ptrs, shp = _tables([depths[i] for i in sel], [xyz[i] for i in sel], [shapes[i] for i in sel], device)
         cams = torch.from_numpy(cams).to(device)
         with torch.cuda.device(device):
-            _check(_lib.load_library().cotr_world_points(_ptr(ptrs), _ptr(shp), _ptr(cams), len(sel), max(h * w for h, w in shapes),
-                                                         _lib.current_stream_ptr()), 'cotr_world_points')
+            check_op(_lib.load_library().cotr_world_points(ptr(ptrs), ptr(shp), ptr(cams), len(sel), max(h * w for h, w in shapes),
+                                                           _lib.current_stream_ptr()), 'cotr_world_points')
     return xyz
 
 
@@ -82,7 +83,7 @@ def world_points(caps):
     Rule: DESIGN.md 3k step 1 (float64 arithmetic, the result rounded to float32)."""
     caps, shapes = _check_caps(caps)
     device = _device_of(caps)
-    depths = [_on(c.depth, device) for c in caps]
+    depths = [on(c.depth, device) for c in caps]
     xyz = _world_points(caps, shapes, depths, [True] * len(caps), device)
     return [(x, ~torch.isnan(x[:, 2])) for x in xyz]
 
@@ -106,7 +107,7 @@ def overlap_pairs(caps, pairs, max_pairs_in_flight=None):
     if n == 0:
         return ratio, counts
     lib = _lib.load_library()
-    depths = [_on(c.depth, device) for c in caps]
+    depths = [on(c.depth, device) for c in caps]
     need = [True] * len(caps) if host_pairs is None else [bool(x) for x in np.isin(np.arange(len(caps)), host_pairs[:, 1])]
     xyz = _world_points(caps, shapes, depths, need, device)
     max_px = max(h * w for h, w in shapes)
@@ -119,8 +120,8 @@ def overlap_pairs(caps, pairs, max_pairs_in_flight=None):
     proj = torch.from_numpy(proj).to(device)
     dpairs = dev_pairs.to(device) if dev_pairs is not None else torch.from_numpy(host_pairs).to(device)
     with torch.cuda.device(device):
-        _check(lib.cotr_overlap_pairs(_ptr(ptrs), _ptr(shp), _ptr(proj), len(caps), _ptr(dpairs), n, max_px, _ptr(ratio), _ptr(counts),
-                                      _ptr(scratch), nbytes, _lib.current_stream_ptr()), 'cotr_overlap_pairs')
+        check_op(lib.cotr_overlap_pairs(ptr(ptrs), ptr(shp), ptr(proj), len(caps), ptr(dpairs), n, max_px, ptr(ratio), ptr(counts),
+                                        ptr(scratch), nbytes, _lib.current_stream_ptr()), 'cotr_overlap_pairs')
     return ratio, counts
 
 
@@ -210,7 +211,7 @@ def draw_pairs(pool, counts, u):
         raise _lib.CotrHipError('u: got a CPU tensor; pass a numpy array or move the tensor with .cuda()')
     if pool.dim() != 2 or tuple(counts.shape) != (pool.shape[0],):
         raise ValueError('pool must be [N, k] and counts [N]')
-    u = _on(np.asarray(u, dtype=np.float64) if not torch.is_tensor(u) else u, pool.device).double()
+    u = on(np.asarray(u, dtype=np.float64) if not torch.is_tensor(u) else u, pool.device).double()
     if tuple(u.shape) != (pool.shape[0],):
         raise ValueError(f'u must have shape ({pool.shape[0]},), got {tuple(u.shape)}')
     return torch.gather(pool, 1, _pick(u.unsqueeze(1), counts))[:, 0]

@@ -16,22 +16,19 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SHAPES = ['256x4', '128x8', '64x16', '32x32', '16x64', '64x4', '32x8']
-STUB = ('#include <stdio.h>\nnamespace cotr_detail { int handleless_fail(int code, const char* msg) '
-        '{ fprintf(stderr, "warp: %s\\n", msg); return code; } }\n')
 
 
 def build_variants():
     from cotr_amd.build import CSRC, _hipcc
     d = os.path.join(ROOT, 'build', 'warp_tiles')
     os.makedirs(d, exist_ok=True)
-    stub = os.path.join(d, 'stub.cpp')
-    open(stub, 'w').write(STUB)
     libs = {}
     for v in SHAPES:
         tw, th = v.split('x')
         libs[v] = os.path.join(d, f'libwarp_{v}.so')
         subprocess.run([_hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-mcode-object-version=5', '-ffp-contract=off',
-                        f'-DWARP_TW={tw}', f'-DWARP_TH={th}', '-shared', '-o', libs[v], os.path.join(CSRC, 'warp.hip'), stub], check=True)
+                        f'-DWARP_TW={tw}', f'-DWARP_TH={th}', '-shared', '-o', libs[v], os.path.join(CSRC, 'warp.hip'),
+                        os.path.join(CSRC, 'handleless.hip')], check=True)
     return libs
 
 
