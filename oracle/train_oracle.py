@@ -3,7 +3,7 @@
 TEST INFRASTRUCTURE ONLY (see ``oracle/__init__.py``): the checker of the HIP training step (``cotr_amd/training.py``).
 
 The loss is ``COTRTrainer.train_batch`` (COTR/trainers/cotr_trainer.py:124-142) with ``cycle_consis`` and
-``bidirectional`` on, dropout 0, on the oracle's forward (``cotr_oracle.cotr_forward_grad``):
+``bidirectional`` on, dropout 0 (or the caller's masks: ``dropout``), on the oracle's forward (``cotr_oracle.cotr_forward_grad``):
 
     pred  = f(img, query)                    loss = mse(pred, target) + mse(cycle[mask], query[mask])
     cycle = f(img, pred.detach())            mask = |cycle - query| < 10/256
@@ -27,14 +27,17 @@ from . import cotr_oracle
 CYCLE_RADIUS = 10 / 256       # cotr_trainer.py:131 (10 / MAX_SIZE)
 
 
-def train_loss_and_grads(sd, img, query, target, trainable_names, dtype=torch.float64, pairs_per_chunk=2):
+def train_loss_and_grads(sd, img, query, target, trainable_names, dtype=torch.float64, pairs_per_chunk=2, dropout=None):
     """-> namespace with ``loss`` (the reference's value, float), ``pred_loss``, ``cycle_loss``, ``pred`` [B,Q,2],
     ``cycle`` [B,Q,2], ``mask`` [B,Q] (bool), ``margin`` (the smallest | |cycle - query| - 10/256 | over all queries: how
     far the mask is from flipping), ``grads`` {name: d loss / d weight} and ``cycle_grads`` {name: d cycle_loss / d weight}.
 
     ``trainable_names``: the parameters that train (a HIP model's ``named_parameters()`` with ``requires_grad``).  Those
     the forward never touches (the decoder's ``norm1``) get no entry, as they get no ``.grad`` in a backward pass.
-    ``pairs_per_chunk``: pairs per forward / backward (memory); the result does not depend on it beyond rounding."""
+    ``pairs_per_chunk``: pairs per forward / backward (memory); the result does not depend on it beyond rounding.
+    ``dropout``: None, or the training-mode dropouts with the caller's masks: ``dropout(site, tensor) -> tensor * mask factor``
+    as in ``cotr_oracle.cotr_encode``, the site prefixed with the pass and the chunk's first pair, ``'pred.<lo>.'`` or
+    ``'cycle.<lo>.'`` (e.g. ``'cycle.2.decoder.0.attn'``: the tensor holds pairs lo .. of that pass)."""
     sd = {k: v.detach().to(dtype) for k, v in sd.items()}
     names = list(trainable_names)
     params = [sd[n].requires_grad_() for n in names]
@@ -50,10 +53,13 @@ def train_loss_and_grads(sd, img, query, target, trainable_names, dtype=torch.fl
     preds, cycles = [], []
     for lo in range(0, bsz, pairs_per_chunk):
         hi = min(bsz, lo + pairs_per_chunk)
-        pred = cotr_oracle.cotr_forward_grad(sd, img[lo:hi], query[lo:hi], dtype=dtype)
+        kw = [{}, {}]
+        if dropout is not None:
+            kw = [{'dropout': (lambda site, t, pre=f'{which}.{lo}.': dropout(pre + site, t))} for which in ('pred', 'cycle')]
+        pred = cotr_oracle.cotr_forward_grad(sd, img[lo:hi], query[lo:hi], dtype=dtype, **kw[0])
         accumulate(acc_pred, ((pred - target[lo:hi]) ** 2).sum())
         pred = pred.detach()
-        cycle = cotr_oracle.cotr_forward_grad(sd, img[lo:hi], pred, dtype=dtype)
+        cycle = cotr_oracle.cotr_forward_grad(sd, img[lo:hi], pred, dtype=dtype, **kw[1])
         mask = torch.norm(cycle.detach() - query[lo:hi], dim=-1) < CYCLE_RADIUS
         accumulate(acc_cycle, ((cycle - query[lo:hi])[mask] ** 2).sum())
         preds.append(pred)

@@ -1,6 +1,8 @@
 """Op-level parity of the training-step kernels (cotr_amd/csrc/train.hip, attention_train.hip) through their autograd
 wrappers (cotr_amd/train_ops.py): forward values and every gradient against the same op written with torch in fp64 on the
-CPU.  Dropout is 0 here (exact comparison); the masks' forward / backward consistency is pinned end to end by
+CPU.  Dropout is 0 in the fp64 comparisons of this file; the same comparisons with dropout on, the reference given the kernels'
+exact masks (tests/dropout_oracle.py restates them on the host), are in tests/test_train_dropout_fp64_gpu.py.  The masks'
+forward / backward consistency is also pinned end to end by
 tests/test_training_gpu.py::test_dropout_masks_are_consistent_between_forward_and_backward."""
 import math
 
@@ -141,8 +143,9 @@ def test_attention_forward_backward(nb, nq, packed, form):
 @pytest.mark.parametrize('nb,nq,packed', [(2, 512, True), (3, 200, False), (1, 33, False), (16, 200, False), (8, 100, False)])
 def test_attention_backward_forms_agree_with_dropout(nb, nq, packed):
     """Dropout on the probabilities (p = 0.1): the two forms of the backward kernels regenerate the same mask from (seed, element
-    index) and give the same dq / dk / dv up to summation order (the dropout path has no closed-form torch reference: the mask is
-    this library's own counter-based one; checked statistically below and by finite differences in test_training_gpu.py)."""
+    index) and give the same dq / dk / dv up to summation order.  (The mask is this library's own counter-based one, so torch's dropout
+    is no reference for it; tests/test_train_dropout_fp64_gpu.py compares every form with an fp64 reference that applies the same
+    mask, restated on the host.  Here: the forms against each other; statistics below; finite differences in test_training_gpu.py.)"""
     from cotr_amd import _lib
     g = _g(nb * 77 + nq)
     q, k, v = torch.randn(nb * nq, 256, generator=g), torch.randn(nb * 512, 256, generator=g), torch.randn(nb * 512, 256, generator=g)
