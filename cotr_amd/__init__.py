@@ -17,7 +17,8 @@ def default_args(**over):
     return a
 
 
-_DATA_NAMES = ('Capture', 'depth_corrs', 'crop_capture', 'make_batch', 'make_zoom_batch', 'draw_rand')
+_DATA_NAMES = ('Capture', 'depth_corrs', 'crop_capture', 'make_batch', 'make_zoom_batch', 'draw_rand', 'rotation_matrix', 'rotated_c2w',
+               'rotate_captures', 'rotate_capture', 'rotate_image', 'draw_rotations')
 _SCENE_NAMES = ('world_points', 'overlap_pairs', 'overlap_matrix', 'knn_pool', 'draw_pairs')
 __all__ = ['default_args'] + list(_DATA_NAMES) + list(_SCENE_NAMES)
 

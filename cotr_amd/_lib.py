@@ -138,6 +138,7 @@ _PROTOS = {
     'cotr_depth_valid': (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] +
                          [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
     'cotr_crop_depth_nearest': (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    'cotr_rotate_captures': (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
     'cotr_world_points': (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'cotr_overlap_scratch': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     'cotr_overlap_pairs': (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] +

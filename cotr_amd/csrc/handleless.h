@@ -1,5 +1,5 @@
 // Host plumbing of the entry points that take no cotr_handle (triangulate.hip, guided.hip, warp.hip, reproject.hip,
-// overlap.hip): they report a failure through a per-thread message that cotr_raster_last_error() returns (handleless.hip).
+// overlap.hip, rotate.hip): they report a failure through a per-thread message that cotr_raster_last_error() returns (handleless.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -9,7 +9,12 @@ builders reads a count back to the host.
 
 A capture is a ``Capture(image, depth, K, c2w)``: ``image`` uint8 [H, W, 3] and ``depth`` float32 [H, W] (device tensors,
 or numpy arrays that get uploaded), ``K`` 3 x 3 and ``c2w`` 4 x 4 float64 on the host.  A CPU tensor is refused: there is
-no CPU fallback."""
+no CPU fallback.
+
+The reference's one augmentation, ``--need_rotation`` (``capture.rotate_capture`` before any reprojection), is
+``rotate_captures`` / ``draw_rotations`` and the ``rotations`` keyword of the batch builders: cv2's ``warpAffine`` rule in
+``cotr_amd/csrc/rotate.hip`` (``cotr_rotate_captures``), DESIGN.md 3l."""
+import math
 from typing import NamedTuple
 
 import numpy as np
@@ -20,6 +25,7 @@ from ._lib import check_op, on, ptr
 
 OUT = 256              # constants.MAX_SIZE of the reference
 MAX_TRY = 100          # get_seed_corr's max_try
+ROT_MAX = 16384        # the longest side cotr_rotate_captures takes (csrc/rotate.hip)
 _RAND_SHAPES = {'seed': lambda b, kp, t: (b, t), 'zoom': lambda b, kp, t: (b,), 'jitter': lambda b, kp, t: (b, 2),
                 'trim': lambda b, kp, t: (b, kp), 'flip': lambda b, kp, t: (b,)}
 
@@ -324,17 +330,198 @@ def _upload(query_caps, nn_caps):
     return [up(c) for c in query_caps], [up(c) for c in nn_caps], device
 
 
-def make_batch(query_caps, nn_caps, num_kp, bidirectional=True, rand=None, generator=None):
+def _angle(angle):
+    try:
+        a = float(angle)
+    except (TypeError, ValueError):
+        a = math.nan
+    if not math.isfinite(a):
+        raise ValueError(f'the angle must be a finite number of degrees, got {angle!r}')
+    return a
+
+
+def _angles(angles, n):
+    try:
+        a = np.asarray(angles, dtype=np.float64)
+    except (TypeError, ValueError, RuntimeError):
+        a = np.full(0, np.nan)
+    if a.shape != (n,) or not np.isfinite(a).all():
+        raise ValueError(f'angles must be {n} finite floats (degrees), one per capture')
+    return a
+
+
+def _rot_sides(H, W, what):
+    if not (1 <= H <= ROT_MAX and 1 <= W <= ROT_MAX):
+        raise ValueError(f'{what}: the rotation takes sides in [1, {ROT_MAX}], got {H} x {W}')
+
+
+def rotation_matrix(shape_hw, angle):
+    """``m0..m5`` float64 [6]: what ``cv2.warpAffine`` works with for ``capture.rotate_image(image, angle)`` - the matrix of
+    ``cv2.getRotationMatrix2D((W / 2, H / 2), angle, 1.0)``, inverted the way ``warpAffine`` inverts it, so that it maps a
+    destination pixel to the source: ``(m0 x + m1 y + m2, m3 x + m4 y + m5)``.  Host float64, the C library's cos / sin
+    (DESIGN.md 3l)."""
+    H, W = (int(v) for v in shape_hw)
+    _rot_sides(H, W, 'shape_hw')
+    t = _angle(angle) * (math.pi / 180)                  # cv2: angle *= CV_PI / 180
+    al, be = math.cos(t), math.sin(t)
+    cx, cy = W / 2, H / 2
+    m = [al, be, (1 - al) * cx - be * cy, -be, al, be * cx + (1 - al) * cy]
+    D = m[0] * m[4] - m[1] * m[3]
+    D = 1.0 / D if D != 0 else 0.0
+    A11, A22 = m[4] * D, m[0] * D
+    m[0] = A11
+    m[1] *= -D
+    m[3] *= -D
+    m[4] = A22
+    b1 = -m[0] * m[2] - m[1] * m[5]
+    b2 = -m[3] * m[2] - m[4] * m[5]
+    m[2], m[5] = b1, b2
+    return np.array(m, dtype=np.float64)
+
+
+def rotated_c2w(c2w, angle):
+    """``rotate_camera_pose``: ``w2c' = Rz . inv(c2w)`` with ``Rz = [[cos r, sin r, 0, 0], [-sin r, cos r, 0, 0], [0, 0, 1, 0],
+    [0, 0, 0, 1]]``, ``r = angle / 180 * pi`` -> ``c2w' = inv(w2c')``, float64 4 x 4 on the host.  The reference's float32
+    quaternion + translation storage of the result is not reproduced.  Angle 0 returns ``c2w`` as it is."""
+    c2w = np.asarray(c2w)
+    if c2w.shape != (4, 4) or c2w.dtype != np.float64 or not np.isfinite(c2w).all():
+        raise ValueError('c2w must be a finite float64 4 x 4 host array')
+    a = _angle(angle)
+    if a == 0:
+        return c2w
+    r = a / 180 * np.pi
+    s, c = np.sin(r), np.cos(r)
+    rz = np.array([[c, s, 0.0, 0.0], [-s, c, 0.0, 0.0], [0.0, 0.0, 1.0, 0.0], [0.0, 0.0, 0.0, 1.0]])
+    return np.linalg.inv(np.matmul(rz, np.linalg.inv(c2w)))
+
+
+def _rotate_launch(items, device):
+    """ONE cotr_rotate_captures launch: items = [(image uint8 [H, W, 3] or None, depth float32 [H, W] or None, m float64 [6])],
+    contiguous tensors on ``device`` -> [(rotated image or None, rotated depth or None)], freshly allocated.  The three
+    tables travel as one upload."""
+    n = len(items)
+    table = np.zeros(11 * n, dtype=np.int64)
+    ptrs, shapes, mats = table[:4 * n].reshape(n, 4), table[4 * n:5 * n].view(np.int32).reshape(n, 2), table[5 * n:].view(np.float64).reshape(n, 6)
+    outs = []
+    for k, (image, depth, m) in enumerate(items):
+        out = tuple(None if x is None else torch.empty_like(x) for x in (image, depth))
+        ptrs[k] = [0 if x is None else x.data_ptr() for x in (image, out[0], depth, out[1])]
+        shapes[k] = (image if depth is None else depth).shape[:2]
+        mats[k] = m
+        outs.append(out)
+    dev = torch.from_numpy(table).to(device)
+    with torch.cuda.device(device):
+        check_op(_lib.load_library().cotr_rotate_captures(ptr(dev[:4 * n]), ptr(dev[4 * n:5 * n]), ptr(dev[5 * n:]), n,
+                                                          int(shapes[:, 0].max()), int(shapes[:, 1].max()),
+                                                          _lib.current_stream_ptr()), 'cotr_rotate_captures')
+    return outs
+
+
+def _rotate(caps, angles, device):
+    """rotate_captures after its checks"""
+    caps = list(caps)
+    turn = [k for k, a in enumerate(angles) if a != 0]
+    if not turn:
+        return caps
+    items = []
+    for k in turn:
+        c = caps[k]
+        items.append((None if c.image is None else on(c.image, device), on(c.depth, device),
+                      rotation_matrix(c.depth.shape, angles[k])))
+    for k, (image, depth) in zip(turn, _rotate_launch(items, device)):
+        caps[k] = Capture(image, depth, caps[k].K, rotated_c2w(caps[k].c2w, angles[k]))
+    return caps
+
+
+def rotate_captures(caps, angles):
+    """``capture.rotate_capture(cap, angle)`` for a list of captures (any mix of shapes) in ONE launch: the image through
+    ``cv2.warpAffine(..., INTER_LINEAR)`` and the depth through ``cv2.warpAffine(..., INTER_NEAREST)`` about the centre
+    ``(W / 2, H / 2)`` with the border value 0, the pose turned about the optical axis (``rotated_c2w``); the rule is in
+    DESIGN.md 3l.  angles: degrees, one finite float per capture.  -> list of ``Capture`` with device tensors, ``K`` the same
+    array; a capture whose ``image`` is None has only its depth rotated, and a capture with angle 0 comes back as it is
+    (the same object, no kernel work), as in the reference's ``rot == 0`` branch."""
+    caps = list(caps)
+    if not caps:
+        raise ValueError('caps must be a non-empty list of captures')
+    for i, c in enumerate(caps):
+        _rot_sides(*_check_capture(c, f'caps[{i}]', need_image=False), f'caps[{i}]')
+    angles = _angles(angles, len(caps))
+    return _rotate(caps, angles, _device_of(caps))
+
+
+def rotate_capture(cap, angle):
+    """``rotate_captures`` for one capture"""
+    return rotate_captures([cap], [_angle(angle)])[0]
+
+
+def rotate_image(image, angle, nearest=False):
+    """``capture.rotate_image(image, angle)`` for one uint8 [H, W, 3] image (``cv2.INTER_LINEAR``), or with ``nearest=True``
+    for one float32 [H, W] map (``interpolation=cv2.INTER_NEAREST``, what the reference applies to a depth map) -> device
+    tensor of the same shape.  numpy array or device tensor; one ``cotr_rotate_captures`` launch."""
+    want = 'a float32 [H, W] map' if nearest else 'a uint8 [H, W, 3] image'
+    if torch.is_tensor(image):
+        if not image.is_cuda:
+            raise _lib.CotrHipError('image: the batch builders run on an MI355X only (HIP kernels, no CPU fallback): '
+                                    'got a CPU tensor; pass a numpy array or move the tensor with .cuda()')
+    elif not isinstance(image, np.ndarray):
+        raise ValueError(f'image must be a numpy array or a device tensor, got {type(image).__name__}')
+    ok = image.dtype in ((np.float32, torch.float32) if nearest else (np.uint8, torch.uint8)) and \
+        (len(image.shape) == 2 if nearest else len(image.shape) == 3 and image.shape[2] == 3)
+    if not ok:
+        raise ValueError(f'image must be {want}, got {image.dtype} {tuple(image.shape)}')
+    _rot_sides(int(image.shape[0]), int(image.shape[1]), 'image')
+    m = rotation_matrix(image.shape[:2], angle)
+    device = image.device if torch.is_tensor(image) else torch.device('cuda', torch.cuda.current_device())
+    x = on(image, device)
+    return _rotate_launch([(None, x, m) if nearest else (x, None, m)], device)[0][1 if nearest else 0]
+
+
+def draw_rotations(batch, max_rotation, rotation_chance, rng=None):
+    """The angles of ``augment_with_rotation`` for one batch -> float64 [B, 2] degrees on the host, column 0 the query
+    capture, column 1 the nn capture: per capture two uniforms ``u_c``, ``u_t`` from ``rng`` (a ``numpy.random.Generator``;
+    None: a fresh ``default_rng()``), in the order query then nn; the angle is ``(2 u_t - 1) max_rotation`` if
+    ``u_c < rotation_chance``, else 0.  Host-side because the pose and the matrix are formed there; bit-parity with the
+    reference's ``random.random()`` / ``np.random.uniform`` streams is not a goal (it draws ``u_t`` only after a hit)."""
+    if int(batch) != batch or batch < 1:
+        raise ValueError('batch must be a positive integer')
+    if not (math.isfinite(max_rotation) and math.isfinite(rotation_chance)):
+        raise ValueError('max_rotation and rotation_chance must be finite')
+    rng = np.random.default_rng() if rng is None else rng
+    u = rng.random((int(batch), 2, 2))                    # [sample, (query, nn), (u_c, u_t)]
+    return np.where(u[..., 0] < rotation_chance, (2.0 * u[..., 1] - 1.0) * float(max_rotation), 0.0)
+
+
+def _rotated_pairs(q, n, rotations):
+    """the ``rotations`` [B, 2] of a batch builder applied to its validated captures: all 2B in one launch"""
+    B = len(q)
+    try:
+        rot = np.asarray(rotations, dtype=np.float64)
+    except (TypeError, ValueError, RuntimeError):
+        rot = None
+    if rot is None or rot.shape != (B, 2) or not np.isfinite(rot).all():
+        raise ValueError(f'rotations [B, 2] must be {B} x 2 finite floats (degrees): column 0 the query capture, column 1 the nn capture')
+    rot = rot.T.ravel()                                   # the order of q + n
+    if not rot.any():
+        return q, n
+    for i, c in enumerate(q + n):
+        _rot_sides(c.depth.shape[0], c.depth.shape[1], ('query_caps' if i < B else 'nn_caps') + f'[{i % B}]')
+    caps = _rotate(q + n, rot, _device_of(q + n))
+    return caps[:B], caps[B:]
+
+
+def make_batch(query_caps, nn_caps, num_kp, bidirectional=True, rand=None, generator=None, rotations=None):
     """``COTRDataset.__getitem__`` for a batch of 256 x 256 capture pairs (no zoom) ->
     ``{'image' [B, 3, 256, 512] float32, 'corrs' [B, num_kp, 4], 'queries', 'targets', 'valid' [B] bool}`` on the device.
     As the reference does there, the nn capture is projected into the query capture (rows in the nn capture's row-major
     order) and a row of ``corrs`` is (x_query, y_query, x_nn + 256, y_nn) / (512, 256, 512, 256).  Uniforms: ``rand`` with
-    'trim' [B, num_kp] and 'flip' [B], else ``draw_rand``.  See ``make_zoom_batch`` for the steps and the contract."""
+    'trim' [B, num_kp] and 'flip' [B], else ``draw_rand``.  See ``make_zoom_batch`` for the steps, the contract and ``rotations``."""
     q, n = _validate(query_caps, nn_caps, num_kp)
     B = len(q)
     for c in q + n:
         if tuple(c.depth.shape) != (OUT, OUT):
             raise ValueError(f'make_batch takes {OUT} x {OUT} captures (make_zoom_batch crops larger ones)')
+    if rotations is not None:
+        q, n = _rotated_pairs(q, n, rotations)
     q, n, device = _upload(q, n)
     rand = _rand_on(rand, B, num_kp, generator, device, ('trim', 'flip'))
     rows, counts = depth_corrs(n, q)
@@ -346,7 +533,7 @@ def make_batch(query_caps, nn_caps, num_kp, bidirectional=True, rand=None, gener
     return _assemble(image, rows, counts, torch.ones(B, dtype=torch.bool, device=device), num_kp, rand['trim'], rand['flip'], bidirectional)
 
 
-def make_zoom_batch(query_caps, nn_caps, num_kp, zooms, zoom_jitter, bidirectional=True, rand=None, generator=None):
+def make_zoom_batch(query_caps, nn_caps, num_kp, zooms, zoom_jitter, bidirectional=True, rand=None, generator=None, rotations=None):
     """``COTRZoomDataset.__getitem__`` for a batch of capture pairs ->
     ``{'image' [B, 3, 256, 512] float32, 'corrs' [B, num_kp, 4], 'queries', 'targets', 'valid' [B] bool}`` on the device.
 
@@ -366,7 +553,11 @@ def make_zoom_batch(query_caps, nn_caps, num_kp, zooms, zoom_jitter, bidirection
     floor(u * count), with replacement; flip: u < 0.5.  Bit-parity with ``np.random`` is not a goal.
     Two deliberate differences from the reference: seed candidates are drawn WITH replacement (the reference draws 100
     without), and the shuffle before the trim is dropped (it does not change the distribution of a with-replacement
-    draw; the seed is likewise the first survivor in draw order instead of a shuffled one)."""
+    draw; the seed is likewise the first survivor in draw order instead of a shuffled one).
+
+    rotations: None, or float64 [B, 2] degrees (column 0 the query capture, column 1 the nn capture; ``draw_rotations``):
+    step 0, the reference's ``augment_with_rotation`` - all 2B captures go through ``rotate_captures`` in one launch before
+    step 1; a capture with angle 0 is left alone, and None or all zeros add no launch."""
     q, n = _validate(query_caps, nn_caps, num_kp)
     B = len(q)
     zooms_h = np.asarray(zooms, dtype=np.float64).ravel()
@@ -375,6 +566,8 @@ def make_zoom_batch(query_caps, nn_caps, num_kp, zooms, zoom_jitter, bidirection
     shorts = [min(c.depth.shape) for c in q + n]
     if min(shorts) * float(np.clip(zooms_h, 0.0, 1.0).min()) < 2 or max(shorts) > 7936:
         raise ValueError('every zoom must leave a patch of at least 2 pixels, and the short sides must be <= 7936')
+    if rotations is not None:
+        q, n = _rotated_pairs(q, n, rotations)
     q, n, device = _upload(q, n)
     rand = _rand_on(rand, B, num_kp, generator, device, ('seed', 'zoom', 'jitter', 'trim', 'flip'))
     f64 = dict(dtype=torch.float64, device=device)

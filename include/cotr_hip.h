@@ -509,6 +509,32 @@ int cotr_depth_valid(const uint64_t* ptrs, const int32_t* shapes, int n, int max
 int cotr_crop_depth_nearest(const uint64_t* srcs, const int32_t* shapes, const int32_t* boxes, int n, float* dst, int out,
                             cotr_stream stream);
 
+/* ---- rotation augmentation of captures: cv2.warpAffine about the centre (cotr_amd/csrc/rotate.hip, cotr_amd/data.py) -------
+ * capture.rotate_capture of the reference (COTR/cameras/capture.py:128-132, 407-418) on the device: the image through
+ * warpAffine(INTER_LINEAR), the depth through warpAffine(INTER_NEAREST), BORDER_CONSTANT 0.  Rule in DESIGN.md 3l.
+ *
+ * cotr_rotate_captures: n items, each described by one row of three DEVICE tables (so items may differ in size):
+ *   ptrs   [n][4] uint64: image src [H,W,3] uint8, image dst [H,W,3] uint8, depth src [H,W] float32, depth dst [H,W] float32 -
+ *          DEVICE addresses; an image or a depth half with a 0 address is absent and skipped
+ *   shapes [n][2] int32:  H, W (an item with a side outside [1, 16384] is skipped)
+ *   mats   [n][6] float64: m0..m5, destination -> source (what warpAffine holds after inverting the 2 x 3 matrix)
+ *   Per destination pixel (x, y), in double, products and sums in this order, not contracted; rint = ties to even, saturated
+ *   to int32:  ad = rint((m0 x) 1024), bd = rint((m3 x) 1024), X0 = rint(((m1 y) + m2) 1024), Y0 = rint(((m4 y) + m5) 1024)
+ *     image: X = (X0 + 16 + ad) >> 5, Y = (Y0 + 16 + bd) >> 5 (arithmetic shifts): the source position in 1/32 px, then the
+ *            8-bit bilinear of cotr_warp_map (ix = X >> 5, fx = X & 31, four taps, a tap outside reads 0, (sum + 512) >> 10)
+ *     depth: X = (X0 + 512 + ad) >> 10, Y = (Y0 + 512 + bd) >> 10; dst = src[Y][X] if inside, else 0.0f; the 32 bits are
+ *            copied (a NaN payload, -0.0 or a denormal arrives unchanged)
+ *   The int32 sums do not overflow for a rotation about the centre of an item with sides <= 16384 (every term is below 2^26);
+ *   for any other matrix they wrap, and every tap stays bounds-checked.
+ *   max_h, max_w: host upper bounds of every H and W (they size the grid; pixels of an item beyond them are not written).
+ *   A dst must not overlap any src of the call: the tables live on the device, so this is NOT checked here; the caller
+ *   allocates the destinations (cotr_amd.data.rotate_captures does).
+ * 1 <= n <= 65535, 1 <= max_h, max_w <= 16384; ptrs and mats 8-byte aligned.  One launch for the whole batch, images and depths
+ * together; stream-ordered, no host waits, no allocation (capturable).  Bad arguments are checked before any HIP call:
+ * COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_rotate_captures(const uint64_t* ptrs, const int32_t* shapes, const double* mats, int n, int max_h, int max_w,
+                         cotr_stream stream);
+
 /* ---- overlap of the captures of a scene (cotr_amd/csrc/overlap.hip, cotr_amd/scene.py) ------------------------------------
  * The per-scene "distance matrix" of scripts/prepare_nn_distance_mat.py (distance_between_two_caps) on the device: the world
  * points of capture d projected into capture q, and the intersection over union of the two depth supports.  Rule in DESIGN.md 3k.
