@@ -66,6 +66,9 @@ _PROTOS = {
                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'cotr_op_ln_reduce': (ctypes.c_int, [c_float_p, ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
                                          ctypes.c_int, ctypes.c_void_p]),
+    'cotr_op_ln_reduce1': (ctypes.c_int, [c_float_p, ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                          ctypes.c_int, ctypes.c_void_p]),
+    'cotr_op_ln_reduce_post': (ctypes.c_int, [c_float_p, ctypes.c_int] + [c_float_p] * 7 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'cotr_op_layernorm': (ctypes.c_int, [c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_void_p]),
     'cotr_op_ffn_block': (ctypes.c_int, [c_float_p] * 9 + [ctypes.c_int, ctypes.c_void_p]),
     'cotr_op_ffn_chunks': (ctypes.c_int, [ctypes.c_int]),

@@ -1769,7 +1769,21 @@ int cotr_op_attention_fused(const float* q, int ldq, const float* x, const float
 int cotr_op_ln_reduce(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
                       float* y, int rows, cotr_stream stream) {
   if (!parts || np < 1 || !bias || !w || !b || !y) return COTR_ERR_ARG;
-  return op_ret(launch_ln_reduce(parts, np, bias, residual, w, b, y, rows, static_cast<hipStream_t>(stream)));
+  return op_ret(launch_ln_reduce_ref(parts, np, bias, residual, w, b, nullptr, nullptr, y, rows, static_cast<hipStream_t>(stream)));
+}
+// what the forward path launches: ln_reduce1.hip for np 8 / 16, ln_reduce_kernel otherwise
+int cotr_op_ln_reduce1(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
+                       float* y, int rows, cotr_stream stream) {
+  if (!parts || np < 1 || !bias || !w || !b || !y) return COTR_ERR_ARG;
+  return op_ret(launch_ln_reduce_post(parts, np, bias, residual, w, b, nullptr, nullptr, y, rows, static_cast<hipStream_t>(stream)));
+}
+// both with the second LayerNorm (decoder.norm inside the last layer's launch; post_w / post_b may be NULL): form 0 = ln_reduce_kernel, 1 = the forward path's
+int cotr_op_ln_reduce_post(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
+                           const float* post_w, const float* post_b, float* y, int rows, int form, cotr_stream stream) {
+  if (!parts || np < 1 || !bias || !w || !b || !y || (post_w == nullptr) != (post_b == nullptr) || form < 0 || form > 1) return COTR_ERR_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return op_ret(form ? launch_ln_reduce_post(parts, np, bias, residual, w, b, post_w, post_b, y, rows, s)
+                     : launch_ln_reduce_ref(parts, np, bias, residual, w, b, post_w, post_b, y, rows, s));
 }
 
 int cotr_op_layernorm(const float* x, const float* w, const float* b, float* y, int rows, cotr_stream stream) {

@@ -335,6 +335,13 @@ int launch_ln_reduce_post(const float* parts, int np, const float* bias, const f
                           const float* post_w, const float* post_b, float* y, int rows, hipStream_t s);
 int launch_ln_reduce(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
                      float* y, int rows, hipStream_t s);
+// ... launch_ln_reduce_post = launch_ln_reduce1 (ln_reduce1.hip: np 8 / 16, the launch without serialised round trips, same bits) where it
+// applies, launch_ln_reduce_ref (ln_reduce_kernel, pointwise.hip) otherwise
+bool ln_reduce1_applies(int np);
+int launch_ln_reduce1(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
+                      const float* post_w, const float* post_b, float* y, int rows, hipStream_t s);
+int launch_ln_reduce_ref(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
+                         const float* post_w, const float* post_b, float* y, int rows, hipStream_t s);
 // the FFN block for many rows in one launch (ffn_rows.hip): Y = [LN_post] LN(X + W2 relu(W1 X + b1) + b2); Y != X
 int launch_ffn_rows(const float* X, const float* W1, const float* b1, const float* W2, const float* b2, const float* ln_w,
                     const float* ln_b, const float* post_w, const float* post_b, float* Y, int M, hipStream_t s);

@@ -80,12 +80,20 @@ __global__ __launch_bounds__(256) void ln_reduce_kernel(const float* __restrict_
   *reinterpret_cast<f32x4*>(y + (size_t)row * 256 + lane * 4) = out;
 }
 
-int launch_ln_reduce_post(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
-                          const float* post_w, const float* post_b, float* y, int rows, hipStream_t s) {
+// ln_reduce_kernel whatever np is: the reference of ln_reduce1.hip (cotr_op_ln_reduce) and every slab count that kernel does not take
+int launch_ln_reduce_ref(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
+                         const float* post_w, const float* post_b, float* y, int rows, hipStream_t s) {
   if (rows <= 0) return 0;
   hipLaunchKernelGGL(ln_reduce_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, parts, np, bias, residual, w, b,
                      post_w, post_b, y, rows);
   return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// 8 and 16 slabs (attention heads, fused-FFN chunks: every ln_reduce launch of the forward path): ln_reduce1.hip, same bits
+int launch_ln_reduce_post(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
+                          const float* post_w, const float* post_b, float* y, int rows, hipStream_t s) {
+  if (ln_reduce1_applies(np)) return launch_ln_reduce1(parts, np, bias, residual, w, b, post_w, post_b, y, rows, s);
+  return launch_ln_reduce_ref(parts, np, bias, residual, w, b, post_w, post_b, y, rows, s);
 }
 
 

@@ -197,8 +197,17 @@ int cotr_op_attention_fused(const float* q, int ldq, const float* x, const float
                             float qscale, const float* k, const float* v, int ldkv, float* o, int ldo, const float* wo,
                             float* part, int nb, int nq, cotr_stream stream);
 /* y = LayerNorm(sum_c parts[c] + bias + residual) over rows of 256; parts [np][rows][256]; residual may be NULL */
+/* (always ln_reduce_kernel, pointwise.hip: the reference of the next two) */
 int cotr_op_ln_reduce(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
                       float* y, int rows, cotr_stream stream);
+/* the same as the forward path launches it: np 8 / 16 by ln_reduce1.hip (no serialised round trips; the same bits), any other np by
+ * ln_reduce_kernel */
+int cotr_op_ln_reduce1(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
+                       float* y, int rows, cotr_stream stream);
+/* ... followed by a second LayerNorm (post_w, post_b; both NULL = none), as the last decoder layer's launch applies decoder.norm:
+ * form 0 = ln_reduce_kernel, form 1 = the forward path's choice */
+int cotr_op_ln_reduce_post(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
+                           const float* post_w, const float* post_b, float* y, int rows, int form, cotr_stream stream);
 int cotr_op_layernorm(const float* x, const float* w, const float* b, float* y, int rows, cotr_stream stream);
 /* fused FFN block y = LN(x + W2 relu(W1 x + b1) + b2) in two launches (ffn.hip + ln_reduce); scratch holds
  * cotr_op_ffn_chunks(M) * M * 256 floats */
