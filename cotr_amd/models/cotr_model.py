@@ -137,6 +137,73 @@ class _MLP(nn.Module):
         self.layers = nn.ModuleList(nn.Linear(a, b) for a, b in zip(dims[:-1], dims[1:]))
 
 
+class _Workspace:
+    """The scratch a model hands to its library handle (cotr_set_workspace) and what it was sized for.  The library's encode cache +
+    scratch come from torch's caching allocator: a larger batch then costs one torch allocation instead of hipFree + hipMalloc
+    (device synchronisations) inside the library.  Per process like the handle: never pickled / deep-copied (COTR.__getstate__)."""
+
+    def __init__(self):
+        self.buffer = None      # uint8 tensor; the library gets its first 256-byte boundary
+        self.shape = (0, 0)     # (pairs, queries) it serves
+        self.varlen = False     # sized for varlen calls of that many pairs and pairs * queries rows as well; remembered once asked for
+        self.images = 0         # sized for pairs calls of up to that many distinct images as well; the largest count asked for
+        self.stale = False      # a knob changed: the library's carving of the buffer is re-done at the next call
+        self.pins = set()       # ids of captured graphs that have the buffer's addresses baked in (COTR.pin_workspace)
+
+    def ensure(self, lib, handle, device, b, q, keep_encode=False, varlen=False, images=0):
+        """Serve a call of b pairs x q queries; False when that dropped the library's cached encode.  The workspace only grows; with
+        keep_encode a cached encode is carried over into a new one (stream-ordered device copy; the old tensor goes back to torch's
+        pool, which is stream-ordered too)."""
+        b, q = max(b, self.shape[0]), max(q, self.shape[1])
+        m = max(images, self.images)
+        if self.buffer is not None and (b, q) == self.shape and not self.stale and (self.varlen or not varlen) and m == self.images:
+            return True
+        need = ctypes.c_size_t()
+        if varlen or self.varlen:       # the decoder scratch plus the tile tables
+            offsets = (ctypes.c_int * (b + 1))(*[i * max(q, 1) for i in range(b + 1)])
+            _lib.check(lib.cotr_scratch_bytes_varlen(handle, offsets, b, ctypes.byref(need)), handle, 'cotr_scratch_bytes_varlen')
+            self.varlen = True
+        else:
+            _lib.check(lib.cotr_scratch_bytes(handle, b, max(q, 1), ctypes.byref(need)), handle, 'cotr_scratch_bytes')
+        if m:
+            need_p = ctypes.c_size_t()
+            _lib.check(lib.cotr_scratch_bytes_pairs(handle, m, b, max(q, 1), ctypes.byref(need_p)), handle, 'cotr_scratch_bytes_pairs')
+            need.value = max(need.value, need_p.value)
+            self.images = m
+        kept = True
+        if self.buffer is None or self.buffer.numel() < need.value + 256:
+            if self.buffer is not None and self.pins:
+                raise _lib.CotrHipError(
+                    f'the workspace would have to grow to {need.value} bytes for {b} pairs x {q} queries, but a captured training '
+                    'step (GraphedTrainStep) has its addresses baked in: call model.reserve(max_pairs, max_queries) BEFORE '
+                    'capturing, or close() the captured step first')
+            ws = torch.empty(need.value + 256, dtype=torch.uint8, device=device)
+            self.release(device)
+            kept = bool(keep_encode and self.buffer is not None and b == self.shape[0])     # same pairs, more queries: the cached encode moves along
+            self._hand_over(lib, handle, ws, need.value, int(kept))
+            self.buffer = ws
+        elif self.stale and not self.pins:
+            # same buffer, new knobs: the three regions grow in place and never shrink, so regions carved under the old knobs plus one
+            # that is larger under the new ones can exceed what cotr_scratch_bytes promises for either - start the carving afresh
+            self._hand_over(lib, handle, self.buffer, self.buffer.numel() - 256, 0)
+            kept = False
+        self.stale = False
+        self.shape = (b, q)
+        return kept
+
+    @staticmethod
+    def _hand_over(lib, handle, ws, nbytes, keep):
+        off = (-ws.data_ptr()) % 256
+        _lib.check(lib.cotr_set_workspace(handle, ctypes.c_void_p(ws.data_ptr() + off), nbytes, keep, _lib.current_stream_ptr()),
+                   handle, 'cotr_set_workspace')
+
+    def release(self, device=None):
+        """The buffer is about to go back to torch's caching allocator, which may hand it out on ANOTHER stream while kernels
+        enqueued here still use it."""
+        if self.buffer is not None:
+            self.buffer.record_stream(torch.cuda.current_stream(device or self.buffer.device))
+
+
 class COTR(nn.Module):
     def __init__(self, args):
         super().__init__()
@@ -164,9 +231,7 @@ class COTR(nn.Module):
         self._handle_device = None
         self._weights_dirty = True
         self._encoded_batch = 0
-        self._ws = None             # scratch handed to the library (torch caching allocator), see _ensure_workspace
-        self._ws_shape = (0, 0)
-        self._ws_pins = set()       # ids of captured graphs that have the workspace's addresses baked in (pin_workspace)
+        self._workspace = _Workspace()     # scratch handed to the library (torch caching allocator)
         self._knobs = {}            # tuning knobs of THIS model's handle (set_knob); re-applied when the handle is re-created
 
     # ------------------------------------------------------------------ weight synchronisation
@@ -195,14 +260,15 @@ class COTR(nn.Module):
             handle = ctypes.c_void_p()
             _lib.check(lib.cotr_create(ctypes.byref(handle), index), None, 'cotr_create')
             try:                                          # the remembered knobs go on BEFORE the handle is published: a knob the library
-                for name, value in self.__dict__.get('_knobs', {}).items():   # refuses must not leave a half-configured handle behind
+                for name, value in self._knobs.items():   # refuses must not leave a half-configured handle behind
                     _lib.set_knob(name, value, handle)
             except Exception:
                 lib.cotr_destroy(handle)
                 raise
             self._handle, self._handle_device = handle, index
             self._weights_dirty = True
-            self._ws, self._ws_shape = None, (0, 0)
+            # the new handle gets a new buffer; varlen / images / stale stay, so that it is sized at once for the kinds of call this model makes
+            self._workspace.buffer, self._workspace.shape = None, (0, 0)
         if self._weights_dirty:
             sd = {k: v.detach() for k, v in self.state_dict().items()}
             bad = [k for k, v in sd.items() if v.dtype != torch.float32]
@@ -219,61 +285,22 @@ class COTR(nn.Module):
             self._encoded_batch = 0
         return lib
 
-    def _ensure_workspace(self, lib, device, b, q, keep_encode=False, varlen=False, images=0):
-        """The library's encode cache + scratch come from torch's caching allocator (cotr_set_workspace): a larger batch then
-        costs one torch allocation instead of hipFree + hipMalloc (device synchronisations) inside the library.  The
-        workspace only grows; a cached encode is carried over into the new one (stream-ordered device copy; the old tensor
-        goes back to torch's pool, which is stream-ordered too).  varlen: sized for varlen calls of up to b pairs and b * q
-        rows as well (cotr_scratch_bytes_varlen: the decoder scratch plus the tile tables); remembered once asked for.  images: sized
-        for pairs calls of up to that many distinct images as well (cotr_scratch_bytes_pairs); the largest count asked for is kept."""
-        b, q = max(b, self._ws_shape[0]), max(q, self._ws_shape[1])
-        stale = self.__dict__.get('_ws_stale', False)      # a knob changed: the library's carving of the workspace is re-done
-        grow_varlen = varlen and not self.__dict__.get('_ws_varlen', False)
-        m = max(images, self.__dict__.get('_ws_images', 0))
-        grow_pairs = m > self.__dict__.get('_ws_images', 0)
-        if (b, q) == self._ws_shape and not stale and not grow_varlen and not grow_pairs:
-            return
-        need = ctypes.c_size_t()
-        if varlen or self.__dict__.get('_ws_varlen', False):
-            offsets = (ctypes.c_int * (b + 1))(*[i * max(q, 1) for i in range(b + 1)])
-            _lib.check(lib.cotr_scratch_bytes_varlen(self._handle, offsets, b, ctypes.byref(need)), self._handle,
-                       'cotr_scratch_bytes_varlen')
-            self._ws_varlen = True
-        else:
-            _lib.check(lib.cotr_scratch_bytes(self._handle, b, max(q, 1), ctypes.byref(need)), self._handle, 'cotr_scratch_bytes')
-        if m:
-            need_p = ctypes.c_size_t()
-            _lib.check(lib.cotr_scratch_bytes_pairs(self._handle, m, b, max(q, 1), ctypes.byref(need_p)), self._handle,
-                       'cotr_scratch_bytes_pairs')
-            need.value = max(need.value, need_p.value)
-            self._ws_images = m
-        if self._ws is None or self._ws.numel() < need.value + 256:
-            if self._ws is not None and self.__dict__.get('_ws_pins'):
-                raise _lib.CotrHipError(
-                    f'the workspace would have to grow to {need.value} bytes for {b} pairs x {q} queries, but a captured training '
-                    'step (GraphedTrainStep) has its addresses baked in: call model.reserve(max_pairs, max_queries) BEFORE '
-                    'capturing, or close() the captured step first')
-            ws = torch.empty(need.value + 256, dtype=torch.uint8, device=device)
-            if self._ws is not None:
-                # the old workspace goes back to torch's caching allocator, which may hand it out on ANOTHER stream while
-                # kernels enqueued here still use it
-                self._ws.record_stream(torch.cuda.current_stream(device))
-            off = (-ws.data_ptr()) % 256
-            keep = int(keep_encode and b == self._ws_shape[0])     # same pairs, more queries: the cached encode moves along
-            _lib.check(lib.cotr_set_workspace(self._handle, ctypes.c_void_p(ws.data_ptr() + off), need.value, keep,
-                                              _lib.current_stream_ptr()), self._handle, 'cotr_set_workspace')
-            self._ws = ws
-            if not keep:
-                self._encoded_batch = 0
-        elif stale and not self.__dict__.get('_ws_pins'):
-            # same buffer, new knobs: the three regions grow in place and never shrink, so regions carved under the old knobs plus one
-            # that is larger under the new ones can exceed what cotr_scratch_bytes promises for either - start the carving afresh
-            off = (-self._ws.data_ptr()) % 256
-            _lib.check(lib.cotr_set_workspace(self._handle, ctypes.c_void_p(self._ws.data_ptr() + off), self._ws.numel() - 256, 0,
-                                              _lib.current_stream_ptr()), self._handle, 'cotr_set_workspace')
-            self._encoded_batch = 0
-        self._ws_stale = False
-        self._ws_shape = (b, q)
+    def _call(self, name, device, shape, args, encoded=None, keep_encode=False, varlen=False, images=0):
+        """Every library call of the model: the handle and its weights, the workspace for shape = (pairs, queries), then
+        lib.<name>(handle, *args, stream) on the caller's current stream.  keep_encode: the call reads the cached encode of `pairs`
+        pairs.  encoded: the pairs the call leaves in the encode cache (None: it leaves the record as it is)."""
+        lib = self._ensure_ready(device)
+        with torch.cuda.device(device):
+            self._size_workspace(lib, device, *shape, keep_encode=keep_encode, varlen=varlen, images=images)
+            if keep_encode and self._encoded_batch != shape[0]:
+                raise _lib.CotrHipError(f'{name[5:]} of {shape[0]} pairs: the cached encode was dropped by a workspace change')
+            _lib.check(getattr(lib, name)(self._handle, *args, _lib.current_stream_ptr()), self._handle, name)
+        if encoded is not None:
+            self._encoded_batch = encoded
+
+    def _size_workspace(self, lib, device, b, q, **flags):
+        if not self._workspace.ensure(lib, self._handle, device, b, q, **flags):
+            self._encoded_batch = 0         # the library dropped its cached encode with the old carving
 
     def _release(self):
         handle = self.__dict__.get('_handle')
@@ -290,9 +317,14 @@ class COTR(nn.Module):
     def __getstate__(self):  # the HIP handle is per process: never pickled / deep-copied
         state = self.__dict__.copy()
         state['_handle'], state['_handle_device'], state['_weights_dirty'], state['_encoded_batch'] = None, None, True, 0
-        state['_ws'], state['_ws_shape'], state['_ws_pins'] = None, (0, 0), set()
-        state['_knobs'] = dict(state.get('_knobs', {}))
+        state['_workspace'], state['_knobs'] = _Workspace(), dict(self._knobs)
         return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        if not isinstance(state.get('_workspace'), _Workspace):    # a pickle from before the workspace object
+            self._workspace = _Workspace()
+        self.__dict__.setdefault('_knobs', {})
 
     # ------------------------------------------------------------------ the path
     def _check_mode(self):
@@ -328,14 +360,9 @@ class COTR(nn.Module):
         """Query-independent half (backbone, input_proj, encoder, decoder K/V), cached in the
         HIP handle; follow with any number of ``decode(queries)``."""
         self._check_mode()
-        img = self._as_batch(samples)
-        lib = self._ensure_ready(img.device)
-        img = img.contiguous().float()
-        with torch.cuda.device(img.device):
-            self._ensure_workspace(lib, img.device, img.shape[0], self._ws_shape[1])
-            _lib.check(lib.cotr_encode(self._handle, img.data_ptr(), img.shape[0], _lib.current_stream_ptr()),
-                       self._handle, 'cotr_encode')
-        self._encoded_batch = img.shape[0]
+        img = self._as_batch(samples).contiguous().float()
+        b = img.shape[0]
+        self._call('cotr_encode', img.device, (b, 0), (img.data_ptr(), b), encoded=b)
         return self
 
     @torch.no_grad()
@@ -346,15 +373,9 @@ class COTR(nn.Module):
         assert two == 2
         if self._encoded_batch != b:
             raise _lib.CotrHipError(f'decode of {b} pairs but the cached encode holds {self._encoded_batch}')
-        lib = self._ensure_ready(queries.device)
         qs = queries.contiguous().float()
         out = torch.empty((b, q, 2), dtype=torch.float32, device=qs.device)
-        with torch.cuda.device(qs.device):
-            self._ensure_workspace(lib, qs.device, b, q, keep_encode=True)   # the cached encode moves along if it has to grow
-            if self._encoded_batch != b:
-                raise _lib.CotrHipError(f'decode of {b} pairs: the cached encode was dropped by a workspace change')
-            _lib.check(lib.cotr_decode(self._handle, qs.data_ptr(), b, q, out.data_ptr(), _lib.current_stream_ptr()),
-                       self._handle, 'cotr_decode')
+        self._call('cotr_decode', qs.device, (b, q), (qs.data_ptr(), b, q, out.data_ptr()), keep_encode=True)
         return out
 
     @staticmethod
@@ -392,16 +413,12 @@ class COTR(nn.Module):
         offsets = self._varlen_offsets(counts, queries, b)
         if img.device != queries.device:
             raise _lib.CotrHipError(f'samples on {img.device} but queries on {queries.device}')
-        lib = self._ensure_ready(img.device)
         img = img.contiguous().float()
         qs = queries.contiguous().float()
         n = qs.shape[0]
         out = torch.empty((n, 2), dtype=torch.float32, device=img.device)
-        with torch.cuda.device(img.device):
-            self._ensure_workspace(lib, img.device, b, -(-n // b), varlen=True)
-            _lib.check(lib.cotr_forward_varlen(self._handle, img.data_ptr(), qs.data_ptr(), offsets, b, out.data_ptr(),
-                                               _lib.current_stream_ptr()), self._handle, 'cotr_forward_varlen')
-        self._encoded_batch = b
+        self._call('cotr_forward_varlen', img.device, (b, -(-n // b)), (img.data_ptr(), qs.data_ptr(), offsets, b, out.data_ptr()),
+                   encoded=b, varlen=True)
         return out
 
     @torch.no_grad()
@@ -412,16 +429,11 @@ class COTR(nn.Module):
         if b <= 0:
             raise _lib.CotrHipError('decode_varlen before encode')
         offsets = self._varlen_offsets(counts, queries, b)
-        lib = self._ensure_ready(queries.device)
         qs = queries.contiguous().float()
         n = qs.shape[0]
         out = torch.empty((n, 2), dtype=torch.float32, device=qs.device)
-        with torch.cuda.device(qs.device):
-            self._ensure_workspace(lib, qs.device, b, -(-n // b), keep_encode=True, varlen=True)
-            if self._encoded_batch != b:
-                raise _lib.CotrHipError(f'decode_varlen of {b} pairs: the cached encode was dropped by a workspace change')
-            _lib.check(lib.cotr_decode_varlen(self._handle, qs.data_ptr(), offsets, b, out.data_ptr(), _lib.current_stream_ptr()),
-                       self._handle, 'cotr_decode_varlen')
+        self._call('cotr_decode_varlen', qs.device, (b, -(-n // b)), (qs.data_ptr(), offsets, b, out.data_ptr()),
+                   keep_encode=True, varlen=True)
         return out
 
     @staticmethod
@@ -461,13 +473,8 @@ class COTR(nn.Module):
         follow with decode(q) [B, Q, 2] or decode_varlen(q, counts).  Returns self."""
         self._check_mode()
         m, b, idx = self._pairs_args(images, pairs)
-        lib = self._ensure_ready(images.device)
         imgs = images.contiguous().float()
-        with torch.cuda.device(imgs.device):
-            self._ensure_workspace(lib, imgs.device, b, self._ws_shape[1], images=m)
-            _lib.check(lib.cotr_encode_pairs(self._handle, imgs.data_ptr(), m, idx, b, _lib.current_stream_ptr()),
-                       self._handle, 'cotr_encode_pairs')
-        self._encoded_batch = b
+        self._call('cotr_encode_pairs', imgs.device, (b, 0), (imgs.data_ptr(), m, idx, b), encoded=b, images=m)
         return self
 
     @torch.no_grad()
@@ -480,32 +487,50 @@ class COTR(nn.Module):
             raise ValueError(f'queries must be [{b}, Q, 2] for {b} pairs; got {tuple(queries.shape)}')
         if images.device != queries.device:
             raise _lib.CotrHipError(f'images on {images.device} but queries on {queries.device}')
-        lib = self._ensure_ready(images.device)
         imgs = images.contiguous().float()
         qs = queries.contiguous().float()
         q = qs.shape[1]
         out = torch.empty((b, q, 2), dtype=torch.float32, device=imgs.device)
-        with torch.cuda.device(imgs.device):
-            self._ensure_workspace(lib, imgs.device, b, q, images=m)
-            _lib.check(lib.cotr_forward_pairs(self._handle, imgs.data_ptr(), m, idx, qs.data_ptr(), b, q, out.data_ptr(),
-                                              _lib.current_stream_ptr()), self._handle, 'cotr_forward_pairs')
-        self._encoded_batch = b
+        self._call('cotr_forward_pairs', imgs.device, (b, q), (imgs.data_ptr(), m, idx, qs.data_ptr(), b, q, out.data_ptr()),
+                   encoded=b, images=m)
         return {'pred_corrs': out}
 
     def pin_workspace(self, owner):
         """A captured HIP graph (training.GraphedTrainStep) holds the workspace's addresses: until unpin_workspace(owner) the
         workspace may not be replaced - a call that needs a larger one raises instead of silently freeing memory the graph writes."""
-        self.__dict__.setdefault('_ws_pins', set()).add(id(owner))
+        self._workspace.pins.add(id(owner))
 
     def unpin_workspace(self, owner):
-        self.__dict__.setdefault('_ws_pins', set()).discard(id(owner))
+        self._workspace.pins.discard(id(owner))
 
     def reserve(self, pairs, queries):
         """Size the scratch workspace for calls of up to ``pairs`` x ``queries`` (optional; it otherwise grows on demand)."""
         dev = next(self.parameters()).device
         lib = self._ensure_ready(dev)
         with torch.cuda.device(dev):
-            self._ensure_workspace(lib, dev, int(pairs), int(queries))
+            self._size_workspace(lib, dev, int(pairs), int(queries))
+
+    @property
+    def workspace(self):
+        """The model's _Workspace (read-only: its buffer and the (pairs, queries) shape it serves)."""
+        return self._workspace
+
+    @property
+    def _ws(self):      # workspace.buffer under the name it had as an attribute of the model: a plain alias, to read or to assign
+        return self._workspace.buffer
+
+    @_ws.setter
+    def _ws(self, buffer):
+        self._workspace.buffer = buffer
+
+    def drop_workspace(self):
+        """Forget the workspace and the cached encode: the next call sizes a new workspace - for that call alone, whatever varlen or
+        pairs calls came before - and hands it over.  For callers that gave the handle a workspace of their own (cotr_set_workspace)."""
+        if self._workspace.pins:
+            raise _lib.CotrHipError('the workspace cannot be dropped while a captured training step (GraphedTrainStep) has its addresses '
+                                    'baked in: close() the captured step first')
+        self._workspace.release()
+        self._workspace, self._encoded_batch = _Workspace(), 0
 
     def forward(self, samples, queries):
         if self.training:       # stage-1 training step: HIP backbone + HIP GEMMs under an autograd tape (training.py)
@@ -522,23 +547,36 @@ class COTR(nn.Module):
         assert two == 2 and b == img.shape[0]
         if img.device != queries.device:
             raise _lib.CotrHipError(f'samples on {img.device} but queries on {queries.device}')
-        lib = self._ensure_ready(img.device)
         img = img.contiguous().float()
         qs = queries.contiguous().float()
         out = torch.empty((b, q, 2), dtype=torch.float32, device=img.device)
-        with torch.cuda.device(img.device):
-            self._ensure_workspace(lib, img.device, b, q)
-            _lib.check(lib.cotr_forward(self._handle, img.data_ptr(), qs.data_ptr(), b, q, out.data_ptr(),
-                                        _lib.current_stream_ptr()), self._handle, 'cotr_forward')
-        self._encoded_batch = b
+        self._call('cotr_forward', img.device, (b, q), (img.data_ptr(), qs.data_ptr(), b, q, out.data_ptr()), encoded=b)
         return {'pred_corrs': out}
+
+    @torch.no_grad()
+    def backbone_upto(self, img, stage=3, out=None):
+        """The frozen backbone through layer<stage> (1 ... 3) on the inference kernels (no gradient; the training step's frozen part):
+        img [B, 3, 256, 512] -> [B, H, 2W, C] of that stage, NHWC over the side-by-side pair, written into `out` where one is given
+        (float32, contiguous, on img's device, of exactly that shape)."""
+        if stage not in (1, 2, 3):
+            raise ValueError(f'stage must be 1, 2 or 3 (layer1 ... layer3); got {stage!r}')
+        img = self._as_batch(img).detach().contiguous().float()
+        b = img.shape[0]
+        shape = (b, 128 >> stage, 256 >> stage, 128 << stage)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=img.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != img.device or not out.is_contiguous():
+            raise ValueError(f'out must be a contiguous float32 tensor {shape} on {img.device}; got {out.dtype} {tuple(out.shape)} on '
+                             f'{out.device}{"" if out.is_contiguous() else ", not contiguous"}')
+        self._call('cotr_backbone_upto', img.device, (b, 1), (img.data_ptr(), b, stage, out.data_ptr()))
+        return out
 
     # ------------------------------------------------------------------ tuning knobs (per handle: include/cotr_hip.h)
     def set_knob(self, name, value):
         """One tuning knob of this model's library handle (cotr_set_knob(h, ...)): other models - and other threads - keep theirs.
         Remembered, so it survives a move to another GPU; fusion thresholds / encode_chunk change the scratch the library needs,
         so the workspace is re-sized at the next call."""
-        if self.__dict__.get('_ws_pins'):
+        if self._workspace.pins:
             raise _lib.CotrHipError('tuning knobs change the carving of the workspace, and a captured training step (GraphedTrainStep) has '
                                     'its addresses baked in: set knobs before capturing, or close() the captured step first')
         if self._handle is not None:
@@ -546,7 +584,7 @@ class COTR(nn.Module):
         else:
             _lib.validate_knob(name, value)               # no handle yet: checked against the library's registry now, applied later
         self._knobs[name] = int(value)
-        self._ws_stale = True
+        self._workspace.stale = True
 
     def knobs(self):
         """{name: (current, default)} of this model's handle (the shipped defaults + set_knob calls before the handle exists)."""
@@ -555,12 +593,12 @@ class COTR(nn.Module):
         return {k: (self._knobs.get(k, v[1]), v[1]) for k, v in _lib.knobs(None).items()}
 
     def reset_knobs(self):
-        if self.__dict__.get('_ws_pins') and self._knobs:
+        if self._workspace.pins and self._knobs:
             raise _lib.CotrHipError('tuning knobs cannot change while a captured training step has the workspace pinned')
         if self._handle is not None:
             _lib.reset_knobs(self._handle)
         self._knobs = {}
-        self._ws_stale = True
+        self._workspace.stale = True
 
     # ------------------------------------------------------------------ test / profiling hooks
     def debug_tap(self, name):
@@ -581,13 +619,37 @@ class COTR(nn.Module):
         self._ensure_ready(next(self.parameters()).device)
         _lib.check(_lib.load_library().cotr_set_profiling(self._handle, int(level)), self._handle, 'profiling')
 
-    def get_profile(self):
+    def _profile(self, with_ms):
         lib = _lib.load_library()
-        names = (ctypes.c_char_p * 512)()
-        ms = (ctypes.c_float * 512)()
-        n = ctypes.c_int()
-        _lib.check(lib.cotr_get_profile(self._handle, names, ms, 512, ctypes.byref(n)), self._handle, 'profile')
-        return [(names[i].decode(), ms[i]) for i in range(n.value)]
+        cap, n = 256, ctypes.c_int(256)
+        while n.value == cap:           # cotr_get_profile stops at the capacity and cannot report the total: full means ask again
+            cap *= 2
+            names, ms = (ctypes.c_char_p * cap)(), (ctypes.c_float * cap)() if with_ms else None
+            _lib.check(lib.cotr_get_profile(self._handle, names, ms, cap, ctypes.byref(n)), self._handle, 'profile')
+        return names[:n.value], ms[:n.value] if with_ms else None
+
+    def get_profile(self):
+        """[(name, ms)] of every entry of the last profiled call(s) since set_profiling."""
+        names, ms = self._profile(True)
+        return [(name.decode(), t) for name, t in zip(names, ms)]
+
+    def profile_names(self):
+        names, _ = self._profile(False)
+        return [name.decode() for name in names]
+
+    def batch_chunks(self, pairs, queries, which):
+        """The passes a (pairs, queries) call is cut into under the model's knobs: pairs per pass; which = 0 encode, 1 decode."""
+        lib = self._ensure_ready(next(self.parameters()).device)
+
+        def ask(sizes, cap):
+            n = lib.cotr_batch_chunks(self._handle, pairs, queries, which, sizes, cap)
+            if n < 0:
+                _lib.check(n, self._handle, 'cotr_batch_chunks')
+            return n
+        sizes = (ctypes.c_int * ask(None, 0))()     # the library reports the total whatever the capacity: the count first,
+        if len(sizes):                              # then exactly that many slots
+            ask(sizes, len(sizes))
+        return list(sizes)
 
 
 def build(args):

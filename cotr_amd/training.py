@@ -140,14 +140,7 @@ def _ffn(x, layer, p_drop, training):
 
 def backbone_features(model, img):
     """layer3 features [B*512, 1024] of the frozen backbone on the HIP kernels (no gradient)."""
-    lib = model._ensure_ready(img.device)
-    img = img.detach().contiguous().float()
-    feat = torch.empty((img.shape[0] * TOK, CFEAT), dtype=torch.float32, device=img.device)
-    with torch.cuda.device(img.device):
-        model._ensure_workspace(lib, img.device, img.shape[0], 1)
-        _lib.check(lib.cotr_backbone(model._handle, img.data_ptr(), img.shape[0], feat.data_ptr(), _lib.current_stream_ptr()),
-                   model._handle, 'cotr_backbone')
-    return feat
+    return model.backbone_upto(img).view(img.shape[0] * TOK, CFEAT)        # [B,16,32,1024] = the token matrix
 
 
 def _frozen_bn(x, bn):
@@ -204,14 +197,8 @@ def backbone_features_trainable(model, img, use_torch_convs=False):
     kernels forward and backward (train_ops.ConvBN, NHWC side-by-side: both halves of a pair in one tensor, each padded on its
     own).  ``use_torch_convs``: the round-1 path (torch / MIOpen convolutions per 256-wide half), kept as a cross-check.
     -> [B*512, 1024] with graph."""
-    lib = model._ensure_ready(img.device)
-    img = img.detach().contiguous().float()
     b = img.shape[0]
-    l1 = torch.empty((b, 64, 128, 256), dtype=torch.float32, device=img.device)             # NHWC over the pair
-    with torch.cuda.device(img.device):
-        model._ensure_workspace(lib, img.device, b, 1)
-        _lib.check(lib.cotr_backbone_upto(model._handle, img.data_ptr(), b, 1, l1.data_ptr(), _lib.current_stream_ptr()),
-                   model._handle, 'cotr_backbone_upto')
+    l1 = model.backbone_upto(img, 1)                                                         # [B,64,128,256], NHWC over the pair
     body = model.backbone[0].body
     if not use_torch_convs:
         y = l1

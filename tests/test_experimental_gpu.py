@@ -463,13 +463,10 @@ def test_split_f16_stage_taps_against_oracle():
         assert errs[level]['px'] < PX_BAR
     m.set_debug_taps(False)
     # the backbone features through cotr_backbone_upto (unpacked copy-out)
-    lib = _lib.load_library()
     img_d = img.cuda().contiguous()
     with G.model_knobs(m, split_f16=1, split_f16_min_pairs=1):
         for stage, name in ((1, 'layer1'), (3, 'layer3')):
-            out = torch.empty(checks[name].shape, device='cuda')
-            _lib.check(lib.cotr_backbone_upto(m._handle, img_d.data_ptr(), img_d.shape[0], stage, out.data_ptr(), _lib.current_stream_ptr()),
-                       m._handle, 'cotr_backbone_upto')
+            out = m.backbone_upto(img_d, stage, out=torch.full(checks[name].shape, float('nan'), device='cuda'))
             assert G.rel_err(out.cpu(), checks[name]) < 5e-5, name
 
 

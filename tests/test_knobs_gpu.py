@@ -1,11 +1,10 @@
 """Every value of every forward tuning knob against the oracle (a knob changes which kernels run, never the
 contract).  The table is tests/knob_cases.py; each (knob, value, shape) runs on ONE cached model object (the workspace is re-carved as
-knobs change, cotr_model.py _ws_stale) and is checked for: finite and bit-repeatable output; every pair within SHAPE_NOISE_PX of the
+knobs change, cotr_model.py _Workspace.stale) and is checked for: finite and bit-repeatable output; every pair within SHAPE_NOISE_PX of the
 default-knob output (bit for bit where the table says 'same'); three pairs within PX_BAR of the CPU oracle; and reach - the per-launch
 profile (cotr_set_profiling 2) shows the value took its branch at that shape.  A case that does not reach its branch fails.
 Then the interactions the dispatch code shows to matter.  Everything runs eagerly (no graph capture: a captured side stream is a
 graph with parallel branches)."""
-import ctypes
 import re
 
 import pytest
@@ -15,13 +14,14 @@ from cotr_amd import _lib
 from cotr_amd.utils.synth import synth_state_dict, synth_inputs
 from oracle import cotr_oracle
 from tests import gpu_helpers as G
+from tests import raw_abi
 from tests.knob_cases import KNOB_CASES, case_runs
 from tests.test_parity_gpu import PX_BAR, SHAPE_NOISE_PX, hip_model
 
 pytestmark = pytest.mark.gpu
 
 _inputs, _oracle, _default, _names = {}, {}, {}, {}
-_ws_checked = set()
+_sized_checked = set()
 
 
 def inputs(b, q):
@@ -53,7 +53,7 @@ def launch_names(m, b, q):
     try:
         forward(m, b, q)
         torch.cuda.synchronize()
-        return [n for n, _ in m.get_profile()]
+        return m.profile_names()
     finally:
         m.set_profiling(0)
 
@@ -72,32 +72,16 @@ def base_names(m, b, q, base):
     return _names[key]
 
 
-def passes(m, b, q, which):
-    sizes = (ctypes.c_int * 128)()
-    n = _lib.load_library().cotr_batch_chunks(m._handle, b, q, which, sizes, 128)
-    assert 0 < n <= 128
-    return list(sizes[:n])
-
-
 def raw_forward_in_sized_workspace(m, b, q):
     """cotr_forward on a caller workspace of exactly cotr_scratch_bytes(h, B, Q) bytes, 256-aligned, under the handle's current knobs
     (cotr_scratch_bytes: "a knob never makes a sized workspace too small").  The model's own workspace is dropped afterwards."""
     lib = _lib.load_library()
     img, qs = inputs(b, q)
     img, qs = img.cuda().contiguous(), qs.cuda().contiguous()
-    need = ctypes.c_size_t()
-    assert lib.cotr_scratch_bytes(m._handle, b, q, ctypes.byref(need)) == 0
-    ws = torch.empty(need.value + 256, dtype=torch.uint8, device='cuda')
-    off = (-ws.data_ptr()) % 256
     out = torch.empty(b, q, 2, device='cuda')
-    try:
-        assert lib.cotr_set_workspace(m._handle, ctypes.c_void_p(ws.data_ptr() + off), need.value, 0, _lib.current_stream_ptr()) == 0
+    with raw_abi.caller_workspace(m, raw_abi.scratch_bytes(m, b, q)):
         rc = lib.cotr_forward(m._handle, img.data_ptr(), qs.data_ptr(), b, q, out.data_ptr(), _lib.current_stream_ptr())
         assert rc == 0, lib.cotr_last_error(m._handle)
-        torch.cuda.synchronize()
-    finally:
-        torch.cuda.synchronize()
-        m._ws, m._ws_shape, m._encoded_batch = None, (0, 0), 0     # the next model call sizes and hands over a workspace of its own
     return out.cpu()
 
 
@@ -115,12 +99,12 @@ def test_knob_value_against_the_oracle(knob, value, shape, reach, base):
         out = forward(m, b, q)
         assert torch.isfinite(out).all()
         assert torch.equal(out, forward(m, b, q)), 'not bit-repeatable'
-        if (knob, value) not in _ws_checked:
-            _ws_checked.add((knob, value))
+        if (knob, value) not in _sized_checked:
+            _sized_checked.add((knob, value))
             assert torch.equal(raw_forward_in_sized_workspace(m, b, q), out), 'another result in a workspace of cotr_scratch_bytes'
         if reach == 'side':
             chunk = m.knobs()['encode_chunk'][0]
-            assert b <= chunk and b * q <= 8192 and passes(m, b, q, 0) == [b] and passes(m, b, q, 1) == [b], \
+            assert b <= chunk and b * q <= 8192 and m.batch_chunks(b, q, 0) == [b] and m.batch_chunks(b, q, 1) == [b], \
                 'the side stream is not eligible at this shape (api.hip forward_impl)'
         else:
             names = launch_names(m, b, q)
@@ -150,7 +134,7 @@ def split_decode_shape(m):
     kernels' lowest thresholds - found from the handle's own pass lists (the fill rules read the CU count); existing shapes first."""
     with G.model_knobs(m, **ROWS_EVERYWHERE):
         for b, q in [(8, 512), (3, 333), (24, 100), (16, 512), (4, 1000)] + [(b, 512) for b in range(2, 17)]:
-            if b * q <= 8192 and passes(m, b, q, 0) == [b] and len(passes(m, b, q, 1)) > 1:
+            if b * q <= 8192 and m.batch_chunks(b, q, 0) == [b] and len(m.batch_chunks(b, q, 1)) > 1:
                 return b, q
     return None
 
@@ -161,7 +145,6 @@ def test_side_stream_on_a_call_whose_decode_splits(side):
     whose decode walks several passes must run without it - every pair against the oracle, not a sample (pair 7 of 8 x 512 used to be
     decoded with pair 0's query encodings)."""
     m = hip_model()
-    forward(m, 1, 1)                       # the handle exists
     shape = split_decode_shape(m)
     assert shape is not None, 'no shape with one encode pass and several decode passes under the rows kernels\' lowest thresholds'
     b, q = shape
@@ -197,7 +180,7 @@ def test_odd_encode_chunk_across_the_conv23m_gap(b, batch_split):
     q = 40
     ref = default_out(m, b, q)
     with G.model_knobs(m, encode_chunk=7, batch_split=batch_split):
-        enc = passes(m, b, q, 0)
+        enc = m.batch_chunks(b, q, 0)
         assert sum(enc) == b and max(enc) <= 7
         out = forward(m, b, q)
         assert torch.equal(out, forward(m, b, q))

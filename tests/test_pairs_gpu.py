@@ -15,6 +15,7 @@ from cotr_amd.models import build_model
 from cotr_amd.utils.synth import synth_state_dict, synth_inputs
 from oracle import cotr_oracle as O
 from tests import gpu_helpers as G
+from tests import raw_abi
 from tests.knob_cases import KNOB_CASES, case_values
 from tests.test_stages_fp64_gpu import FLOOR, _rel
 
@@ -180,22 +181,17 @@ def test_caller_workspace_of_exactly_cotr_scratch_bytes_pairs():
     qs = queries(len(pairs), 333, seed=51).cuda()
     ref = m.forward_pairs(images, pairs, qs)['pred_corrs'].clone()
     B, Q = len(pairs), 333
-    need = ctypes.c_size_t()
-    assert lib.cotr_scratch_bytes_pairs(m._handle, POOL, B, Q, ctypes.byref(need)) == 0
-    ws = torch.full((need.value + 256,), 255, dtype=torch.uint8, device='cuda')   # 0xffffffff floats: NaN
-    off = (-ws.data_ptr()) % 256
-    m._ws, m._ws_shape, m._encoded_batch = None, (0, 0), 0
-    assert lib.cotr_set_workspace(m._handle, ctypes.c_void_p(ws.data_ptr() + off), need.value, 0, None) == 0
     guard = 4096
     buf = torch.full((B * Q * 2 + guard,), 7.25, device='cuda')
     idx = (ctypes.c_int * (2 * B))(*[v for p in pairs for v in p])
-    rc = lib.cotr_forward_pairs(m._handle, images.data_ptr(), POOL, idx, qs.data_ptr(), B, Q, buf.data_ptr(), _lib.current_stream_ptr())
-    assert rc == 0, lib.cotr_last_error(m._handle)
-    torch.cuda.synchronize()
-    assert torch.equal(buf[:B * Q * 2].view(B, Q, 2), ref)
-    assert bool((buf[B * Q * 2:] == 7.25).all())
-    assert lib.cotr_set_workspace(m._handle, None, 0, 0, None) == 0
-    del ws
+    with raw_abi.caller_workspace(m, raw_abi.scratch_bytes_pairs(m, POOL, B, Q), fill=float('nan')):
+        rc = lib.cotr_forward_pairs(m._handle, images.data_ptr(), POOL, idx, qs.data_ptr(), B, Q, buf.data_ptr(),
+                                    _lib.current_stream_ptr())
+        assert rc == 0, lib.cotr_last_error(m._handle)
+        torch.cuda.synchronize()
+        assert torch.equal(buf[:B * Q * 2].view(B, Q, 2), ref)
+        assert bool((buf[B * Q * 2:] == 7.25).all())
+        assert raw_abi.set_workspace(m, None, 0) == 0
 
 
 # ---- 6. graph capture ---------------------------------------------------------------------------------------------------------------

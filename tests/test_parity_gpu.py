@@ -242,18 +242,6 @@ def test_middle_of_the_batch_axis_against_the_oracle(b, q, mixes, what):
     assert torch.equal(outs[0], plain) != mixes, 'the default dispatch is not the mix this case names: ' + what
 
 
-def _passes(m, b, q, which):
-    import ctypes
-    from cotr_amd import _lib
-    sizes = (ctypes.c_int * 64)()
-    if m._handle is None:   # the handle is made by the first call
-        img0, qs0 = synth_inputs(1, 1, seed=1)
-        m(img0.cuda(), qs0.cuda())
-    n = _lib.load_library().cotr_batch_chunks(m._handle, b, q, which, sizes, 64)
-    assert 0 < n <= 64
-    return list(sizes[:n])
-
-
 @pytest.mark.parametrize('b,q', [(17, 1000), (33, 40), (20, 257)])
 def test_batch_split_walks_a_batch_as_independent_passes(b, q):
     """Knob batch_split (round 6): the forward's time against the pair count is a staircase, so a batch just above a step is walked as
@@ -265,18 +253,18 @@ def test_batch_split_walks_a_batch_as_independent_passes(b, q):
     sd = synth_state_dict(0)
     img, qs = synth_inputs(b, q, seed=300 + b)
     m = hip_model()
-    enc, dec = _passes(m, b, q, 0), _passes(m, b, q, 1)
+    enc, dec = m.batch_chunks(b, q, 0), m.batch_chunks(b, q, 1)
     assert sum(enc) == b and sum(dec) == b and min(enc + dec) >= 1
     out = m(img.cuda(), qs.cuda())['pred_corrs'].cpu()
     assert torch.equal(out, m(img.cuda(), qs.cuda())['pred_corrs'].cpu())
-    if enc == dec and all(_passes(m, c, q, 0) == [c] and _passes(m, c, q, 1) == [c] for c in enc):
+    if enc == dec and all(m.batch_chunks(c, q, 0) == [c] and m.batch_chunks(c, q, 1) == [c] for c in enc):
         parts, a = [], 0
         for c in enc:
             parts.append(m(img[a:a + c].cuda(), qs[a:a + c].cuda())['pred_corrs'].cpu())
             a += c
         assert torch.equal(out, torch.cat(parts)), (enc, dec)
     with G.model_knobs(m, batch_split=0):
-        assert _passes(m, b, q, 0) == [b] and _passes(m, b, q, 1) == [b]
+        assert m.batch_chunks(b, q, 0) == [b] and m.batch_chunks(b, q, 1) == [b]
         one = m(img.cuda(), qs.cuda())['pred_corrs'].cpu()
     assert cotr_oracle.px_err(out, one) < SHAPE_NOISE_PX
     idx = [0, 1, b - 1]
@@ -295,7 +283,7 @@ def test_random_shapes_against_the_oracle_and_the_one_pass_schedule():
     shapes = [(rng.randint(1, 70), rng.choice([1, rng.randint(2, 300), rng.randint(300, 1200)])) for _ in range(24)]
     for i, (b, q) in enumerate(shapes):
         img, qs = synth_inputs(b, q, seed=500 + i)
-        enc, dec = _passes(m, b, q, 0), _passes(m, b, q, 1)
+        enc, dec = m.batch_chunks(b, q, 0), m.batch_chunks(b, q, 1)
         assert sum(enc) == b and sum(dec) == b, (b, q, enc, dec)
         out = m(img.cuda(), qs.cuda())['pred_corrs'].cpu()
         assert torch.isfinite(out).all(), (b, q)
@@ -373,8 +361,8 @@ def test_caller_supplied_workspace():
     """cotr_set_workspace: the library's encode cache + scratch live in the caller's (torch caching allocator's) memory.
     Growing shapes re-carve a larger workspace; a cached encode survives the move; a workspace that is too small is an error,
     not an overrun; NULL goes back to handle-owned memory; results do not depend on where the scratch lives."""
-    import ctypes
     from cotr_amd import _lib
+    from tests import raw_abi
     lib = _lib.load_library()
     sd = synth_state_dict(0)
     m = build_model(cotr_amd.default_args()).cuda().eval()
@@ -382,33 +370,33 @@ def test_caller_supplied_workspace():
     img, qs = synth_inputs(2, 40, seed=23)
     img, qs = img.cuda(), qs.cuda()
     a = m(img[:1], qs[:1, :8])['pred_corrs'].clone()
-    assert m._ws is not None and m._ws_shape == (1, 8)
-    first_ws = m._ws.data_ptr()
+    assert m.workspace.buffer is not None and m.workspace.shape == (1, 8)
+    first_ws = m.workspace.buffer.data_ptr()
     b = m(img, qs)['pred_corrs'].clone()                       # larger B and Q: new workspace
-    assert m._ws_shape == (2, 40) and m._ws.data_ptr() != first_ws
+    assert m.workspace.shape == (2, 40) and m.workspace.buffer.data_ptr() != first_ws
     assert torch.equal(m(img[:1], qs[:1, :8])['pred_corrs'], a)          # smaller call inside the larger workspace
     m.encode(img)
     small = m.decode(qs[:, :8]).clone()
     _, big_q = synth_inputs(2, 3000, seed=24)
     big = m.decode(big_q.cuda())                               # Q beyond the workspace: it grows, the cached encode moves along
-    assert m._ws_shape == (2, 3000)
+    assert m.workspace.shape == (2, 3000)
     assert torch.equal(m.decode(qs[:, :8]), small)
     ref = cotr_oracle.cotr_forward(sd, img.cpu(), big_q[:, ::100])
     assert cotr_oracle.px_err(big.cpu()[:, ::100], ref) < PX_BAR
     assert cotr_oracle.px_err(b.cpu(), cotr_oracle.cotr_forward(sd, img.cpu(), qs.cpu())) < PX_BAR
     # raw ABI: a workspace that is too small is refused with a message; NULL returns to handle-owned memory
     tiny = torch.empty(1 << 20, dtype=torch.uint8, device='cuda')
-    off = (-tiny.data_ptr()) % 256
-    m._ws, m._ws_shape, m._encoded_batch = None, (0, 0), 0
-    assert lib.cotr_set_workspace(m._handle, ctypes.c_void_p(tiny.data_ptr() + off), (1 << 20) - 256, 0, None) == 0
     out = torch.empty(2, 40, 2, device='cuda')
-    rc = lib.cotr_forward(m._handle, img.data_ptr(), qs.data_ptr(), 2, 40, out.data_ptr(), _lib.current_stream_ptr())
-    assert rc == -1 and b'workspace too small' in lib.cotr_last_error(m._handle)
-    assert lib.cotr_set_workspace(m._handle, None, 0, 0, None) == 0
-    rc = lib.cotr_forward(m._handle, img.data_ptr(), qs.data_ptr(), 2, 40, out.data_ptr(), _lib.current_stream_ptr())
-    assert rc == 0 and torch.equal(out, b)
-    need = ctypes.c_size_t()
-    assert lib.cotr_scratch_bytes(m._handle, 2, 40, ctypes.byref(need)) == 0 and need.value > (1 << 20)
+    try:
+        assert raw_abi.set_workspace(m, tiny, (1 << 20) - 256) == 0
+        rc = lib.cotr_forward(m._handle, img.data_ptr(), qs.data_ptr(), 2, 40, out.data_ptr(), _lib.current_stream_ptr())
+        assert rc == -1 and b'workspace too small' in lib.cotr_last_error(m._handle)
+        assert raw_abi.set_workspace(m, None, 0) == 0
+        rc = lib.cotr_forward(m._handle, img.data_ptr(), qs.data_ptr(), 2, 40, out.data_ptr(), _lib.current_stream_ptr())
+        assert rc == 0 and torch.equal(out, b)
+        assert raw_abi.scratch_bytes(m, 2, 40) > (1 << 20)
+    finally:
+        m.drop_workspace()          # the handle no longer holds the model's buffer
 
 
 def test_workspace_serves_smaller_shapes_in_any_order():
@@ -419,13 +407,13 @@ def test_workspace_serves_smaller_shapes_in_any_order():
     m = build_model(cotr_amd.default_args()).cuda().eval()
     m.load_state_dict(sd)
     m.reserve(4, 700)
-    ws = m._ws.data_ptr()
+    ws = m.workspace.buffer.data_ptr()
     shapes = [(1, 700), (2, 300), (4, 16), (1, 700), (3, 1), (4, 700)]
     outs = []
     for b, q in shapes:
         img, qs = synth_inputs(b, q, seed=100 + b * 1000 + q)
         outs.append(m(img.cuda(), qs.cuda())['pred_corrs'].clone())
-        assert m._ws.data_ptr() == ws, 'the reserved workspace must be enough'
+        assert m.workspace.buffer.data_ptr() == ws, 'the reserved workspace must be enough'
     for (b, q), o in zip(shapes[1:4], outs[1:4]):
         fresh = build_model(cotr_amd.default_args()).cuda().eval()
         fresh.load_state_dict(sd)
@@ -480,8 +468,8 @@ def test_config3_256_pairs_x_1000_queries():
 def test_backbone_entry_points_match_the_stage_taps():
     """cotr_backbone / cotr_backbone_upto (the frozen part of the backbone in the training step) return exactly the layer1 /
     layer2 / layer3 activations the full encode produces (debug taps), in NHWC over the side-by-side pair."""
-    import ctypes
     from cotr_amd import _lib
+    from tests import raw_abi
     lib = _lib.load_library()
     img, qs = synth_inputs(3, 4, seed=41)
     m = hip_model()
@@ -492,10 +480,7 @@ def test_backbone_entry_points_match_the_stage_taps():
     m.set_debug_taps(False)
     shapes = {1: (3, 64, 128, 256), 2: (3, 32, 64, 512), 3: (3, 16, 32, 1024)}
     for stage, shape in shapes.items():
-        out = torch.full(shape, float('nan'), device='cuda')
-        _lib.check(lib.cotr_backbone_upto(m._handle, img_d.data_ptr(), 3, stage, out.data_ptr(), _lib.current_stream_ptr()),
-                   m._handle, 'cotr_backbone_upto')
-        torch.cuda.synchronize()
+        out = m.backbone_upto(img_d, stage, out=torch.full(shape, float('nan'), device='cuda'))
         ref = taps[f'layer{stage}'].view(shape)
         # the taps run uses the unfused stem (it keeps the 'stem' tap): same math, different MFMA shape in conv1
         assert (out - ref).abs().max().item() <= 2e-5 * ref.abs().max().item(), stage
@@ -504,7 +489,9 @@ def test_backbone_entry_points_match_the_stage_taps():
                'cotr_backbone')
     torch.cuda.synchronize()
     assert torch.equal(full.view(3, 16, 32, 1024), out)
-    assert lib.cotr_backbone_upto(m._handle, img_d.data_ptr(), 3, 4, out.data_ptr(), _lib.current_stream_ptr()) != 0
+    assert raw_abi.backbone_upto(m, img_d, 4, out) != 0
+    with pytest.raises(ValueError, match='stage'):
+        m.backbone_upto(img_d, 4, out=out)
 
 
 def test_knobs_are_per_handle():

@@ -16,13 +16,11 @@ test_checked_shapes_launch_every_kernel_the_dispatch_can_launch ties SHAPES to t
 forward (cotr_set_profiling 2) at every B in 1 ... 70 and Q in COVERAGE_Q, normalises each name to a key (launch_key) and asserts that
 SHAPES reach every key.
 """
-import ctypes
 import re
 
 import pytest
 import torch
 
-from cotr_amd import _lib
 from cotr_amd.utils.synth import synth_state_dict, synth_inputs
 from oracle import cotr_oracle as O
 from tests.test_parity_gpu import PX_BAR, hip_model
@@ -93,22 +91,6 @@ def shape_queries(b, q):
     return torch.where(wide, torch.rand(b, q, 2, generator=g) * 2 - 0.5, qs)
 
 
-def backbone_upto(m, img, stage):
-    lib = _lib.load_library()
-    out = torch.full((img.shape[0],) + LAYER_SHAPE[stage], float('nan'), device='cuda')
-    _lib.check(lib.cotr_backbone_upto(m._handle, img.data_ptr(), img.shape[0], stage, out.data_ptr(), _lib.current_stream_ptr()),
-               m._handle, 'cotr_backbone_upto')
-    torch.cuda.synchronize()
-    return out
-
-
-def passes(m, b, q, which):
-    sizes = (ctypes.c_int * 128)()
-    n = _lib.load_library().cotr_batch_chunks(m._handle, b, q, which, sizes, 128)
-    assert 0 < n <= 128
-    return list(sizes[:n])
-
-
 @pytest.mark.parametrize('b,q', SHAPES, ids=[f'{b}x{q}' for b, q in SHAPES])
 def test_every_stage_of_every_pair_against_float64(b, q):
     P = pool()
@@ -121,8 +103,8 @@ def test_every_stage_of_every_pair_against_float64(b, q):
     got = {'memory': m.debug_tap('memory').view(b, 512, 256), 'kv': m.debug_tap('kv').view(b, 512, -1)}
     pos = m.debug_tap('pos').view(512, 256)
     for stage in (1, 2, 3):
-        got[f'layer{stage}'] = backbone_upto(m, img, stage)
-    one_decode_pass = passes(m, b, q, 1) == [b]
+        got[f'layer{stage}'] = m.backbone_upto(img, stage, out=torch.full((b,) + LAYER_SHAPE[stage], float('nan'), device='cuda'))
+    one_decode_pass = m.batch_chunks(b, q, 1) == [b]
     if one_decode_pass:
         m.set_debug_taps(True)
         try:
@@ -186,16 +168,13 @@ def launch_key(name):
 
 def launch_keys(m, img, qs):
     """the keys of one profiled forward (profiling turns the side stream off; side_stream is off by default)"""
-    lib = _lib.load_library()
     m.set_profiling(2)
     try:
         m(img, qs)
         torch.cuda.synchronize()
-        cap = 8192
-        names, n = (ctypes.c_char_p * cap)(), ctypes.c_int()
-        _lib.check(lib.cotr_get_profile(m._handle, names, None, cap, ctypes.byref(n)), m._handle, 'profile')
-        assert 0 < n.value < cap
-        return {launch_key(names[i].decode()) for i in range(n.value)}
+        names = m.profile_names()
+        assert 0 < len(names)
+        return {launch_key(name) for name in names}
     finally:
         m.set_profiling(0)
 

@@ -28,6 +28,7 @@ import torch
 from cotr_amd import _lib
 from oracle import cotr_oracle as O
 from tests import gpu_helpers as G
+from tests import raw_abi
 from tests.knob_cases import KNOB_CASES, case_runs
 from tests.test_parity_gpu import PX_BAR, SHAPE_NOISE_PX, hip_model
 from tests.test_stages_fp64_gpu import COVERAGE_Q, FLOOR, POOL, _rel, launch_key, pool
@@ -107,22 +108,14 @@ def offsets(counts):
     return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
 
 
-def profile_names(m):
-    lib = _lib.load_library()
-    torch.cuda.synchronize()
-    cap = 8192
-    names, n = (ctypes.c_char_p * cap)(), ctypes.c_int()
-    _lib.check(lib.cotr_get_profile(m._handle, names, None, cap, ctypes.byref(n)), m._handle, 'profile')
-    assert 0 < n.value < cap
-    return [names[i].decode() for i in range(n.value)]
-
-
 def profiled(m, fn):
     """(result of fn(), the per-launch names of its decoder: from its first posenc launch on; every decode pass starts with one)"""
     m.set_profiling(2)
     try:
         out = fn()
-        names = profile_names(m)
+        torch.cuda.synchronize()
+        names = m.profile_names()
+        assert 0 < len(names)
     finally:
         m.set_profiling(0)
     return out, names[names.index('posenc'):]
@@ -287,47 +280,32 @@ def test_the_patterns_reach_every_planner_branch():
 GUARD = -7.25
 
 
-def sized_workspace(nbytes, fill):
-    ws = torch.empty((nbytes + 256 + 3) // 4, dtype=torch.float32, device='cuda').fill_(fill)
-    return ws, (-ws.data_ptr()) % 256
-
-
 def raw_call(m, nbytes, fill, call, n):
     """call(out_ptr) on a caller workspace of exactly nbytes (cotr_set_workspace, keep_encode 0) filled with `fill`; out: n + 1 rows
     of NaN, the last one a guard.  The model's own workspace is dropped afterwards (its next call sizes and hands over a new one)."""
-    lib = _lib.load_library()
-    ws, off = sized_workspace(nbytes, fill)
     out = torch.full((n + 1, 2), float('nan'), device='cuda')
     out[n] = GUARD
-    try:
-        assert lib.cotr_set_workspace(m._handle, ctypes.c_void_p(ws.data_ptr() + off), nbytes, 0, _lib.current_stream_ptr()) == 0
+    with raw_abi.caller_workspace(m, nbytes, fill):
         rc = call(out.data_ptr())
-        assert rc == 0, lib.cotr_last_error(m._handle)
-        torch.cuda.synchronize()
-    finally:
-        torch.cuda.synchronize()
-        m._ws, m._ws_shape, m._encoded_batch = None, (0, 0), 0
+        assert rc == 0, _lib.load_library().cotr_last_error(m._handle)
     return out.cpu()
 
 
 def varlen_in_workspace(m, img, q, counts, fill):
     lib = _lib.load_library()
     arr = (ctypes.c_int * (len(counts) + 1))(*offsets(counts).tolist())
-    need = ctypes.c_size_t()
-    assert lib.cotr_scratch_bytes_varlen(m._handle, arr, len(counts), ctypes.byref(need)) == 0
     imgd, qd = img.cuda().contiguous(), q.cuda().contiguous()
-    return raw_call(m, need.value, fill, lambda o: lib.cotr_forward_varlen(m._handle, imgd.data_ptr(), qd.data_ptr(), arr, len(counts), o,
-                                                                           _lib.current_stream_ptr()), sum(counts))
+    return raw_call(m, raw_abi.scratch_bytes_varlen(m, arr), fill,
+                    lambda o: lib.cotr_forward_varlen(m._handle, imgd.data_ptr(), qd.data_ptr(), arr, len(counts), o,
+                                                      _lib.current_stream_ptr()), sum(counts))
 
 
 def uniform_in_workspace(m, img, q, fill):
     lib = _lib.load_library()
     b, nq = q.shape[:2]
-    need = ctypes.c_size_t()
-    assert lib.cotr_scratch_bytes(m._handle, b, nq, ctypes.byref(need)) == 0
     imgd, qd = img.cuda().contiguous(), q.cuda().contiguous()
-    return raw_call(m, need.value, fill, lambda o: lib.cotr_forward(m._handle, imgd.data_ptr(), qd.data_ptr(), b, nq, o,
-                                                                    _lib.current_stream_ptr()), b * nq)
+    return raw_call(m, raw_abi.scratch_bytes(m, b, nq), fill,
+                    lambda o: lib.cotr_forward(m._handle, imgd.data_ptr(), qd.data_ptr(), b, nq, o, _lib.current_stream_ptr()), b * nq)
 
 
 def check_poisoned(nan, zero, n):

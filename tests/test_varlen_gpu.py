@@ -15,6 +15,7 @@ from cotr_amd.models import build_model
 from cotr_amd.utils.synth import synth_state_dict, synth_inputs
 from oracle import cotr_oracle
 from tests import gpu_helpers as G
+from tests import raw_abi
 from tests.engine_fixtures import ids, synthetic_pair
 
 pytestmark = pytest.mark.gpu
@@ -108,7 +109,7 @@ def test_every_varlen_attention_form_matches_the_oracle(form):
         m.set_profiling(2)
         try:
             out = m.forward_varlen(img.cuda(), q.cuda(), counts).cpu()
-            names = [n for n, _ in m.get_profile()]
+            names = m.profile_names()
         finally:
             m.set_profiling(0)
     assert any(n.startswith(launch) for n in names), (form, sorted(set(names)))
@@ -189,22 +190,17 @@ def test_caller_workspace_from_cotr_scratch_bytes_varlen():
     img, q = inputs(counts, seed=56)
     ref = m.forward_varlen(img.cuda(), q.cuda(), counts)       # the binding's own workspace
     offsets = (ctypes.c_int * (len(counts) + 1))(*np.concatenate([[0], np.cumsum(counts)]).tolist())
-    need = ctypes.c_size_t()
-    assert lib.cotr_scratch_bytes_varlen(m._handle, offsets, len(counts), ctypes.byref(need)) == 0
-    ws = torch.empty(need.value + 256, dtype=torch.uint8, device='cuda')
-    off = (-ws.data_ptr()) % 256
-    m._ws, m._ws_shape, m._encoded_batch = None, (0, 0), 0
-    assert lib.cotr_set_workspace(m._handle, ctypes.c_void_p(ws.data_ptr() + off), need.value, 0, None) == 0
     out = torch.empty(sum(counts), 2, device='cuda')
     imgd, qd = img.cuda(), q.cuda()
-    rc = lib.cotr_forward_varlen(m._handle, imgd.data_ptr(), qd.data_ptr(), offsets, len(counts), out.data_ptr(),
-                                 _lib.current_stream_ptr())
-    assert rc == 0, lib.cotr_last_error(m._handle)
-    assert torch.equal(out, ref)
-    # and the varlen decode against that encode, same workspace
-    rc = lib.cotr_decode_varlen(m._handle, qd.data_ptr(), offsets, len(counts), out.data_ptr(), _lib.current_stream_ptr())
-    assert rc == 0 and torch.equal(out, ref)
-    assert lib.cotr_set_workspace(m._handle, None, 0, 0, None) == 0
+    with raw_abi.caller_workspace(m, raw_abi.scratch_bytes_varlen(m, offsets)):
+        rc = lib.cotr_forward_varlen(m._handle, imgd.data_ptr(), qd.data_ptr(), offsets, len(counts), out.data_ptr(),
+                                     _lib.current_stream_ptr())
+        assert rc == 0, lib.cotr_last_error(m._handle)
+        assert torch.equal(out, ref)
+        # and the varlen decode against that encode, same workspace
+        rc = lib.cotr_decode_varlen(m._handle, qd.data_ptr(), offsets, len(counts), out.data_ptr(), _lib.current_stream_ptr())
+        assert rc == 0 and torch.equal(out, ref)
+        assert raw_abi.set_workspace(m, None, 0) == 0
 
 
 def test_malformed_offsets_on_a_real_handle():
