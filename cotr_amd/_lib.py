@@ -170,6 +170,8 @@ _PROTOS = {
     'cotr_debug_ffn_times': (ctypes.c_int, [ctypes.c_void_p]),
     'cotr_debug_attention_times': (ctypes.c_int, [ctypes.c_void_p]),
     'cotr_gemm_pick_conv': (ctypes.c_int, [ctypes.c_int] * 7),
+    'cotr_gemm_pick_linear': (ctypes.c_int, [ctypes.c_int] * 4),
+    'cotr_gemm_config_info': (ctypes.c_int, [ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 3),
     'cotr_debug_conv_times': (ctypes.c_int, [c_float_p, c_float_p, c_float_p, c_float_p, c_float_p] + [ctypes.c_int] * 8 +
                               [ctypes.c_void_p, ctypes.c_void_p]),
 }

@@ -1723,15 +1723,8 @@ int cotr_op_linear(const float* x, const float* x2, int x2_row_mod, const float*
 int cotr_op_conv(const float* x, const float* w, const float* scale, const float* bias,
                  const float* residual, int relu, float* y, int B, int Hin, int Win, int Cin, int Cout,
                  int ksize, int stride, cotr_stream stream) {
-  GemmParams p = base_params();
-  const int pad = ksize / 2;
-  p.Hin = Hin; p.Win = Win; p.Cin = Cin;
-  p.Hout = (Hin + 2 * pad - ksize) / stride + 1;
-  p.Wout = (Win + 2 * pad - ksize) / stride + 1;
-  p.ksize = ksize; p.stride = stride; p.pad = pad;
-  p.M = B * p.Hout * 2 * p.Wout; p.N = Cout; p.K = ksize * ksize * Cin;
-  p.A = x; p.lda = Cin; p.W = w; p.C = y; p.ldc = Cout;
-  p.scale = scale; p.bias = bias; p.residual = residual; p.ldr = Cout; p.relu = relu;
+  const ConvW c = {w, scale, bias, Cin, Cout, ksize, stride};
+  const GemmParams p = conv_params(c, x, residual, relu, y, B, Hin, Win);
   return op_ret(launch_gemm(GEMM_CONV, p, static_cast<hipStream_t>(stream)));
 }
 
@@ -1920,14 +1913,8 @@ int cotr_bench_linear(const float* x, const float* w, const float* bias, float* 
 
 int cotr_bench_conv(const float* x, const float* w, const float* scale, const float* bias, float* y, int B, int Hin,
                     int Win, int Cin, int Cout, int ksize, int stride, int cfg, int iters, float* us) {
-  GemmParams p = base_params();
-  const int pad = ksize / 2;
-  p.Hin = Hin; p.Win = Win; p.Cin = Cin;
-  p.Hout = (Hin + 2 * pad - ksize) / stride + 1;
-  p.Wout = (Win + 2 * pad - ksize) / stride + 1;
-  p.ksize = ksize; p.stride = stride; p.pad = pad;
-  p.M = B * p.Hout * 2 * p.Wout; p.N = Cout; p.K = ksize * ksize * Cin;
-  p.A = x; p.lda = Cin; p.W = w; p.C = y; p.ldc = Cout; p.scale = scale; p.bias = bias; p.relu = 1;
+  const ConvW c = {w, scale, bias, Cin, Cout, ksize, stride};
+  const GemmParams p = conv_params(c, x, nullptr, 1, y, B, Hin, Win);
   if (cfg < 0) cfg = gemm_pick_config(GEMM_CONV, p);
   return bench_launches(GEMM_CONV, cfg, p, iters, us);
 }
@@ -1944,15 +1931,8 @@ int cotr_op_linear_cfg(const float* x, const float* w, const float* bias, const 
 int cotr_op_conv_cfg(const float* x, const float* w, const float* scale, const float* bias, const float* residual,
                      int relu, float* y, int B, int Hin, int Win, int Cin, int Cout, int ksize, int stride, int cfg,
                      cotr_stream stream) {
-  GemmParams p = base_params();
-  const int pad = ksize / 2;
-  p.Hin = Hin; p.Win = Win; p.Cin = Cin;
-  p.Hout = (Hin + 2 * pad - ksize) / stride + 1;
-  p.Wout = (Win + 2 * pad - ksize) / stride + 1;
-  p.ksize = ksize; p.stride = stride; p.pad = pad;
-  p.M = B * p.Hout * 2 * p.Wout; p.N = Cout; p.K = ksize * ksize * Cin;
-  p.A = x; p.lda = Cin; p.W = w; p.C = y; p.ldc = Cout;
-  p.scale = scale; p.bias = bias; p.residual = residual; p.ldr = Cout; p.relu = relu;
+  const ConvW c = {w, scale, bias, Cin, Cout, ksize, stride};
+  const GemmParams p = conv_params(c, x, residual, relu, y, B, Hin, Win);
   return op_ret(launch_gemm_cfg(GEMM_CONV, cfg, p, static_cast<hipStream_t>(stream)));
 }
 
@@ -1972,30 +1952,38 @@ int cotr_debug_attention_times(unsigned long long* times) {
 
 // the configuration the library would pick for this convolution (tools)
 int cotr_gemm_pick_conv(int B, int Hin, int Win, int Cin, int Cout, int ksize, int stride) {
-  GemmParams p = base_params();
-  const int pad = ksize / 2;
-  p.Hin = Hin; p.Win = Win; p.Cin = Cin;
-  p.Hout = (Hin + 2 * pad - ksize) / stride + 1;
-  p.Wout = (Win + 2 * pad - ksize) / stride + 1;
-  p.ksize = ksize; p.stride = stride; p.pad = pad;
-  p.M = B * p.Hout * 2 * p.Wout; p.N = Cout; p.K = ksize * ksize * Cin;
-  p.lda = Cin; p.ldc = Cout; p.ldr = Cout;
+  const ConvW c = {nullptr, nullptr, nullptr, Cin, Cout, ksize, stride};   // the pick reads the geometry only
+  const GemmParams p = conv_params(c, nullptr, nullptr, 0, nullptr, B, Hin, Win);
   return gemm_pick_config(GEMM_CONV, p);
+}
+
+// tile and dual form of a launch configuration, from its row (gemm.hip kCfgs); no HIP call
+int cotr_gemm_config_info(int cfg, int* bm, int* bn, int* has_dual) {
+  const GemmCfg* c = gemm_config(cfg);
+  if (c == nullptr) return COTR_ERR_ARG;
+  if (bm) *bm = c->bm;
+  if (bn) *bn = c->bn;
+  if (has_dual) *has_dual = c->dual != nullptr;
+  return COTR_OK;
+}
+
+// the configuration launch_gemm would pick for a dense product with lda = K, ldc = ldr = N and aligned pointers (tests, tools); flags bit 0:
+// the x + pos prologue is present, bit 1: the residual is a row-periodic table.  No HIP call: the operands are never dereferenced
+int cotr_gemm_pick_linear(int M, int N, int K, int flags) {
+  alignas(16) static const float operand[4] = {};
+  GemmParams p = base_params();
+  p.M = M; p.N = N; p.K = K; p.lda = K; p.ldc = N; p.ldr = N;
+  if (flags & 1) { p.A2 = operand; p.lda2 = K; p.a2_width = 1; }
+  if (flags & 2) { p.residual = operand; p.res_row_mod = M; }
+  return gemm_pick_config(GEMM_DENSE, p);
 }
 
 // one convolution launch with the k-split kernels' phase timestamps written to `times` (device, [workgroups][8] uint64, 100 MHz
 // wall clock; slots 0..4 = entry, loads issued, first data usable, K loop done, stored): tools/conv_phases.py
 int cotr_debug_conv_times(const float* x, const float* w, const float* scale, const float* bias, float* y, int B, int Hin, int Win,
                           int Cin, int Cout, int ksize, int stride, int cfg, unsigned long long* times, cotr_stream stream) {
-  GemmParams p = base_params();
-  const int pad = ksize / 2;
-  p.Hin = Hin; p.Win = Win; p.Cin = Cin;
-  p.Hout = (Hin + 2 * pad - ksize) / stride + 1;
-  p.Wout = (Win + 2 * pad - ksize) / stride + 1;
-  p.ksize = ksize; p.stride = stride; p.pad = pad;
-  p.M = B * p.Hout * 2 * p.Wout; p.N = Cout; p.K = ksize * ksize * Cin;
-  p.A = x; p.lda = Cin; p.W = w; p.C = y; p.ldc = Cout;
-  p.scale = scale; p.bias = bias; p.relu = 1;
+  const ConvW c = {w, scale, bias, Cin, Cout, ksize, stride};
+  GemmParams p = conv_params(c, x, nullptr, 1, y, B, Hin, Win);
   p.dbg = times;
   return op_ret(launch_gemm_cfg(GEMM_CONV, cfg, p, static_cast<hipStream_t>(stream)));
 }

@@ -256,21 +256,57 @@ static inline bool gemm_fill_divs(GemmParams& p, int mode, int bm, int bn) {
   return ok;
 }
 
+// ---------------------------------------------------------------------------------------------
+// One launch configuration of the GEMM / implicit-GEMM kernels: everything the host asks about it.  A row is built by a constexpr
+// maker next to its kernel (spatial_cfg / ks_cfg in gemm.hip, big_cfg / ws_cfg in gemm_big.hip, wp_cfg in gemm_wp.hip) from the SAME
+// template arguments that instantiate the kernel and its launchers, so a row cannot disagree with the code it launches.  The table
+// kCfgs[] (gemm.hip) maps the configuration index - what gemm_tuned.inc, the profile names, the tools and the tests speak of - to
+// its row and is the only place that does; cfg_fits, the cost model, the XCD mapping and the launches read the row.
+// ---------------------------------------------------------------------------------------------
+typedef int (*GemmLaunchFn)(const GemmParams& p, hipStream_t s);
+typedef int (*GemmDualFn)(const GemmParams& p0, const GemmParams& p1, hipStream_t s);
+enum GemmFamily {
+  GF_NONE,     // an index this library has no kernel for (it never fits; the index stays)
+  GF_SPATIAL,  // 2 x 2 wavefronts share the tile, each walks the whole K (gemm_kernel)
+  GF_KSPLIT,   // every wavefront computes the whole tile over its own 32-wide slice of a K step, summed through LDS (gemm_ks_kernel)
+  GF_BIG,      // 128-row tiles, LDS-DMA operands, swizzled LDS, float4 epilogue (gemm_big.hip)
+  GF_WP,       // wave-private K chunks: no barrier in the K loop (gemm_wp.hip)
+};
+enum : unsigned {
+  GC_A2 = 1,           // takes the x + pos prologue (register-staged operands)
+  GC_RES_ROW_MOD = 2,  // takes a row-periodic residual table (res_row_mod)
+  GC_VEC4 = 4,         // float4 epilogue: ldc, ldr multiples of 4, C and the residual 16-byte aligned
+  GC_PATCH = 8,        // 3x3 stride-1 convolutions over 256 channels only: the input patch of a tile is loaded once
+  GC_TABLE_ONLY = 16,  // entered through the measured table (or forced) only: the cost model never proposes it
+};
+struct GemmCfg {
+  GemmFamily family;
+  int waves;           // wavefronts per workgroup
+  int bm, bn;          // workgroup tile
+  int stages;          // LDS stages of the operand tiles
+  size_t lds;          // LDS bytes of a workgroup: the dynamic size its launchers pass (spatial: its static array)
+  unsigned flags;      // GC_*
+  GemmLaunchFn dense, conv;   // nullptr: no such form
+  GemmDualFn dual;            // two convolutions in one grid, nullptr where that form is not instantiated
+};
+// the rows of gemm_big.hip (two LDS stages; ws: 4 loader + 4 MFMA wavefronts, four stages) and of gemm_wp.hip (wavefronts, tile, ring
+// slots).  Functions, not constants: a host function's body is also parsed by the device pass, which is what instantiates the kernels
+// its launchers name there (a constant with launcher addresses would have to be hidden from that pass, and the kernels with it).
+GemmCfg big128x128_cfg(), big128x64_cfg(), ws128x128_cfg(), ws128x64_cfg();
+GemmCfg wp8w32x32s2_cfg(), wp8w32x16s3_cfg(), wp4w32x32s2_cfg(), wp8w32x64s1_cfg(), wp4w32x32s1_cfg(), wp8w64x32s1_cfg(), wp4w32x32s4_cfg(),
+    wp8w32x16s2_cfg();
+
 int launch_gemm(int mode, const GemmParams& p, hipStream_t s);            // tuned / modelled config
 int launch_gemm_cfg(int mode, int cfg, const GemmParams& p, hipStream_t s);  // explicit config (tuning, tests)
 int gemm_pick_config(int mode, const GemmParams& p);
 bool gemm_conv_as_dense(const GemmParams& p);   // a 1x1 stride-1 convolution launched as the dense product (knob conv1x1_dense)
-int launch_gemm_big(int mode, int variant, const GemmParams& p, hipStream_t s);  // gemm_big.hip: 0 = 128x128, 1 = 128x64
-int launch_gemm_wp(int mode, int variant, const GemmParams& p, hipStream_t s);   // gemm_wp.hip: wave-private K chunks
-int launch_gemm_wp_dual(int mode, int variant, const GemmParams& p0, const GemmParams& p1, hipStream_t s);
-int wp_variant_tile(int variant, int* bm, int* bn, size_t* lds);
 // Two INDEPENDENT problems of the same mode in ONE launch (grid = tiles of p0 followed by tiles of p1, same kernel
 // configuration): the downsample branch of a bottleneck next to its conv1 (torchvision Bottleneck.forward: both read the block
-// input).  Supported configurations: the k-split ones without LDS-DMA (kinds 1, 2) and the large tiles (kind 4).
+// input).  Convolutions only, and only the configurations whose row has a dual launcher.
 int launch_gemm_dual_cfg(int mode, int cfg, const GemmParams& p0, const GemmParams& p1, hipStream_t s);
-int launch_gemm_big_dual(int mode, int variant, const GemmParams& p0, const GemmParams& p1, hipStream_t s);
 bool gemm_cfg_supports_dual(int cfg);
 int gemm_num_configs();
+const GemmCfg* gemm_config(int cfg);   // the row, nullptr outside the table
 const float* gemm_zero_buffer();  // per-DEVICE buffer of zeros (LDS-DMA padding source), on the current device
 // softmax(q k^T) v for 8 heads of 32; q rows are [nb][nq], keys/values [nb][512]
 int launch_attention(const float* q, int ldq, const float* k, const float* v, int ldkv, float* o, int ldo,

@@ -38,16 +38,17 @@ int launch_dec_head(const float* x, const float* nw, const float* nb, const floa
                     hipStream_t s);
 // pointwise.hip: the next ln_reduce launch also pulls two regions (the next launch's weights) through every XCD's L2 (knob l2_warm)
 void set_ln_reduce_warm(const float* p0, size_t bytes0, const float* p1, size_t bytes1);
-// gemm_pp.hip: persistent ping-pong large tiles (1 = 128 x 64 staged write-out, 3 = 128 x 64 LDS-free write-out)
-int launch_gemm_pp(int mode, int variant, const GemmParams& p, hipStream_t s);
+// the research rows of the launch-configuration table (common.h GemmCfg; gemm.hip kCfgs 28, 29, 42 - 51), functions like the product's
+GemmCfg big3s128x128_cfg(), big3s128x64_cfg(), bigDirect128x128_cfg(), bigDirect128x64_cfg();   // gemm_big.hip: three LDS stages; LDS-free epilogue
+GemmCfg bigH2_128x128_cfg(), bigH2_128x64_cfg(), wsH2_128x128_cfg(), wsH2_128x64_cfg(), bigH2_256x128_cfg();   // ... on packed split-f16 operands
+GemmCfg pp128x64_cfg(), ppDirect128x64_cfg();   // gemm_pp.hip: persistent ping-pong large tiles (staged / LDS-free write-out)
+GemmCfg h2r128x128_cfg();                  // gemm_h2r.hip: K = 256 dense GEMM on packed operands, A tile resident in registers
 int gemm_pp_workgroups();
 // gemm_h2.hip / gemm_h2.h (research): fp32 -> packed split-f16 dwords, the operand format of GEMM configurations 46 / 47
 int launch_split_h2(const float* x, void* y, size_t n, hipStream_t s, const float* x2 = nullptr);   // y = pack(x [+ x2])
 int launch_unsplit_h2(const void* x, float* y, size_t n, hipStream_t s);
 int* h2_overflow_flag();   // per-device flag raised by every kernel that packs an activation outside f16's range (round 5: range safety)
 // y = LayerNorm(x) (bits of launch_layernorm) and yp = pack(y [+ add]) in one launch
-// gemm_h2r.hip: K = 256 dense GEMM on packed operands, A tile resident in registers (configuration 50)
-int launch_gemm_h2r(const GemmParams& p, hipStream_t s);
 int launch_layernorm_h2(const float* x, const float* w, const float* b, float* y, void* yp, const float* add, int rows, hipStream_t s);
 // attention_h2.hip: the resident-K/V attention kernel on packed k / v (q fp32 or packed, o fp32 or packed)
 int launch_attention_h2(const float* q, int ldq, int q_packed, const float* k, const float* v, int ldkv, float* o, int ldo, int out_packed,

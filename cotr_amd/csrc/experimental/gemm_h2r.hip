@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }  // namespace
 
 // dense only, K = 256, N a multiple of 128, packed A / W (16-byte aligned rows: lda % 4 == 0)
-int launch_gemm_h2r(const GemmParams& p0, hipStream_t s) {
+static int launch_gemm_h2r(const GemmParams& p0, hipStream_t s) {
   GemmParams p = p0;
   if (p.K != RK || p.N % 128 != 0 || p.M <= 0 || p.A2 != nullptr || p.lda % 4 != 0 || p.scale != nullptr || p.res_row_mod > 0) return -1;
   if (!gemm_fill_divs(p, GEMM_DENSE, 128, 128)) return -1;
@@ -146,3 +146,6 @@ int launch_gemm_h2r(const GemmParams& p0, hipStream_t s) {
   hipLaunchKernelGGL(gemm_h2r_kernel, dim3(row_tiles * nsplit), dim3(256), H2R_SMEM, s, p, nsplit);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+
+// the configuration row (gemm.hip kCfgs 50): no convolution form; forced only
+GemmCfg h2r128x128_cfg() { return GemmCfg{GF_BIG, 4, 128, 128, 8, H2R_SMEM, GC_RES_ROW_MOD | GC_TABLE_ONLY, &launch_gemm_h2r, nullptr, nullptr}; }

@@ -363,11 +363,16 @@ int gemm_pp_workgroups() {
   return v;
 }
 
+static constexpr int pp_stages(int TN) { return TN == 2 ? 3 : 4; }
+template <int TN>
+static constexpr size_t pp_smem() {   // the operand stages + the epilogue staging tile
+  return ((size_t)pp_stages(TN) * (128 + 64 * TN) * BK + (size_t)4 * 32 * (32 * TN + 4)) * sizeof(float);
+}
+
 template <int TN, int MODE, bool DIRECT>
 static int launch_pp_t(const GemmParams& p0, hipStream_t s) {
   constexpr int BM = 128, BN = 64 * TN;
-  constexpr int NSTG = TN == 2 ? 3 : 4;
-  constexpr size_t smem = ((size_t)NSTG * (BM + BN) * BK + (size_t)4 * 32 * (32 * TN + 4)) * sizeof(float);
+  constexpr size_t smem = pp_smem<TN>();
   GemmParams p = p0;
   if (p.N % BN != 0 || p.K % BK != 0 || p.K < 2 * BK || p.M <= 0 || p.A2 != nullptr) return -1;
   if (p.ldc % 4 != 0 || (p.residual && p.ldr % 4 != 0)) return -1;
@@ -390,16 +395,13 @@ static int launch_pp_t(const GemmParams& p0, hipStream_t s) {
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-// variant 0: 128 x 128 tiles, 1: 128 x 64
-int launch_gemm_pp(int mode, int variant, const GemmParams& p, hipStream_t s) {
-  if (mode == GEMM_DENSE && p.lda % 4 != 0) return -1;
-  if (mode != GEMM_DENSE && mode != GEMM_CONV) return -1;
-  const bool d = mode == GEMM_DENSE;
-  switch (variant) {
-    // (the 128 x 128 instantiations are not built: with the piece-wise write-out hipcc keeps half of their accumulators in scratch -
-    //  43 TFLOP/s; their item-by-item form measured 375 us against 311 us for configuration 26 at 262144 x 256 x 256)
-    case 1: return d ? launch_pp_t<1, GEMM_DENSE, false>(p, s) : launch_pp_t<1, GEMM_CONV, false>(p, s);
-    case 3: return d ? launch_pp_t<1, GEMM_DENSE, true>(p, s) : launch_pp_t<1, GEMM_CONV, true>(p, s);    // LDS-free write-out
-    default: return -1;
-  }
+// the configuration rows (gemm.hip kCfgs 42, 43): 4 loader + 2 x 4 MFMA wavefronts, LDS-DMA operands, float4 epilogue; forced only.
+// (The 128 x 128 instantiations are not built: with the piece-wise write-out hipcc keeps half of their accumulators in scratch -
+//  43 TFLOP/s; their item-by-item form measured 375 us against 311 us for configuration 26 at 262144 x 256 x 256)
+template <int TN, bool DIRECT>
+static constexpr GemmCfg pp_cfg() {
+  return {GF_BIG, 12, 128, 64 * TN, pp_stages(TN), pp_smem<TN>(), GC_RES_ROW_MOD | GC_VEC4 | GC_TABLE_ONLY,
+          &launch_pp_t<TN, GEMM_DENSE, DIRECT>, &launch_pp_t<TN, GEMM_CONV, DIRECT>, nullptr};
 }
+GemmCfg pp128x64_cfg() { return pp_cfg<1, false>(); }
+GemmCfg ppDirect128x64_cfg() { return pp_cfg<1, true>(); }

@@ -688,64 +688,6 @@ __global__ __launch_bounds__(NWK * 64) void gemm_ks_dual_kernel(const GemmParams
   else gemm_ks_body<NWK, TM, TN, MODE, DB>(p1, (int)blockIdx.x - tiles0);
 }
 
-// ---------------------------------------------------------------------------------------------
-// launch configurations; the per-shape choice comes from a table measured on the MI355X
-// (tools/tune_gemm.py -> gemm_tuned.inc) with a heuristic for shapes not in the table.
-// ---------------------------------------------------------------------------------------------
-struct GemmCfg {
-  int kind;  // 0 = spatial (WM=WN=2), 1 = k-split, 2 = k-split with two LDS stages, 3 = k-split LDS-DMA (two stages),
-             // 4 = large tile, LDS-DMA, swizzled LDS, coalesced epilogue (gemm_big.hip)
-  int a, tm, tn;  // spatial: a unused; k-split: a = NWK
-};
-static const GemmCfg kCfgs[] = {
-    {0, 0, 2, 2},   // 0  spatial 128x128
-    {0, 0, 2, 1},   // 1  spatial 128x64
-    {0, 0, 1, 1},   // 2  spatial 64x64
-    {1, 8, 1, 1},   // 3  k-split 8 waves, 32x32
-    {1, 4, 1, 1},   // 4  k-split 4 waves, 32x32
-    {1, 4, 2, 2},   // 5  k-split 4 waves, 64x64
-    {1, 2, 2, 2},   // 6  k-split 2 waves, 64x64
-    {1, 8, 2, 1},   // 7  k-split 8 waves, 64x32
-    {1, 16, 1, 1},  // 8  k-split 16 waves, 32x32
-    {1, 4, 2, 1},   // 9  k-split 4 waves, 64x32
-    {1, 8, 1, 2},   // 10 k-split 8 waves, 32x64
-    {1, 2, 1, 1},   // 11 k-split 2 waves, 32x32
-    {1, 8, 2, 2},   // 12 k-split 8 waves, 64x64
-    {2, 8, 1, 1},   // 13 k-split 8 waves, 32x32, double-buffered LDS
-    {2, 4, 1, 1},   // 14 k-split 4 waves, 32x32, double-buffered
-    {2, 4, 2, 2},   // 15 k-split 4 waves, 64x64, double-buffered
-    {2, 8, 1, 2},   // 16 k-split 8 waves, 32x64, double-buffered
-    {2, 4, 2, 1},   // 17 k-split 4 waves, 64x32, double-buffered
-    {2, 2, 2, 2},   // 18 k-split 2 waves, 64x64, double-buffered
-    {3, 8, 1, 1},   // 19 k-split 8 waves, 32x32, LDS-DMA (global_load_lds) double-buffered
-    {3, 8, 1, 2},   // 20 k-split 8 waves, 32x64, LDS-DMA
-    {3, 8, 2, 1},   // 21 k-split 8 waves, 64x32, LDS-DMA
-    {1, 8, 1, 0},   // 22 k-split 8 waves, 32x16 (16x16x4 MFMA)
-    {2, 8, 1, 0},   // 23 k-split 8 waves, 32x16, double-buffered
-    {3, 8, 1, 0},   // 24 k-split 8 waves, 32x16, LDS-DMA double-buffered
-    {1, 4, 1, 0},   // 25 k-split 4 waves, 32x16
-    {4, 0, 2, 2},   // 26 large tile 128x128 (gemm_big.hip)
-    {4, 0, 2, 1},   // 27 large tile 128x64
-    {12, 0, 2, 2},  // 28 (research library only: large tile 128x128 with three LDS stages; kind 12 = never fits here, the index stays)
-    {12, 0, 2, 1},  // 29 (research library only: 128x64, three LDS stages)
-    {6, 8, 1, 0},   // 30 k-split 8 waves, 32x16, LDS-DMA with THREE stages (two tiles in flight, counted vmcnt)
-    {7, 8, 1, 0},   // 31 the same for 3x3 stride-1 convolutions over 256 channels with the input patch loaded once (DB == 4)
-    // kind 8: wave-private K chunks (gemm_wp.hip): every wavefront requests and reads its own run of 32-wide K chunks through
-    // its own ring of LDS slots - no barrier in the K loop, everything (or NSLOT chunks) requested up front; a = variant
-    {8, 0, 1, 1},   // 32 wave-private, 8 waves, 32x32, 2 slots
-    {8, 1, 1, 0},   // 33 wave-private, 8 waves, 32x16, 3 slots
-    {8, 2, 1, 1},   // 34 wave-private, 4 waves, 32x32, 2 slots (two workgroups per CU)
-    {8, 3, 1, 2},   // 35 wave-private, 8 waves, 32x64, 1 slot
-    {8, 4, 1, 1},   // 36 wave-private, 4 waves, 32x32, 1 slot (four workgroups per CU)
-    {8, 5, 2, 1},   // 37 wave-private, 8 waves, 64x32, 1 slot
-    {8, 6, 1, 1},   // 38 wave-private, 4 waves, 32x32, 4 slots
-    {8, 7, 1, 0},   // 39 wave-private, 8 waves, 32x16, 2 slots
-    {5, 0, 2, 2},   // 40 large tile 128x128, wave-specialised: 4 loader + 4 MFMA wavefronts, three LDS stages (gemm_big.hip, gemm_ws_body)
-    {5, 0, 2, 1},   // 41 large tile 128x64, wave-specialised
-};
-static const int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-int gemm_num_configs() { return kNumCfgs; }
-
 template <int WM, int WN, int TM, int TN, int MODE>
 static int launch_t(const GemmParams& p, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -757,10 +699,14 @@ static int launch_t(const GemmParams& p, hipStream_t s) {
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// LDS stages of the k-split kernels by operand path DB: 0 one, 1 two (register-staged), 2 two (LDS-DMA), 3 three (LDS-DMA, counted
+// waits), 4 the input patch of a 3x3 convolution loaded once (costed like two)
+static constexpr int ks_stages(int DB) { return DB == 3 ? 3 : DB ? 2 : 1; }
+
 template <int NWK, int TM, int TN, int DB>
 static constexpr size_t ks_smem() {
   size_t rows = (size_t)TM * 32 + (TN == 0 ? 16 : TN * 32);
-  size_t tile = (size_t)(DB == 3 ? 3 : DB ? 2 : 1) * rows * (NWK * BK + 4) * sizeof(float);
+  size_t tile = (size_t)ks_stages(DB) * rows * (NWK * BK + 4) * sizeof(float);
   if (DB == 4) tile = (size_t)(2 * 3 * 18 + 1) * (NWK * BK + 4) * sizeof(float);  // the input patch + a dummy row (weights go to registers)
   size_t red = (size_t)NWK * (TN == 0 ? 8 : TM * TN * 16) * 64 * sizeof(float);
   return tile > red ? tile : red;
@@ -821,68 +767,75 @@ static int launch_ks(const GemmParams& p, hipStream_t s) {
   }
 }
 
-template <int MODE>
-static int launch_cfg(int cfg, const GemmParams& p, hipStream_t s) {
-  switch (cfg) {
-    case 0: return launch_t<2, 2, 2, 2, MODE>(p, s);
-    case 1: return launch_t<2, 2, 2, 1, MODE>(p, s);
-    case 2: return launch_t<2, 2, 1, 1, MODE>(p, s);
-    case 3: return launch_ks<8, 1, 1, MODE>(p, s);
-    case 4: return launch_ks<4, 1, 1, MODE>(p, s);
-    case 5: return launch_ks<4, 2, 2, MODE>(p, s);
-    case 6: return launch_ks<2, 2, 2, MODE>(p, s);
-    case 7: return launch_ks<8, 2, 1, MODE>(p, s);
-    case 8: return launch_ks<16, 1, 1, MODE>(p, s);
-    case 9: return launch_ks<4, 2, 1, MODE>(p, s);
-    case 10: return launch_ks<8, 1, 2, MODE>(p, s);
-    case 11: return launch_ks<2, 1, 1, MODE>(p, s);
-    case 12: return launch_ks<8, 2, 2, MODE>(p, s);
-    case 13: return launch_ks<8, 1, 1, MODE, 1>(p, s);
-    case 14: return launch_ks<4, 1, 1, MODE, 1>(p, s);
-    case 15: return launch_ks<4, 2, 2, MODE, 1>(p, s);
-    case 16: return launch_ks<8, 1, 2, MODE, 1>(p, s);
-    case 17: return launch_ks<4, 2, 1, MODE, 1>(p, s);
-    case 18: return launch_ks<2, 2, 2, MODE, 1>(p, s);
-    case 19: return launch_ks<8, 1, 1, MODE, 2>(p, s);
-    case 20: return launch_ks<8, 1, 2, MODE, 2>(p, s);
-    case 21: return launch_ks<8, 2, 1, MODE, 2>(p, s);
-    case 22: return launch_ks<8, 1, 0, MODE, 0>(p, s);
-    case 23: return launch_ks<8, 1, 0, MODE, 1>(p, s);
-    case 24: return launch_ks<8, 1, 0, MODE, 2>(p, s);
-    case 25: return launch_ks<4, 1, 0, MODE, 0>(p, s);
-    case 26: return launch_gemm_big(MODE, 0, p, s);
-    case 27: return launch_gemm_big(MODE, 1, p, s);
-    case 30: return launch_ks<8, 1, 0, MODE, 3>(p, s);
-    case 31: return launch_ks<8, 1, 0, MODE, 4>(p, s);
-    case 32: case 33: case 34: case 35: case 36: case 37: case 38: case 39: return launch_gemm_wp(MODE, kCfgs[cfg].a, p, s);
-    case 40: return launch_gemm_big(MODE, 4, p, s);
-    case 41: return launch_gemm_big(MODE, 5, p, s);
-    default: return -1;
-  }
+// ---------------------------------------------------------------------------------------------
+// launch configurations: one row each (common.h GemmCfg), made from the template arguments that instantiate its launchers; the
+// per-shape choice comes from a table measured on the MI355X (tools/tune_gemm.py -> gemm_tuned.inc) with a cost model for shapes
+// not in the table.
+// ---------------------------------------------------------------------------------------------
+template <int TM, int TN>   // 2 x 2 wavefronts of TM x TN MFMA blocks; register-staged, one static LDS stage
+static constexpr GemmCfg spatial_cfg() {
+  return {GF_SPATIAL, 4, 2 * TM * 32, 2 * TN * 32, 1, (size_t)(2 * TM * 32 + 2 * TN * 32) * LDSLD * sizeof(float), GC_A2,
+          &launch_t<2, 2, TM, TN, GEMM_DENSE>, &launch_t<2, 2, TM, TN, GEMM_CONV>, nullptr};
 }
-
-// dual launches are instantiated for the convolution mode only, and only for the configurations the one-pair schedule of
-// the bottleneck entry blocks uses (measured table): k-split 4 waves 32x32 (4), 8 waves 32x64 (10), their double-buffered
-// forms (14, 16), 8 waves 32x32 (3, 13) and the large tiles (26, 27)
-bool gemm_cfg_supports_dual(int cfg) {
-  return cfg == 3 || cfg == 4 || cfg == 10 || cfg == 13 || cfg == 14 || cfg == 16 || cfg == 26 || cfg == 27 ||
-         cfg == 32 || cfg == 34 || cfg == 35 || cfg == 36;
+// NWK wavefronts on a (TM*32) x (TN*32) tile (TN == 0: 32 x 16), operand path DB (ks_stages).  The LDS-DMA paths have no register
+// prologue (x + pos); the dual form is instantiated for the configurations the one-pair entry blocks use (measured table).
+template <int NWK, int TM, int TN, int DB = 0, bool DUAL = false>
+static constexpr GemmCfg ks_cfg() {
+  GemmDualFn dual = nullptr;
+  if constexpr (DUAL) dual = &launch_ks_dual<NWK, TM, TN, GEMM_CONV, DB>;
+  return {GF_KSPLIT, NWK, TM * 32, TN == 0 ? 16 : TN * 32, ks_stages(DB), ks_smem<NWK, TM, TN, DB>(),
+          (DB < 2 ? GC_A2 : 0u) | (DB == 4 ? GC_PATCH : 0u), &launch_ks<NWK, TM, TN, GEMM_DENSE, DB>, &launch_ks<NWK, TM, TN, GEMM_CONV, DB>, dual};
 }
-
-static int launch_dual_conv(int cfg, const GemmParams& p0, const GemmParams& p1, hipStream_t s) {
-  switch (cfg) {
-    case 3: return launch_ks_dual<8, 1, 1, GEMM_CONV, 0>(p0, p1, s);
-    case 4: return launch_ks_dual<4, 1, 1, GEMM_CONV, 0>(p0, p1, s);
-    case 10: return launch_ks_dual<8, 1, 2, GEMM_CONV, 0>(p0, p1, s);
-    case 13: return launch_ks_dual<8, 1, 1, GEMM_CONV, 1>(p0, p1, s);
-    case 14: return launch_ks_dual<4, 1, 1, GEMM_CONV, 1>(p0, p1, s);
-    case 16: return launch_ks_dual<8, 1, 2, GEMM_CONV, 1>(p0, p1, s);
-    case 26: return launch_gemm_big_dual(GEMM_CONV, 0, p0, p1, s);
-    case 27: return launch_gemm_big_dual(GEMM_CONV, 1, p0, p1, s);
-    case 32: case 34: case 35: case 36: return launch_gemm_wp_dual(GEMM_CONV, kCfgs[cfg].a, p0, p1, s);
-    default: return -1;
-  }
-}
+static const GemmCfg kCfgs[] = {
+    spatial_cfg<2, 2>(),           // 0  spatial 128x128
+    spatial_cfg<2, 1>(),           // 1  spatial 128x64
+    spatial_cfg<1, 1>(),           // 2  spatial 64x64
+    ks_cfg<8, 1, 1, 0, true>(),    // 3  k-split 8 waves, 32x32
+    ks_cfg<4, 1, 1, 0, true>(),    // 4  k-split 4 waves, 32x32
+    ks_cfg<4, 2, 2>(),             // 5  k-split 4 waves, 64x64
+    ks_cfg<2, 2, 2>(),             // 6  k-split 2 waves, 64x64
+    ks_cfg<8, 2, 1>(),             // 7  k-split 8 waves, 64x32
+    ks_cfg<16, 1, 1>(),            // 8  k-split 16 waves, 32x32
+    ks_cfg<4, 2, 1>(),             // 9  k-split 4 waves, 64x32
+    ks_cfg<8, 1, 2, 0, true>(),    // 10 k-split 8 waves, 32x64
+    ks_cfg<2, 1, 1>(),             // 11 k-split 2 waves, 32x32
+    ks_cfg<8, 2, 2>(),             // 12 k-split 8 waves, 64x64
+    ks_cfg<8, 1, 1, 1, true>(),    // 13 k-split 8 waves, 32x32, double-buffered LDS
+    ks_cfg<4, 1, 1, 1, true>(),    // 14 k-split 4 waves, 32x32, double-buffered
+    ks_cfg<4, 2, 2, 1>(),          // 15 k-split 4 waves, 64x64, double-buffered
+    ks_cfg<8, 1, 2, 1, true>(),    // 16 k-split 8 waves, 32x64, double-buffered
+    ks_cfg<4, 2, 1, 1>(),          // 17 k-split 4 waves, 64x32, double-buffered
+    ks_cfg<2, 2, 2, 1>(),          // 18 k-split 2 waves, 64x64, double-buffered
+    ks_cfg<8, 1, 1, 2>(),          // 19 k-split 8 waves, 32x32, LDS-DMA (global_load_lds) double-buffered
+    ks_cfg<8, 1, 2, 2>(),          // 20 k-split 8 waves, 32x64, LDS-DMA (195 KB of LDS: never fits)
+    ks_cfg<8, 2, 1, 2>(),          // 21 k-split 8 waves, 64x32, LDS-DMA (195 KB of LDS: never fits)
+    ks_cfg<8, 1, 0>(),             // 22 k-split 8 waves, 32x16 (16x16x4 MFMA)
+    ks_cfg<8, 1, 0, 1>(),          // 23 k-split 8 waves, 32x16, double-buffered
+    ks_cfg<8, 1, 0, 2>(),          // 24 k-split 8 waves, 32x16, LDS-DMA double-buffered
+    ks_cfg<4, 1, 0>(),             // 25 k-split 4 waves, 32x16
+    big128x128_cfg(),              // 26 large tile 128x128 (gemm_big.hip)
+    big128x64_cfg(),               // 27 large tile 128x64
+    {},                            // 28 (research library only: large tile 128x128 with three LDS stages; the index stays)
+    {},                            // 29 (research library only: 128x64, three LDS stages)
+    ks_cfg<8, 1, 0, 3>(),          // 30 k-split 8 waves, 32x16, LDS-DMA with THREE stages (two tiles in flight, counted vmcnt)
+    ks_cfg<8, 1, 0, 4>(),          // 31 the same for 3x3 stride-1 convolutions over 256 channels with the input patch loaded once
+    // wave-private K chunks (gemm_wp.hip): every wavefront requests and reads its own run of 32-wide K chunks through its own ring
+    // of LDS slots - no barrier in the K loop, everything (or NSLOT chunks) requested up front
+    wp8w32x32s2_cfg(),             // 32 wave-private, 8 waves, 32x32, 2 slots
+    wp8w32x16s3_cfg(),             // 33 wave-private, 8 waves, 32x16, 3 slots
+    wp4w32x32s2_cfg(),             // 34 wave-private, 4 waves, 32x32, 2 slots (two workgroups per CU)
+    wp8w32x64s1_cfg(),             // 35 wave-private, 8 waves, 32x64, 1 slot
+    wp4w32x32s1_cfg(),             // 36 wave-private, 4 waves, 32x32, 1 slot (four workgroups per CU)
+    wp8w64x32s1_cfg(),             // 37 wave-private, 8 waves, 64x32, 1 slot
+    wp4w32x32s4_cfg(),             // 38 wave-private, 4 waves, 32x32, 4 slots
+    wp8w32x16s2_cfg(),             // 39 wave-private, 8 waves, 32x16, 2 slots
+    ws128x128_cfg(),               // 40 large tile 128x128, wave-specialised: 4 loader + 4 MFMA wavefronts (gemm_big.hip, gemm_ws_body)
+    ws128x64_cfg(),                // 41 large tile 128x64, wave-specialised
+};
+static const int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
+int gemm_num_configs() { return kNumCfgs; }
+const GemmCfg* gemm_config(int cfg) { return cfg >= 0 && cfg < kNumCfgs ? &kCfgs[cfg] : nullptr; }
+bool gemm_cfg_supports_dual(int cfg) { return cfg >= 0 && cfg < kNumCfgs && kCfgs[cfg].dual != nullptr; }
 
 struct TunedEntry {
   int mode, M, N, K;
@@ -895,56 +848,39 @@ static const TunedEntry kTuned[] = {
 
 static bool cfg_fits(int cfg, const GemmParams& p) {
   const GemmCfg& c = kCfgs[cfg];
-  if (c.kind == 12) return false;   // a configuration of the research library: not compiled into this one
-  if (c.kind == 4 || c.kind == 5) {  // LDS-DMA operands (no x + pos prologue), float4 epilogue
-    if (p.A2 != nullptr || p.ldc % 4 != 0 || ((uintptr_t)p.C & 15)) return false;
+  if (c.family == GF_NONE) return false;      // a configuration of the research library: not compiled into this one
+  if (c.lds > 163840) return false;           // the CU's 160 KB
+  if (p.A2 != nullptr && !(c.flags & GC_A2)) return false;
+  if (p.res_row_mod > 0 && !(c.flags & GC_RES_ROW_MOD)) return false;
+  if (c.flags & GC_VEC4) {
+    if (p.ldc % 4 != 0 || ((uintptr_t)p.C & 15)) return false;
     if (p.residual && (p.ldr % 4 != 0 || ((uintptr_t)p.residual & 15))) return false;
-    return p.N % (64 * c.tn) == 0;
   }
-  if (c.kind == 8) {  // wave-private chunks: LDS-DMA operands (no x + pos prologue); row-periodic residual supported
-    int bm, bn;
-    size_t lds;
-    if (wp_variant_tile(c.a, &bm, &bn, &lds) != 0) return false;
-    return p.A2 == nullptr && p.N % bn == 0 && p.K % BK == 0;
-  }
-  if (p.res_row_mod > 0) return false;  // row-periodic residual tables: large-tile and wave-private kernels only
-  if (c.kind == 7)
-    return p.A2 == nullptr && p.ksize == 3 && p.stride == 1 && p.Cin == 256 && (p.Wout == 16 || p.Wout % 32 == 0) && p.M % 32 == 0 && p.N % 16 == 0;
-  const int bn = c.tn == 0 ? 16 : (c.kind == 0 ? 2 : 1) * c.tn * 32;
-  if (c.kind != 0) {  // dynamic LDS of the k-split kernels must fit the CU's 160 KB
-    const size_t rows = (size_t)c.tm * 32 + (c.tn == 0 ? 16 : c.tn * 32);
-    const size_t tile = (size_t)(c.kind == 6 ? 3 : c.kind >= 2 ? 2 : 1) * rows * (c.a * BK + 4) * sizeof(float);
-    const size_t red = (size_t)c.a * (c.tn == 0 ? 8 : c.tm * c.tn * 16) * 64 * sizeof(float);
-    if ((tile > red ? tile : red) > 163840) return false;
-    if ((c.kind == 3 || c.kind == 6) && p.A2 != nullptr) return false;  // LDS-DMA has no register prologue (x + pos)
-  }
-  return p.N % bn == 0;
+  if ((c.flags & GC_PATCH) && !(p.ksize == 3 && p.stride == 1 && p.Cin == 256 && (p.Wout == 16 || p.Wout % 32 == 0) && p.M % 32 == 0)) return false;
+  return p.N % c.bn == 0;
 }
 
 // rough cost model (cycles) for shapes outside the tuned table
 static double model_cost(const GemmCfg& c, const GemmParams& p) {
-  if (c.kind == 8 || c.kind == 9) return 1e30;   // wave-private / persistent configurations enter through the measured table only
-  if (c.kind == 4 || c.kind == 5) {  // pays off once the chip is covered several times over
-    const int bm = 128, bn = 64 * c.tn;
-    const double wgs = (double)((p.M + bm - 1) / bm) * (p.N / bn);
-    const double rounds = ceil(wgs / 512.0);
-    return rounds * ((p.K / BK) * (2 * c.tn * 16 * 64.0 * 2 + 150.0) + 3500.0) * (wgs < 1024 ? 4.0 : 1.0);
-  }
-  const int waves = c.kind == 0 ? 4 : c.a;
-  const int bm = (c.kind == 0 ? 2 : 1) * c.tm * 32, bn = c.tn == 0 ? 16 : (c.kind == 0 ? 2 : 1) * c.tn * 32;
-  const double wgs = (double)((p.M + bm - 1) / bm) * (p.N / bn);
+  if (c.flags & GC_TABLE_ONLY) return 1e30;
+  const double wgs = (double)((p.M + c.bm - 1) / c.bm) * (p.N / c.bn);
   const int kt = p.K / BK;
-  const int steps = c.kind == 0 ? kt : (kt + c.a - 1) / c.a;
-  const double lds = c.kind == 0 ? (bm + bn) * 36 * 4.0 : (double)(c.kind == 6 ? 3 : c.kind >= 2 ? 2 : 1) * (bm + bn) * (c.a * 32 + 4) * 4.0;
-  double per_cu = floor(163840.0 / lds);
-  if (per_cu > 32.0 / waves) per_cu = 32.0 / waves;
+  if (c.family == GF_BIG) {  // pays off once the chip is covered several times over
+    const double rounds = ceil(wgs / 512.0);
+    return rounds * (kt * (2 * (c.bn / 64) * 16 * 64.0 * 2 + 150.0) + 3500.0) * (wgs < 1024 ? 4.0 : 1.0);
+  }
+  const bool ks = c.family == GF_KSPLIT;
+  const int steps = ks ? (kt + c.waves - 1) / c.waves : kt;
+  double per_cu = floor(163840.0 / (double)c.lds);
+  if (per_cu > 32.0 / c.waves) per_cu = 32.0 / c.waves;
   if (per_cu > 4) per_cu = 4;
   if (per_cu < 1) per_cu = 1;
   const double rounds = ceil(wgs / (256.0 * per_cu));
   const double resident = wgs < 256.0 * per_cu ? ceil(wgs / 256.0) : per_cu;
-  const double share = (waves * resident) / 4.0 > 1.0 ? (waves * resident) / 4.0 : 1.0;
-  const double step = c.tm * (c.tn == 0 ? 0.5 : (double)c.tn) * 16 * 64.0 * share + (c.kind >= 2 ? 300.0 : 700.0);
-  return rounds * (steps * step + 2500.0 + (c.kind != 0 ? 600.0 : 0.0));
+  const double share = (c.waves * resident) / 4.0 > 1.0 ? (c.waves * resident) / 4.0 : 1.0;
+  const double blocks = (c.bm / 32) * (c.bn / 32.0) / (ks ? 1 : 4);   // 32x32 MFMA blocks of a wavefront per 32-deep K tile
+  const double step = blocks * 16 * 64.0 * share + (c.stages >= 2 ? 300.0 : 700.0);
+  return rounds * (steps * step + 2500.0 + (ks ? 600.0 : 0.0));
 }
 
 // knobs KN_KS3: the three-stage LDS-DMA k-split (30) where the measured table says its two-stage form (24); KN_CONV_PATCH: 3x3
@@ -997,8 +933,7 @@ static int gemm_pick_config_table(int mode, const GemmParams& p) {
 
 // which operand should cross the fabric once: the one that is larger (gemm_tile_coords, common.h)
 static void set_xcd_split(int mode, int cfg, GemmParams& p) {
-  const GemmCfg& c = kCfgs[cfg];
-  const int bm = (c.kind == 4 || c.kind == 5) ? 128 : (c.kind == 0 ? 2 : 1) * c.tm * 32;
+  const int bm = kCfgs[cfg].bm;
   const double a_bytes = mode == GEMM_CONV ? (double)p.M * p.stride * p.stride * p.Cin * 4.0 : (double)p.M * p.K * 4.0;
   const double w_bytes = (double)p.N * p.K * 4.0;
   const bool fits = (p.M + bm - 1) / bm >= 8;
@@ -1018,7 +953,12 @@ int launch_gemm_dual_cfg(int mode, int cfg, const GemmParams& a, const GemmParam
     if (p->N % 16 != 0 || p->Cin % BK != 0 || p->K != p->ksize * p->ksize * p->Cin) return -1;
     set_xcd_split(mode, cfg, *p);
   }
-  return launch_dual_conv(cfg, p0, p1, s);
+  return kCfgs[cfg].dual(p0, p1, s);
+}
+
+static int launch_cfg(int cfg, bool dense, const GemmParams& p, hipStream_t s) {
+  const GemmLaunchFn fn = dense ? kCfgs[cfg].dense : kCfgs[cfg].conv;
+  return fn ? fn(p, s) : -1;
 }
 
 int launch_gemm_cfg(int mode, int cfg, const GemmParams& p0, hipStream_t s) {
@@ -1032,14 +972,13 @@ int launch_gemm_cfg(int mode, int cfg, const GemmParams& p0, hipStream_t s) {
   switch (mode) {
     case GEMM_DENSE:
       if (p.lda % 4 != 0 || (p.A2 && p.lda2 % 4 != 0)) return -1;
-      return launch_cfg<GEMM_DENSE>(cfg, p, s);
+      return launch_cfg(cfg, true, p, s);
     case GEMM_CONV:
       if (p.Cin % BK != 0 || p.K != p.ksize * p.ksize * p.Cin) return -1;
       // a 1x1 stride-1 convolution IS the dense product of the pixel rows (row m = pixel m, lda = Cin, no padding): the
       // dense instantiation of the same configuration computes the same sums in the same order without the per-row pixel
       // decomposition - ~640 fewer instructions between workgroup entry and the first load (profiles/r3_prologue_*.txt)
-      if (gemm_conv_as_dense(p)) return launch_cfg<GEMM_DENSE>(cfg, p, s);
-      return launch_cfg<GEMM_CONV>(cfg, p, s);
+      return launch_cfg(cfg, gemm_conv_as_dense(p), p, s);
     case GEMM_STEM:
       if (p.N != 64 || p.K != 160) return -1;
       return launch_t<2, 2, 2, 1, GEMM_STEM>(p, s);  // BM must be 128

@@ -405,12 +405,18 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(const GemmParams p) {
   gemm_ws_body<TN, MODE>(p, blockIdx.x);
 }
 
+// dynamic LDS of a 128 x 64 TN tile with NSTG operand stages (the epilogue staging reuses them)
+template <int TN, int NSTG>
+static constexpr size_t big_smem() {
+  return (size_t)NSTG * (128 + 64 * TN) * BK * sizeof(float);
+}
+
 // knob KN_WS_FLAGS: bit 0 = s_setprio(1) around the MFMA wavefronts' loop, bit 1 = s_setprio(3) for the loaders
 
 template <int TN, int MODE>
 static int launch_ws_t(const GemmParams& p0, hipStream_t s) {
   constexpr int BM = 128, BN = 64 * TN;
-  constexpr size_t smem = (size_t)4 * (BM + BN) * BK * sizeof(float);
+  constexpr size_t smem = big_smem<TN, 4>();
   static_assert(smem >= (size_t)4 * 32 * (32 * TN + 4) * sizeof(float), "epilogue staging fits in the operand stages");
   GemmParams p = p0;
   if (p.N % BN != 0 || p.K % BK != 0 || p.M <= 0 || p.A2 != nullptr) return -1;
@@ -447,7 +453,7 @@ __global__ __launch_bounds__(256, 2) void gemm_big_dual_kernel(const GemmParams 
 template <int TN>
 static int launch_big_dual_t(const GemmParams& a, const GemmParams& b, hipStream_t s) {
   constexpr int BM = 128, BN = 64 * TN;
-  constexpr size_t smem = (size_t)2 * (BM + BN) * BK * sizeof(float);
+  constexpr size_t smem = big_smem<TN, 2>();
   GemmParams p0 = a, p1 = b;
   for (GemmParams* p : {&p0, &p1}) {
     if (p->N % BN != 0 || p->K % BK != 0 || p->M <= 0 || p->A2 != nullptr) return -1;
@@ -469,15 +475,10 @@ static int launch_big_dual_t(const GemmParams& a, const GemmParams& b, hipStream
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int launch_gemm_big_dual(int mode, int variant, const GemmParams& p0, const GemmParams& p1, hipStream_t s) {
-  if (mode != GEMM_CONV) return -1;
-  return variant == 0 ? launch_big_dual_t<2>(p0, p1, s) : variant == 1 ? launch_big_dual_t<1>(p0, p1, s) : -1;
-}
-
 template <int TN, int MODE>
 static int launch_big_t(const GemmParams& p0, hipStream_t s) {
   constexpr int BM = 128, BN = 64 * TN;
-  constexpr size_t smem = (size_t)2 * (BM + BN) * BK * sizeof(float);
+  constexpr size_t smem = big_smem<TN, 2>();
   static_assert(smem >= (size_t)4 * 32 * (32 * TN + 4) * sizeof(float), "epilogue staging fits in the operand stages");
   GemmParams p = p0;
   if (p.N % BN != 0 || p.K % BK != 0 || p.M <= 0 || p.A2 != nullptr) return -1;
@@ -498,17 +499,19 @@ static int launch_big_t(const GemmParams& p0, hipStream_t s) {
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-// variant 0: 128 x 128 tile, 1: 128 x 64 (two LDS stages); 4, 5: the same
-// tiles with 4 loader + 4 MFMA wavefronts (gemm_ws_body)
-int launch_gemm_big(int mode, int variant, const GemmParams& p, hipStream_t s) {
-  if (mode == GEMM_DENSE && p.lda % 4 != 0) return -1;
-  if (mode != GEMM_DENSE && mode != GEMM_CONV) return -1;
-  const bool d = mode == GEMM_DENSE;
-  switch (variant) {
-    case 0: return d ? launch_big_t<2, GEMM_DENSE>(p, s) : launch_big_t<2, GEMM_CONV>(p, s);
-    case 1: return d ? launch_big_t<1, GEMM_DENSE>(p, s) : launch_big_t<1, GEMM_CONV>(p, s);
-    case 4: return d ? launch_ws_t<2, GEMM_DENSE>(p, s) : launch_ws_t<2, GEMM_CONV>(p, s);   // wave-specialised 128 x 128
-    case 5: return d ? launch_ws_t<1, GEMM_DENSE>(p, s) : launch_ws_t<1, GEMM_CONV>(p, s);   // wave-specialised 128 x 64
-    default: return -1;
-  }
+// the configuration rows (common.h GemmCfg; gemm.hip kCfgs 26, 27, 40, 41): LDS-DMA operands (no x + pos prologue), float4 epilogue, a
+// row-periodic residual is taken.  The dual form exists for the two-stage tiles.
+template <int TN>
+static constexpr GemmCfg big_cfg() {
+  return {GF_BIG, 4, 128, 64 * TN, 2, big_smem<TN, 2>(), GC_RES_ROW_MOD | GC_VEC4,
+          &launch_big_t<TN, GEMM_DENSE>, &launch_big_t<TN, GEMM_CONV>, &launch_big_dual_t<TN>};
 }
+template <int TN>
+static constexpr GemmCfg ws_cfg() {   // 4 loader + 4 MFMA wavefronts (gemm_ws_body)
+  return {GF_BIG, 8, 128, 64 * TN, 4, big_smem<TN, 4>(), GC_RES_ROW_MOD | GC_VEC4,
+          &launch_ws_t<TN, GEMM_DENSE>, &launch_ws_t<TN, GEMM_CONV>, nullptr};
+}
+GemmCfg big128x128_cfg() { return big_cfg<2>(); }
+GemmCfg big128x64_cfg() { return big_cfg<1>(); }
+GemmCfg ws128x128_cfg() { return ws_cfg<2>(); }
+GemmCfg ws128x64_cfg() { return ws_cfg<1>(); }

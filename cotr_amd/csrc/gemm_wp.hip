@@ -335,52 +335,20 @@ static int launch_wp_dual_t(const GemmParams& a, const GemmParams& b, hipStream_
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-// variants (gemm.hip, kCfgs kind 8): wavefronts x tile x ring slots
-//   0: 8 x 32x32 x 2 (128 KB)   1: 8 x 32x16 x 3 (144 KB)   2: 4 x 32x32 x 2 (64 KB, two workgroups per CU)
-//   3: 8 x 32x64 x 1 (96 KB)    4: 4 x 32x32 x 1 (32 KB)    5: 8 x 64x32 x 1 (96 KB)    6: 4 x 32x32 x 4 (128 KB)
-//   7: 8 x 32x16 x 2 (96 KB)
-int wp_variant_tile(int variant, int* bm, int* bn, size_t* lds) {
-  switch (variant) {
-    case 0: *bm = 32; *bn = 32; *lds = wp_smem<8, 1, 1, 2>(); return 0;
-    case 1: *bm = 32; *bn = 16; *lds = wp_smem<8, 1, 0, 3>(); return 0;
-    case 2: *bm = 32; *bn = 32; *lds = wp_smem<4, 1, 1, 2>(); return 0;
-    case 3: *bm = 32; *bn = 64; *lds = wp_smem<8, 1, 2, 1>(); return 0;
-    case 4: *bm = 32; *bn = 32; *lds = wp_smem<4, 1, 1, 1>(); return 0;
-    case 5: *bm = 64; *bn = 32; *lds = wp_smem<8, 2, 1, 1>(); return 0;
-    case 6: *bm = 32; *bn = 32; *lds = wp_smem<4, 1, 1, 4>(); return 0;
-    case 7: *bm = 32; *bn = 16; *lds = wp_smem<8, 1, 0, 2>(); return 0;
-    default: return -1;
-  }
+// the configuration rows (common.h GemmCfg; gemm.hip kCfgs 32 - 39): LDS-DMA operands (no x + pos prologue), a row-periodic residual is
+// taken, entered through the measured table only.  The dual form is instantiated where the one-pair entry blocks use it.
+template <int NWK, int TM, int TN, int NSLOT, bool DUAL = false>
+static constexpr GemmCfg wp_cfg() {
+  GemmDualFn dual = nullptr;
+  if constexpr (DUAL) dual = &launch_wp_dual_t<NWK, TM, TN, NSLOT>;
+  return {GF_WP, NWK, TM * 32, TN == 0 ? 16 : TN * 32, NSLOT, wp_smem<NWK, TM, TN, NSLOT>(), GC_RES_ROW_MOD | GC_TABLE_ONLY,
+          &launch_wp_t<NWK, TM, TN, GEMM_DENSE, NSLOT>, &launch_wp_t<NWK, TM, TN, GEMM_CONV, NSLOT>, dual};
 }
-
-template <int MODE>
-static int launch_wp_mode(int variant, const GemmParams& p, hipStream_t s) {
-  switch (variant) {
-    case 0: return launch_wp_t<8, 1, 1, MODE, 2>(p, s);
-    case 1: return launch_wp_t<8, 1, 0, MODE, 3>(p, s);
-    case 2: return launch_wp_t<4, 1, 1, MODE, 2>(p, s);
-    case 3: return launch_wp_t<8, 1, 2, MODE, 1>(p, s);
-    case 4: return launch_wp_t<4, 1, 1, MODE, 1>(p, s);
-    case 5: return launch_wp_t<8, 2, 1, MODE, 1>(p, s);
-    case 6: return launch_wp_t<4, 1, 1, MODE, 4>(p, s);
-    case 7: return launch_wp_t<8, 1, 0, MODE, 2>(p, s);
-    default: return -1;
-  }
-}
-
-int launch_gemm_wp(int mode, int variant, const GemmParams& p, hipStream_t s) {
-  if (mode == GEMM_DENSE) return p.lda % 4 != 0 ? -1 : launch_wp_mode<GEMM_DENSE>(variant, p, s);
-  if (mode == GEMM_CONV) return launch_wp_mode<GEMM_CONV>(variant, p, s);
-  return -1;
-}
-
-int launch_gemm_wp_dual(int mode, int variant, const GemmParams& p0, const GemmParams& p1, hipStream_t s) {
-  if (mode != GEMM_CONV) return -1;
-  switch (variant) {
-    case 0: return launch_wp_dual_t<8, 1, 1, 2>(p0, p1, s);
-    case 2: return launch_wp_dual_t<4, 1, 1, 2>(p0, p1, s);
-    case 3: return launch_wp_dual_t<8, 1, 2, 1>(p0, p1, s);
-    case 4: return launch_wp_dual_t<4, 1, 1, 1>(p0, p1, s);
-    default: return -1;
-  }
-}
+GemmCfg wp8w32x32s2_cfg() { return wp_cfg<8, 1, 1, 2, true>(); }   // 128 KB
+GemmCfg wp8w32x16s3_cfg() { return wp_cfg<8, 1, 0, 3>(); }         // 144 KB
+GemmCfg wp4w32x32s2_cfg() { return wp_cfg<4, 1, 1, 2, true>(); }   // 64 KB: two workgroups per CU
+GemmCfg wp8w32x64s1_cfg() { return wp_cfg<8, 1, 2, 1, true>(); }   // 96 KB
+GemmCfg wp4w32x32s1_cfg() { return wp_cfg<4, 1, 1, 1, true>(); }   // 32 KB: four workgroups per CU
+GemmCfg wp8w64x32s1_cfg() { return wp_cfg<8, 2, 1, 1>(); }         // 96 KB
+GemmCfg wp4w32x32s4_cfg() { return wp_cfg<4, 1, 1, 4>(); }         // 128 KB
+GemmCfg wp8w32x16s2_cfg() { return wp_cfg<8, 1, 0, 2>(); }         // 96 KB

@@ -674,6 +674,12 @@ int cotr_debug_ffn_times(unsigned long long* times);
 int cotr_debug_attention_times(unsigned long long* times);
 /* the launch configuration the library picks for this convolution (tools) */
 int cotr_gemm_pick_conv(int B, int Hin, int Win, int Cin, int Cout, int ksize, int stride);
+/* the launch configuration the library picks for the dense product [M,K] x [N,K]^T with lda = K, ldc = ldr = N and aligned pointers;
+ * flags bit 0: the x + pos prologue is present, bit 1: the residual is a row-periodic table.  Makes no HIP call (tests, tools) */
+int cotr_gemm_pick_linear(int M, int N, int K, int flags);
+/* workgroup tile (rows, columns) of launch configuration `cfg` and whether it has a dual-launch form (any pointer may be NULL);
+ * COTR_ERR_ARG outside [0, cotr_gemm_num_configs()).  An index the library has no kernel for reports 0 x 0.  Makes no HIP call */
+int cotr_gemm_config_info(int cfg, int* bm, int* bn, int* has_dual);
 /* one convolution launch whose k-split kernel writes phase timestamps (100 MHz wall clock) of every workgroup to `times`
  * (device memory, [workgroups][8] uint64; slots 0..4 = entry, loads issued, first data usable, K loop done, stored) */
 int cotr_debug_conv_times(const float* x, const float* w, const float* scale, const float* bias, float* y, int B, int Hin, int Win,

@@ -497,13 +497,22 @@ def _cfgs():
     return [c for c in range(_lib.load_library().cotr_gemm_num_configs()) if c not in (46, 47, 48, 49, 50, 51)]
 
 
-def test_every_gemm_config_linear():
-    """All configurations (spatial, k-split, LDS-DMA, large-tile) compute the same bias+residual+ReLU linear; a
-    configuration may decline a shape (rc -1: tile does not divide N), never return a wrong result."""
+def _accepts_fixture(test):
+    """tests/golden/gemm_cfg_accepts.json (tests/golden/make_gemm_fixtures.py): the configurations that took each shape of the three
+    tests below, recorded before the launch configurations became one table - keyed by cotr_is_experimental()"""
+    import json
+    import os
+    from cotr_amd import _lib
+    with open(os.path.join(os.path.dirname(__file__), 'golden', 'gemm_cfg_accepts.json')) as f:
+        return json.load(f)[str(_lib.load_library().cotr_is_experimental())][test]
+
+
+def every_gemm_config_linear():
+    """-> {shape: [configurations that ran]}; every one that ran is checked against torch"""
     from cotr_amd import _lib
     lib = _lib.load_library()
     d = G.dev()
-    ran = 0
+    accepted = {}
     for M, N, K in [(1000, 256, 256), (300, 128, 64), (4133, 1024, 256)]:
         g = _g(M + N)
         x, w = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / math.sqrt(K)
@@ -517,15 +526,24 @@ def test_every_gemm_config_linear():
                 continue
             e = G.rel_err(y, ref)
             assert e < 2e-5, (cfg, M, N, K, e)
-            ran += 1
-    assert ran >= 60
+            accepted.setdefault(f'{M}x{N}x{K}', []).append(cfg)
+    return accepted
 
 
-def test_every_gemm_config_conv():
+def test_every_gemm_config_linear():
+    """All configurations (spatial, k-split, LDS-DMA, large-tile) compute the same bias+residual+ReLU linear; a
+    configuration may decline a shape (rc -1: tile does not divide N), never return a wrong result - and the set that takes
+    each shape is the recorded one."""
+    accepted = every_gemm_config_linear()
+    assert sum(len(v) for v in accepted.values()) >= 60
+    assert accepted == _accepts_fixture('linear')
+
+
+def every_gemm_config_conv():
     from cotr_amd import _lib
     lib = _lib.load_library()
     d = G.dev()
-    ran = 0
+    accepted = {}
     for B, H, cin, cout, k, stride in [(3, 16, 64, 128, 3, 1), (2, 16, 128, 256, 3, 2), (5, 8, 64, 256, 1, 1), (2, 32, 256, 128, 1, 2),
                                        (2, 32, 256, 64, 3, 1)]:   # (the last one also fits the input-patch variant, cfg 31)
         g = _g(B + H + cin + cout)
@@ -547,8 +565,14 @@ def test_every_gemm_config_conv():
                 continue
             e = G.rel_err(G.sbs_to_nchw(y.cpu()), ref)
             assert e < 3e-5, (cfg, B, H, cin, cout, k, stride, e)
-            ran += 1
-    assert ran >= 80
+            accepted.setdefault(f'{B},{H},{cin},{cout},{k},{stride}', []).append(cfg)
+    return accepted
+
+
+def test_every_gemm_config_conv():
+    accepted = every_gemm_config_conv()
+    assert sum(len(v) for v in accepted.values()) >= 80
+    assert accepted == _accepts_fixture('conv')
 
 
 @pytest.mark.parametrize('B,H,W', [(1, 16, 16), (3, 16, 16), (1, 16, 32), (1, 32, 64), (2, 8, 32)])
@@ -583,12 +607,11 @@ def test_conv3x3_input_patch_variant(B, H, W):
         assert lib.cotr_op_conv_cfg(G.P(xx), G.P(wx), G.P(scd), G.P(bd), None, 1, G.P(yy), 1, H, ww, ci, cout, k, st, 31, G.sptr()) != 0
 
 
-@pytest.mark.parametrize('B,H,cin,c_ds,c_1,stride', [(1, 64, 64, 256, 64, 1), (1, 64, 256, 512, 128, 2), (1, 32, 512, 1024, 256, 2),
-                                                     (2, 16, 64, 256, 64, 2)])
-def test_dual_conv_launch(B, H, cin, c_ds, c_1, stride):
-    """Entry block of a ResNet stage: downsample (1x1, stride s, FrozenBN, no ReLU) and conv1 (1x1, stride 1, FrozenBN,
-    ReLU) of the same input as ONE launch, under every configuration that has a dual form; a configuration may decline
-    (rc -1), never return a wrong result.  Each output against torch on CPU."""
+DUAL_CASES = [(1, 64, 64, 256, 64, 1), (1, 64, 256, 512, 128, 2), (1, 32, 512, 1024, 256, 2), (2, 16, 64, 256, 64, 2)]
+
+
+def dual_conv_launch(B, H, cin, c_ds, c_1, stride):
+    """-> the configurations that ran; both outputs of each against torch on CPU"""
     from cotr_amd import _lib
     lib = _lib.load_library()
     g = _g(B * 100 + H + cin)
@@ -602,7 +625,7 @@ def test_dual_conv_launch(B, H, cin, c_ds, c_1, stride):
     xd = G.nchw_to_sbs(x).to(d)
     wdd, w1d = G.pack_conv_weight(wd).to(d), G.pack_conv_weight(w1).to(d)
     sdd, bdd, s1d, b1d = sd.to(d), bd.to(d), s1.to(d), b1.to(d)
-    ran = 0
+    ran = []
     for cfg in _cfgs():
         yd = torch.full((B, H // stride, 2 * H // stride, c_ds), float('nan'), device=d)
         y1 = torch.full((B, H, 2 * H, c_1), float('nan'), device=d)
@@ -613,8 +636,18 @@ def test_dual_conv_launch(B, H, cin, c_ds, c_1, stride):
             continue
         assert G.rel_err(G.sbs_to_nchw(yd.cpu()), ref_d) < 3e-5, cfg
         assert G.rel_err(G.sbs_to_nchw(y1.cpu()), ref_1) < 3e-5, cfg
-        ran += 1
-    assert ran >= 5, ran
+        ran.append(cfg)
+    return ran
+
+
+@pytest.mark.parametrize('B,H,cin,c_ds,c_1,stride', DUAL_CASES)
+def test_dual_conv_launch(B, H, cin, c_ds, c_1, stride):
+    """Entry block of a ResNet stage: downsample (1x1, stride s, FrozenBN, no ReLU) and conv1 (1x1, stride 1, FrozenBN,
+    ReLU) of the same input as ONE launch, under every configuration that has a dual form; a configuration may decline
+    (rc -1), never return a wrong result - and the set that takes each shape is the recorded one."""
+    ran = dual_conv_launch(B, H, cin, c_ds, c_1, stride)
+    assert len(ran) >= 5, ran
+    assert ran == _accepts_fixture('dual')[f'{B},{H},{cin},{c_ds},{c_1},{stride}']
 
 
 @pytest.mark.parametrize('B,cin', [(1, 64), (1, 256), (3, 256), (2, 64)])

@@ -26,7 +26,8 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PEAK, CUS, CU_INGEST, FIXED = 157.3e12, 256, 55e9, 4.1
-# launch configuration -> (tile rows, tile columns) of csrc/gemm.hip kCfgs (k-split / wave-private tiles contract over the WHOLE K)
+# launch configuration -> (tile rows, tile columns) of csrc/gemm.hip kCfgs (k-split / wave-private tiles contract over the WHOLE K); kept here
+# because this tool works from a profile file alone - tests/test_gemm_table_cpu.py checks it against cotr_gemm_config_info
 TILE = {2: (64, 64), 3: (32, 32), 4: (32, 32), 9: (64, 32), 10: (32, 64), 12: (64, 64), 13: (32, 32), 14: (32, 32), 19: (32, 32),
         22: (32, 16), 23: (32, 16), 24: (32, 16), 25: (32, 16), 26: (128, 128), 27: (128, 64), 30: (32, 16), 31: (32, 16),
         32: (32, 32), 33: (32, 16), 34: (32, 32), 35: (32, 64), 36: (32, 32), 37: (64, 32), 38: (32, 32), 39: (32, 16)}
