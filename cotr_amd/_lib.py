@@ -126,6 +126,9 @@ _PROTOS = {
     'cotr_raster_mesh': (ctypes.c_int, [c_float_p, ctypes.c_int, c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'cotr_raster_last_error': (ctypes.c_char_p, []),
+    'cotr_delaunay_max_tris': (ctypes.c_int, [ctypes.c_int]),
+    'cotr_delaunay_scratch_bytes': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'cotr_delaunay': (ctypes.c_int, [c_float_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),
     'cotr_nearest_mutual_scratch_bytes': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     'cotr_nearest_mutual': (ctypes.c_int, [c_float_p] * 4 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_size_t,
                                                                                                                ctypes.c_void_p]),

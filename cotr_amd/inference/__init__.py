@@ -12,10 +12,10 @@ device calls; ``ZoomEngine.guided_match`` runs the whole demo.  ``warp_by_map``,
 bilinear, one launch each); ``warp_by_corr`` and ``paste_by_corners`` are the last lines of demo_single_pair.py and
 demo_homography.py."""
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
-from .triangulate import triangulate_corr
+from .triangulate import delaunay, triangulate_corr
 from .warp import get_perspective_transform, paste_by_corners, warp_by_corr, warp_by_map, warp_perspective
 from .zoom_engine import FasterSparseEngine, RefineResult, SparseEngine, ZoomEngine, patch_boxes
 
-__all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'RefineResult', 'triangulate_corr',
+__all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'RefineResult', 'triangulate_corr', 'delaunay',
            'mutual_matches', 'find_fundamental_mat', 'filter_guided_matches', 'warp_by_map', 'warp_perspective',
            'get_perspective_transform', 'warp_by_corr', 'paste_by_corners']

@@ -203,7 +203,8 @@ def warp_by_corr(img_a, img_b, corrs, alpha=0.5, as_tensor=False, simplices=None
     """demo_single_pair.py:42-44: ``triangulate_corr`` of the correspondences, ``img_b`` warped by that map onto A, and the
     blend with ``img_a`` -> (overlay float32 [H_a, W_a, 3] = warped / 255 * alpha + img_a / 255 * (1 - alpha), warped uint8
     [H_a, W_a, 3]).  The dense map stays on the device.  Outside the correspondences' hull the map is 0, so ``warped``
-    reads ``img_b`` at (0, 0) there, exactly as the demo's cv2 call does.  simplices: as in ``triangulate_corr``."""
+    reads ``img_b`` at (0, 0) there, exactly as the demo's cv2 call does.  simplices: as in ``triangulate_corr``; with 'device', device tensors for the images
+    and ``corrs`` and as_tensor=True nothing passes through the host, and the call can be captured into a graph."""
     _check_image(img_a, 'img_a')
     _check_image(img_b, 'img_b')
     device = _pick_device(img_a, img_b)

@@ -425,6 +425,26 @@ int cotr_raster_mesh(const float* verts, int n_verts, const float* attrs, const 
                      float* out, uint8_t* mask, void* scratch, size_t scratch_bytes, cotr_stream stream);
 const char* cotr_raster_last_error(void);
 
+/* ---- delaunay: the triangles cotr_raster_mesh draws, made on the device (cotr_amd/csrc/delaunay.hip) -------------------
+ * Replaces scipy.spatial.Delaunay(corr[:, :2]) of inference_helper.py:239,293-308 by an exact rule that is unique for
+ * every input: points snapped to 2^-24, orientation in int64, the in-circle test in 128-bit integers,
+ * cocircular points decided as if point i were lifted by an infinitesimal amount that is larger for a lower i.
+ *
+ * cotr_delaunay: verts [n,2] float32 normalised points (u, v), DEVICE -> tris [cotr_delaunay_max_tris(n), 3] int32 (DEVICE):
+ *   the triangles, each counter-clockwise with its lowest index first, ordered by that index and then in the order of its
+ *   walk; rows past the count are -1 (cotr_raster_mesh skips them: the whole capacity can be passed on, no count read
+ *   back).  info: DEVICE int32[2] = {count, status}; status 0 = ok, 1 = a walk reached its bound of n steps (never seen).
+ *   A point that is not finite, has |u| or |v| > 4, or snaps onto a valid point of lower index is in no triangle.
+ *   0 <= n <= 65536.  The cost is quadratic in n.  scratch: DEVICE, 16-byte aligned, at least
+ *   cotr_delaunay_scratch_bytes(n) bytes.  Stream-ordered, no host waits, no allocation, capturable; bit-identical from
+ *   run to run.
+ * cotr_delaunay_max_tris: 2 n, the capacity of tris in triangles (COTR_ERR_ARG for n outside [0, 65536]).
+ * Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_delaunay_max_tris(int n);
+int cotr_delaunay_scratch_bytes(int n, size_t* bytes);
+int cotr_delaunay(const float* verts, int n, int32_t* tris, int32_t* info, void* scratch, size_t scratch_bytes,
+                  cotr_stream stream);
+
 /* ---- guided matching: nearest / mutual keypoints and fundamental-matrix RANSAC (cotr_amd/csrc/guided.hip) --------------
  * The host post-processing of demo_guided_matching.py:48-63 (scipy distance matrices + argmin, the mutual double loop,
  * cv2.findFundamentalMat(FM_RANSAC)) on the device.  Rules in DESIGN.md 3h.
