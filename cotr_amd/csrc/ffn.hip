@@ -10,7 +10,8 @@
 //   phase 1  H[32 x 64] = X[32 x 256] . W1_sub[64 x 256]^T as 2 x 4 tiles of 16 x 16 (v_mfma_f32_16x16x4_f32): wave w -> ONE tile
 //            over the whole K = 256 (64 MFMAs), + b1, ReLU -> H in LDS; no cross-wave reduction
 //   phase 2  out[32 x 256] += H . W2[:, sub]^T: wave w -> output columns 32w..32w+31, K = 64: 32 MFMAs; the W2 operand
-//            goes global -> registers in MFMA layout (each element is used once per workgroup), prefetched under phase 1
+//            goes global -> registers in MFMA layout (each element is used once per workgroup), requested near the end of phase 1
+//            (see the note at the loads)
 // X and W1 sub-chunks arrive by LDS-DMA (one wave instruction = one padded 1040-B row).
 #include <string.h>
 
@@ -93,7 +94,14 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const FfnParams p) {
     __syncthreads();  // X and W1_sub have landed, previous phase 2 is done with Hs
     if (sub == 0) FFN_STAMP(2);
     else if (sub == 1) FFN_STAMP(5);
-    f32x4 w2f[8];     // issued after the barrier (which drains vmcnt), in flight under phase 1
+    // What hipcc makes of the source order below (-S listing, all three copies of the loop body): the eight W2 loads and the b1 load are
+    // SUNK behind 60 of the 64 phase-1 MFMAs, so W2 is in flight under the H write and the "H complete" barrier only; and because the
+    // next W1 request sits under a run-time `if`, the two paths into phase 2 differ in what is outstanding and the wait in front of the
+    // first phase-2 MFMA is vmcnt(0): it covers the next W1 sub-chunk's DMA too.  Pinning the W2 / b1 requests in front of phase 1
+    // (counted vmcnt(9), raw s_barrier) and making the last sub-chunk a compile-time case (phase-2 wait covers W2 only, the DMA stays in
+    // flight across phase 2) was built and measured: same bits, no gain - the phases moved (phase 1 3.1 -> 2.5 us, but X + W1 usable
+    // 1 us later: the kernel is bound by what a CU can pull, not by when it asks; docs/LABNOTES.md 4b).
+    f32x4 w2f[8];
     const float* w2g = p.W2 + (size_t)(32 * wave + l31) * FF_H + h0 + sub * 64 + hh * 4;
 #pragma unroll
     for (int j = 0; j < 8; ++j) w2f[j] = *reinterpret_cast<const f32x4*>(w2g + j * 8);
@@ -130,7 +138,7 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const FfnParams p) {
     }
     __syncthreads();  // H complete
     if (sub == 0) FFN_STAMP(3);
-    if (sub + 1 < nsub) dma_w1(sub + 1);  // next W1 sub-chunk streams in under phase 2 (drained by the next barrier)
+    if (sub + 1 < nsub) dma_w1(sub + 1);  // next W1 sub-chunk: requested here, but phase 2 waits for it too (vmcnt(0), see above)
 
     // ---- phase 2 ---------------------------------------------------------------------------------
 #pragma unroll

@@ -377,6 +377,40 @@ __device__ __forceinline__ void gemm_ks_body(const GemmParams& p, const int bid)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
+  // ---- epilogue operands: scale, bias and every residual value this lane will add depend on nothing the kernel computes, so they
+  // are requested HERE, in front of the first operand request of the K loop (the oldest entries of the in-order VM queue: the counted
+  // waits of the LDS-DMA paths stay valid as written) instead of behind the cross-wave barrier, where they were one serialised round
+  // trip for scale / bias and one per row for the residual.  No branch between the loads: an absent operand reads a valid address (the
+  // weights' first row) and a select discards the value; rows past M read row M - 1 and are never stored.  Where a lane finishes more
+  // than 8 values (2-wavefront forms, 64-row tiles of 4 wavefronts, the 64 x 64 tile) the registers are not free under the K loop -
+  // those forms would lose a workgroup per CU - and the same requests go out together behind the barrier instead.
+  constexpr int EB = N16 ? 1 : TN, ER = (N16 ? 8 : 16) / NWK;   // column blocks; rows per wavefront and block
+  constexpr bool EPI_EARLY = ER * TM * EB + 2 * EB <= 8;
+  float e_sc[EB], e_bi[EB], e_res[TM][EB][ER];
+  auto load_epilogue = [&]() {
+    const float* sc_src = p.scale ? p.scale : p.W;
+    const float* bi_src = p.bias ? p.bias : p.W;
+    const float* res_src = p.residual ? p.residual : p.W;
+    const int res_ld = p.residual ? p.ldr : 0;
+#pragma unroll
+    for (int b = 0; b < EB; ++b) {
+      const int n = N16 ? n0 + l15 : n0 + b * 32 + l31;
+      e_sc[b] = sc_src[n];
+      e_bi[b] = bi_src[n];
+#pragma unroll
+      for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int i = 0; i < ER; ++i) {
+          const int r = wave + i * NWK;
+          const int m = N16 ? m0 + (r >> 2) * 16 + q4 * 4 + (r & 3) : m0 + a * 32 + 4 * hh + (r & 3) + 8 * (r >> 2);
+          const int mc = m < p.M ? m : p.M - 1;
+          e_res[a][b][i] = res_src[(size_t)mc * res_ld + n];
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);   // hipcc otherwise sinks these loads to their first use
+  };
+  if constexpr (EPI_EARLY) load_epilogue();
+
   auto compute = [&](int buf) {
     const float* As = smem + buf * TILE;
     const float* Ws = As + BM * LD;
@@ -622,22 +656,22 @@ __device__ __forceinline__ void gemm_ks_body(const GemmParams& p, const int bid)
 #pragma unroll
       for (int r = 0; r < 4; ++r) red[((wave * 8) + blk * 4 + r) * 64 + lane] = acc16[blk][r];
     __syncthreads();
+    if constexpr (!EPI_EARLY) load_epilogue();
     const int n = n0 + l15;
-    const float sc = p.scale ? p.scale[n] : 1.f;
-    const float bi = p.bias ? p.bias[n] : 0.f;
+    const float bi = p.bias ? e_bi[0] : 0.f;
     const float cs = (n < p.colscale_n) ? p.colscale : 1.f;
-    for (int slot = wave; slot < 8; slot += NWK) {
+#pragma unroll
+    for (int i = 0; i < ER; ++i) {
+      const int slot = wave + i * NWK;
       float v = 0.f;
 #pragma unroll
       for (int w = 0; w < NWK; ++w) v += red[(w * 8 + slot) * 64 + lane];
       const int m = m0 + (slot >> 2) * 16 + q4 * 4 + (slot & 3);
-      if (m < p.M) {
-        v = p.scale ? fmaf(v, sc, bi) : v + bi;
-        v *= cs;
-        if (p.residual) v += p.residual[(size_t)m * p.ldr + n];
-        if (p.relu) v = (v < 0.f) ? 0.f : v;
-        p.C[(size_t)m * p.ldc + n] = v;
-      }
+      v = p.scale ? fmaf(v, e_sc[0], bi) : v + bi;
+      v *= cs;
+      v = p.residual ? v + e_res[0][0][i] : v;
+      if (p.relu) v = (v < 0.f) ? 0.f : v;
+      if (m < p.M) p.C[(size_t)m * p.ldc + n] = v;
     }
     KS_STAMP(4);
     return;
@@ -649,29 +683,27 @@ __device__ __forceinline__ void gemm_ks_body(const GemmParams& p, const int bid)
 #pragma unroll
       for (int r = 0; r < 16; ++r) red[((wave * NB + a * TN + b) * 16 + r) * 64 + lane] = acc[a][b][r];
   __syncthreads();
+  if constexpr (!EPI_EARLY) load_epilogue();
   // wave w finishes accumulator rows r = w, w+NWK, ... of every block
 #pragma unroll
   for (int a = 0; a < TM; ++a)
 #pragma unroll
     for (int b = 0; b < TN; ++b) {
       const int n = n0 + b * 32 + l31;
-      const float sc = p.scale ? p.scale[n] : 1.f;
-      const float bi = p.bias ? p.bias[n] : 0.f;
+      const float bi = p.bias ? e_bi[b] : 0.f;
       const float cs = (n < p.colscale_n) ? p.colscale : 1.f;
 #pragma unroll
-      for (int rr = 0; rr < 16 / NWK; ++rr) {
+      for (int rr = 0; rr < ER; ++rr) {
         const int r = wave + rr * NWK;
         float v = 0.f;
 #pragma unroll
         for (int w = 0; w < NWK; ++w) v += red[((w * NB + a * TN + b) * 16 + r) * 64 + lane];
         const int m = m0 + a * 32 + 4 * hh + (r & 3) + 8 * (r >> 2);
-        if (m < p.M) {
-          v = p.scale ? fmaf(v, sc, bi) : v + bi;
-          v *= cs;
-          if (p.residual) v += p.residual[(size_t)m * p.ldr + n];
-          if (p.relu) v = (v < 0.f) ? 0.f : v;
-          p.C[(size_t)m * p.ldc + n] = v;
-        }
+        v = p.scale ? fmaf(v, e_sc[b], bi) : v + bi;
+        v *= cs;
+        v = p.residual ? v + e_res[a][b][rr] : v;
+        if (p.relu) v = (v < 0.f) ? 0.f : v;
+        if (m < p.M) p.C[(size_t)m * p.ldc + n] = v;
       }
     }
 }

@@ -127,12 +127,44 @@ __device__ __forceinline__ void gemm_wp_body(const GemmParams& p, const int bid)
     if (p.dbg != nullptr && t == 0) p.dbg[(size_t)bid * 8 + (slot_)] = wall_clock64();  \
   } while (0)
   WP_STAMP(0);
+  const int l31 = lane & 31, hh = lane >> 5;
+  const int l15 = lane & 15, q4 = lane >> 4;
+  // ---- epilogue operands: scale, bias and every residual value this lane will add depend on nothing the kernel computes, so they
+  // are requested HERE, in front of the first DMA - the oldest entries of this wavefront's in-order VM queue (every counted
+  // wp_wait_chunks below stays valid as written), landed long before the epilogue.  Loaded behind the cross-wave barrier they were
+  // one serialised round trip for scale / bias and one per row (load, vmcnt(0), store) for the residual.  No branch between the
+  // loads: an absent operand reads a valid address (the weights' first row) and a select discards the value; rows past M read row M - 1 and
+  // are never stored.  Wave w finishes accumulator rows r = w + i * NWK of every block (slots of the 16-column tile alike).
+  constexpr int EB = N16 ? 1 : TN, ER = (N16 ? 8 : 16) / NWK;   // column blocks; rows per wavefront and block
+  float e_sc[EB], e_bi[EB], e_res[TM][EB][ER];
+  {
+    // wave-uniform selects only (no branch for hipcc to form): residual row = m - (m / mod) * mod, or m itself with the step at 0
+    const float* sc_src = p.scale ? p.scale : p.W;
+    const float* bi_src = p.bias ? p.bias : p.W;
+    const float* res_src = p.residual ? p.residual : p.W;
+    const int res_ld = p.residual ? p.ldr : 0;
+    const int res_mod = p.res_row_mod > 0 ? p.fd_resrow.d : 0;
+#pragma unroll
+    for (int b = 0; b < EB; ++b) {
+      const int n = N16 ? n0 + l15 : n0 + b * 32 + l31;
+      e_sc[b] = sc_src[n];
+      e_bi[b] = bi_src[n];
+#pragma unroll
+      for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int i = 0; i < ER; ++i) {
+          const int r = wave + i * NWK;
+          const int m = N16 ? m0 + (r >> 2) * 16 + q4 * 4 + (r & 3) : m0 + a * 32 + 4 * hh + (r & 3) + 8 * (r >> 2);
+          const int mc = m < p.M ? m : p.M - 1;
+          e_res[a][b][i] = res_src[(size_t)(mc - fastdiv(mc, p.fd_resrow) * res_mod) * res_ld + n];
+        }
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);   // hipcc otherwise sinks these loads to their first use
   const int pre = n_my < NSLOT ? n_my : NSLOT;
   for (int c = 0; c < pre; ++c) dma_chunk(c, c);
   WP_STAMP(1);
 
-  const int l31 = lane & 31, hh = lane >> 5;
-  const int l15 = lane & 15, q4 = lane >> 4;
   const int sw = N16 ? ((l15 >> 1) & 7) : ((l31 >> 1) & 7);   // swizzle of this lane's fragment rows (row bases: multiples of 16 / 32)
   f32x16 acc[TM][N16 ? 1 : TN];
   f32x4 acc16[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -213,21 +245,20 @@ __device__ __forceinline__ void gemm_wp_body(const GemmParams& p, const int bid)
       for (int r = 0; r < 4; ++r) slots[(blk * 4 + r) * 64 + lane] = acc16[blk][r];
     __syncthreads();
     const int n = n0 + l15;
-    const float sc = p.scale ? p.scale[n] : 1.f;
-    const float bi = p.bias ? p.bias[n] : 0.f;
+    const float bi = p.bias ? e_bi[0] : 0.f;
     const float cs = (n < p.colscale_n) ? p.colscale : 1.f;
-    for (int sl = wave; sl < 8; sl += NWK) {
+#pragma unroll
+    for (int i = 0; i < ER; ++i) {
+      const int sl = wave + i * NWK;
       float v = 0.f;
 #pragma unroll
       for (int w = 0; w < NWK; ++w) v += smem[w * WSTRIDE + sl * 64 + lane];
       const int m = m0 + (sl >> 2) * 16 + q4 * 4 + (sl & 3);
-      if (m < p.M) {
-        v = p.scale ? fmaf(v, sc, bi) : v + bi;
-        v *= cs;
-        if (p.residual) v += p.residual[(size_t)(p.res_row_mod > 0 ? fastmod(m, p.fd_resrow) : m) * p.ldr + n];
-        if (p.relu) v = (v < 0.f) ? 0.f : v;  // NaN passes through like torch.relu (fmaxf would drop it)
-        p.C[(size_t)m * p.ldc + n] = v;
-      }
+      v = p.scale ? fmaf(v, e_sc[0], bi) : v + bi;
+      v *= cs;
+      v = p.residual ? v + e_res[0][0][i] : v;
+      if (p.relu) v = (v < 0.f) ? 0.f : v;  // NaN passes through like torch.relu (fmaxf would drop it)
+      if (m < p.M) p.C[(size_t)m * p.ldc + n] = v;
     }
     WP_STAMP(4);
     return;
@@ -246,21 +277,20 @@ __device__ __forceinline__ void gemm_wp_body(const GemmParams& p, const int bid)
 #pragma unroll
       for (int b = 0; b < TNN; ++b) {
         const int n = n0 + b * 32 + l31;
-        const float sc = p.scale ? p.scale[n] : 1.f;
-        const float bi = p.bias ? p.bias[n] : 0.f;
+        const float bi = p.bias ? e_bi[b] : 0.f;
         const float cs = (n < p.colscale_n) ? p.colscale : 1.f;
-        for (int r = wave; r < 16; r += NWK) {
+#pragma unroll
+        for (int i = 0; i < ER; ++i) {
+          const int r = wave + i * NWK;
           float v = 0.f;
 #pragma unroll
           for (int w = 0; w < NWK; ++w) v += smem[w * WSTRIDE + ((a * TNN + b) * 16 + r) * 64 + lane];
           const int m = m0 + a * 32 + 4 * hh + (r & 3) + 8 * (r >> 2);
-          if (m < p.M) {
-            v = p.scale ? fmaf(v, sc, bi) : v + bi;
-            v *= cs;
-            if (p.residual) v += p.residual[(size_t)(p.res_row_mod > 0 ? fastmod(m, p.fd_resrow) : m) * p.ldr + n];
-            if (p.relu) v = (v < 0.f) ? 0.f : v;
-            p.C[(size_t)m * p.ldc + n] = v;
-          }
+          v = p.scale ? fmaf(v, e_sc[b], bi) : v + bi;
+          v *= cs;
+          v = p.residual ? v + e_res[a][b][i] : v;
+          if (p.relu) v = (v < 0.f) ? 0.f : v;
+          if (m < p.M) p.C[(size_t)m * p.ldc + n] = v;
         }
       }
     WP_STAMP(4);
