@@ -135,6 +135,9 @@ _PROTOS = {
     'cotr_ransac_fundamental_scratch_bytes': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     'cotr_ransac_fundamental': (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                                ctypes.c_uint64] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]),
+    'cotr_ransac_homography_scratch_bytes': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'cotr_ransac_homography': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_uint64] + [ctypes.c_void_p] * 8 + [ctypes.c_size_t, ctypes.c_void_p]),
     'cotr_warp_map': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4),
     'cotr_warp_perspective': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                              ctypes.c_int] + [ctypes.c_void_p] * 4),

@@ -13,7 +13,8 @@
 //                         null space of the 7x9 system by full-pivot elimination (in LDS), det cubic, up to 3 candidates
 //   2. rs_count_kernel    grid (3 * max_iters slots) x (2048-point chunks): symmetric epipolar error, ballot + popcount per
 //                         wavefront, one integer atomicAdd per wavefront (integer sums: deterministic)
-//   3. rs_select_kernel   one workgroup replays the sequential selection loop on the counts
+//   3. rs_select_kernel   one workgroup replays the sequential selection loop on the counts (ransac.h, shared with
+//                         homography.hip, as are the sampler and the iteration update)
 //   4. rs_mask_kernel     the chosen candidate's mask (same error code as 2) and F_out
 // No host waits, no allocation: capturable.  Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -23,6 +24,7 @@
 #include <stdint.h>
 
 #include "handleless.h"
+#include "ransac.h"
 
 using namespace cotr_detail;
 
@@ -32,15 +34,6 @@ using namespace cotr_detail;
 #define NN_MAX_POINTS (1 << 24)
 
 #define RS_MODEL 7
-#define RS_MAX_DRAWS 64
-#define RS_SOLVE_THREADS 64
-#define RS_COUNT_THREADS 256
-#define RS_COUNT_STEPS 8       // points per thread per workgroup: chunks of 2048 points
-#define RS_CHUNK (RS_COUNT_THREADS * RS_COUNT_STEPS)
-#define RS_SELECT_THREADS 1024
-#define RS_MAX_ITERS (1 << 16)
-#define RS_MAX_POINTS (1 << 24)
-#define RS_RANK_TOL 1e-12      // a pivot below this times the first one: the sample is degenerate
 
 // ---- nearest keypoint ---------------------------------------------------------------------------------------------------
 struct NnDir {
@@ -129,15 +122,6 @@ __global__ __launch_bounds__(256) void nn_mutual_kernel(const int32_t* __restric
 }
 
 // ---- fundamental-matrix RANSAC ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ double f32r(double v) { return (double)(float)v; }
-
 __device__ __forceinline__ double det3(const double* m) {
   return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
 }
@@ -226,18 +210,7 @@ __global__ __launch_bounds__(RS_SOLVE_THREADS) void rs_solve_kernel(const double
 #define S_(k) shI[(k) * RS_SOLVE_THREADS + lane]
 #define P_(c) shI[(RS_MODEL + (c)) * RS_SOLVE_THREADS + lane]
   // 1. sample: draw d of iteration it is splitmix64(splitmix64(seed) ^ (it << 6 | d)); duplicates are rejected
-  const uint64_t sk = splitmix64(seed);
-  int got = 0;
-  for (int d = 0; d < RS_MAX_DRAWS && got < RS_MODEL; ++d) {
-    const uint64_t z = splitmix64(sk ^ (((uint64_t)it << 6) | (uint64_t)d));
-    const int c = (int)((z >> 32) % (uint64_t)n);
-    bool dup = false;
-    for (int k = 0; k < got; ++k) dup = dup || S_(k) == c;
-    if (!dup) {
-      S_(got) = c;
-      ++got;
-    }
-  }
+  const int got = rs_sample<RS_MODEL>(seed, it, n, &shI[lane], RS_SOLVE_THREADS);
   if (hyp_samples) {
     for (int k = 0; k < RS_MODEL; ++k) hyp_samples[(size_t)it * RS_MODEL + k] = k < got ? S_(k) : -1;
   }
@@ -439,66 +412,6 @@ __global__ __launch_bounds__(RS_COUNT_THREADS) void rs_count_kernel(const double
   if ((threadIdx.x & 63) == 0 && wc > 0) atomicAdd(&count[slot], wc);
 }
 
-// OpenCV's RANSACUpdateNumIters
-__device__ int ransac_update(double p, double ep, int m, int N) {
-  const double num = log(fmax(1.0 - p, DBL_MIN));
-  const double denom = 1.0 - pow(1.0 - ep, (double)m);
-  if (denom < DBL_MIN) return 0;
-  const double lden = log(denom);
-  return (lden >= 0.0 || -num >= (double)N * (-lden)) ? N : (int)rint(num / lden);
-}
-
-// The sequential loop, replayed: the next slot that beats max(best, 6) within the iterations still to run is found by a
-// parallel minimum over the slots after the last one taken.
-__global__ __launch_bounds__(RS_SELECT_THREADS) void rs_select_kernel(const int* __restrict__ count, int max_iters, int n, double confidence,
-                                                                      int32_t* __restrict__ info, int32_t* __restrict__ hyp_count) {
-  __shared__ int st[4];   // next slot to look at (-1: done), best, niters, chosen slot
-  __shared__ int red[RS_SELECT_THREADS / 64];
-  const int tid = threadIdx.x;
-  const int nslots = 3 * max_iters;
-  if (hyp_count)
-    for (int s = tid; s < nslots; s += RS_SELECT_THREADS) hyp_count[s] = count[s];
-  if (tid == 0) st[0] = 0, st[1] = 0, st[2] = max_iters, st[3] = -1;
-  __syncthreads();
-  for (;;) {
-    const int pos = st[0], best = st[1], niters = st[2], chosen = st[3];
-    if (pos < 0) break;   // uniform
-    const int thr = max(best, RS_MODEL - 1);
-    // slots of the iterations it < niters, and the rest of the iteration of the last slot taken
-    const int limit = 3 * max(niters, chosen >= 0 ? chosen / 3 + 1 : 0);
-    int local = INT_MAX;
-    for (int s = pos + tid; s < limit; s += RS_SELECT_THREADS)
-      if (count[s] > thr) {
-        local = s;
-        break;
-      }
-    for (int off = 32; off > 0; off >>= 1) local = min(local, __shfl_xor(local, off));
-    if ((tid & 63) == 0) red[tid >> 6] = local;
-    __syncthreads();
-    if (tid == 0) {
-      int m = INT_MAX;
-      for (int w = 0; w < RS_SELECT_THREADS / 64; ++w) m = min(m, red[w]);
-      if (m == INT_MAX) {
-        st[0] = -1;
-      } else {
-        const int nb = count[m];
-        st[0] = m + 1;
-        st[1] = nb;
-        st[2] = ransac_update(confidence, (double)(n - nb) / (double)n, RS_MODEL, niters);
-        st[3] = m;
-      }
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const int chosen = st[3];
-    info[0] = chosen >= 0 ? 1 : 0;
-    info[1] = st[1];
-    info[2] = chosen >= 0 ? max(st[2], chosen / 3 + 1) : max_iters;
-    info[3] = chosen;
-  }
-}
-
 __global__ __launch_bounds__(256) void rs_mask_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2, int n,
                                                       const double* __restrict__ F, const int32_t* __restrict__ info, float thr,
                                                       double* __restrict__ F_out, uint8_t* __restrict__ mask) {
@@ -627,7 +540,7 @@ int cotr_ransac_fundamental(const double* pts1, const double* pts2, int n, doubl
                      pts1, pts2, n, max_iters, seed, F, count, hyp_F, hyp_samples);
   hipLaunchKernelGGL(rs_count_kernel, dim3((unsigned)(3 * max_iters), (unsigned)((n + RS_CHUNK - 1) / RS_CHUNK)), dim3(RS_COUNT_THREADS), 0,
                      s, pts1, pts2, n, F, count, thr);
-  hipLaunchKernelGGL(rs_select_kernel, dim3(1), dim3(RS_SELECT_THREADS), 0, s, count, max_iters, n, confidence, info_out, hyp_count);
+  hipLaunchKernelGGL((rs_select_kernel<RS_MODEL, 3>), dim3(1), dim3(RS_SELECT_THREADS), 0, s, count, max_iters, n, confidence, info_out, hyp_count);
   hipLaunchKernelGGL(rs_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pts1, pts2, n, F, info_out, thr, F_out, mask_out);
   return launched();
 }

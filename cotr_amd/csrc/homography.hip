@@ -1,0 +1,621 @@
+// Homography RANSAC with a least-squares refit on the inliers, in the structure of OpenCV's findHomography(RANSAC).
+// Rules in DESIGN.md 3h-2.  H maps pts1 to pts2: [u, v, 1]^T ~ H [x, y, 1]^T.
+//
+// cotr_ransac_homography: 4 + 2 * (3 + refine_iters + 1) launches on the caller's stream (4 + 2 * 3 with refine_iters = 0):
+//   1. hg_solve_kernel    one thread per iteration: counter-based sample of 4 distinct indices (ransac.h), cv2's checkSubset,
+//                         Hartley normalisation, the 8x8 system of get_perspective_transform by full-pivot elimination (LDS)
+//   2. hg_count_kernel    grid (max_iters slots) x (2048-point chunks): transfer error, ballot + popcount per wavefront, one
+//                         integer atomicAdd per wavefront
+//   3. rs_select_kernel   the sequential selection loop replayed on the counts (ransac.h), model size 4, one slot per iteration
+//   4. hg_mask_kernel     the chosen candidate's mask, H_ransac, and the refit's state
+//   5. the refit chain, pairs of hg_accum_kernel<STAGE> (per 2048-point chunk: up to 45 sums over the mask, every thread
+//      over its points in order, every wavefront in a fixed tree, the 4 wavefronts in order -> scratch) and
+//      hg_finish_kernel (one workgroup: the chunks in chunk order, then the stage's small serial problem):
+//        CENTROID, DISTANCE          the Hartley normalisation of the inliers
+//        DLT                         L^T L (45 sums) -> the eigenvector of the smallest eigenvalue by cyclic Jacobi
+//        GN x (refine_iters + 1)     (none with refine_iters = 0) J^T J, J^T r, squared error (45 sums) -> accept or undo the last step, take the next
+//      A device-side flag ends the chain's work early; its length never depends on the data.
+// No floating-point atomics: the same input gives the same bits.  No host waits, no allocation: capturable.
+// Compiled with -ffp-contract=off.
+#include <hip/hip_runtime.h>
+#include <float.h>
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "handleless.h"
+#include "ransac.h"
+
+using namespace cotr_detail;
+
+#define HG_MODEL 4
+#define HG_SUMS 45
+#define HG_MAX_REFINE 64
+#define HG_JACOBI_SWEEPS 30
+#define HG_H22_TOL 1e-12       // |Hn[2,2]| <= this times ||Hn||: the DLT result is kept as it is
+
+enum { HG_CENTROID = 0, HG_DISTANCE = 1, HG_DLT = 2, HG_GN = 3 };
+
+// the refit's state, in scratch; written by hg_mask_kernel (done, status, kept) and the finish kernels
+struct HgState {
+  double c1x, c1y, s1, c2x, c2y, s2;   // T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]] of each point set
+  double cnt;                          // number of inliers, as a sum over the mask
+  double h[9];                         // current Hn (normalised frame); h[8] = 1 while refining
+  double hprev[9];                     // Hn before the step on trial
+  double err_prev;                     // squared error at hprev
+  int done;                            // nothing more to accumulate
+  int status;                          // 0 DLT + refine, 1 DLT only, 2 none
+  int kept;                            // Gauss-Newton steps kept
+  int trial;                           // h is a step whose error is not known yet
+};
+
+// ---- the error -----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float hg_error(const double* h, double x, double y, double u, double v) {
+  const double w = 1.0 / (h[6] * x + h[7] * y + h[8]);
+  const double dx = (h[0] * x + h[1] * y + h[2]) * w - u;
+  const double dy = (h[3] * x + h[4] * y + h[5]) * w - v;
+  return (float)(dx * dx + dy * dy);
+}
+
+__device__ __forceinline__ bool hg_inlier(const double* h, const double* __restrict__ pts1, const double* __restrict__ pts2, int p, float thr) {
+  const double x = f32r(pts1[(size_t)p * 2]), y = f32r(pts1[(size_t)p * 2 + 1]);
+  const double u = f32r(pts2[(size_t)p * 2]), v = f32r(pts2[(size_t)p * 2 + 1]);
+  return hg_error(h, x, y, u, v) <= thr;   // false for NaN
+}
+
+// ---- 8x8 full-pivot solve ------------------------------------------------------------------------------------------
+// a: the augmented 8 x 9 system, entry (r, c) at a[(r * 9 + c) * STRIDE]; perm: 8 ints at perm[c * STRIDE] -> z[8] with
+// A z = b.  false when a pivot falls below RS_RANK_TOL times the first one (or is NaN).
+template <int STRIDE>
+__device__ bool hg_solve8(double* a, int* perm, double* z) {
+#define A_(r, c) a[((r) * 9 + (c)) * STRIDE]
+#define P_(c) perm[(c) * STRIDE]
+  for (int c = 0; c < 8; ++c) P_(c) = c;
+  double piv0 = 0.0;
+  for (int k = 0; k < 8; ++k) {
+    double pv = -1.0;
+    int pr = k, pc = k;
+    for (int r = k; r < 8; ++r)
+      for (int c = k; c < 8; ++c) {
+        const double v = fabs(A_(r, c));
+        if (v > pv) pv = v, pr = r, pc = c;
+      }
+    if (k == 0) piv0 = pv;
+    if (!(pv > RS_RANK_TOL * piv0)) return false;   // also for NaN
+    if (pr != k)
+      for (int c = 0; c < 9; ++c) {
+        const double t = A_(k, c);
+        A_(k, c) = A_(pr, c);
+        A_(pr, c) = t;
+      }
+    if (pc != k) {
+      for (int r = 0; r < 8; ++r) {
+        const double t = A_(r, k);
+        A_(r, k) = A_(r, pc);
+        A_(r, pc) = t;
+      }
+      const int t = P_(k);
+      P_(k) = P_(pc);
+      P_(pc) = t;
+    }
+    const double akk = A_(k, k);
+    for (int r = k + 1; r < 8; ++r) {
+      const double m = A_(r, k) / akk;
+      for (int c = k + 1; c < 9; ++c) A_(r, c) = A_(r, c) - m * A_(k, c);
+      A_(r, k) = 0.0;
+    }
+  }
+  double y[8];
+#pragma unroll
+  for (int r = 7; r >= 0; --r) {
+    double acc = A_(r, 8);
+#pragma unroll
+    for (int c = r + 1; c < 8; ++c) acc -= A_(r, c) * y[c];
+    y[r] = acc / A_(r, r);
+  }
+  // z[perm[c]] = y[c], without indexing registers at run time
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    double v = 0.0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v = P_(c) == i ? y[c] : v;
+    z[i] = v;
+  }
+#undef A_
+#undef P_
+  return true;
+}
+
+// H = T2^-1 Hn T1
+__device__ __forceinline__ void hg_denormalise(const double* hn, double c1x, double c1y, double s1, double c2x, double c2y, double s2,
+                                               double* H) {
+  double gm[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    gm[r * 3 + 0] = hn[r * 3 + 0] * s1;
+    gm[r * 3 + 1] = hn[r * 3 + 1] * s1;
+    gm[r * 3 + 2] = hn[r * 3 + 0] * (-s1 * c1x) + hn[r * 3 + 1] * (-s1 * c1y) + hn[r * 3 + 2];
+  }
+  const double i2 = 1.0 / s2;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    H[0 * 3 + c] = i2 * gm[0 * 3 + c] + c2x * gm[2 * 3 + c];
+    H[1 * 3 + c] = i2 * gm[1 * 3 + c] + c2y * gm[2 * 3 + c];
+    H[2 * 3 + c] = gm[2 * 3 + c];
+  }
+}
+
+// unit Frobenius norm, then H[2,2] = 1 unless |H[2,2]| <= DBL_EPSILON (then: the first entry of largest magnitude positive)
+__device__ __forceinline__ void hg_scale(double* H) {
+  double ss = 0.0;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) ss += H[i] * H[i];
+  const double nrm = sqrt(ss);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) H[i] = H[i] / nrm;
+  if (fabs(H[8]) > DBL_EPSILON) {
+    const double h22 = H[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) H[i] = H[i] / h22;
+    H[8] = 1.0;
+  } else {
+    double big = H[0];
+#pragma unroll
+    for (int i = 1; i < 9; ++i)
+      if (fabs(H[i]) > fabs(big)) big = H[i];
+    if (big < 0.0) {
+#pragma unroll
+      for (int i = 0; i < 9; ++i) H[i] = -H[i];
+    }
+  }
+}
+
+// cv2's checkSubset on the 4 pairs: three points on a line in either set, or a sample that does not keep its orientation
+__device__ __forceinline__ bool hg_sample_ok(const double* x1, const double* y1, const double* x2, const double* y2) {
+  const int TI[4] = {0, 0, 0, 1}, TJ[4] = {1, 1, 2, 2}, TK[4] = {2, 3, 3, 3};
+  int negative = 0;
+  bool ok = true;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int i = TI[t], j = TJ[t], k = TK[t];
+#pragma unroll
+    for (int set = 0; set < 2; ++set) {
+      const double* x = set == 0 ? x1 : x2;
+      const double* y = set == 0 ? y1 : y2;
+      const double d1x = x[j] - x[i], d1y = y[j] - y[i], d2x = x[k] - x[i], d2y = y[k] - y[i];
+      if (fabs(d1y * d2x - d1x * d2y) <= (double)FLT_EPSILON * (fabs(d1x) + fabs(d1y) + fabs(d2x) + fabs(d2y))) ok = false;
+    }
+    const double da = x1[i] * (y1[j] - y1[k]) - y1[i] * (x1[j] - x1[k]) + (x1[j] * y1[k] - y1[j] * x1[k]);
+    const double db = x2[i] * (y2[j] - y2[k]) - y2[i] * (x2[j] - x2[k]) + (x2[j] * y2[k] - y2[j] * x2[k]);
+    if (da * db < 0.0) ++negative;
+  }
+  return ok && (negative == 0 || negative == 4);
+}
+
+__global__ __launch_bounds__(RS_SOLVE_THREADS) void hg_solve_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2,
+                                                                    int n, int max_iters, uint64_t seed, double* __restrict__ Hc,
+                                                                    int* __restrict__ count, double* __restrict__ hyp_H,
+                                                                    int32_t* __restrict__ hyp_samples) {
+  // per-thread LDS columns: sh[e * 64 + lane] (the elimination indexes rows and columns at run time)
+  __shared__ double shA[72 * RS_SOLVE_THREADS];
+  __shared__ int shI[(HG_MODEL + 8) * RS_SOLVE_THREADS];
+  const int lane = threadIdx.x;
+  const int it = blockIdx.x * RS_SOLVE_THREADS + lane;
+  if (it >= max_iters) return;   // no workgroup barrier below
+#define S_(k) shI[(k) * RS_SOLVE_THREADS + lane]
+#define A_(r, c) shA[((r) * 9 + (c)) * RS_SOLVE_THREADS + lane]
+  const int got = rs_sample<HG_MODEL>(seed, it, n, &shI[lane], RS_SOLVE_THREADS);
+  if (hyp_samples) {
+    for (int k = 0; k < HG_MODEL; ++k) hyp_samples[(size_t)it * HG_MODEL + k] = k < got ? S_(k) : -1;
+  }
+  bool ok = got == HG_MODEL;
+  double H[9];
+  if (ok) {
+    double x1[HG_MODEL], y1[HG_MODEL], x2[HG_MODEL], y2[HG_MODEL];
+    double c1x = 0.0, c1y = 0.0, c2x = 0.0, c2y = 0.0;
+#pragma unroll
+    for (int k = 0; k < HG_MODEL; ++k) {
+      const int i = S_(k);
+      x1[k] = f32r(pts1[(size_t)i * 2]);
+      y1[k] = f32r(pts1[(size_t)i * 2 + 1]);
+      x2[k] = f32r(pts2[(size_t)i * 2]);
+      y2[k] = f32r(pts2[(size_t)i * 2 + 1]);
+      c1x += x1[k], c1y += y1[k], c2x += x2[k], c2y += y2[k];
+    }
+    ok = hg_sample_ok(x1, y1, x2, y2);
+    c1x /= HG_MODEL, c1y /= HG_MODEL, c2x /= HG_MODEL, c2y /= HG_MODEL;
+    double m1 = 0.0, m2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < HG_MODEL; ++k) {
+      const double ax = x1[k] - c1x, ay = y1[k] - c1y, bx = x2[k] - c2x, by = y2[k] - c2y;
+      m1 += sqrt(ax * ax + ay * ay);
+      m2 += sqrt(bx * bx + by * by);
+    }
+    m1 /= HG_MODEL, m2 /= HG_MODEL;
+    ok = ok && m1 > 0.0 && m2 > 0.0 && m1 < INFINITY && m2 < INFINITY;
+    const double s1 = M_SQRT2 / m1, s2 = M_SQRT2 / m2;
+    if (ok) {
+      // rows [x, y, 1, 0, 0, 0, -xu, -yu | u] (k) and [0, 0, 0, x, y, 1, -xv, -yv | v] (k + 4) in normalised coordinates
+#pragma unroll
+      for (int k = 0; k < HG_MODEL; ++k) {
+        const double x = (x1[k] - c1x) * s1, y = (y1[k] - c1y) * s1;
+        const double u = (x2[k] - c2x) * s2, v = (y2[k] - c2y) * s2;
+        A_(k, 0) = x, A_(k, 1) = y, A_(k, 2) = 1.0, A_(k, 3) = 0.0, A_(k, 4) = 0.0, A_(k, 5) = 0.0;
+        A_(k, 6) = -(x * u), A_(k, 7) = -(y * u), A_(k, 8) = u;
+        A_(k + 4, 0) = 0.0, A_(k + 4, 1) = 0.0, A_(k + 4, 2) = 0.0, A_(k + 4, 3) = x, A_(k + 4, 4) = y, A_(k + 4, 5) = 1.0;
+        A_(k + 4, 6) = -(x * v), A_(k + 4, 7) = -(y * v), A_(k + 4, 8) = v;
+      }
+      double hn[9];
+      ok = hg_solve8<RS_SOLVE_THREADS>(&shA[lane], &shI[HG_MODEL * RS_SOLVE_THREADS + lane], hn);
+      if (ok) {
+        hn[8] = 1.0;
+        hg_denormalise(hn, c1x, c1y, s1, c2x, c2y, s2, H);
+        hg_scale(H);
+      }
+    }
+  }
+#undef S_
+#undef A_
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    const double v = ok ? H[i] : NAN;   // a slot without a candidate: NaN, count -1
+    Hc[(size_t)it * 9 + i] = v;
+    if (hyp_H) hyp_H[(size_t)it * 9 + i] = v;
+  }
+  count[it] = ok ? 0 : -1;
+}
+
+__global__ __launch_bounds__(RS_COUNT_THREADS) void hg_count_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2, int n,
+                                                                    const double* __restrict__ Hc, int* __restrict__ count, float thr) {
+  const int slot = blockIdx.x;
+  if (count[slot] < 0) return;   // no candidate in this slot (uniform)
+  double h[9];
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    h[i] = Hc[(size_t)slot * 9 + i];
+    finite = finite && isfinite(h[i]);
+  }
+  if (!finite) return;           // a non-finite candidate counts 0 inliers
+  const int base = blockIdx.y * RS_CHUNK;
+  int wc = 0;
+#pragma unroll
+  for (int s = 0; s < RS_COUNT_STEPS; ++s) {
+    const int p = base + s * RS_COUNT_THREADS + threadIdx.x;
+    const bool in = p < n && hg_inlier(h, pts1, pts2, p, thr);
+    wc += __popcll(__ballot(in));
+  }
+  if ((threadIdx.x & 63) == 0 && wc > 0) atomicAdd(&count[slot], wc);
+}
+
+__global__ __launch_bounds__(256) void hg_mask_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2, int n,
+                                                      const double* __restrict__ Hc, const int32_t* __restrict__ info, float thr,
+                                                      double* __restrict__ H_ransac, uint8_t* __restrict__ mask, HgState* __restrict__ st) {
+  const int found = info[0], slot = info[3];
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  double h[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) h[i] = found ? Hc[(size_t)slot * 9 + i] : 0.0;
+  if (p < n) mask[p] = (found && hg_inlier(h, pts1, pts2, p, thr)) ? 1 : 0;
+  if (p < 9 && H_ransac) H_ransac[p] = found ? Hc[(size_t)slot * 9 + p] : 0.0;
+  if (p == 0) {
+    st->done = found ? 0 : 1;
+    st->status = 2;
+    st->kept = 0;
+    st->trial = 0;
+  }
+}
+
+// ---- the refit -----------------------------------------------------------------------------------------------------
+template <int STAGE>
+struct HgSums {
+  static constexpr int N = STAGE == HG_CENTROID ? 5 : STAGE == HG_DISTANCE ? 2 : HG_SUMS;
+};
+
+// index of (i, j), i <= j, in the row-major upper triangle of an N x N matrix
+__host__ __device__ constexpr int hg_tri(int N, int i, int j) { return i * N - i * (i - 1) / 2 + (j - i); }
+
+// One inlier's terms, added to acc: every stage reads the point rounded to float32.
+template <int STAGE>
+__device__ __forceinline__ void hg_terms(const HgState* __restrict__ st, double x, double y, double u, double v, double* acc) {
+  if (STAGE == HG_CENTROID) {
+    acc[0] += x, acc[1] += y, acc[2] += u, acc[3] += v, acc[4] += 1.0;
+    return;
+  }
+  const double ax = x - st->c1x, ay = y - st->c1y, bx = u - st->c2x, by = v - st->c2y;
+  if (STAGE == HG_DISTANCE) {
+    acc[0] += sqrt(ax * ax + ay * ay);
+    acc[1] += sqrt(bx * bx + by * by);
+    return;
+  }
+  const double X = ax * st->s1, Y = ay * st->s1, U = bx * st->s2, V = by * st->s2;
+  if (STAGE == HG_DLT) {
+    const double r1[9] = {X, Y, 1.0, 0.0, 0.0, 0.0, -(U * X), -(U * Y), -U};
+    const double r2[9] = {0.0, 0.0, 0.0, X, Y, 1.0, -(V * X), -(V * Y), -V};
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+#pragma unroll
+      for (int j = i; j < 9; ++j) acc[hg_tri(9, i, j)] += r1[i] * r1[j] + r2[i] * r2[j];
+    return;
+  }
+  // HG_GN: residual and Jacobian of the 8 free entries at st->h (h[8] = 1)
+  const double* h = st->h;
+  const double w = 1.0 / (h[6] * X + h[7] * Y + h[8]);
+  const double px = (h[0] * X + h[1] * Y + h[2]) * w, py = (h[3] * X + h[4] * Y + h[5]) * w;
+  const double rx = px - U, ry = py - V;
+  const double xw = X * w, yw = Y * w;
+  const double j1[8] = {xw, yw, w, 0.0, 0.0, 0.0, -(xw * px), -(yw * px)};
+  const double j2[8] = {0.0, 0.0, 0.0, xw, yw, w, -(xw * py), -(yw * py)};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+#pragma unroll
+    for (int j = i; j < 8; ++j) acc[hg_tri(8, i, j)] += j1[i] * j1[j] + j2[i] * j2[j];
+    acc[36 + i] += j1[i] * rx + j2[i] * ry;
+  }
+  acc[44] += rx * rx + ry * ry;
+}
+
+template <int STAGE>
+__global__ __launch_bounds__(RS_COUNT_THREADS) void hg_accum_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2, int n,
+                                                                    const uint8_t* __restrict__ mask, const HgState* __restrict__ st,
+                                                                    double* __restrict__ parts) {
+  constexpr int NS = HgSums<STAGE>::N;
+  __shared__ double sh[RS_COUNT_THREADS / 64][HG_SUMS];
+  if (st->done) return;   // uniform
+  double acc[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) acc[k] = 0.0;
+  const int base = blockIdx.x * RS_CHUNK;
+#pragma unroll 1
+  for (int s = 0; s < RS_COUNT_STEPS; ++s) {   // every thread: its points in ascending order
+    const int p = base + s * RS_COUNT_THREADS + threadIdx.x;
+    if (p < n && mask[p]) {
+      const double x = f32r(pts1[(size_t)p * 2]), y = f32r(pts1[(size_t)p * 2 + 1]);
+      const double u = f32r(pts2[(size_t)p * 2]), v = f32r(pts2[(size_t)p * 2 + 1]);
+      hg_terms<STAGE>(st, x, y, u, v, acc);
+    }
+  }
+  // every wavefront: a fixed butterfly (each lane ends with the same bits), then the 4 wavefronts in order
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    double a = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a = a + __shfl_xor(a, off);
+    acc[k] = a;
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k) sh[threadIdx.x >> 6][k] = acc[k];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < NS) {
+    double a = sh[0][threadIdx.x];
+    for (int w = 1; w < RS_COUNT_THREADS / 64; ++w) a = a + sh[w][threadIdx.x];
+    parts[(size_t)blockIdx.x * HG_SUMS + threadIdx.x] = a;
+  }
+}
+
+// the eigenvector of the smallest eigenvalue of the symmetric 9 x 9 a (destroyed), by cyclic Jacobi -> e[9]
+__device__ void hg_jacobi9(double (*a)[9], double (*v)[9], double* e) {
+  for (int i = 0; i < 9; ++i)
+    for (int j = 0; j < 9; ++j) v[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < HG_JACOBI_SWEEPS; ++sweep) {
+    double off = 0.0, all = 0.0;
+    for (int i = 0; i < 9; ++i)
+      for (int j = 0; j < 9; ++j) {
+        const double t = a[i][j] * a[i][j];
+        all += t;
+        if (i != j) off += t;
+      }
+    if (!(sqrt(off) >= DBL_EPSILON * sqrt(all))) break;   // converged (or NaN)
+    for (int p = 0; p < 8; ++p)
+      for (int q = p + 1; q < 9; ++q) {
+        const double apq = a[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+        const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < 9; ++k) {   // columns p and q
+          const double akp = a[k][p], akq = a[k][q];
+          a[k][p] = c * akp - s * akq;
+          a[k][q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < 9; ++k) {   // rows p and q
+          const double apk = a[p][k], aqk = a[q][k];
+          a[p][k] = c * apk - s * aqk;
+          a[q][k] = s * apk + c * aqk;
+        }
+        for (int k = 0; k < 9; ++k) {
+          const double vkp = v[k][p], vkq = v[k][q];
+          v[k][p] = c * vkp - s * vkq;
+          v[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+  int m = 0;
+  for (int i = 1; i < 9; ++i)
+    if (a[i][i] < a[m][m]) m = i;
+  for (int i = 0; i < 9; ++i) e[i] = v[i][m];
+}
+
+// stage: which sums the accumulate before it made;
+// last: the chain's last launch (no further step is taken; writes H_out and info[4..7])
+__global__ __launch_bounds__(64) void hg_finish_kernel(int stage, int chunks, int last, const double* __restrict__ parts,
+                                                       HgState* __restrict__ st, const double* __restrict__ Hc,
+                                                       double* __restrict__ H_out, int32_t* __restrict__ info) {
+  __shared__ double sums[HG_SUMS];
+  __shared__ double A[9][9], Vv[9][9];
+  __shared__ double S8[72];
+  __shared__ int P8[8];
+  const int tid = threadIdx.x;
+  const bool active = !st->done;   // uniform; read before anything below writes it
+  const int ns = stage == HG_CENTROID ? 5 : stage == HG_DISTANCE ? 2 : HG_SUMS;
+  if (active && tid < ns) {
+    double a = 0.0;
+    for (int c = 0; c < chunks; ++c) a = a + parts[(size_t)c * HG_SUMS + tid];   // the chunks in chunk order
+    sums[tid] = a;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  if (active) {
+    if (stage == HG_CENTROID) {
+      const double cnt = sums[4];
+      st->cnt = cnt;
+      st->c1x = sums[0] / cnt, st->c1y = sums[1] / cnt, st->c2x = sums[2] / cnt, st->c2y = sums[3] / cnt;
+    } else if (stage == HG_DISTANCE) {
+      const double m1 = sums[0] / st->cnt, m2 = sums[1] / st->cnt;
+      if (m1 > 0.0 && m2 > 0.0 && m1 < INFINITY && m2 < INFINITY) {
+        st->s1 = M_SQRT2 / m1, st->s2 = M_SQRT2 / m2;
+      } else {
+        st->done = 1;   // status stays 2: no refit
+      }
+    } else if (stage == HG_DLT) {
+      for (int i = 0; i < 9; ++i)
+        for (int j = i; j < 9; ++j) A[i][j] = A[j][i] = sums[hg_tri(9, i, j)];
+      double e[9];
+      hg_jacobi9(A, Vv, e);
+      double ss = 0.0;
+      bool finite = true;
+      for (int i = 0; i < 9; ++i) ss += e[i] * e[i], finite = finite && isfinite(e[i]);
+      if (!finite || !(ss > 0.0)) {
+        st->done = 1;   // status stays 2
+      } else {
+        const bool refine = fabs(e[8]) > HG_H22_TOL * sqrt(ss);
+        for (int i = 0; i < 9; ++i) st->h[i] = refine ? e[i] / e[8] : e[i];
+        if (refine) st->h[8] = 1.0;
+        st->status = 1;
+        st->trial = 0;
+        if (!refine || last) st->done = 1;
+      }
+    } else {   // HG_GN
+      const double err = sums[44];
+      bool go_on = true;
+      if (st->trial) {
+        if (err < st->err_prev) {
+          st->kept = st->kept + 1;
+        } else {   // not smaller (or NaN): undo the step, the refinement ends
+          for (int i = 0; i < 9; ++i) st->h[i] = st->hprev[i];
+          go_on = false;
+        }
+        st->trial = 0;
+      }
+      st->status = 0;
+      if (go_on && !last) {
+        for (int i = 0; i < 8; ++i) {
+          for (int j = i; j < 8; ++j) S8[i * 9 + j] = S8[j * 9 + i] = sums[hg_tri(8, i, j)];
+          S8[i * 9 + 8] = -sums[36 + i];
+        }
+        double d[8];
+        if (hg_solve8<1>(S8, P8, d)) {
+          for (int i = 0; i < 9; ++i) st->hprev[i] = st->h[i];
+          st->err_prev = err;
+          for (int i = 0; i < 8; ++i) st->h[i] = st->h[i] + d[i];
+          st->trial = 1;
+        } else {
+          go_on = false;   // singular system
+        }
+      }
+      if (!go_on || last) st->done = 1;
+    }
+  }
+  if (last) {
+    const int found = info[0], status = st->status;
+    double H[9];
+    if (!found) {
+      for (int i = 0; i < 9; ++i) H[i] = 0.0;
+    } else if (status == 2) {
+      for (int i = 0; i < 9; ++i) H[i] = Hc[(size_t)info[3] * 9 + i];
+    } else {
+      hg_denormalise(st->h, st->c1x, st->c1y, st->s1, st->c2x, st->c2y, st->s2, H);
+      hg_scale(H);
+    }
+    for (int i = 0; i < 9; ++i) H_out[i] = H[i];
+    info[4] = st->kept;
+    info[5] = status;
+    info[6] = 0;
+    info[7] = 0;
+  }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+namespace {
+
+struct HgPlan {
+  size_t H, count, state, parts, bytes;
+  int chunks;
+};
+
+HgPlan hg_plan(int n, int max_iters) {
+  HgPlan l;
+  l.chunks = (n + RS_CHUNK - 1) / RS_CHUNK;
+  l.H = 0;
+  l.count = align_up((size_t)max_iters * 9 * sizeof(double));
+  l.state = l.count + align_up((size_t)max_iters * sizeof(int));
+  l.parts = l.state + align_up(sizeof(HgState));
+  l.bytes = l.parts + align_up((size_t)l.chunks * HG_SUMS * sizeof(double));
+  return l;
+}
+
+const char* hg_check_shape(int n, int max_iters) {
+  if (n < HG_MODEL || n > RS_MAX_POINTS) return "cotr_ransac_homography: n must be in [4, 2^24]";
+  if (max_iters < 1 || max_iters > RS_MAX_ITERS) return "cotr_ransac_homography: max_iters must be in [1, 65536]";
+  return nullptr;
+}
+
+template <int STAGE>
+void hg_pair(hipStream_t s, const HgPlan& l, int last, const double* pts1, const double* pts2, int n, const uint8_t* mask, HgState* st,
+             double* parts, const double* Hc, double* H_out, int32_t* info) {
+  hipLaunchKernelGGL(hg_accum_kernel<STAGE>, dim3((unsigned)l.chunks), dim3(RS_COUNT_THREADS), 0, s, pts1, pts2, n, mask, st, parts);
+  hipLaunchKernelGGL(hg_finish_kernel, dim3(1), dim3(64), 0, s, STAGE, l.chunks, last, parts, st, Hc, H_out, info);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cotr_ransac_homography_scratch_bytes(int n, int max_iters, size_t* bytes) {
+  if (!bytes) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography_scratch_bytes: bytes is NULL");
+  if (const char* e = hg_check_shape(n, max_iters)) return handleless_fail(COTR_ERR_ARG, e);
+  *bytes = hg_plan(n, max_iters).bytes;
+  return COTR_OK;
+}
+
+int cotr_ransac_homography(const double* pts1, const double* pts2, int n, double threshold, double confidence, int max_iters,
+                           int refine_iters, uint64_t seed, double* H_out, uint8_t* mask_out, int32_t* info_out, double* H_ransac,
+                           double* hyp_H, int32_t* hyp_count, int32_t* hyp_samples, void* scratch, size_t scratch_bytes,
+                           cotr_stream stream) {
+  if (const char* e = hg_check_shape(n, max_iters)) return handleless_fail(COTR_ERR_ARG, e);
+  if (refine_iters < 0 || refine_iters > HG_MAX_REFINE) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: refine_iters must be in [0, 64]");
+  if (!(threshold > 0.0) || !(threshold < INFINITY)) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: threshold must be finite and > 0");
+  if (!(confidence > 0.0 && confidence < 1.0)) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: confidence must be in (0, 1)");
+  if (!pts1 || !pts2 || !H_out || !mask_out || !info_out || !scratch)
+    return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: pts1, pts2, H_out, mask_out, info_out and scratch must not be NULL");
+  if (!aligned(pts1, 8) || !aligned(pts2, 8) || !aligned(H_out, 8) || !aligned(info_out, 4) || !aligned(H_ransac, 8) ||
+      !aligned(hyp_H, 8) || !aligned(hyp_count, 4) || !aligned(hyp_samples, 4) || !aligned(scratch, 16))
+    return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: doubles must be 8-byte, ints 4-byte and scratch 16-byte aligned");
+  const HgPlan l = hg_plan(n, max_iters);
+  if (scratch_bytes < l.bytes) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: scratch is smaller than cotr_ransac_homography_scratch_bytes");
+  char* base = static_cast<char*>(scratch);
+  double* Hc = reinterpret_cast<double*>(base + l.H);
+  int* count = reinterpret_cast<int*>(base + l.count);
+  HgState* st = reinterpret_cast<HgState*>(base + l.state);
+  double* parts = reinterpret_cast<double*>(base + l.parts);
+  const float thr = (float)(threshold * threshold);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(hg_solve_kernel, dim3((unsigned)((max_iters + RS_SOLVE_THREADS - 1) / RS_SOLVE_THREADS)), dim3(RS_SOLVE_THREADS), 0, s,
+                     pts1, pts2, n, max_iters, seed, Hc, count, hyp_H, hyp_samples);
+  hipLaunchKernelGGL(hg_count_kernel, dim3((unsigned)max_iters, (unsigned)l.chunks), dim3(RS_COUNT_THREADS), 0, s, pts1, pts2, n, Hc, count,
+                     thr);
+  hipLaunchKernelGGL((rs_select_kernel<HG_MODEL, 1>), dim3(1), dim3(RS_SELECT_THREADS), 0, s, count, max_iters, n, confidence, info_out,
+                     hyp_count);
+  hipLaunchKernelGGL(hg_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pts1, pts2, n, Hc, info_out, thr, H_ransac, mask_out,
+                     st);
+  hg_pair<HG_CENTROID>(s, l, 0, pts1, pts2, n, mask_out, st, parts, Hc, H_out, info_out);
+  hg_pair<HG_DISTANCE>(s, l, 0, pts1, pts2, n, mask_out, st, parts, Hc, H_out, info_out);
+  // refine_iters = 0: the DLT's finish is the last launch (status 1); else pair j judges step j - 1 and takes step j
+  hg_pair<HG_DLT>(s, l, refine_iters == 0, pts1, pts2, n, mask_out, st, parts, Hc, H_out, info_out);
+  for (int j = 0; refine_iters > 0 && j <= refine_iters; ++j) hg_pair<HG_GN>(s, l, j == refine_iters, pts1, pts2, n, mask_out, st, parts, Hc, H_out, info_out);
+  return launched();
+}
+
+}  // extern "C"

@@ -10,12 +10,16 @@ are the guided-matching post-processing of demo_guided_matching.py (nearest keyp
 device calls; ``ZoomEngine.guided_match`` runs the whole demo.  ``warp_by_map``, ``warp_perspective`` and
 ``get_perspective_transform`` are the demos' ``cv2.remap`` / ``cv2.warpPerspective`` / ``cv2.getPerspectiveTransform`` (8-bit
 bilinear, one launch each); ``warp_by_corr`` and ``paste_by_corners`` are the last lines of demo_single_pair.py and
-demo_homography.py."""
+demo_homography.py.  ``find_homography`` is ``cv2.findHomography(..., cv2.RANSAC)`` on the device (RANSAC, then a
+least-squares refit on the inliers), ``paste_by_homography`` the robust form of ``paste_by_corners`` and
+``ZoomEngine.homography`` the robust form of the whole demo."""
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
+from .homography import find_homography, paste_by_homography, ransac_homography
 from .triangulate import delaunay, triangulate_corr
 from .warp import get_perspective_transform, paste_by_corners, warp_by_corr, warp_by_map, warp_perspective
 from .zoom_engine import FasterSparseEngine, RefineResult, SparseEngine, ZoomEngine, patch_boxes
 
 __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'RefineResult', 'triangulate_corr', 'delaunay',
            'mutual_matches', 'find_fundamental_mat', 'filter_guided_matches', 'warp_by_map', 'warp_perspective',
-           'get_perspective_transform', 'warp_by_corr', 'paste_by_corners']
+           'get_perspective_transform', 'warp_by_corr', 'paste_by_corners', 'find_homography', 'ransac_homography',
+           'paste_by_homography']

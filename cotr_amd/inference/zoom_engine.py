@@ -676,6 +676,24 @@ class ZoomEngine:
                                               force=True)
         return filter_guided_matches(corrs_a_b, corrs_b_a, kp_a, kp_b, **filter_kw)
 
+    def homography(self, img_a, img_b, queries_a=None, zoom_ins=np.linspace(0.5, 0.0625, 4), converge_iters=1, max_corrs=1000,
+                   **ransac_kw):
+        """The robust form of demo_homography.py: ``cotr_corr_multiscale`` from A into B (from ``queries_a`` [N, 2] with
+        force=True, one row per query as the demo asks for its corners, or from the engine's own grid when None), then
+        ``find_homography`` on the correspondences -> (H float64 [3,3] mapping A to B, corrs [K, 4], mask uint8 [K, 1]);
+        H and mask are None when no model is found.  ``ransac_kw``: ransac_reproj_threshold (3), max_iters (2000),
+        confidence (0.995), seed (0).  Fewer than 4 correspondences: ValueError."""
+        from .homography import find_homography
+        if queries_a is None:
+            corrs = self.cotr_corr_multiscale(img_a, img_b, zoom_ins, converge_iters, max_corrs=max_corrs)
+        else:
+            queries_a = np.asarray(queries_a)
+            corrs = self.cotr_corr_multiscale(img_a, img_b, zoom_ins, converge_iters, max_corrs=max_corrs, queries_a=queries_a,
+                                              force=True)
+        corrs = np.asarray(corrs)
+        H, mask = find_homography(corrs[:, :2], corrs[:, 2:], **ransac_kw)
+        return H, corrs, mask
+
     @staticmethod
     def _task_objects(shape_a, shape_b, loc_from, loc_to, ident, area_a, area_b, zoom_ins, converge_iters, results, executed,
                       with_ident):

@@ -477,6 +477,35 @@ int cotr_ransac_fundamental(const double* pts1, const double* pts2, int n, doubl
                             uint64_t seed, double* F_out, uint8_t* mask_out, int32_t* info_out, double* hyp_F, int32_t* hyp_count,
                             int32_t* hyp_samples, void* scratch, size_t scratch_bytes, cotr_stream stream);
 
+/* ---- homography RANSAC with a least-squares refit on the inliers (cotr_amd/csrc/homography.hip) -------------------------
+ * The structure of cv2.findHomography(pts1, pts2, cv2.RANSAC, threshold) on the device, by rules of the library's own
+ * (no bit-compatibility with OpenCV is claimed).  H maps pts1 to pts2: [u, v, 1]^T ~ H [x, y, 1]^T.
+ *
+ * cotr_ransac_homography: pts1 [n,2], pts2 [n,2] float64 DEVICE pointers (rounded to float32 first) -> H_out [9] (float64,
+ *   row-major; the refit on the inliers of the chosen candidate), mask_out [n] uint8 (the inliers of the chosen candidate:
+ *   the RANSAC mask, as in cv2), info_out [8] int32 = {found, best inlier count, sequential iterations run, chosen slot
+ *   (-1: none), Gauss-Newton steps kept, refit status (0: DLT + refinement, 1: DLT only, 2: none), 0, 0}; H_out = 0 and
+ *   mask_out = 0 when nothing is found.  Iteration it draws 4 distinct indices with the sampler of
+ *   cotr_ransac_fundamental, rejects degenerate samples (three points on a line in either set, or an orientation that is
+ *   not kept), solves the Hartley-normalised 8x8 system by full-pivot elimination (slot it); the candidates are counted in
+ *   parallel and the sequential RANSAC loop is replayed on the counts.  An inlier has
+ *   float(dx^2 + dy^2) <= float(threshold^2), (dx, dy) = H(x, y) - (u, v).  The refit: Hartley normalisation of the
+ *   inliers, the eigenvector of the smallest eigenvalue of the 9x9 DLT matrix (cyclic Jacobi), then refine_iters
+ *   Gauss-Newton steps on the 8 free entries, each kept only while the squared error falls.  Every floating-point sum is
+ *   taken in a fixed order (no atomics): the same input gives the same bits on any stream, with any scratch contents.
+ *   4 <= n <= 2^24, 1 <= max_iters <= 65536, 0 <= refine_iters <= 64, threshold > 0 finite, 0 < confidence < 1.
+ *   H_ransac [9] (the chosen candidate, 0 when nothing is found), hyp_H [max_iters][9] float64, hyp_count [max_iters]
+ *   int32 (-1: no candidate in the slot; its H is NaN), hyp_samples [max_iters][4] int32 (-1 past the indices drawn):
+ *   optional DEVICE outputs (NULL: not written).
+ *   scratch: DEVICE, 16-byte aligned, at least cotr_ransac_homography_scratch_bytes(n, max_iters) bytes.
+ * Stream-ordered, 4 + 2 * (refine_iters + 4) launches (10 with refine_iters = 0) whatever the data, no host waits and no allocation (capturable).
+ * Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_ransac_homography_scratch_bytes(int n, int max_iters, size_t* bytes);
+int cotr_ransac_homography(const double* pts1, const double* pts2, int n, double threshold, double confidence, int max_iters,
+                           int refine_iters, uint64_t seed, double* H_out, uint8_t* mask_out, int32_t* info_out, double* H_ransac,
+                           double* hyp_H, int32_t* hyp_count, int32_t* hyp_samples, void* scratch, size_t scratch_bytes,
+                           cotr_stream stream);
+
 /* ---- warps of 8-bit images: cv2.remap / cv2.warpPerspective, INTER_LINEAR, BORDER_CONSTANT 0 (cotr_amd/csrc/warp.hip) ----
  * The last host step of demo_single_pair.py:43 (image B warped by triangulate_corr's dense map) and of
  * demo_homography.py:46-49 (a picture pasted through four corners).  Rule in DESIGN.md 3i: OpenCV's 8-bit bilinear remap.
