@@ -31,7 +31,6 @@ using namespace cotr_detail;
 #define HG_MODEL 4
 #define HG_SUMS 45
 #define HG_MAX_REFINE 64
-#define HG_JACOBI_SWEEPS 30
 #define HG_H22_TOL 1e-12       // |Hn[2,2]| <= this times ||Hn||: the DLT result is kept as it is
 
 enum { HG_CENTROID = 0, HG_DISTANCE = 1, HG_DLT = 2, HG_GN = 3 };
@@ -395,43 +394,9 @@ __global__ __launch_bounds__(RS_COUNT_THREADS) void hg_accum_kernel(const double
   }
 }
 
-// the eigenvector of the smallest eigenvalue of the symmetric 9 x 9 a (destroyed), by cyclic Jacobi -> e[9]
+// the eigenvector of the smallest eigenvalue of the symmetric 9 x 9 a (destroyed), by cyclic Jacobi (ransac.h) -> e[9]
 __device__ void hg_jacobi9(double (*a)[9], double (*v)[9], double* e) {
-  for (int i = 0; i < 9; ++i)
-    for (int j = 0; j < 9; ++j) v[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < HG_JACOBI_SWEEPS; ++sweep) {
-    double off = 0.0, all = 0.0;
-    for (int i = 0; i < 9; ++i)
-      for (int j = 0; j < 9; ++j) {
-        const double t = a[i][j] * a[i][j];
-        all += t;
-        if (i != j) off += t;
-      }
-    if (!(sqrt(off) >= DBL_EPSILON * sqrt(all))) break;   // converged (or NaN)
-    for (int p = 0; p < 8; ++p)
-      for (int q = p + 1; q < 9; ++q) {
-        const double apq = a[p][q];
-        if (apq == 0.0) continue;
-        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-        const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 9; ++k) {   // columns p and q
-          const double akp = a[k][p], akq = a[k][q];
-          a[k][p] = c * akp - s * akq;
-          a[k][q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < 9; ++k) {   // rows p and q
-          const double apk = a[p][k], aqk = a[q][k];
-          a[p][k] = c * apk - s * aqk;
-          a[q][k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < 9; ++k) {
-          const double vkp = v[k][p], vkq = v[k][q];
-          v[k][p] = c * vkp - s * vkq;
-          v[k][q] = s * vkp + c * vkq;
-        }
-      }
-  }
+  rs_jacobi<9>(a, v);
   int m = 0;
   for (int i = 1; i < 9; ++i)
     if (a[i][i] < a[m][m]) m = i;

@@ -1,6 +1,6 @@
-// The pieces the RANSAC estimators share (guided.hip: fundamental matrix, homography.hip: homography): the counter-based
-// sampler, OpenCV's iteration update and the kernel that replays the sequential selection loop on the counts.  Rules in
-// DESIGN.md 3h.  Included by translation units compiled with -ffp-contract=off.
+// The pieces the RANSAC estimators share (guided.hip: fundamental matrix, homography.hip: homography, essential.hip:
+// essential matrix): the counter-based sampler, OpenCV's iteration update, the kernel that replays the sequential selection
+// loop on the counts, and the cyclic Jacobi iteration of the symmetric eigenproblems.  Rules in DESIGN.md 3h.  Included by translation units compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -17,6 +17,7 @@
 #define RS_MAX_ITERS (1 << 16)
 #define RS_MAX_POINTS (1 << 24)
 #define RS_RANK_TOL 1e-12      // a pivot below this times the first one: the sample is degenerate
+#define RS_JACOBI_SWEEPS 30
 
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   uint64_t z = x + 0x9E3779B97F4A7C15ull;
@@ -53,6 +54,48 @@ __device__ inline int ransac_update(double p, double ep, int m, int N) {
   if (denom < DBL_MIN) return 0;
   const double lden = log(denom);
   return (lden >= 0.0 || -num >= (double)N * (-lden)) ? N : (int)rint(num / lden);
+}
+
+// Cyclic Jacobi on the symmetric N x N a: rotations (p, q) in row-major order until the off-diagonal norm falls below
+// DBL_EPSILON times the Frobenius norm, at most RS_JACOBI_SWEEPS sweeps.  a ends (nearly) diagonal with the eigenvalues, the
+// columns of v are the eigenvectors.  One thread.
+template <int N>
+__device__ void rs_jacobi(double (*a)[N], double (*v)[N]) {
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < N; ++j) v[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < RS_JACOBI_SWEEPS; ++sweep) {
+    double off = 0.0, all = 0.0;
+    for (int i = 0; i < N; ++i)
+      for (int j = 0; j < N; ++j) {
+        const double t = a[i][j] * a[i][j];
+        all += t;
+        if (i != j) off += t;
+      }
+    if (!(sqrt(off) >= DBL_EPSILON * sqrt(all))) break;   // converged (or NaN)
+    for (int p = 0; p < N - 1; ++p)
+      for (int q = p + 1; q < N; ++q) {
+        const double apq = a[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+        const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < N; ++k) {   // columns p and q
+          const double akp = a[k][p], akq = a[k][q];
+          a[k][p] = c * akp - s * akq;
+          a[k][q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < N; ++k) {   // rows p and q
+          const double apk = a[p][k], aqk = a[q][k];
+          a[p][k] = c * apk - s * aqk;
+          a[q][k] = s * apk + c * aqk;
+        }
+        for (int k = 0; k < N; ++k) {
+          const double vkp = v[k][p], vkq = v[k][q];
+          v[k][p] = c * vkp - s * vkq;
+          v[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
 }
 
 // The sequential loop, replayed: the next slot that beats max(best, MODEL - 1) within the iterations still to run is found

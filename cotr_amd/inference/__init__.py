@@ -12,7 +12,11 @@ device calls; ``ZoomEngine.guided_match`` runs the whole demo.  ``warp_by_map``,
 bilinear, one launch each); ``warp_by_corr`` and ``paste_by_corners`` are the last lines of demo_single_pair.py and
 demo_homography.py.  ``find_homography`` is ``cv2.findHomography(..., cv2.RANSAC)`` on the device (RANSAC, then a
 least-squares refit on the inliers), ``paste_by_homography`` the robust form of ``paste_by_corners`` and
-``ZoomEngine.homography`` the robust form of the whole demo."""
+``ZoomEngine.homography`` the robust form of the whole demo.  ``find_essential_mat`` and ``recover_pose`` are
+``cv2.findEssentialMat(..., cv2.RANSAC)`` (five-point RANSAC) and ``cv2.recoverPose`` on the device, ``ransac_essential`` the
+former with device tensors, ``relative_pose`` both as one device sequence and ``ZoomEngine.relative_pose`` the pose after
+demo_wbs.py's correspondences."""
+from .essential import find_essential_mat, ransac_essential, recover_pose, relative_pose
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .homography import find_homography, paste_by_homography, ransac_homography
 from .triangulate import delaunay, triangulate_corr
@@ -22,4 +26,4 @@ from .zoom_engine import FasterSparseEngine, RefineResult, SparseEngine, ZoomEng
 __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'RefineResult', 'triangulate_corr', 'delaunay',
            'mutual_matches', 'find_fundamental_mat', 'filter_guided_matches', 'warp_by_map', 'warp_perspective',
            'get_perspective_transform', 'warp_by_corr', 'paste_by_corners', 'find_homography', 'ransac_homography',
-           'paste_by_homography']
+           'paste_by_homography', 'find_essential_mat', 'ransac_essential', 'recover_pose', 'relative_pose']

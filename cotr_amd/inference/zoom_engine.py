@@ -694,6 +694,25 @@ class ZoomEngine:
         H, mask = find_homography(corrs[:, :2], corrs[:, 2:], **ransac_kw)
         return H, corrs, mask
 
+    def relative_pose(self, img_a, img_b, K_a, K_b, queries_a=None, zoom_ins=np.linspace(0.5, 0.0625, 4), converge_iters=1,
+                      max_corrs=1000, **ransac_kw):
+        """demo_wbs.py followed by the pose its evaluation takes from the correspondences: ``cotr_corr_multiscale`` from A
+        into B (from ``queries_a`` [N, 2] with force=True, or from the engine's own grid when None), then ``relative_pose``
+        on them with the camera matrices ``K_a``, ``K_b`` [3,3] -> (R float64 [3,3], t float64 [3,1] of unit length with
+        x_b ~ R x_a + t, corrs [K, 4], mask uint8 [K, 1]: the inliers in front of both cameras); R, t and mask are None when
+        no model is found.  ``ransac_kw``: threshold (1.0), confidence (0.999), max_iters (1000), seed (0), distance_thresh
+        (50).  Fewer than 5 correspondences: ValueError."""
+        from .essential import relative_pose
+        if queries_a is None:
+            corrs = self.cotr_corr_multiscale(img_a, img_b, zoom_ins, converge_iters, max_corrs=max_corrs)
+        else:
+            queries_a = np.asarray(queries_a)
+            corrs = self.cotr_corr_multiscale(img_a, img_b, zoom_ins, converge_iters, max_corrs=max_corrs, queries_a=queries_a,
+                                              force=True)
+        corrs = np.asarray(corrs)
+        R, t, mask = relative_pose(corrs[:, :2], corrs[:, 2:], K_a, K_b, **ransac_kw)
+        return R, t, corrs, mask
+
     @staticmethod
     def _task_objects(shape_a, shape_b, loc_from, loc_to, ident, area_a, area_b, zoom_ins, converge_iters, results, executed,
                       with_ident):

@@ -506,6 +506,50 @@ int cotr_ransac_homography(const double* pts1, const double* pts2, int n, double
                            double* hyp_H, int32_t* hyp_count, int32_t* hyp_samples, void* scratch, size_t scratch_bytes,
                            cotr_stream stream);
 
+/* ---- essential-matrix RANSAC and the pose of an essential matrix (cotr_amd/csrc/essential.hip) --------------------------
+ * The structure of cv2.findEssentialMat(pts1, pts2, K1, dist1, K2, dist2, cv2.RANSAC, prob, threshold) and
+ * cv2.recoverPose(E, pts1, pts2, K1, ..., distanceThresh) on the device, by rules of the library's own (no
+ * bit-compatibility with OpenCV is claimed).  x2h^T E x1h = 0 on camera-normalised points; x2 ~ R x1 + t.
+ *
+ * K1, K2: HOST pointers to 9 doubles each, row-major upper-triangular camera matrices (fx, skew, cx; 0, fy, cy; 0, 0, 1;
+ *   only those five entries are read), finite, fx and fy not 0.  A pixel (u, v), rounded to float32, becomes
+ *   y = (v - cy) / fy, x = (u - cx - skew y) / fx.
+ * cotr_ransac_essential: pts1 [n,2], pts2 [n,2] float64 DEVICE pointers (rounded to float32 first) -> E_out [9] (float64,
+ *   row-major, unit Frobenius norm, the first entry of largest magnitude positive: the chosen candidate, no refit),
+ *   mask_out [n] uint8 (its inliers), info_out [8] int32 = {found, best inlier count, sequential iterations run, chosen
+ *   slot (-1: none), 0, 0, 0, 0}; E_out = 0 and mask_out = 0 when nothing is found.  Iteration it draws 5 distinct indices
+ *   with the sampler of cotr_ransac_fundamental and solves the five-point problem (0..10 real candidates, slots
+ *   10 * it + k, in ascending order of the root): a 4-dimensional null space, the ten cubic constraints in 20 monomials,
+ *   Gauss-Jordan elimination of the cubic monomials, the real eigenvalues of the 10 x 10 action matrix by Hessenberg
+ *   reduction and shifted QR iteration, then 3 Gauss-Newton steps on every root.  The candidates are counted in parallel
+ *   and the sequential RANSAC loop is replayed on the counts.  An inlier has float(Sampson error) <= float(thr^2) with
+ *   thr = threshold / ((fx1 + fy1 + fx2 + fy2) / 4).  5 <= n <= 2^24, 1 <= max_iters <= 6553, threshold > 0 finite,
+ *   0 < confidence < 1.
+ *   hyp_E [10*max_iters][9] float64, hyp_count [10*max_iters] int32 (-1: no candidate in the slot; its E is NaN),
+ *   hyp_samples [max_iters][5] int32 (-1 past the indices drawn): optional DEVICE outputs (NULL: not written).
+ *   scratch: DEVICE, 16-byte aligned, at least cotr_ransac_essential_scratch_bytes(n, max_iters) bytes.
+ * cotr_recover_pose: E [9] float64 DEVICE pointer, pts1, pts2 as above, mask_in [n] uint8 DEVICE (NULL: every point),
+ *   found: DEVICE pointer to an int32 (NULL: taken as 1; 0: nothing to decompose, e.g. info_out of cotr_ransac_essential)
+ *   -> R_out [9], t_out [3] float64 (unit length), mask_out [n] uint8 = mask_in and in front of both cameras under the
+ *   chosen candidate, info_out [8] int32 = {points in front, chosen candidate (-1: none), the four counts, 0, 0}.  The
+ *   candidates, in cv2's order: (R1, t), (R2, t), (R1, -t), (R2, -t) with R1 = U W V^T, R2 = U W^T V^T, t = U[:, 2], U and V
+ *   from cyclic Jacobi on E^T E.  A point is in front when its least-squares depths in both cameras lie in
+ *   (0, distance_thresh).  The first candidate with the largest count is taken.  found = 0 or a non-finite E: R_out = 0,
+ *   t_out = 0, mask_out = 0, info_out = {0, -1, 0, ...}.  5 <= n <= 2^24, distance_thresh > 0 finite.
+ *   scratch: DEVICE, 16-byte aligned, at least cotr_recover_pose_scratch_bytes(n) bytes.
+ * Stream-ordered, 5 and 3 launches whatever the data, no host waits and no allocation (capturable); integer atomics only:
+ * the same input gives the same bits.  Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the message in
+ * cotr_raster_last_error(). */
+int cotr_ransac_essential_scratch_bytes(int n, int max_iters, size_t* bytes);
+int cotr_ransac_essential(const double* pts1, const double* pts2, int n, const double* K1, const double* K2, double threshold,
+                          double confidence, int max_iters, uint64_t seed, double* E_out, uint8_t* mask_out, int32_t* info_out,
+                          double* hyp_E, int32_t* hyp_count, int32_t* hyp_samples, void* scratch, size_t scratch_bytes,
+                          cotr_stream stream);
+int cotr_recover_pose_scratch_bytes(int n, size_t* bytes);
+int cotr_recover_pose(const double* E, const double* pts1, const double* pts2, int n, const double* K1, const double* K2,
+                      double distance_thresh, const uint8_t* mask_in, const int32_t* found, double* R_out, double* t_out,
+                      uint8_t* mask_out, int32_t* info_out, void* scratch, size_t scratch_bytes, cotr_stream stream);
+
 /* ---- warps of 8-bit images: cv2.remap / cv2.warpPerspective, INTER_LINEAR, BORDER_CONSTANT 0 (cotr_amd/csrc/warp.hip) ----
  * The last host step of demo_single_pair.py:43 (image B warped by triangulate_corr's dense map) and of
  * demo_homography.py:46-49 (a picture pasted through four corners).  Rule in DESIGN.md 3i: OpenCV's 8-bit bilinear remap.
