@@ -3,12 +3,12 @@
 //
 // cotr_ransac_essential: 5 launches on the caller's stream:
 //   1. es_normalise_kernel  the points rounded to float32, then through the inverse camera matrices (float64) -> scratch
-//   2. es_solve_kernel      one thread per iteration, 32 per workgroup: counter-based sample of 5 distinct indices (ransac.h),
-//                           the five-point solver in per-thread LDS columns -> 0..10 candidates in slots 10 * it + k
-//   3. es_count_kernel      grid (10 * max_iters slots) x (2048-point chunks): Sampson error, ballot + popcount per wavefront,
-//                           one integer atomicAdd per wavefront
-//   4. rs_select_kernel     the sequential selection loop replayed on the counts (ransac.h), model size 5, 10 slots per iteration
-//   5. es_mask_kernel       the chosen candidate and its mask
+//   2. es_solve_kernel          one thread per iteration, 32 per workgroup: counter-based sample of 5 distinct indices, the
+//                               five-point solver in per-thread LDS columns -> 0..10 candidates in slots 10 * it + k
+//   3. rs_count_kernel<EsModel> grid (10 * max_iters slots) x (2048-point chunks): Sampson error
+//   4. rs_select_kernel<5, 10>  the sequential selection loop replayed on the counts
+//   5. rs_mask_kernel<EsModel>  the chosen candidate and its mask; (the model's tail) info[4..7] = 0
+//      (3 - 5: ransac.h's frame on the model EsModel, as are the sampler and the elimination of the 5 x 9 system)
 // cotr_recover_pose: 3 launches:
 //   1. es_decompose_kernel  one workgroup: V from cyclic Jacobi on E^T E (ransac.h), U, the two rotations and t
 //   2. es_front_kernel      per 2048-point chunk: the least-squares depths of every masked point under the four candidates,
@@ -74,12 +74,13 @@ ES_HD __forceinline__ void es_mul21(const double* q, const double* l, double* c)
       for (int k = 0; k < 4; ++k) c[es_col(i, j, k)] += q[es_q2(i, j)] * l[k];
 }
 
-// ---- full-pivot solve of an N x N system ------------------------------------------------------------------------------
-// a: the augmented N x (N + 1) system, entry (r, c) at a[(r * (N + 1) + c) * STRIDE]; perm: N ints at perm[c * STRIDE] ->
-// z[N] with A z = b.  false when a pivot falls below RS_RANK_TOL times the first one (or is NaN): the rule of the 8 x 8
-// solve of homography.hip.
-template <int N, int STRIDE>
-ES_HD bool es_solve_full_pivot(double* a, int* perm, double* z) {
+// ---- the 3 x 3 solve of the polish step ---------------------------------------------------------------------------------
+// rs_solve<3, STRIDE> of ransac.h written out (the same rule, operation for operation; a: the augmented 3 x 4 system).  Kept
+// in this form for es_solve_kernel alone, which sits at the register limit: with the shared template, the same arithmetic
+// inlined in another shape, it spills two registers more (164 -> 172 bytes of scratch per lane) in its hottest loop.
+template <int STRIDE>
+ES_HD bool es_solve3(double* a, int* perm, double* z) {
+  constexpr int N = 3;
 #define A_(r, c) a[((r) * (N + 1) + (c)) * STRIDE]
 #define P_(c) perm[(c) * STRIDE]
   for (int c = 0; c < N; ++c) P_(c) = c;
@@ -358,7 +359,7 @@ ES_HD bool es_polish_step(double* mem, int* perm, double* p) {
   T_(4) = JtJ[1], T_(5) = JtJ[3], T_(6) = JtJ[4], T_(7) = Jtr[1];
   T_(8) = JtJ[2], T_(9) = JtJ[4], T_(10) = JtJ[5], T_(11) = Jtr[2];
   double d[3];
-  if (!es_solve_full_pivot<3, STRIDE>(&T_(0), perm, d)) return false;
+  if (!es_solve3<STRIDE>(&T_(0), perm, d)) return false;
   p[0] = x - d[0], p[1] = y - d[1], p[2] = z - d[2];
   return true;
 }
@@ -374,53 +375,11 @@ ES_HD int es_five_point(const double* x1, const double* y1, const double* x2, co
     Q_(k, 3) = y2[k] * x1[k], Q_(k, 4) = y2[k] * y1[k], Q_(k, 5) = y2[k];
     Q_(k, 6) = x1[k], Q_(k, 7) = y1[k], Q_(k, 8) = 1.0;
   }
-  for (int c = 0; c < 9; ++c) P_(c) = c;
-  double piv0 = 0.0;
-  for (int k = 0; k < ES_MODEL; ++k) {
-    double pv = -1.0;
-    int pr = k, pc = k;
-    for (int r = k; r < ES_MODEL; ++r)
-      for (int c = k; c < 9; ++c) {
-        const double v = fabs(Q_(r, c));
-        if (v > pv) pv = v, pr = r, pc = c;
-      }
-    if (k == 0) piv0 = pv;
-    if (!(pv > RS_RANK_TOL * piv0)) return 0;   // also for NaN
-    if (pr != k)
-      for (int c = 0; c < 9; ++c) {
-        const double t = Q_(k, c);
-        Q_(k, c) = Q_(pr, c);
-        Q_(pr, c) = t;
-      }
-    if (pc != k) {
-      for (int r = 0; r < ES_MODEL; ++r) {
-        const double t = Q_(r, k);
-        Q_(r, k) = Q_(r, pc);
-        Q_(r, pc) = t;
-      }
-      const int t = P_(k);
-      P_(k) = P_(pc);
-      P_(pc) = t;
-    }
-    const double akk = Q_(k, k);
-    for (int r = k + 1; r < ES_MODEL; ++r) {
-      const double m = Q_(r, k) / akk;
-      for (int c = k + 1; c < 9; ++c) Q_(r, c) = Q_(r, c) - m * Q_(k, c);
-      Q_(r, k) = 0.0;
-    }
-  }
+  if (!rs_eliminate<ES_MODEL, 9, 9, STRIDE>(&Q_(0, 0), perm)) return 0;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     double z[9];
-#pragma unroll
-    for (int c = ES_MODEL; c < 9; ++c) z[c] = c == ES_MODEL + t ? 1.0 : 0.0;
-#pragma unroll
-    for (int r = ES_MODEL - 1; r >= 0; --r) {
-      double acc = 0.0;
-#pragma unroll
-      for (int c = r + 1; c < 9; ++c) acc += Q_(r, c) * z[c];
-      z[r] = -acc / Q_(r, r);
-    }
+    rs_null_vector<ES_MODEL, 9, STRIDE>(&Q_(0, 0), ES_MODEL + t, z);
 #pragma unroll
     for (int c = 0; c < 9; ++c) NS_(t, P_(c)) = z[c];
   }
@@ -500,6 +459,7 @@ ES_HD int es_five_point(const double* x1, const double* y1, const double* x2, co
     for (int m = 0; m < 20; ++m) M_(9, m) = acc[m] / nrm;
   }
   // 3. Gauss-Jordan elimination of the ten cubic monomials with row pivoting: [I | B]
+  double piv0 = 0.0;
   for (int k = 0; k < 10; ++k) {
     double pv = -1.0;
     int pr = k;
@@ -613,12 +573,9 @@ ES_HD int es_five_point(const double* x1, const double* y1, const double* x2, co
     const double nrm = sqrt(ss);
 #pragma unroll
     for (int e = 0; e < 9; ++e) E[e] = E[e] / nrm;
-    double big = E[0];   // the first entry of largest magnitude
+    const bool negative = rs_negative9(E);
 #pragma unroll
-    for (int e = 1; e < 9; ++e)
-      if (fabs(E[e]) > fabs(big)) big = E[e];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) out[k * 9 + e] = big < 0.0 ? -E[e] : E[e];
+    for (int e = 0; e < 9; ++e) out[k * 9 + e] = negative ? -E[e] : E[e];
   }
   return nreal;
 }
@@ -646,10 +603,26 @@ ES_HD __forceinline__ float es_error(const double* e, double x1, double y1, doub
   return (float)(d * d / (a0 * a0 + a1 * a1 + b0 * b0 + b1 * b1));
 }
 
-__device__ __forceinline__ bool es_inlier(const double* e, const double* __restrict__ xn, int p, float thr) {
-  const double* q = xn + (size_t)p * 4;
-  return es_error(e, q[0], q[1], q[2], q[3]) <= thr;   // false for NaN
-}
+// the model of ransac.h's frame: up to 10 candidates per 5-point sample, on the normalised pairs xn [n, 4]; the tail zeroes
+// info[4..7]
+struct EsModel {
+  static constexpr int MODEL = ES_MODEL, SLOTS = ES_SLOTS;
+  struct Points {
+    const double* __restrict__ xn;
+  };
+  struct Tail {
+    int32_t* info_tail;
+  };
+
+  static __device__ __forceinline__ bool inlier(const double* e, const Points& pts, int p, float thr) {
+    const double* q = pts.xn + (size_t)p * 4;
+    return es_error(e, q[0], q[1], q[2], q[3]) <= thr;   // false for NaN
+  }
+
+  static __device__ __forceinline__ void tail(const Tail& t, int) {
+    for (int i = 0; i < 4; ++i) t.info_tail[i] = 0;
+  }
+};
 
 // The least-squares depths (z1, z2) of z2 x2h = z1 a + t, a = R x1h, for t and for -t: in front iff both lie in (0, dist).
 // bit 0: (R, t), bit 1: (R, -t).  A zero determinant: in front of neither.
@@ -712,46 +685,6 @@ __global__ __launch_bounds__(ES_SOLVE_THREADS) void es_solve_kernel(const double
       for (int i = 0; i < 9; ++i) hyp_E[slot * 9 + i] = out[k * 9 + i];
     count[slot] = k < nc ? 0 : -1;
   }
-}
-
-__global__ __launch_bounds__(RS_COUNT_THREADS) void es_count_kernel(const double* __restrict__ xn, int n, const double* __restrict__ Ec,
-                                                                    int* __restrict__ count, float thr) {
-  const int slot = blockIdx.x;
-  if (count[slot] < 0) return;   // no candidate in this slot (uniform)
-  double e[9];
-  bool finite = true;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    e[i] = Ec[(size_t)slot * 9 + i];
-    finite = finite && isfinite(e[i]);
-  }
-  if (!finite) return;           // a non-finite candidate counts 0 inliers
-  const int base = blockIdx.y * RS_CHUNK;
-  int wc = 0;
-#pragma unroll
-  for (int s = 0; s < RS_COUNT_STEPS; ++s) {
-    const int p = base + s * RS_COUNT_THREADS + threadIdx.x;
-    const bool in = p < n && es_inlier(e, xn, p, thr);
-    wc += __popcll(__ballot(in));
-  }
-  if ((threadIdx.x & 63) == 0 && wc > 0) atomicAdd(&count[slot], wc);
-}
-
-__global__ __launch_bounds__(256) void es_mask_kernel(const double* __restrict__ xn, int n, const double* __restrict__ Ec,
-                                                      const int32_t* __restrict__ info, float thr, double* __restrict__ E_out,
-                                                      uint8_t* __restrict__ mask, int32_t* __restrict__ info_tail) {
-  const int found = info[0], slot = info[3];
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  double e[9];
-  bool finite = true;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    e[i] = found ? Ec[(size_t)slot * 9 + i] : 0.0;
-    finite = finite && isfinite(e[i]);
-  }
-  if (p < n) mask[p] = (found && finite && es_inlier(e, xn, p, thr)) ? 1 : 0;
-  if (p < 9) E_out[p] = e[p];
-  if (p < 4) info_tail[p] = 0;
 }
 
 // ---- kernels of cotr_recover_pose ---------------------------------------------------------------------------------------
@@ -874,26 +807,10 @@ __global__ __launch_bounds__(256) void es_pose_kernel(const double* __restrict__
 // ---- host side ------------------------------------------------------------------------------------------------------
 namespace {
 
-struct EsPlan {
-  size_t E, count, xn, bytes;
-  int chunks;
-};
+const RsEntry ES_ENTRY = {"cotr_ransac_essential", "E_out", ES_MODEL, "", ES_SLOTS, ES_MAX_ITERS};
 
-EsPlan es_plan(int n, int max_iters) {
-  EsPlan l;
-  l.chunks = (n + RS_CHUNK - 1) / RS_CHUNK;
-  l.E = 0;
-  l.count = align_up((size_t)max_iters * ES_SLOTS * 9 * sizeof(double));
-  l.xn = l.count + align_up((size_t)max_iters * ES_SLOTS * sizeof(int));
-  l.bytes = l.xn + align_up((size_t)n * 4 * sizeof(double));
-  return l;
-}
-
-const char* es_check_shape(int n, int max_iters) {
-  if (n < ES_MODEL || n > RS_MAX_POINTS) return "cotr_ransac_essential: n must be in [5, 2^24]";
-  if (max_iters < 1 || max_iters > ES_MAX_ITERS) return "cotr_ransac_essential: max_iters must be in [1, 6553]";
-  return nullptr;
-}
+// after the frame's candidates and counts: the normalised pairs xn [n, 4]
+size_t es_scratch_bytes(const RsPlan& l, int n) { return l.bytes + align_up((size_t)n * 4 * sizeof(double)); }
 
 // the camera of an upper-triangular K (row-major 9 doubles, on the host); false unless fx and fy are finite and non-zero and
 // the rest is finite
@@ -908,46 +825,34 @@ bool es_camera(const double* K, EsCam* c) {
 extern "C" {
 
 int cotr_ransac_essential_scratch_bytes(int n, int max_iters, size_t* bytes) {
-  if (!bytes) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_essential_scratch_bytes: bytes is NULL");
-  if (const char* e = es_check_shape(n, max_iters)) return handleless_fail(COTR_ERR_ARG, e);
-  *bytes = es_plan(n, max_iters).bytes;
+  if (const int rc = rs_scratch_bytes(ES_ENTRY, n, max_iters, bytes)) return rc;
+  *bytes = es_scratch_bytes(rs_plan(ES_ENTRY, max_iters), n);
   return COTR_OK;
 }
 
 int cotr_ransac_essential(const double* pts1, const double* pts2, int n, const double* K1, const double* K2, double threshold,
                           double confidence, int max_iters, uint64_t seed, double* E_out, uint8_t* mask_out, int32_t* info_out,
                           double* hyp_E, int32_t* hyp_count, int32_t* hyp_samples, void* scratch, size_t scratch_bytes, cotr_stream stream) {
-  if (const char* e = es_check_shape(n, max_iters)) return handleless_fail(COTR_ERR_ARG, e);
-  if (!(threshold > 0.0) || !(threshold < INFINITY)) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_essential: threshold must be finite and > 0");
-  if (!(confidence > 0.0 && confidence < 1.0)) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_essential: confidence must be in (0, 1)");
-  if (!pts1 || !pts2 || !K1 || !K2 || !E_out || !mask_out || !info_out || !scratch)
-    return handleless_fail(COTR_ERR_ARG, "cotr_ransac_essential: pts1, pts2, K1, K2, E_out, mask_out, info_out and scratch must not be NULL");
+  const RsPlan l = rs_plan(ES_ENTRY, max_iters);
+  if (const int rc = rs_check_call(ES_ENTRY, n, max_iters, threshold, confidence, pts1, pts2, E_out, mask_out, info_out, hyp_E, hyp_count,
+                                   hyp_samples, scratch, scratch_bytes, es_scratch_bytes(l, n)))
+    return rc;
+  if (!K1 || !K2) return rs_fail(ES_ENTRY, "K1 and K2 must not be NULL");
   EsCam k1, k2;
-  if (!es_camera(K1, &k1) || !es_camera(K2, &k2))
-    return handleless_fail(COTR_ERR_ARG, "cotr_ransac_essential: the camera matrices must be finite with focal lengths that are not 0");
+  if (!es_camera(K1, &k1) || !es_camera(K2, &k2)) return rs_fail(ES_ENTRY, "the camera matrices must be finite with focal lengths that are not 0");
   const double focal = (k1.fx + k1.fy + k2.fx + k2.fy) / 4.0;
   const double thr = threshold / focal;
   if (!(thr * thr > 0.0) || !(thr * thr < INFINITY))
-    return handleless_fail(COTR_ERR_ARG, "cotr_ransac_essential: the threshold over the mean focal length must be finite and not 0");
-  if (!aligned(pts1, 8) || !aligned(pts2, 8) || !aligned(E_out, 8) || !aligned(info_out, 4) || !aligned(hyp_E, 8) || !aligned(hyp_count, 4) ||
-      !aligned(hyp_samples, 4) || !aligned(scratch, 16))
-    return handleless_fail(COTR_ERR_ARG, "cotr_ransac_essential: doubles must be 8-byte, ints 4-byte and scratch 16-byte aligned");
-  const EsPlan l = es_plan(n, max_iters);
-  if (scratch_bytes < l.bytes) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_essential: scratch is smaller than cotr_ransac_essential_scratch_bytes");
-  char* base = static_cast<char*>(scratch);
-  double* Ec = reinterpret_cast<double*>(base + l.E);
-  int* count = reinterpret_cast<int*>(base + l.count);
-  double* xn = reinterpret_cast<double*>(base + l.xn);
-  const float thr2 = (float)(thr * thr);
+    return rs_fail(ES_ENTRY, "the threshold over the mean focal length must be finite and not 0");
+  double* xn = reinterpret_cast<double*>(static_cast<char*>(scratch) + l.bytes);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(es_normalise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pts1, pts2, n, k1, k2, xn);
-  hipLaunchKernelGGL(es_solve_kernel, dim3((unsigned)((max_iters + ES_SOLVE_THREADS - 1) / ES_SOLVE_THREADS)), dim3(ES_SOLVE_THREADS), 0, s, xn, n,
-                     max_iters, seed, Ec, count, hyp_E, hyp_samples);
-  hipLaunchKernelGGL(es_count_kernel, dim3((unsigned)(max_iters * ES_SLOTS), (unsigned)l.chunks), dim3(RS_COUNT_THREADS), 0, s, xn, n, Ec, count,
-                     thr2);
-  hipLaunchKernelGGL((rs_select_kernel<ES_MODEL, ES_SLOTS>), dim3(1), dim3(RS_SELECT_THREADS), 0, s, count, max_iters, n, confidence, info_out,
-                     hyp_count);
-  hipLaunchKernelGGL(es_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xn, n, Ec, info_out, thr2, E_out, mask_out, info_out + 4);
+  const auto solve = [&](double* Ec, int* count) {
+    hipLaunchKernelGGL(es_solve_kernel, dim3((unsigned)((max_iters + ES_SOLVE_THREADS - 1) / ES_SOLVE_THREADS)), dim3(ES_SOLVE_THREADS), 0, s, xn, n,
+                       max_iters, seed, Ec, count, hyp_E, hyp_samples);
+  };
+  rs_enqueue<EsModel>(s, solve, {xn}, n, max_iters, confidence, (float)(thr * thr), l, scratch, E_out, mask_out, info_out, hyp_count,
+                      {info_out + 4});
   return launched();
 }
 

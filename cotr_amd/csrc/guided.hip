@@ -8,14 +8,12 @@
 //                         distance_matrix); NaN counts as the minimum, as in numpy's argmin
 //   2. nn_merge_kernel    one thread per query: lexicographic minimum of the split partials in split order (lowest j on ties)
 //   3. nn_mutual_kernel   mutual[i] = idx_ba[idx_ab[i]] == i
-// cotr_ransac_fundamental: four launches:
-//   1. rs_solve_kernel    one thread per iteration: counter-based sample of 7 distinct indices, Hartley normalisation,
-//                         null space of the 7x9 system by full-pivot elimination (in LDS), det cubic, up to 3 candidates
-//   2. rs_count_kernel    grid (3 * max_iters slots) x (2048-point chunks): symmetric epipolar error, ballot + popcount per
-//                         wavefront, one integer atomicAdd per wavefront (integer sums: deterministic)
-//   3. rs_select_kernel   one workgroup replays the sequential selection loop on the counts (ransac.h, shared with
-//                         homography.hip, as are the sampler and the iteration update)
-//   4. rs_mask_kernel     the chosen candidate's mask (same error code as 2) and F_out
+// cotr_ransac_fundamental: four launches, the last three those of ransac.h's frame on the model FmModel:
+//   1. fm_solve_kernel          one thread per iteration: counter-based sample of 7 distinct indices, Hartley normalisation,
+//                               null space of the 7x9 system by full-pivot elimination (in LDS), det cubic, up to 3 candidates
+//   2. rs_count_kernel<FmModel> grid (3 * max_iters slots) x (2048-point chunks): symmetric epipolar error
+//   3. rs_select_kernel<7, 3>   one workgroup replays the sequential selection loop on the counts
+//   4. rs_mask_kernel<FmModel>  the chosen candidate's mask (same error code as 2) and F_out
 // No host waits, no allocation: capturable.  Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -176,26 +174,34 @@ __device__ int cubic_roots(double c3, double c2, double c1, double c0, double* r
   return nr;
 }
 
-// the symmetric epipolar error of DESIGN.md 3h, operation order fixed (compiled without contraction)
-__device__ __forceinline__ bool is_inlier(const double* f, const double* __restrict__ pts1, const double* __restrict__ pts2, int p,
-                                          float thr) {
-  const double x = f32r(pts1[(size_t)p * 2]), y = f32r(pts1[(size_t)p * 2 + 1]);
-  const double u = f32r(pts2[(size_t)p * 2]), v = f32r(pts2[(size_t)p * 2 + 1]);
-  const double a = f[0] * x + f[1] * y + f[2];
-  const double b = f[3] * x + f[4] * y + f[5];
-  const double c = f[6] * x + f[7] * y + f[8];
-  const double d2 = u * a + v * b + c;
-  const double e2 = d2 * d2 / (a * a + b * b);
-  const double at = f[0] * u + f[3] * v + f[6];
-  const double bt = f[1] * u + f[4] * v + f[7];
-  const double ct = f[2] * u + f[5] * v + f[8];
-  const double d1 = x * at + y * bt + ct;
-  const double e1 = d1 * d1 / (at * at + bt * bt);
-  const float err = (float)(e1 < e2 ? e2 : e1);
-  return err <= thr;
-}
+// the model of ransac.h's frame: up to 3 candidates per 7-point sample, no tail
+struct FmModel {
+  static constexpr int MODEL = RS_MODEL, SLOTS = 3;
+  using Points = RsPixelPairs;
+  struct Tail {};
 
-__global__ __launch_bounds__(RS_SOLVE_THREADS) void rs_solve_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2,
+  // the symmetric epipolar error of DESIGN.md 3h, operation order fixed (compiled without contraction)
+  static __device__ __forceinline__ bool inlier(const double* f, const Points& pts, int p, float thr) {
+    const double x = f32r(pts.pts1[(size_t)p * 2]), y = f32r(pts.pts1[(size_t)p * 2 + 1]);
+    const double u = f32r(pts.pts2[(size_t)p * 2]), v = f32r(pts.pts2[(size_t)p * 2 + 1]);
+    const double a = f[0] * x + f[1] * y + f[2];
+    const double b = f[3] * x + f[4] * y + f[5];
+    const double c = f[6] * x + f[7] * y + f[8];
+    const double d2 = u * a + v * b + c;
+    const double e2 = d2 * d2 / (a * a + b * b);
+    const double at = f[0] * u + f[3] * v + f[6];
+    const double bt = f[1] * u + f[4] * v + f[7];
+    const double ct = f[2] * u + f[5] * v + f[8];
+    const double d1 = x * at + y * bt + ct;
+    const double e1 = d1 * d1 / (at * at + bt * bt);
+    const float err = (float)(e1 < e2 ? e2 : e1);
+    return err <= thr;
+  }
+
+  static __device__ __forceinline__ void tail(const Tail&, int) {}
+};
+
+__global__ __launch_bounds__(RS_SOLVE_THREADS) void fm_solve_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2,
                                                                     int n, int max_iters, uint64_t seed, double* __restrict__ F,
                                                                     int* __restrict__ count, double* __restrict__ hyp_F,
                                                                     int32_t* __restrict__ hyp_samples) {
@@ -217,76 +223,20 @@ __global__ __launch_bounds__(RS_SOLVE_THREADS) void rs_solve_kernel(const double
   int nr = 0;
   if (got == RS_MODEL) {
     // 2. Hartley normalisation of the 7 pairs (points rounded to float32 first)
-    double x1[RS_MODEL], y1[RS_MODEL], x2[RS_MODEL], y2[RS_MODEL];
-    double c1x = 0.0, c1y = 0.0, c2x = 0.0, c2y = 0.0;
-#pragma unroll
-    for (int k = 0; k < RS_MODEL; ++k) {
-      const int i = S_(k);
-      x1[k] = f32r(pts1[(size_t)i * 2]);
-      y1[k] = f32r(pts1[(size_t)i * 2 + 1]);
-      x2[k] = f32r(pts2[(size_t)i * 2]);
-      y2[k] = f32r(pts2[(size_t)i * 2 + 1]);
-      c1x += x1[k], c1y += y1[k], c2x += x2[k], c2y += y2[k];
-    }
-    c1x /= RS_MODEL, c1y /= RS_MODEL, c2x /= RS_MODEL, c2y /= RS_MODEL;
-    double m1 = 0.0, m2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < RS_MODEL; ++k) {
-      const double ax = x1[k] - c1x, ay = y1[k] - c1y, bx = x2[k] - c2x, by = y2[k] - c2y;
-      m1 += sqrt(ax * ax + ay * ay);
-      m2 += sqrt(bx * bx + by * by);
-    }
-    m1 /= RS_MODEL, m2 /= RS_MODEL;
-    bool ok = m1 > 0.0 && m2 > 0.0 && m1 < INFINITY && m2 < INFINITY;
-    const double s1 = M_SQRT2 / m1, s2 = M_SQRT2 / m2;
+    RsHartley<RS_MODEL> h;
+    bool ok = rs_hartley<RS_MODEL>(pts1, pts2, &shI[lane], RS_SOLVE_THREADS, h);
+    const double c1x = h.c1x, c1y = h.c1y, s1 = h.s1, c2x = h.c2x, c2y = h.c2y, s2 = h.s2;
     // 3. rows [x'x, x'y, x', y'x, y'y, y', x, y, 1] in normalised coordinates; full-pivot elimination
     if (ok) {
 #pragma unroll
       for (int k = 0; k < RS_MODEL; ++k) {
-        const double u1 = (x1[k] - c1x) * s1, v1 = (y1[k] - c1y) * s1;
-        const double u2 = (x2[k] - c2x) * s2, v2 = (y2[k] - c2y) * s2;
+        const double u1 = (h.x1[k] - c1x) * s1, v1 = (h.y1[k] - c1y) * s1;
+        const double u2 = (h.x2[k] - c2x) * s2, v2 = (h.y2[k] - c2y) * s2;
         A_(k, 0) = u2 * u1, A_(k, 1) = u2 * v1, A_(k, 2) = u2;
         A_(k, 3) = v2 * u1, A_(k, 4) = v2 * v1, A_(k, 5) = v2;
         A_(k, 6) = u1, A_(k, 7) = v1, A_(k, 8) = 1.0;
       }
-      for (int c = 0; c < 9; ++c) P_(c) = c;
-      double piv0 = 0.0;
-      for (int k = 0; k < RS_MODEL && ok; ++k) {
-        double pv = -1.0;
-        int pr = k, pc = k;
-        for (int r = k; r < RS_MODEL; ++r)
-          for (int c = k; c < 9; ++c) {
-            const double v = fabs(A_(r, c));
-            if (v > pv) pv = v, pr = r, pc = c;
-          }
-        if (k == 0) piv0 = pv;
-        if (!(pv > RS_RANK_TOL * piv0)) {   // also false for NaN
-          ok = false;
-          break;
-        }
-        if (pr != k)
-          for (int c = 0; c < 9; ++c) {
-            const double t = A_(k, c);
-            A_(k, c) = A_(pr, c);
-            A_(pr, c) = t;
-          }
-        if (pc != k) {
-          for (int r = 0; r < RS_MODEL; ++r) {
-            const double t = A_(r, k);
-            A_(r, k) = A_(r, pc);
-            A_(r, pc) = t;
-          }
-          const int t = P_(k);
-          P_(k) = P_(pc);
-          P_(pc) = t;
-        }
-        const double akk = A_(k, k);
-        for (int r = k + 1; r < RS_MODEL; ++r) {
-          const double m = A_(r, k) / akk;
-          for (int c = k + 1; c < 9; ++c) A_(r, c) = A_(r, c) - m * A_(k, c);
-          A_(r, k) = 0.0;
-        }
-      }
+      ok = rs_eliminate<RS_MODEL, 9, 9, RS_SOLVE_THREADS>(&shA[lane], &P_(0));
     }
     if (ok) {
       // 4. the null space: the two free (permuted) columns 7 and 8 set to unit vectors, back substitution
@@ -294,15 +244,7 @@ __global__ __launch_bounds__(RS_SOLVE_THREADS) void rs_solve_kernel(const double
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         double z[9];
-        z[7] = t == 0 ? 1.0 : 0.0;
-        z[8] = t == 0 ? 0.0 : 1.0;
-#pragma unroll
-        for (int r = RS_MODEL - 1; r >= 0; --r) {
-          double acc = 0.0;
-#pragma unroll
-          for (int c = r + 1; c < 9; ++c) acc += A_(r, c) * z[c];
-          z[r] = -acc / A_(r, r);
-        }
+        rs_null_vector<RS_MODEL, 9, RS_SOLVE_THREADS>(&shA[lane], RS_MODEL + t, z);
 #pragma unroll
         for (int c = 0; c < 9; ++c) shF[(t * 9 + P_(c)) * RS_SOLVE_THREADS + lane] = z[c];
       }
@@ -344,27 +286,7 @@ __global__ __launch_bounds__(RS_SOLVE_THREADS) void rs_solve_kernel(const double
           Fk[1 * 3 + c] = s2 * gm[1 * 3 + c];
           Fk[2 * 3 + c] = (-s2 * c2x) * gm[0 * 3 + c] + (-s2 * c2y) * gm[1 * 3 + c] + gm[2 * 3 + c];
         }
-        double ss = 0.0;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) ss += Fk[i] * Fk[i];
-        const double nrm = sqrt(ss);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) Fk[i] = Fk[i] / nrm;
-        if (fabs(Fk[8]) > DBL_EPSILON) {
-          const double f22 = Fk[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) Fk[i] = Fk[i] / f22;
-          Fk[8] = 1.0;
-        } else {
-          double big = Fk[0];   // the first entry of largest magnitude
-#pragma unroll
-          for (int i = 1; i < 9; ++i)
-            if (fabs(Fk[i]) > fabs(big)) big = Fk[i];
-          if (big < 0.0) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) Fk[i] = -Fk[i];
-          }
-        }
+        rs_scale9(Fk);
         const size_t slot = (size_t)it * 3 + k;
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
@@ -387,41 +309,6 @@ __global__ __launch_bounds__(RS_SOLVE_THREADS) void rs_solve_kernel(const double
     }
     count[slot] = -1;
   }
-}
-
-__global__ __launch_bounds__(RS_COUNT_THREADS) void rs_count_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2, int n,
-                                                                    const double* __restrict__ F, int* __restrict__ count, float thr) {
-  const int slot = blockIdx.x;
-  if (count[slot] < 0) return;   // no candidate in this slot (uniform)
-  double f[9];
-  bool finite = true;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    f[i] = F[(size_t)slot * 9 + i];
-    finite = finite && isfinite(f[i]);
-  }
-  if (!finite) return;           // a non-finite candidate counts 0 inliers
-  const int base = blockIdx.y * RS_CHUNK;
-  int wc = 0;
-#pragma unroll
-  for (int s = 0; s < RS_COUNT_STEPS; ++s) {
-    const int p = base + s * RS_COUNT_THREADS + threadIdx.x;
-    const bool in = p < n && is_inlier(f, pts1, pts2, p, thr);
-    wc += __popcll(__ballot(in));
-  }
-  if ((threadIdx.x & 63) == 0 && wc > 0) atomicAdd(&count[slot], wc);
-}
-
-__global__ __launch_bounds__(256) void rs_mask_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2, int n,
-                                                      const double* __restrict__ F, const int32_t* __restrict__ info, float thr,
-                                                      double* __restrict__ F_out, uint8_t* __restrict__ mask) {
-  const int found = info[0], slot = info[3];
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  double f[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) f[i] = found ? F[(size_t)slot * 9 + i] : 0.0;
-  if (p < n) mask[p] = (found && is_inlier(f, pts1, pts2, p, thr)) ? 1 : 0;
-  if (p < 9) F_out[p] = found ? F[(size_t)slot * 9 + p] : 0.0;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -457,24 +344,8 @@ const char* nn_check_shape(int na, int nb) {
   return nullptr;
 }
 
-struct RsPlan {
-  size_t F, count, bytes;
-};
-
-RsPlan rs_plan(int max_iters) {
-  RsPlan l;
-  const size_t slots = (size_t)3 * max_iters;
-  l.F = 0;
-  l.count = align_up(slots * 9 * sizeof(double));
-  l.bytes = l.count + align_up(slots * sizeof(int));
-  return l;
-}
-
-const char* rs_check_shape(int n, int max_iters) {
-  if (n < 15 || n > RS_MAX_POINTS) return "n must be in [15, 2^24] (the 7-point LMedS fallback below 15 points is not provided)";
-  if (max_iters < 1 || max_iters > RS_MAX_ITERS) return "max_iters must be in [1, 65536]";
-  return nullptr;
-}
+const RsEntry FM_ENTRY = {"cotr_ransac_fundamental", "F_out", 15, " (the 7-point LMedS fallback below 15 points is not provided)", FmModel::SLOTS,
+                          RS_MAX_ITERS};
 
 }  // namespace
 
@@ -511,38 +382,22 @@ int cotr_nearest_mutual(const double* pred_ab, const double* kp_b, const double*
   return launched();
 }
 
-int cotr_ransac_fundamental_scratch_bytes(int n, int max_iters, size_t* bytes) {
-  if (!bytes) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_fundamental_scratch_bytes: bytes is NULL");
-  if (const char* e = rs_check_shape(n, max_iters)) return handleless_fail(COTR_ERR_ARG, e);
-  *bytes = rs_plan(max_iters).bytes;
-  return COTR_OK;
-}
+int cotr_ransac_fundamental_scratch_bytes(int n, int max_iters, size_t* bytes) { return rs_scratch_bytes(FM_ENTRY, n, max_iters, bytes); }
 
 int cotr_ransac_fundamental(const double* pts1, const double* pts2, int n, double threshold, double confidence, int max_iters,
                             uint64_t seed, double* F_out, uint8_t* mask_out, int32_t* info_out, double* hyp_F, int32_t* hyp_count,
                             int32_t* hyp_samples, void* scratch, size_t scratch_bytes, cotr_stream stream) {
-  if (const char* e = rs_check_shape(n, max_iters)) return handleless_fail(COTR_ERR_ARG, e);
-  if (!(threshold > 0.0) || !(threshold < INFINITY)) return handleless_fail(COTR_ERR_ARG, "threshold must be finite and > 0");
-  if (!(confidence > 0.0 && confidence < 1.0)) return handleless_fail(COTR_ERR_ARG, "confidence must be in (0, 1)");
-  if (!pts1 || !pts2 || !F_out || !mask_out || !info_out || !scratch)
-    return handleless_fail(COTR_ERR_ARG, "cotr_ransac_fundamental: pts1, pts2, F_out, mask_out, info_out and scratch must not be NULL");
-  if (!aligned(pts1, 8) || !aligned(pts2, 8) || !aligned(F_out, 8) || !aligned(info_out, 4) || !aligned(hyp_F, 8) ||
-      !aligned(hyp_count, 4) || !aligned(hyp_samples, 4) || !aligned(scratch, 16))
-    return handleless_fail(COTR_ERR_ARG, "cotr_ransac_fundamental: doubles must be 8-byte, ints 4-byte and scratch 16-byte aligned");
-  const RsPlan l = rs_plan(max_iters);
-  if (scratch_bytes < l.bytes) return handleless_fail(COTR_ERR_ARG, "scratch is smaller than cotr_ransac_fundamental_scratch_bytes");
-  char* base = static_cast<char*>(scratch);
-  double* F = reinterpret_cast<double*>(base + l.F);
-  int* count = reinterpret_cast<int*>(base + l.count);
-  const float thr = (float)(threshold * threshold);
+  const RsPlan l = rs_plan(FM_ENTRY, max_iters);
+  if (const int rc = rs_check_call(FM_ENTRY, n, max_iters, threshold, confidence, pts1, pts2, F_out, mask_out, info_out, hyp_F, hyp_count,
+                                   hyp_samples, scratch, scratch_bytes, l.bytes))
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rs_solve_kernel, dim3((unsigned)((max_iters + RS_SOLVE_THREADS - 1) / RS_SOLVE_THREADS)), dim3(RS_SOLVE_THREADS), 0, s,
-                     pts1, pts2, n, max_iters, seed, F, count, hyp_F, hyp_samples);
-  hipLaunchKernelGGL(rs_count_kernel, dim3((unsigned)(3 * max_iters), (unsigned)((n + RS_CHUNK - 1) / RS_CHUNK)), dim3(RS_COUNT_THREADS), 0,
-                     s, pts1, pts2, n, F, count, thr);
-  hipLaunchKernelGGL((rs_select_kernel<RS_MODEL, 3>), dim3(1), dim3(RS_SELECT_THREADS), 0, s, count, max_iters, n, confidence, info_out, hyp_count);
-  hipLaunchKernelGGL(rs_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pts1, pts2, n, F, info_out, thr, F_out, mask_out);
+  const auto solve = [&](double* F, int* count) {
+    hipLaunchKernelGGL(fm_solve_kernel, dim3((unsigned)((max_iters + RS_SOLVE_THREADS - 1) / RS_SOLVE_THREADS)), dim3(RS_SOLVE_THREADS), 0, s,
+                       pts1, pts2, n, max_iters, seed, F, count, hyp_F, hyp_samples);
+  };
+  rs_enqueue<FmModel>(s, solve, {pts1, pts2}, n, max_iters, confidence, (float)(threshold * threshold), l, scratch, F_out, mask_out, info_out,
+                      hyp_count, {});
   return launched();
 }
-
 }  // extern "C"

@@ -2,12 +2,12 @@
 // Rules in DESIGN.md 3h-2.  H maps pts1 to pts2: [u, v, 1]^T ~ H [x, y, 1]^T.
 //
 // cotr_ransac_homography: 4 + 2 * (3 + refine_iters + 1) launches on the caller's stream (4 + 2 * 3 with refine_iters = 0):
-//   1. hg_solve_kernel    one thread per iteration: counter-based sample of 4 distinct indices (ransac.h), cv2's checkSubset,
-//                         Hartley normalisation, the 8x8 system of get_perspective_transform by full-pivot elimination (LDS)
-//   2. hg_count_kernel    grid (max_iters slots) x (2048-point chunks): transfer error, ballot + popcount per wavefront, one
-//                         integer atomicAdd per wavefront
-//   3. rs_select_kernel   the sequential selection loop replayed on the counts (ransac.h), model size 4, one slot per iteration
-//   4. hg_mask_kernel     the chosen candidate's mask, H_ransac, and the refit's state
+//   1. hg_solve_kernel          one thread per iteration: counter-based sample of 4 distinct indices, cv2's checkSubset, Hartley
+//                               normalisation, the 8x8 system of get_perspective_transform by full-pivot elimination (LDS)
+//   2. rs_count_kernel<HgModel> grid (max_iters slots) x (2048-point chunks): transfer error
+//   3. rs_select_kernel<4, 1>   the sequential selection loop replayed on the counts
+//   4. rs_mask_kernel<HgModel>  the chosen candidate's mask, H_ransac, and (the model's tail) the refit's state
+//      (2 - 4: ransac.h's frame on the model HgModel, as are the sampler, the normalisation and the elimination of 1)
 //   5. the refit chain, pairs of hg_accum_kernel<STAGE> (per 2048-point chunk: up to 45 sums over the mask, every thread
 //      over its points in order, every wavefront in a fixed tree, the 4 wavefronts in order -> scratch) and
 //      hg_finish_kernel (one workgroup: the chunks in chunk order, then the stage's small serial problem):
@@ -35,7 +35,7 @@ using namespace cotr_detail;
 
 enum { HG_CENTROID = 0, HG_DISTANCE = 1, HG_DLT = 2, HG_GN = 3 };
 
-// the refit's state, in scratch; written by hg_mask_kernel (done, status, kept) and the finish kernels
+// the refit's state, in scratch; written by the mask kernel's tail (done, status, kept, trial) and by the finish kernels
 struct HgState {
   double c1x, c1y, s1, c2x, c2y, s2;   // T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]] of each point set
   double cnt;                          // number of inliers, as a sum over the mask
@@ -48,82 +48,34 @@ struct HgState {
   int trial;                           // h is a step whose error is not known yet
 };
 
-// ---- the error -----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float hg_error(const double* h, double x, double y, double u, double v) {
-  const double w = 1.0 / (h[6] * x + h[7] * y + h[8]);
-  const double dx = (h[0] * x + h[1] * y + h[2]) * w - u;
-  const double dy = (h[3] * x + h[4] * y + h[5]) * w - v;
-  return (float)(dx * dx + dy * dy);
-}
+// ---- the model of ransac.h's frame: one candidate per 4-point sample; the tail starts the refit's state -------------------
+struct HgModel {
+  static constexpr int MODEL = HG_MODEL, SLOTS = 1;
+  using Points = RsPixelPairs;
+  struct Tail {
+    HgState* st;
+  };
 
-__device__ __forceinline__ bool hg_inlier(const double* h, const double* __restrict__ pts1, const double* __restrict__ pts2, int p, float thr) {
-  const double x = f32r(pts1[(size_t)p * 2]), y = f32r(pts1[(size_t)p * 2 + 1]);
-  const double u = f32r(pts2[(size_t)p * 2]), v = f32r(pts2[(size_t)p * 2 + 1]);
-  return hg_error(h, x, y, u, v) <= thr;   // false for NaN
-}
+  static __device__ __forceinline__ float error(const double* h, double x, double y, double u, double v) {
+    const double w = 1.0 / (h[6] * x + h[7] * y + h[8]);
+    const double dx = (h[0] * x + h[1] * y + h[2]) * w - u;
+    const double dy = (h[3] * x + h[4] * y + h[5]) * w - v;
+    return (float)(dx * dx + dy * dy);
+  }
 
-// ---- 8x8 full-pivot solve ------------------------------------------------------------------------------------------
-// a: the augmented 8 x 9 system, entry (r, c) at a[(r * 9 + c) * STRIDE]; perm: 8 ints at perm[c * STRIDE] -> z[8] with
-// A z = b.  false when a pivot falls below RS_RANK_TOL times the first one (or is NaN).
-template <int STRIDE>
-__device__ bool hg_solve8(double* a, int* perm, double* z) {
-#define A_(r, c) a[((r) * 9 + (c)) * STRIDE]
-#define P_(c) perm[(c) * STRIDE]
-  for (int c = 0; c < 8; ++c) P_(c) = c;
-  double piv0 = 0.0;
-  for (int k = 0; k < 8; ++k) {
-    double pv = -1.0;
-    int pr = k, pc = k;
-    for (int r = k; r < 8; ++r)
-      for (int c = k; c < 8; ++c) {
-        const double v = fabs(A_(r, c));
-        if (v > pv) pv = v, pr = r, pc = c;
-      }
-    if (k == 0) piv0 = pv;
-    if (!(pv > RS_RANK_TOL * piv0)) return false;   // also for NaN
-    if (pr != k)
-      for (int c = 0; c < 9; ++c) {
-        const double t = A_(k, c);
-        A_(k, c) = A_(pr, c);
-        A_(pr, c) = t;
-      }
-    if (pc != k) {
-      for (int r = 0; r < 8; ++r) {
-        const double t = A_(r, k);
-        A_(r, k) = A_(r, pc);
-        A_(r, pc) = t;
-      }
-      const int t = P_(k);
-      P_(k) = P_(pc);
-      P_(pc) = t;
-    }
-    const double akk = A_(k, k);
-    for (int r = k + 1; r < 8; ++r) {
-      const double m = A_(r, k) / akk;
-      for (int c = k + 1; c < 9; ++c) A_(r, c) = A_(r, c) - m * A_(k, c);
-      A_(r, k) = 0.0;
-    }
+  static __device__ __forceinline__ bool inlier(const double* h, const Points& pts, int p, float thr) {
+    const double x = f32r(pts.pts1[(size_t)p * 2]), y = f32r(pts.pts1[(size_t)p * 2 + 1]);
+    const double u = f32r(pts.pts2[(size_t)p * 2]), v = f32r(pts.pts2[(size_t)p * 2 + 1]);
+    return error(h, x, y, u, v) <= thr;   // false for NaN
   }
-  double y[8];
-#pragma unroll
-  for (int r = 7; r >= 0; --r) {
-    double acc = A_(r, 8);
-#pragma unroll
-    for (int c = r + 1; c < 8; ++c) acc -= A_(r, c) * y[c];
-    y[r] = acc / A_(r, r);
+
+  static __device__ __forceinline__ void tail(const Tail& t, int found) {
+    t.st->done = found ? 0 : 1;
+    t.st->status = 2;
+    t.st->kept = 0;
+    t.st->trial = 0;
   }
-  // z[perm[c]] = y[c], without indexing registers at run time
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    double v = 0.0;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) v = P_(c) == i ? y[c] : v;
-    z[i] = v;
-  }
-#undef A_
-#undef P_
-  return true;
-}
+};
 
 // H = T2^-1 Hn T1
 __device__ __forceinline__ void hg_denormalise(const double* hn, double c1x, double c1y, double s1, double c2x, double c2y, double s2,
@@ -141,31 +93,6 @@ __device__ __forceinline__ void hg_denormalise(const double* hn, double c1x, dou
     H[0 * 3 + c] = i2 * gm[0 * 3 + c] + c2x * gm[2 * 3 + c];
     H[1 * 3 + c] = i2 * gm[1 * 3 + c] + c2y * gm[2 * 3 + c];
     H[2 * 3 + c] = gm[2 * 3 + c];
-  }
-}
-
-// unit Frobenius norm, then H[2,2] = 1 unless |H[2,2]| <= DBL_EPSILON (then: the first entry of largest magnitude positive)
-__device__ __forceinline__ void hg_scale(double* H) {
-  double ss = 0.0;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) ss += H[i] * H[i];
-  const double nrm = sqrt(ss);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) H[i] = H[i] / nrm;
-  if (fabs(H[8]) > DBL_EPSILON) {
-    const double h22 = H[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) H[i] = H[i] / h22;
-    H[8] = 1.0;
-  } else {
-    double big = H[0];
-#pragma unroll
-    for (int i = 1; i < 9; ++i)
-      if (fabs(H[i]) > fabs(big)) big = H[i];
-    if (big < 0.0) {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) H[i] = -H[i];
-    }
   }
 }
 
@@ -210,6 +137,8 @@ __global__ __launch_bounds__(RS_SOLVE_THREADS) void hg_solve_kernel(const double
   bool ok = got == HG_MODEL;
   double H[9];
   if (ok) {
+    // The sample's load and Hartley normalisation, rs_hartley<4> of ransac.h written out with checkSubset between the load
+    // and the centroids: through rs_hartley the kernel took 132 registers instead of 104 and the call measured slower.
     double x1[HG_MODEL], y1[HG_MODEL], x2[HG_MODEL], y2[HG_MODEL];
     double c1x = 0.0, c1y = 0.0, c2x = 0.0, c2y = 0.0;
 #pragma unroll
@@ -245,11 +174,11 @@ __global__ __launch_bounds__(RS_SOLVE_THREADS) void hg_solve_kernel(const double
         A_(k + 4, 6) = -(x * v), A_(k + 4, 7) = -(y * v), A_(k + 4, 8) = v;
       }
       double hn[9];
-      ok = hg_solve8<RS_SOLVE_THREADS>(&shA[lane], &shI[HG_MODEL * RS_SOLVE_THREADS + lane], hn);
+      ok = rs_solve<8, RS_SOLVE_THREADS>(&shA[lane], &shI[HG_MODEL * RS_SOLVE_THREADS + lane], hn);
       if (ok) {
         hn[8] = 1.0;
         hg_denormalise(hn, c1x, c1y, s1, c2x, c2y, s2, H);
-        hg_scale(H);
+        rs_scale9(H);
       }
     }
   }
@@ -262,47 +191,6 @@ __global__ __launch_bounds__(RS_SOLVE_THREADS) void hg_solve_kernel(const double
     if (hyp_H) hyp_H[(size_t)it * 9 + i] = v;
   }
   count[it] = ok ? 0 : -1;
-}
-
-__global__ __launch_bounds__(RS_COUNT_THREADS) void hg_count_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2, int n,
-                                                                    const double* __restrict__ Hc, int* __restrict__ count, float thr) {
-  const int slot = blockIdx.x;
-  if (count[slot] < 0) return;   // no candidate in this slot (uniform)
-  double h[9];
-  bool finite = true;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    h[i] = Hc[(size_t)slot * 9 + i];
-    finite = finite && isfinite(h[i]);
-  }
-  if (!finite) return;           // a non-finite candidate counts 0 inliers
-  const int base = blockIdx.y * RS_CHUNK;
-  int wc = 0;
-#pragma unroll
-  for (int s = 0; s < RS_COUNT_STEPS; ++s) {
-    const int p = base + s * RS_COUNT_THREADS + threadIdx.x;
-    const bool in = p < n && hg_inlier(h, pts1, pts2, p, thr);
-    wc += __popcll(__ballot(in));
-  }
-  if ((threadIdx.x & 63) == 0 && wc > 0) atomicAdd(&count[slot], wc);
-}
-
-__global__ __launch_bounds__(256) void hg_mask_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2, int n,
-                                                      const double* __restrict__ Hc, const int32_t* __restrict__ info, float thr,
-                                                      double* __restrict__ H_ransac, uint8_t* __restrict__ mask, HgState* __restrict__ st) {
-  const int found = info[0], slot = info[3];
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  double h[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) h[i] = found ? Hc[(size_t)slot * 9 + i] : 0.0;
-  if (p < n) mask[p] = (found && hg_inlier(h, pts1, pts2, p, thr)) ? 1 : 0;
-  if (p < 9 && H_ransac) H_ransac[p] = found ? Hc[(size_t)slot * 9 + p] : 0.0;
-  if (p == 0) {
-    st->done = found ? 0 : 1;
-    st->status = 2;
-    st->kept = 0;
-    st->trial = 0;
-  }
 }
 
 // ---- the refit -----------------------------------------------------------------------------------------------------
@@ -471,7 +359,7 @@ __global__ __launch_bounds__(64) void hg_finish_kernel(int stage, int chunks, in
           S8[i * 9 + 8] = -sums[36 + i];
         }
         double d[8];
-        if (hg_solve8<1>(S8, P8, d)) {
+        if (rs_solve<8, 1>(S8, P8, d)) {
           for (int i = 0; i < 9; ++i) st->hprev[i] = st->h[i];
           st->err_prev = err;
           for (int i = 0; i < 8; ++i) st->h[i] = st->h[i] + d[i];
@@ -492,7 +380,7 @@ __global__ __launch_bounds__(64) void hg_finish_kernel(int stage, int chunks, in
       for (int i = 0; i < 9; ++i) H[i] = Hc[(size_t)info[3] * 9 + i];
     } else {
       hg_denormalise(st->h, st->c1x, st->c1y, st->s1, st->c2x, st->c2y, st->s2, H);
-      hg_scale(H);
+      rs_scale9(H);
     }
     for (int i = 0; i < 9; ++i) H_out[i] = H[i];
     info[4] = st->kept;
@@ -505,26 +393,23 @@ __global__ __launch_bounds__(64) void hg_finish_kernel(int stage, int chunks, in
 // ---- host side -----------------------------------------------------------------------------------------------------
 namespace {
 
+const RsEntry HG_ENTRY = {"cotr_ransac_homography", "H_out", HG_MODEL, "", HgModel::SLOTS, RS_MAX_ITERS};
+
+// after the frame's candidates and counts: the refit's state, then its partial sums [chunks, HG_SUMS]
 struct HgPlan {
-  size_t H, count, state, parts, bytes;
+  RsPlan rs;
+  size_t state, parts, bytes;
   int chunks;
 };
 
 HgPlan hg_plan(int n, int max_iters) {
   HgPlan l;
+  l.rs = rs_plan(HG_ENTRY, max_iters);
   l.chunks = (n + RS_CHUNK - 1) / RS_CHUNK;
-  l.H = 0;
-  l.count = align_up((size_t)max_iters * 9 * sizeof(double));
-  l.state = l.count + align_up((size_t)max_iters * sizeof(int));
+  l.state = l.rs.bytes;
   l.parts = l.state + align_up(sizeof(HgState));
   l.bytes = l.parts + align_up((size_t)l.chunks * HG_SUMS * sizeof(double));
   return l;
-}
-
-const char* hg_check_shape(int n, int max_iters) {
-  if (n < HG_MODEL || n > RS_MAX_POINTS) return "cotr_ransac_homography: n must be in [4, 2^24]";
-  if (max_iters < 1 || max_iters > RS_MAX_ITERS) return "cotr_ransac_homography: max_iters must be in [1, 65536]";
-  return nullptr;
 }
 
 template <int STAGE>
@@ -539,8 +424,7 @@ void hg_pair(hipStream_t s, const HgPlan& l, int last, const double* pts1, const
 extern "C" {
 
 int cotr_ransac_homography_scratch_bytes(int n, int max_iters, size_t* bytes) {
-  if (!bytes) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography_scratch_bytes: bytes is NULL");
-  if (const char* e = hg_check_shape(n, max_iters)) return handleless_fail(COTR_ERR_ARG, e);
+  if (const int rc = rs_scratch_bytes(HG_ENTRY, n, max_iters, bytes)) return rc;
   *bytes = hg_plan(n, max_iters).bytes;
   return COTR_OK;
 }
@@ -549,32 +433,23 @@ int cotr_ransac_homography(const double* pts1, const double* pts2, int n, double
                            int refine_iters, uint64_t seed, double* H_out, uint8_t* mask_out, int32_t* info_out, double* H_ransac,
                            double* hyp_H, int32_t* hyp_count, int32_t* hyp_samples, void* scratch, size_t scratch_bytes,
                            cotr_stream stream) {
-  if (const char* e = hg_check_shape(n, max_iters)) return handleless_fail(COTR_ERR_ARG, e);
-  if (refine_iters < 0 || refine_iters > HG_MAX_REFINE) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: refine_iters must be in [0, 64]");
-  if (!(threshold > 0.0) || !(threshold < INFINITY)) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: threshold must be finite and > 0");
-  if (!(confidence > 0.0 && confidence < 1.0)) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: confidence must be in (0, 1)");
-  if (!pts1 || !pts2 || !H_out || !mask_out || !info_out || !scratch)
-    return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: pts1, pts2, H_out, mask_out, info_out and scratch must not be NULL");
-  if (!aligned(pts1, 8) || !aligned(pts2, 8) || !aligned(H_out, 8) || !aligned(info_out, 4) || !aligned(H_ransac, 8) ||
-      !aligned(hyp_H, 8) || !aligned(hyp_count, 4) || !aligned(hyp_samples, 4) || !aligned(scratch, 16))
-    return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: doubles must be 8-byte, ints 4-byte and scratch 16-byte aligned");
   const HgPlan l = hg_plan(n, max_iters);
-  if (scratch_bytes < l.bytes) return handleless_fail(COTR_ERR_ARG, "cotr_ransac_homography: scratch is smaller than cotr_ransac_homography_scratch_bytes");
+  if (const int rc = rs_check_call(HG_ENTRY, n, max_iters, threshold, confidence, pts1, pts2, H_out, mask_out, info_out, hyp_H, hyp_count,
+                                   hyp_samples, scratch, scratch_bytes, l.bytes))
+    return rc;
+  if (refine_iters < 0 || refine_iters > HG_MAX_REFINE) return rs_fail(HG_ENTRY, "refine_iters must be in [0, 64]");
+  if (!aligned(H_ransac, 8)) return rs_fail(HG_ENTRY, "H_ransac must be 8-byte aligned");
   char* base = static_cast<char*>(scratch);
-  double* Hc = reinterpret_cast<double*>(base + l.H);
-  int* count = reinterpret_cast<int*>(base + l.count);
+  const double* Hc = reinterpret_cast<const double*>(base + l.rs.candidates);
   HgState* st = reinterpret_cast<HgState*>(base + l.state);
   double* parts = reinterpret_cast<double*>(base + l.parts);
-  const float thr = (float)(threshold * threshold);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(hg_solve_kernel, dim3((unsigned)((max_iters + RS_SOLVE_THREADS - 1) / RS_SOLVE_THREADS)), dim3(RS_SOLVE_THREADS), 0, s,
-                     pts1, pts2, n, max_iters, seed, Hc, count, hyp_H, hyp_samples);
-  hipLaunchKernelGGL(hg_count_kernel, dim3((unsigned)max_iters, (unsigned)l.chunks), dim3(RS_COUNT_THREADS), 0, s, pts1, pts2, n, Hc, count,
-                     thr);
-  hipLaunchKernelGGL((rs_select_kernel<HG_MODEL, 1>), dim3(1), dim3(RS_SELECT_THREADS), 0, s, count, max_iters, n, confidence, info_out,
-                     hyp_count);
-  hipLaunchKernelGGL(hg_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pts1, pts2, n, Hc, info_out, thr, H_ransac, mask_out,
-                     st);
+  const auto solve = [&](double* cand, int* count) {
+    hipLaunchKernelGGL(hg_solve_kernel, dim3((unsigned)((max_iters + RS_SOLVE_THREADS - 1) / RS_SOLVE_THREADS)), dim3(RS_SOLVE_THREADS), 0, s,
+                       pts1, pts2, n, max_iters, seed, cand, count, hyp_H, hyp_samples);
+  };
+  rs_enqueue<HgModel>(s, solve, {pts1, pts2}, n, max_iters, confidence, (float)(threshold * threshold), l.rs, scratch, H_ransac, mask_out,
+                      info_out, hyp_count, {st});
   hg_pair<HG_CENTROID>(s, l, 0, pts1, pts2, n, mask_out, st, parts, Hc, H_out, info_out);
   hg_pair<HG_DISTANCE>(s, l, 0, pts1, pts2, n, mask_out, st, parts, Hc, H_out, info_out);
   // refine_iters = 0: the DLT's finish is the last launch (status 1); else pair j judges step j - 1 and takes step j
@@ -582,5 +457,4 @@ int cotr_ransac_homography(const double* pts1, const double* pts2, int n, double
   for (int j = 0; refine_iters > 0 && j <= refine_iters; ++j) hg_pair<HG_GN>(s, l, j == refine_iters, pts1, pts2, n, mask_out, st, parts, Hc, H_out, info_out);
   return launched();
 }
-
 }  // extern "C"

@@ -16,7 +16,8 @@ import torch
 
 from .. import _lib
 from .._lib import check_op, on, ptr
-from .guided import _device, _points
+from . import _ransac
+from ._ransac import _device
 
 MAX_ITERS = 6553
 _K9 = ctypes.c_double * 9
@@ -33,44 +34,22 @@ def _camera(K, what):
 
 
 def _pairs(points1, points2):
-    p1, p2 = _points(points1, 'points1'), _points(points2, 'points2')
-    n = p1.shape[0]
-    if p2.shape[0] != n:
-        raise ValueError(f'points1 and points2 must have the same length, got {n} and {p2.shape[0]}')
-    if n < 5:
-        raise ValueError(f'an essential matrix needs at least 5 correspondences, got {n}')
-    if n > 1 << 24:
-        raise ValueError(f'at most 2^24 correspondences, got {n}')
-    return p1, p2, n
+    return _ransac.pairs(points1, points2, 5, 'an essential matrix needs at least 5 correspondences')
 
 
 def _check_ransac(K1, K2, threshold, confidence, max_iters):
-    if not 1 <= max_iters <= MAX_ITERS:
-        raise ValueError(f'max_iters must be in [1, {MAX_ITERS}], got {max_iters}')
-    if not (threshold > 0 and np.isfinite(threshold)):
-        raise ValueError(f'the RANSAC threshold must be finite and > 0, got {threshold}')
-    if not 0 < confidence < 1:
-        raise ValueError(f'confidence must be in (0, 1), got {confidence}')
+    _ransac.check_ransac(threshold, confidence, max_iters, MAX_ITERS)
     thr = threshold / ((K1[0] + K1[4] + K2[0] + K2[4]) / 4.0) if (K1[0] + K1[4] + K2[0] + K2[4]) != 0 else np.inf
     if not (thr * thr > 0 and np.isfinite(thr * thr)):
         raise ValueError('the RANSAC threshold over the mean focal length must be finite and not 0')
 
 
 def _enqueue_essential(lib, p1, p2, n, k1, k2, threshold, confidence, max_iters, seed, hypotheses, device):
-    nbytes = ctypes.c_size_t()
-    check_op(lib.cotr_ransac_essential_scratch_bytes(n, max_iters, ctypes.byref(nbytes)), 'cotr_ransac_essential_scratch_bytes')
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    E = torch.empty(9, dtype=torch.float64, device=device)
-    mask = torch.empty(n, dtype=torch.uint8, device=device)
-    info = torch.empty(8, dtype=torch.int32, device=device)
-    out = dict(info=info)
-    if hypotheses:
-        out.update(samples=torch.empty((max_iters, 5), dtype=torch.int32, device=device),
-                   hyp_E=torch.empty((10 * max_iters, 9), dtype=torch.float64, device=device),
-                   hyp_count=torch.empty(10 * max_iters, dtype=torch.int32, device=device))
+    scratch, E, mask, out = _ransac.outputs(lib.cotr_ransac_essential_scratch_bytes, 'cotr_ransac_essential_scratch_bytes', n,
+                                            max_iters, 5, 10, 8, 'hyp_E', hypotheses, device)
     check_op(lib.cotr_ransac_essential(ptr(p1), ptr(p2), n, k1, k2, float(threshold), float(confidence), int(max_iters),
-                                       int(seed) & ((1 << 64) - 1), ptr(E), ptr(mask), ptr(info), ptr(out.get('hyp_E')),
-                                       ptr(out.get('hyp_count')), ptr(out.get('samples')), ptr(scratch), nbytes.value,
+                                       _ransac.seed64(seed), ptr(E), ptr(mask), ptr(out['info']), ptr(out.get('hyp_E')),
+                                       ptr(out.get('hyp_count')), ptr(out.get('samples')), ptr(scratch), scratch.numel(),
                                        _lib.current_stream_ptr()), 'cotr_ransac_essential')
     out['E'] = E.view(3, 3)
     out['mask_u8'] = mask

@@ -13,18 +13,8 @@ import torch
 
 from .. import _lib
 from .._lib import check_op, on, ptr
-
-
-def _device(device):
-    return torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-
-
-def _points(p, what):
-    """[N,2] float64 tensor, where it was (float32 input is widened exactly)"""
-    t = p if torch.is_tensor(p) else torch.from_numpy(np.ascontiguousarray(np.asarray(p, dtype=np.float64)))
-    if t.dim() != 2 or t.shape[1] != 2:
-        raise ValueError(f'{what} must be [N, 2], got shape {tuple(t.shape)}')
-    return t.to(dtype=torch.float64)
+from . import _ransac
+from ._ransac import _device, _points
 
 
 def nearest_mutual(pred_ab, kp_b, pred_ba, kp_a, device=None):
@@ -71,37 +61,18 @@ def ransac_fundamental(points1, points2, threshold=3.0, confidence=0.99, max_ite
     """One ``cotr_ransac_fundamental`` call on the current stream -> dict of device tensors: F float64 [3,3], mask bool [n],
     info int32 [4] = (found, best count, iterations run, chosen slot); with hypotheses=True also samples int32
     [max_iters, 7], hyp_F float64 [3*max_iters, 9] and hyp_count int32 [3*max_iters] (the tables tests check)."""
-    p1, p2 = _points(points1, 'points1'), _points(points2, 'points2')
-    n = p1.shape[0]
-    if p2.shape[0] != n:
-        raise ValueError(f'points1 and points2 must have the same length, got {n} and {p2.shape[0]}')
-    if n < 15:
-        raise ValueError(f'find_fundamental_mat needs at least 15 correspondences for RANSAC, got {n} '
-                         '(cv2\'s 7-point / LMedS fallback below 15 points is not provided)')
-    if not 1 <= max_iters <= 1 << 16:
-        raise ValueError(f'max_iters must be in [1, 65536], got {max_iters}')
-    if not (threshold > 0 and np.isfinite(threshold)):
-        raise ValueError(f'the RANSAC threshold must be finite and > 0, got {threshold}')
-    if not 0 < confidence < 1:
-        raise ValueError(f'confidence must be in (0, 1), got {confidence}')
+    p1, p2, n = _ransac.pairs(points1, points2, 15, 'find_fundamental_mat needs at least 15 correspondences for RANSAC '
+                              '(cv2\'s 7-point / LMedS fallback below 15 points is not provided)')
+    _ransac.check_ransac(threshold, confidence, max_iters)
     device = _device(device)
     p1, p2 = on(p1, device), on(p2, device)
     lib = _lib.load_library()
-    nbytes = ctypes.c_size_t()
-    check_op(lib.cotr_ransac_fundamental_scratch_bytes(n, max_iters, ctypes.byref(nbytes)), 'cotr_ransac_fundamental_scratch_bytes')
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    F = torch.empty(9, dtype=torch.float64, device=device)
-    mask = torch.empty(n, dtype=torch.uint8, device=device)
-    info = torch.empty(4, dtype=torch.int32, device=device)
-    out = dict(F=F, info=info)
-    if hypotheses:
-        out.update(samples=torch.empty((max_iters, 7), dtype=torch.int32, device=device),
-                   hyp_F=torch.empty((3 * max_iters, 9), dtype=torch.float64, device=device),
-                   hyp_count=torch.empty(3 * max_iters, dtype=torch.int32, device=device))
+    scratch, F, mask, out = _ransac.outputs(lib.cotr_ransac_fundamental_scratch_bytes, 'cotr_ransac_fundamental_scratch_bytes', n,
+                                            max_iters, 7, 3, 4, 'hyp_F', hypotheses, device)
     with torch.cuda.device(device):
         check_op(lib.cotr_ransac_fundamental(ptr(p1), ptr(p2), n, float(threshold), float(confidence), int(max_iters),
-                                             int(seed) & ((1 << 64) - 1), ptr(F), ptr(mask), ptr(info), ptr(out.get('hyp_F')),
-                                             ptr(out.get('hyp_count')), ptr(out.get('samples')), ptr(scratch), nbytes.value,
+                                             _ransac.seed64(seed), ptr(F), ptr(mask), ptr(out['info']), ptr(out.get('hyp_F')),
+                                             ptr(out.get('hyp_count')), ptr(out.get('samples')), ptr(scratch), scratch.numel(),
                                              _lib.current_stream_ptr()), 'cotr_ransac_fundamental')
     out['F'] = F.view(3, 3)
     out['mask'] = mask.bool()

@@ -6,14 +6,13 @@ library's own: they follow the structure of OpenCV's estimator 
 check, adaptive iteration count, a refit on the inliers of the best sample, the mask staying the RANSAC mask - with the
 F path's counter-based sampler, and claim no bit-compatibility with it.  ``paste_by_homography`` is the robust form of
 ``paste_by_corners`` (demo_homography.py from any number of correspondences).  No CPU fallback."""
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib
 from .._lib import check_op, on, ptr
-from .guided import _device, _points
+from . import _ransac
+from ._ransac import _device
 
 MAX_REFINE = 64
 
@@ -25,42 +24,21 @@ def ransac_homography(points1, points2, threshold=3.0, confidence=0.995, max_ite
     info int32 [8] = (found, best count, iterations run, chosen slot, Gauss-Newton steps kept, refit status: 0 DLT +
     refinement, 1 DLT only, 2 none, 0, 0); with hypotheses=True also samples int32 [max_iters, 4], hyp_H float64
     [max_iters, 9] and hyp_count int32 [max_iters] (the tables tests check).  Nothing found: H = 0, mask = 0, info[0] = 0."""
-    p1, p2 = _points(points1, 'points1'), _points(points2, 'points2')
-    n = p1.shape[0]
-    if p2.shape[0] != n:
-        raise ValueError(f'points1 and points2 must have the same length, got {n} and {p2.shape[0]}')
-    if n < 4:
-        raise ValueError(f'a homography needs at least 4 correspondences, got {n}')
-    if n > 1 << 24:
-        raise ValueError(f'at most 2^24 correspondences, got {n}')
-    if not 1 <= max_iters <= 1 << 16:
-        raise ValueError(f'max_iters must be in [1, 65536], got {max_iters}')
+    p1, p2, n = _ransac.pairs(points1, points2, 4, 'a homography needs at least 4 correspondences')
+    _ransac.check_ransac(threshold, confidence, max_iters)
     if not 0 <= refine_iters <= MAX_REFINE:
         raise ValueError(f'refine_iters must be in [0, {MAX_REFINE}], got {refine_iters}')
-    if not (threshold > 0 and np.isfinite(threshold)):
-        raise ValueError(f'the RANSAC threshold must be finite and > 0, got {threshold}')
-    if not 0 < confidence < 1:
-        raise ValueError(f'confidence must be in (0, 1), got {confidence}')
     device = _device(device)
     p1, p2 = on(p1, device), on(p2, device)
     lib = _lib.load_library()
-    nbytes = ctypes.c_size_t()
-    check_op(lib.cotr_ransac_homography_scratch_bytes(n, max_iters, ctypes.byref(nbytes)), 'cotr_ransac_homography_scratch_bytes')
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    H = torch.empty(9, dtype=torch.float64, device=device)
+    scratch, H, mask, out = _ransac.outputs(lib.cotr_ransac_homography_scratch_bytes, 'cotr_ransac_homography_scratch_bytes', n,
+                                            max_iters, 4, 1, 8, 'hyp_H', hypotheses, device)
     H_ransac = torch.empty(9, dtype=torch.float64, device=device)
-    mask = torch.empty(n, dtype=torch.uint8, device=device)
-    info = torch.empty(8, dtype=torch.int32, device=device)
-    out = dict(info=info)
-    if hypotheses:
-        out.update(samples=torch.empty((max_iters, 4), dtype=torch.int32, device=device),
-                   hyp_H=torch.empty((max_iters, 9), dtype=torch.float64, device=device),
-                   hyp_count=torch.empty(max_iters, dtype=torch.int32, device=device))
     with torch.cuda.device(device):
         check_op(lib.cotr_ransac_homography(ptr(p1), ptr(p2), n, float(threshold), float(confidence), int(max_iters), int(refine_iters),
-                                            int(seed) & ((1 << 64) - 1), ptr(H), ptr(mask), ptr(info), ptr(H_ransac),
+                                            _ransac.seed64(seed), ptr(H), ptr(mask), ptr(out['info']), ptr(H_ransac),
                                             ptr(out.get('hyp_H')), ptr(out.get('hyp_count')), ptr(out.get('samples')), ptr(scratch),
-                                            nbytes.value, _lib.current_stream_ptr()), 'cotr_ransac_homography')
+                                            scratch.numel(), _lib.current_stream_ptr()), 'cotr_ransac_homography')
     out['H'] = H.view(3, 3)
     out['H_ransac'] = H_ransac.view(3, 3)
     out['mask'] = mask.bool()
@@ -69,12 +47,7 @@ def ransac_homography(points1, points2, threshold=3.0, confidence=0.995, max_ite
 
 def _check_ransac_kw(ransac_reproj_threshold=3.0, max_iters=2000, confidence=0.995, seed=0):
     """``find_homography``'s keywords, checked as ``ransac_homography`` checks them (an unknown one: TypeError)"""
-    if not 1 <= max_iters <= 1 << 16:
-        raise ValueError(f'max_iters must be in [1, 65536], got {max_iters}')
-    if not (ransac_reproj_threshold > 0 and np.isfinite(ransac_reproj_threshold)):
-        raise ValueError(f'the RANSAC threshold must be finite and > 0, got {ransac_reproj_threshold}')
-    if not 0 < confidence < 1:
-        raise ValueError(f'confidence must be in (0, 1), got {confidence}')
+    _ransac.check_ransac(ransac_reproj_threshold, confidence, max_iters)
     int(seed)
 
 

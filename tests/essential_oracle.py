@@ -8,14 +8,12 @@ import functools
 
 import numpy as np
 
-from tests.guided_oracle import DBL_EPSILON, RANK_TOL, f32, update
-from tests.guided_oracle import samples as _samples7
-from tests.homography_oracle import solve_full_pivot
+from tests import ransac_oracle as ro
+from tests.ransac_oracle import JACOBI_SWEEPS, RANK_TOL, f32, jacobi, solve_full_pivot  # noqa: F401
 
 MODEL = 5
 SLOTS = 10
 POLISH = 3
-JACOBI_SWEEPS = 30
 MAX_ITERS = 6553
 # exponents (x, y, z) of the 20 columns: the ten cubic monomials, then x2 xy y2 xz yz z2 x y z 1
 MON = [(3, 0, 0), (2, 1, 0), (1, 2, 0), (0, 3, 0), (2, 0, 1), (1, 1, 1), (0, 2, 1), (1, 0, 2), (0, 1, 2), (0, 0, 3),
@@ -39,7 +37,7 @@ def scaled_threshold(threshold, K1, K2):
 
 def samples(n, max_iters, seed):
     """[max_iters, 5] int64: the first 5 distinct indices of the F path's 64 draws of every iteration, -1 past them"""
-    return _samples7(n, max_iters, seed)[:, :MODEL]
+    return ro.samples(n, max_iters, seed, MODEL)
 
 
 # ---- five-point solver ----------------------------------------------------------------------------------------------------
@@ -208,14 +206,7 @@ def inliers(E, xn1, xn2, thr):
 
 def counts(E, has, xn1, xn2, thr, rows=256):
     """-1 for a slot without a candidate, 0 for a non-finite candidate"""
-    E = np.asarray(E, np.float64)
-    out = np.zeros(len(E), np.int64)
-    finite = np.isfinite(E).all(axis=1)
-    for r in range(0, len(E), rows):
-        out[r:r + rows] = inliers(E[r:r + rows], xn1, xn2, thr).sum(axis=1)
-    out[~finite] = 0
-    out[~np.asarray(has, bool)] = -1
-    return out
+    return ro.counts(E, has, lambda Ec: inliers(Ec, xn1, xn2, thr), rows)
 
 
 def slots_used(nc):
@@ -224,36 +215,14 @@ def slots_used(nc):
 
 
 # ---- selection ------------------------------------------------------------------------------------------------------------
-# The loops of guided_oracle / homography_oracle with their model size (7, 4) and slots per iteration (3, 1) made 5 and 10;
-# both modules fix those as constants, so the loop is written out here on their `update`.
 def select_sequential(cnt, max_iters, n, confidence):
     """the RANSAC loop written out: -> (found, best, iterations run, chosen slot)"""
-    niters, best, chosen, it = max_iters, 0, -1, 0
-    while it < niters:
-        for k in range(SLOTS):
-            c = int(cnt[SLOTS * it + k])
-            if c > max(best, MODEL - 1):
-                best, chosen = c, SLOTS * it + k
-                niters = update(confidence, (n - best) / n, MODEL, niters)
-        it += 1
-    return int(chosen >= 0), best, it, chosen
+    return ro.select_sequential(cnt, max_iters, n, confidence, MODEL, SLOTS)
 
 
 def select(cnt, max_iters, n, confidence):
     """the same rule as the device replays it"""
-    cnt = np.asarray(cnt)
-    pos, best, niters, chosen = 0, 0, max_iters, -1
-    while True:
-        limit = SLOTS * max(niters, chosen // SLOTS + 1 if chosen >= 0 else 0)
-        hit = np.flatnonzero(cnt[pos:limit] > max(best, MODEL - 1))
-        if not len(hit):
-            break
-        chosen = pos + int(hit[0])
-        best = int(cnt[chosen])
-        niters = update(confidence, (n - best) / n, MODEL, niters)
-        pos = chosen + 1
-    runs = max(niters, chosen // SLOTS + 1) if chosen >= 0 else max_iters
-    return int(chosen >= 0), best, runs, chosen
+    return ro.select(cnt, max_iters, n, confidence, MODEL, SLOTS)
 
 
 def ransac(pts1, pts2, K1, K2=None, threshold=1.0, confidence=0.999, max_iters=1000, seed=0, var='x'):
@@ -272,34 +241,6 @@ def ransac(pts1, pts2, K1, K2=None, threshold=1.0, confidence=0.999, max_iters=1
 
 
 # ---- the pose of an essential matrix --------------------------------------------------------------------------------------
-def jacobi(A, sweeps=JACOBI_SWEEPS):
-    """cyclic Jacobi on the symmetric A, the device's rotations -> (diagonal, V): the loop of homography_oracle's
-    jacobi_smallest, which returns one column only"""
-    a = np.array(A, np.float64)
-    n = len(a)
-    v = np.eye(n)
-    for _ in range(sweeps):
-        sq = a * a
-        if not np.sqrt(sq[~np.eye(n, dtype=bool)].sum()) >= DBL_EPSILON * np.sqrt(sq.sum()):
-            break
-        for p in range(n - 1):
-            for q in range(p + 1, n):
-                if a[p, q] == 0.0:
-                    continue
-                with np.errstate(over='ignore'):
-                    theta = (a[q, q] - a[p, p]) / (2.0 * a[p, q])
-                    t = np.copysign(1.0, theta) / (abs(theta) + np.sqrt(theta * theta + 1.0))
-                c = 1.0 / np.sqrt(t * t + 1.0)
-                s = t * c
-                ap, aq = a[:, p].copy(), a[:, q].copy()
-                a[:, p], a[:, q] = c * ap - s * aq, s * ap + c * aq
-                ap, aq = a[p].copy(), a[q].copy()
-                a[p], a[q] = c * ap - s * aq, s * ap + c * aq
-                vp, vq = v[:, p].copy(), v[:, q].copy()
-                v[:, p], v[:, q] = c * vp - s * vq, s * vp + c * vq
-    return np.diag(a).copy(), v
-
-
 def decompose(E):
     """-> (U, V, R1, R2, t) or None: V from Jacobi on E^T E with the column of the smallest eigenvalue last and the other two
     in their order; U = E v / sigma for the two leading columns, their cross product for the third; V's last column signed so

@@ -5,12 +5,11 @@ import math
 
 import numpy as np
 
+from tests import ransac_oracle as ro
+from tests.ransac_oracle import DBL_EPSILON, DBL_MIN, M64, MAX_DRAWS, RANK_TOL, f32, splitmix64, update  # noqa: F401
+
 MODEL = 7
-MAX_DRAWS = 64
-RANK_TOL = 1e-12
-DBL_EPSILON = np.finfo(np.float64).eps
-DBL_MIN = np.finfo(np.float64).tiny
-M64 = (1 << 64) - 1
+SLOTS = 3
 
 
 # ---- nearest keypoint and the mutual check ------------------------------------------------------------------------------
@@ -51,31 +50,9 @@ def demo_double_loop(idx_ab, idx_ba):
 
 
 # ---- sampler --------------------------------------------------------------------------------------------------------------
-def splitmix64(x):
-    """splitmix64 on uint64 arrays (wrapping arithmetic)"""
-    x = np.asarray(x, dtype=np.uint64)
-    with np.errstate(over='ignore'):
-        z = x + np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return z ^ (z >> np.uint64(31))
-
-
 def samples(n, max_iters, seed):
-    """[max_iters, 7] int64: draw d of iteration it is (splitmix64(splitmix64(seed) ^ (it << 6 | d)) >> 32) % n; a duplicate
-    is rejected; -1 past the indices drawn when 64 draws give fewer than 7 distinct ones"""
-    sk = splitmix64(np.uint64(seed & M64))
-    it = np.arange(max_iters, dtype=np.uint64)[:, None]
-    d = np.arange(MAX_DRAWS, dtype=np.uint64)[None, :]
-    z = splitmix64(sk ^ ((it << np.uint64(6)) | d))
-    c = ((z >> np.uint64(32)) % np.uint64(n)).astype(np.int64)                    # [it, 64]
-    earlier = np.tril(np.ones((MAX_DRAWS, MAX_DRAWS), bool), -1)                  # earlier[d, e]: e < d
-    dup = ((c[:, :, None] == c[:, None, :]) & earlier[None]).any(axis=2)
-    out = np.full((max_iters, MODEL), -1, np.int64)
-    for i in range(max_iters):
-        first = c[i][~dup[i]][:MODEL]
-        out[i, :len(first)] = first
-    return out
+    """[max_iters, 7] int64: the first 7 distinct indices of the 64 draws of every iteration, -1 past them"""
+    return ro.samples(n, max_iters, seed, MODEL)
 
 
 # ---- 7-point solver -------------------------------------------------------------------------------------------------------
@@ -171,10 +148,6 @@ def candidates(pts1, pts2, smp):
     return H
 
 
-def f32(p):
-    return np.asarray(p, np.float64).astype(np.float32).astype(np.float64)
-
-
 # ---- error, count ---------------------------------------------------------------------------------------------------------
 def errors(F, pts1, pts2):
     """float32 [H, n] symmetric epipolar errors of the candidates F [H, 9], in the device's operation order"""
@@ -203,55 +176,18 @@ def inliers(F, pts1, pts2, threshold):
 def counts(H, pts1, pts2, threshold, rows=256):
     """inlier counts of the slot table H [S, 9]: -1 for an empty (all-NaN) slot, 0 for any other non-finite candidate"""
     H = np.asarray(H, np.float64)
-    out = np.zeros(len(H), np.int64)
-    empty = np.isnan(H).all(axis=1)
-    finite = np.isfinite(H).all(axis=1)
-    for r in range(0, len(H), rows):
-        out[r:r + rows] = inliers(H[r:r + rows], pts1, pts2, threshold).sum(axis=1)
-    out[~finite] = 0
-    out[empty] = -1
-    return out
+    return ro.counts(H, ~np.isnan(H).all(axis=1), lambda F: inliers(F, pts1, pts2, threshold), rows)
 
 
-# ---- iteration update and selection ---------------------------------------------------------------------------------------
-def update(p, ep, m, N):
-    """OpenCV's RANSACUpdateNumIters"""
-    num = math.log(max(1.0 - p, DBL_MIN))
-    denom = 1.0 - math.pow(1.0 - ep, m)
-    if denom < DBL_MIN:
-        return 0
-    lden = math.log(denom)
-    return N if (lden >= 0 or -num >= N * (-lden)) else int(np.rint(num / lden))
-
-
+# ---- selection (the iteration update is ransac_oracle's) ------------------------------------------------------------------
 def select_sequential(cnt, max_iters, n, confidence):
     """the FM_RANSAC loop written out: -> (found, best, iterations run, chosen slot)"""
-    niters, best, chosen, it = max_iters, 0, -1, 0
-    while it < niters:
-        for k in range(3):
-            c = int(cnt[3 * it + k])
-            if c > max(best, MODEL - 1):
-                best, chosen = c, 3 * it + k
-                niters = update(confidence, (n - best) / n, MODEL, niters)
-        it += 1
-    return int(chosen >= 0), best, it, chosen
+    return ro.select_sequential(cnt, max_iters, n, confidence, MODEL, SLOTS)
 
 
 def select(cnt, max_iters, n, confidence):
     """the same rule as the device replays it: jump to the next slot that beats max(best, 6) within the iterations left"""
-    cnt = np.asarray(cnt)
-    pos, best, niters, chosen = 0, 0, max_iters, -1
-    while True:
-        limit = 3 * max(niters, chosen // 3 + 1 if chosen >= 0 else 0)
-        hit = np.flatnonzero(cnt[pos:limit] > max(best, MODEL - 1))
-        if not len(hit):
-            break
-        chosen = pos + int(hit[0])
-        best = int(cnt[chosen])
-        niters = update(confidence, (n - best) / n, MODEL, niters)
-        pos = chosen + 1
-    runs = max(niters, chosen // 3 + 1) if chosen >= 0 else max_iters
-    return int(chosen >= 0), best, runs, chosen
+    return ro.select(cnt, max_iters, n, confidence, MODEL, SLOTS)
 
 
 def ransac(pts1, pts2, threshold, confidence, max_iters, seed):
@@ -297,3 +233,13 @@ def two_view_scene(n, outlier_frac, seed, noise=0.5, size=(640, 480)):
     Kinv = np.linalg.inv(K)
     F = Kinv.T @ tx @ R @ Kinv
     return p1, p2, ~out, F / F[2, 2]
+
+
+# ---- the edge cases the tests use -----------------------------------------------------------------------------------------
+# (n, outlier share, threshold, confidence, max_iters, seed = scene seed): the wavefront, chunk (2048 points) and
+# solve-workgroup (64 iterations) edges, n and max_iters paired as homography_oracle.EDGES pairs them, from the 15 points the
+# estimator starts at.  Seeds chosen on the CPU so that the restatement finds a model wherever max_iters >= 63
+# (tests/test_guided_cpu.py checks it).
+EDGES = [(15, 0.0, 3.0, 0.99, 1, 0), (15, 0.0, 3.0, 0.99, 63, 0), (63, 0.3, 3.0, 0.99, 64, 0), (65, 0.3, 3.0, 0.99, 65, 0),
+         (2047, 0.4, 3.0, 0.99, 63, 0), (2049, 0.4, 3.0, 0.99, 65, 0), (5000, 0.3, 3.0, 0.99, 1, 0),
+         (5000, 0.3, 3.0, 0.99, 63, 0)]

@@ -4,29 +4,20 @@ sequential selection, and the refit on the inliers (DLT by cyclic Jacobi, Gauss-
 numpy only.  Test infrastructure."""
 import numpy as np
 
-from tests.guided_oracle import DBL_EPSILON, M64, MAX_DRAWS, RANK_TOL, f32, splitmix64, update
+from tests import ransac_oracle as ro
+from tests.ransac_oracle import DBL_EPSILON, JACOBI_SWEEPS, f32, solve_full_pivot  # noqa: F401
 
 MODEL = 4
+SLOTS = 1
 FLT_EPSILON = float(np.finfo(np.float32).eps)
 H22_TOL = 1e-12
-JACOBI_SWEEPS = 30
 TRIPLES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))
 
 
 # ---- sampler --------------------------------------------------------------------------------------------------------------
 def samples(n, max_iters, seed):
     """[max_iters, 4] int64: the first 4 distinct indices of the F path's 64 draws of every iteration, -1 past them"""
-    sk = splitmix64(np.uint64(seed & M64))
-    it = np.arange(max_iters, dtype=np.uint64)[:, None]
-    d = np.arange(MAX_DRAWS, dtype=np.uint64)[None, :]
-    z = splitmix64(sk ^ ((it << np.uint64(6)) | d))
-    c = ((z >> np.uint64(32)) % np.uint64(n)).astype(np.int64)
-    out = np.full((max_iters, MODEL), -1, np.int64)
-    for i in range(max_iters):
-        _, first = np.unique(c[i], return_index=True)
-        keep = c[i][np.sort(first)][:MODEL]
-        out[i, :len(keep)] = keep
-    return out
+    return ro.samples(n, max_iters, seed, MODEL)
 
 
 # ---- degenerate samples ---------------------------------------------------------------------------------------------------
@@ -49,41 +40,6 @@ def sample_ok(p1, p2):
 
 
 # ---- 4-point solver -------------------------------------------------------------------------------------------------------
-def solve_full_pivot(A, b):
-    """A z = b by the device's full-pivot elimination; None when a pivot falls below RANK_TOL times the first one.  As on the
-    device, the pivot scan passes over NaN entries (no comparison with a NaN holds) and takes the largest of the others"""
-    n = len(b)
-    M = np.concatenate([np.array(A, np.float64), np.array(b, np.float64)[:, None]], axis=1)
-    perm = list(range(n))
-    piv0 = 0.0
-    for k in range(n):
-        sub = np.abs(M[k:, k:n])
-        sub = np.where(np.isnan(sub), -1.0, sub)
-        pv = sub.max()
-        if k == 0:
-            piv0 = pv
-        if not pv > RANK_TOL * piv0:
-            return None
-        pr, pc = np.unravel_index(np.argmax(sub), sub.shape)     # first maximum in row-major order, as the device's scan
-        pr, pc = pr + k, pc + k
-        M[[k, pr]] = M[[pr, k]]
-        M[:, [k, pc]] = M[:, [pc, k]]
-        perm[k], perm[pc] = perm[pc], perm[k]
-        for r in range(k + 1, n):
-            m = M[r, k] / M[k, k]
-            M[r, k + 1:] = M[r, k + 1:] - m * M[k, k + 1:]
-            M[r, k] = 0.0
-    y = np.zeros(n)
-    for r in range(n - 1, -1, -1):
-        acc = M[r, n]
-        for c in range(r + 1, n):
-            acc -= M[r, c] * y[c]
-        y[r] = acc / M[r, r]
-    z = np.zeros(n)
-    z[perm] = y
-    return z
-
-
 def solve_numpy(A, b):
     try:
         return np.linalg.solve(A, b)
@@ -177,73 +133,25 @@ def inliers(H, pts1, pts2, threshold):
 
 def counts(H, has_model, pts1, pts2, threshold, rows=256):
     """-1 for a slot without a model, 0 for a non-finite candidate"""
-    H = np.asarray(H, np.float64)
-    out = np.zeros(len(H), np.int64)
-    empty = ~np.asarray(has_model, bool)
-    finite = np.isfinite(H).all(axis=1)
-    for r in range(0, len(H), rows):
-        out[r:r + rows] = inliers(H[r:r + rows], pts1, pts2, threshold).sum(axis=1)
-    out[~finite] = 0
-    out[empty] = -1
-    return out
+    return ro.counts(H, has_model, lambda Hc: inliers(Hc, pts1, pts2, threshold), rows)
 
 
 # ---- selection ------------------------------------------------------------------------------------------------------------
 def select_sequential(cnt, max_iters, n, confidence):
     """the RANSAC loop written out: -> (found, best, iterations run, chosen slot)"""
-    niters, best, chosen, it = max_iters, 0, -1, 0
-    while it < niters:
-        c = int(cnt[it])
-        if c > max(best, MODEL - 1):
-            best, chosen = c, it
-            niters = update(confidence, (n - best) / n, MODEL, niters)
-        it += 1
-    return int(chosen >= 0), best, it, chosen
+    return ro.select_sequential(cnt, max_iters, n, confidence, MODEL, SLOTS)
 
 
 def select(cnt, max_iters, n, confidence):
     """the same rule as the device replays it"""
-    cnt = np.asarray(cnt)
-    pos, best, niters, chosen = 0, 0, max_iters, -1
-    while True:
-        limit = max(niters, chosen + 1 if chosen >= 0 else 0)
-        hit = np.flatnonzero(cnt[pos:limit] > max(best, MODEL - 1))
-        if not len(hit):
-            break
-        chosen = pos + int(hit[0])
-        best = int(cnt[chosen])
-        niters = update(confidence, (n - best) / n, MODEL, niters)
-        pos = chosen + 1
-    runs = max(niters, chosen + 1) if chosen >= 0 else max_iters
-    return int(chosen >= 0), best, runs, chosen
+    return ro.select(cnt, max_iters, n, confidence, MODEL, SLOTS)
 
 
 # ---- refit ----------------------------------------------------------------------------------------------------------------
 def jacobi_smallest(A, sweeps=JACOBI_SWEEPS):
     """the eigenvector of the smallest eigenvalue of the symmetric A by cyclic Jacobi, the device's rotations"""
-    a = np.array(A, np.float64)
-    n = len(a)
-    v = np.eye(n)
-    for _ in range(sweeps):
-        sq = a * a
-        if not np.sqrt(sq[~np.eye(n, dtype=bool)].sum()) >= DBL_EPSILON * np.sqrt(sq.sum()):
-            break
-        for p in range(n - 1):
-            for q in range(p + 1, n):
-                if a[p, q] == 0.0:
-                    continue
-                with np.errstate(over='ignore'):
-                    theta = (a[q, q] - a[p, p]) / (2.0 * a[p, q])
-                    t = np.copysign(1.0, theta) / (abs(theta) + np.sqrt(theta * theta + 1.0))
-                c = 1.0 / np.sqrt(t * t + 1.0)
-                s = t * c
-                ap, aq = a[:, p].copy(), a[:, q].copy()
-                a[:, p], a[:, q] = c * ap - s * aq, s * ap + c * aq
-                ap, aq = a[p].copy(), a[q].copy()
-                a[p], a[q] = c * ap - s * aq, s * ap + c * aq
-                vp, vq = v[:, p].copy(), v[:, q].copy()
-                v[:, p], v[:, q] = c * vp - s * vq, s * vp + c * vq
-    return v[:, int(np.argmin(np.diag(a)))]
+    lam, v = ro.jacobi(A, sweeps)
+    return v[:, int(np.argmin(lam))]
 
 
 def eigh_smallest(A):

@@ -156,6 +156,15 @@ def test_counts_of_empty_and_non_finite_slots():
     assert c[0] == -1 and c[1] == 0 and c[2] >= 7
 
 
+@pytest.mark.parametrize('n,outl,thr,conf,iters,seed', go.EDGES)
+def test_edge_scenes_find_a_model(n, outl, thr, conf, iters, seed):
+    p1, p2, _, _ = go.two_view_scene(n, outl, seed)
+    r = go.ransac(p1, p2, thr, conf, iters, seed)
+    assert len(p1) == n and r['samples'].shape == (iters, 7)
+    if iters >= 63:
+        assert r['info'][0] == 1 and r['info'][1] >= 7 and r['mask'].sum() == r['info'][1]
+
+
 # ---- the C ABI's argument checks ----------------------------------------------------------------------------------------
 def test_abi_argument_errors_without_a_gpu():
     lib = _lib.load_library()

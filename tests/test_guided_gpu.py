@@ -234,6 +234,24 @@ def test_ransac_every_stage_against_the_oracle(n, outl, thr, conf, iters, seed):
     assert tp / true_in.sum() >= 0.3, (tp, true_in.sum())
 
 
+@pytest.mark.parametrize('n,outl,thr,conf,iters,seed', go.EDGES)
+def test_ransac_wavefront_chunk_and_workgroup_edges(n, outl, thr, conf, iters, seed):
+    """the shared count and mask kernels on the fundamental model past one wavefront, one 2048-point chunk and one solve
+    workgroup: every stage exact against the restatement on the device's own candidates"""
+    p1, p2, _, _ = go.two_view_scene(n, outl, seed)
+    r = dev_ransac(p1, p2, thr, conf, iters, seed)
+    assert np.array_equal(r['samples'], go.samples(n, iters, seed))
+    dev_H = r['hyp_F']
+    cnt = go.counts(dev_H, p1, p2, thr)
+    assert np.array_equal(r['hyp_count'], cnt)
+    info = tuple(int(v) for v in r['info'])
+    assert info == go.select(cnt, iters, n, conf) == go.select_sequential(cnt, iters, n, conf)
+    found, best, runs, slot = info
+    assert np.array_equal(r['F'].reshape(9), dev_H[slot] if found else np.zeros(9))
+    want = go.inliers(dev_H[slot], p1, p2, thr)[0] if found else np.zeros(n, bool)
+    assert np.array_equal(r['mask'], want) and r['mask'].sum() == best
+
+
 def test_ransac_deterministic_across_calls_streams_and_scratch():
     p1, p2, _, _ = go.two_view_scene(1000, 0.4, 7)
     first = dev_ransac(p1, p2, 2.0, 0.999, 1500, 11)
