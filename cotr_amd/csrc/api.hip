@@ -31,6 +31,7 @@
 
 int init_attention_attributes();
 void set_ffn_debug_times(unsigned long long* p);  // ffn.hip
+void set_ffn_pipe_debug_times(unsigned long long* p);  // ffn_pipe.hip
 void set_attention_debug_times(unsigned long long* p);  // attention.hip
 
 namespace {
@@ -531,7 +532,7 @@ int ffn_block(cotr_ctx* h, const float* x, const float* l1w, const float* l1b, c
   if (post_w != nullptr || (ffn_fused_applies(M) && (size_t)ffn_fused_chunks(M) * M * D <= hid_cap)) {
     const int nch = ffn_fused_chunks(M);
     if ((size_t)nch * M * D > hid_cap) { h->err = "ffn_block: partial-output scratch too small"; return COTR_ERR_STATE; }
-    KCHK(h, launch_ffn_fused(x, l1w, l1b, l2w, hid, M, nch, s), "ffn_fused");
+    KCHK(h, launch_ffn_few_rows(x, l1w, l1b, l2w, hid, M, nch, s), "ffn_fused");
     if (h->prof >= 2) { char nm[64]; snprintf(nm, sizeof nm, "ffn_fused %d rows x%d", M, nch); prof_mark(h, nm, s, 2); }
     KCHK(h, launch_ln_reduce_post(hid, nch, l2b, x, nw, nb, post_w, post_b, y, M, s), "ln_reduce");
     prof_mark(h, post_w ? "ln_reduce +norm" : "ln_reduce", s, 2);
@@ -1937,10 +1938,12 @@ int cotr_op_conv_cfg(const float* x, const float* w, const float* scale, const f
 }
 
 // phase timestamps of the fused FFN launches that follow (device memory [workgroups][8], 100 MHz wall clock; slots: entry, loads
-// issued, first tile usable, H of sub-chunk 0 complete, phase 2 of sub-chunk 0 issued, second W1 usable, loop done, stored);
+// issued, first tile usable, H of sub-chunk 0 complete, phase 2 of sub-chunk 0 issued, second W1 usable, loop done, stored; the
+// pipelined form's slots 3 - 5 are H_0 written, phase 2 of H_0 issued, H_1 written);
 // nullptr = off.  tools/ffn_phases.py
 int cotr_debug_ffn_times(unsigned long long* times) {
   set_ffn_debug_times(times);
+  set_ffn_pipe_debug_times(times);
   return COTR_OK;
 }
 
@@ -2136,7 +2139,7 @@ int cotr_op_ffn_block(const float* x, const float* w1, const float* b1, const fl
                       const float* ln_b, float* scratch, float* y, int M, cotr_stream stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nch = ffn_fused_chunks(M);
-  int r = launch_ffn_fused(x, w1, b1, w2, scratch, M, nch, s);
+  int r = launch_ffn_few_rows(x, w1, b1, w2, scratch, M, nch, s);
   if (r == 0) r = launch_ln_reduce(scratch, nch, b2, x, ln_w, ln_b, y, M, s);
   return op_ret(r);
 }

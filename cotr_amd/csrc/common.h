@@ -367,6 +367,10 @@ int launch_resize_f32(const float* src, int Hs, int Ws, int C, float* dst, int H
 // fused feed-forward block (ffn.hip) and its reduce + bias + residual + LayerNorm tail (pointwise.hip)
 int ffn_fused_chunks(int M);
 int launch_ffn_fused(const float* X, const float* W1, const float* b1, const float* W2, float* P, int M, int nch, hipStream_t s);
+// ... in the form that serves the chunk count: ffn_fused_pipe_kernel (ffn_pipe.hip: the two phases on separate wavefronts, same bits) where
+// ffn_pipe_applies, ffn_fused_kernel otherwise
+bool ffn_pipe_applies(int nch);
+int launch_ffn_few_rows(const float* X, const float* W1, const float* b1, const float* W2, float* P, int M, int nch, hipStream_t s);
 int launch_ln_reduce_post(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
                           const float* post_w, const float* post_b, float* y, int rows, hipStream_t s);
 int launch_ln_reduce(const float* parts, int np, const float* bias, const float* residual, const float* w, const float* b,
