@@ -713,6 +713,26 @@ class ZoomEngine:
         R, t, mask = relative_pose(corrs[:, :2], corrs[:, 2:], K_a, K_b, **ransac_kw)
         return R, t, corrs, mask
 
+    def localize(self, cap_a, img_b, K_b, queries_a=None, zoom_ins=np.linspace(0.5, 0.0625, 4), converge_iters=1, max_corrs=1000,
+                 **ransac_kw):
+        """The metric pose of image B against the posed RGB-D capture ``cap_a`` (a ``cotr_amd.data.Capture``: image, depth, K,
+        c2w): ``cotr_corr_multiscale`` from the capture's image into B (from ``queries_a`` [N, 2] with force=True, or from the
+        engine's own grid when None), then ``localize`` on them: the correspondences' pixels in A lifted through the depth map
+        and pose of A, P3P RANSAC and its refit with the camera matrix ``K_b`` [3,3] -> (c2w_b float64 [4,4] in the world frame
+        of ``cap_a``, corrs [K, 4], mask uint8 [K, 1]: the inliers); c2w_b and mask are None when no pose is found.
+        ``ransac_kw``: threshold (8.0), confidence (0.99), max_iters (100), seed (0), refine_iters (10).  Fewer than 4
+        correspondences: ValueError."""
+        from .pnp import localize
+        if queries_a is None:
+            corrs = self.cotr_corr_multiscale(cap_a.image, img_b, zoom_ins, converge_iters, max_corrs=max_corrs)
+        else:
+            queries_a = np.asarray(queries_a)
+            corrs = self.cotr_corr_multiscale(cap_a.image, img_b, zoom_ins, converge_iters, max_corrs=max_corrs, queries_a=queries_a,
+                                              force=True)
+        corrs = np.asarray(corrs)
+        c2w_b, mask = localize(corrs[:, :2], corrs[:, 2:], cap_a, K_b, **ransac_kw)
+        return c2w_b, corrs, mask
+
     @staticmethod
     def _task_objects(shape_a, shape_b, loc_from, loc_to, ident, area_a, area_b, zoom_ins, converge_iters, results, executed,
                       with_ident):

@@ -550,6 +550,47 @@ int cotr_recover_pose(const double* E, const double* pts1, const double* pts2, i
                       double distance_thresh, const uint8_t* mask_in, const int32_t* found, double* R_out, double* t_out,
                       uint8_t* mask_out, int32_t* info_out, void* scratch, size_t scratch_bytes, cotr_stream stream);
 
+/* ---- absolute pose: P3P RANSAC with a refit, and the lift of pixels through a depth map (cotr_amd/csrc/pnp.hip) ----------
+ * The structure of cv2.solvePnPRansac(object, image, K, None, flags=cv2.SOLVEPNP_P3P) on the device, by rules of the
+ * library's own (no bit-compatibility with OpenCV is claimed).  x_cam = R X + t.
+ *
+ * K: HOST pointer to 9 doubles, a row-major upper-triangular camera matrix (fx, skew, cx; 0, fy, cy; 0, 0, 1; only those
+ *   five entries are read), finite, fx and fy not 0.
+ * cotr_lift_pixels: depth [H,W] float32, points [n,2] float64 (x, y) in pixels, c2w [16] float64 row-major or NULL: DEVICE
+ *   pointers -> out [n,3] float64.  The depth z is read at (rint(x), rint(y)) (ties to even); a point whose rounded index
+ *   lies outside the map, or whose depth is not finite and > 0, gets three NaN.  Otherwise yn = (y - cy) / fy,
+ *   xn = (x - cx - skew yn) / fx, X = (xn z, yn z, z), and with c2w its rows 0..2 applied to (X, 1).  1 <= n <= 2^24,
+ *   H W <= 2^28.  One launch.
+ * cotr_ransac_pnp: object_points [n,3], image_points [n,2] float64 DEVICE pointers (the image points rounded to float32
+ *   first) -> R_out [9] (row-major), t_out [3] float64, mask_out [n] uint8 (the RANSAC inliers of the chosen candidate;
+ *   not re-evaluated after the refit), info_out [8] int32 = {found, best inlier count, sequential iterations run, chosen
+ *   slot (-1: none), refit steps kept, 0, 0, 0}; R_out = 0, t_out = 0, mask_out = 0 when nothing is found.  Iteration it
+ *   draws 4 distinct indices with the sampler of cotr_ransac_fundamental and solves P3P on the first three in sample order
+ *   (Grunert's quartic in the depth ratio v = s2 / s0, its roots in (0, 1e8) in ascending order, three Newton steps on the
+ *   three distance equations, three positive depths, the rigid motion of the two triangles; a solution must re-project the
+ *   three points within 1e-9 px); of the solutions with the fourth point in front of the camera the one with the smallest
+ *   squared reprojection error there is the candidate (the first of equal ones).  No candidate: a short draw, a NaN among
+ *   the four points, the three object points on a line, no solution.  A candidate is 9 doubles: rows 1 and 2 of R, then
+ *   t; row 3 is their cross product.  The candidates are counted in parallel and the sequential RANSAC loop is replayed
+ *   on the counts.  An inlier lies in front of the camera (z > 0) with float(squared reprojection error) <=
+ *   float(threshold^2); a NaN object point never is one.  refine_iters > 0: up to that many Gauss-Newton steps on the
+ *   inliers (R <- exp([w]x) R, t <- t + dt), each kept only if the summed squared error falls and every inlier stays in
+ *   front; the first step not kept ends the refinement.  4 <= n <= 2^24, 1 <= max_iters <= 65536, threshold > 0 finite,
+ *   0 < confidence < 1, 0 <= refine_iters <= 64.
+ *   hyp_pose [max_iters][9] float64, hyp_count [max_iters] int32 (-1: no candidate; its entries are NaN), hyp_samples
+ *   [max_iters][4] int32 (-1 past the indices drawn): optional DEVICE outputs (NULL: not written).
+ *   scratch: DEVICE, 16-byte aligned, at least cotr_ransac_pnp_scratch_bytes(n, max_iters) bytes.
+ * Stream-ordered, 4 + 2 (refine_iters + 1) launches (4 with refine_iters = 0) whatever the data, no host waits and no
+ * allocation (capturable); integer atomics only, sums in a fixed order: the same input gives the same bits.  Bad arguments
+ * are checked before any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_lift_pixels(const float* depth, int H, int W, const double* K, const double* c2w, const double* points, int n, double* out,
+                     cotr_stream stream);
+int cotr_ransac_pnp_scratch_bytes(int n, int max_iters, size_t* bytes);
+int cotr_ransac_pnp(const double* object_points, const double* image_points, int n, const double* K, double threshold,
+                    double confidence, int max_iters, uint64_t seed, int refine_iters, double* R_out, double* t_out,
+                    uint8_t* mask_out, int32_t* info_out, double* hyp_pose, int32_t* hyp_count, int32_t* hyp_samples,
+                    void* scratch, size_t scratch_bytes, cotr_stream stream);
+
 /* ---- warps of 8-bit images: cv2.remap / cv2.warpPerspective, INTER_LINEAR, BORDER_CONSTANT 0 (cotr_amd/csrc/warp.hip) ----
  * The last host step of demo_single_pair.py:43 (image B warped by triangulate_corr's dense map) and of
  * demo_homography.py:46-49 (a picture pasted through four corners).  Rule in DESIGN.md 3i: OpenCV's 8-bit bilinear remap.
