@@ -146,6 +146,10 @@ _PROTOS = {
     'cotr_recover_pose': (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_double), ctypes.c_double] + [ctypes.c_void_p] * 7 +
                           [ctypes.c_size_t, ctypes.c_void_p]),
+    'cotr_refine_pose_scratch_bytes': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'cotr_refine_pose': (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                        ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int] +
+                         [ctypes.c_void_p] * 8 + [ctypes.c_size_t, ctypes.c_void_p]),
     'cotr_lift_pixels': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     'cotr_ransac_pnp_scratch_bytes': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),

@@ -14,6 +14,16 @@
 //   2. es_front_kernel      per 2048-point chunk: the least-squares depths of every masked point under the four candidates,
 //                           ballot + popcount, four integer atomics per wavefront
 //   3. es_pose_kernel       the first candidate with the largest count: R, t, info and mask_out
+// cotr_refine_pose (rules in DESIGN.md 3h-5): 2 + rounds * (1 + 2 * (refine_iters + 1)) launches:
+//   1. es_normalise_kernel  as above
+//   2. rp_init_kernel       one thread: the state (R, unit t, E = [t]x R and its five directional derivatives)
+//   per round:
+//   3. rp_mask_kernel       per 2048-point chunk: the round's mask (round 1: mask_in; later: Sampson inliers of E in front
+//                           under (R, t)) and its integer count
+//   4. refine_iters + 1 pairs of rp_accum_kernel (per chunk: 22 sums over the mask, every thread over its points in order,
+//      every wavefront in a fixed tree, the 4 wavefronts in order -> scratch) and rp_finish_kernel (one workgroup: the chunks
+//      in chunk order, then: accept or undo the last step, take the next; the round's last takes none, the call's last writes
+//      the outputs).  A device-side flag idles the rest of a round's chain; its length never depends on the data.
 // No floating-point atomics: the same input gives the same bits.  No host waits, no allocation: capturable.
 // Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -24,6 +34,7 @@
 
 #include "handleless.h"
 #include "ransac.h"
+#include "rodrigues.h"
 
 using namespace cotr_detail;
 
@@ -804,6 +815,311 @@ __global__ __launch_bounds__(256) void es_pose_kernel(const double* __restrict__
   }
 }
 
+// ---- kernels of cotr_refine_pose ----------------------------------------------------------------------------------------
+#define RP_PARAMS 5            // w (3) of R <- exp([w]x) R, then (u, v) of t <- (t + u b1 + v b2) / |...|
+#define RP_SUMS 22             // 15 of J^T J, 5 of J^T r, the squared error, the points skipped
+#define RP_MAX_ROUNDS 8
+#define RP_MAX_REFINE 64
+
+// index of (i, j), i <= j, in the row-major upper triangle of a 5 x 5 matrix
+__host__ __device__ constexpr int rp_tri(int i, int j) { return i * 5 - i * (i - 1) / 2 + (j - i); }
+
+// in scratch
+struct RpState {
+  double R[9], t[3];           // current pose, |t| = 1
+  double E[9];                 // [t]x R
+  double dE[RP_PARAMS][9];     // its derivative in the five directions
+  double b1[3], b2[3];         // the tangent basis at t
+  double Rprev[9], tprev[3];   // the pose before the step on trial
+  double err_prev;             // squared error at the previous pose
+  int valid;                   // found, and R_in, t_in finite with t_in != 0
+  int done;                    // nothing more to accumulate in this round
+  int trial;                   // R, t are a step whose error is not known yet
+  int kept, kept_total, kept_last, rounds_run, skipped;
+  int count[RP_MAX_ROUNDS];    // points in each round's mask
+};
+
+// out = [v]x M
+__device__ __forceinline__ void rp_cross(const double* v, const double* M, double* out) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    out[c] = v[1] * M[6 + c] - v[2] * M[3 + c];
+    out[3 + c] = v[2] * M[c] - v[0] * M[6 + c];
+    out[6 + c] = v[0] * M[3 + c] - v[1] * M[c];
+  }
+}
+
+// From R and t of st: the tangent basis (k: the first index of smallest |t_k|; b1 = e_k x t normalised, b2 = t x b1),
+// E = [t]x R and dE = [t]x [e_j]x R for j = 0..2, [b1]x R, [b2]x R.  One thread.
+__device__ void rp_derive(RpState* __restrict__ st) {
+  double R[9], t[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = st->R[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t[i] = st->t[i];
+  const double m0 = fabs(t[0]), m1 = fabs(t[1]), m2 = fabs(t[2]);
+  const int k = (m0 <= m1 && m0 <= m2) ? 0 : (m1 <= m2 ? 1 : 2);
+  const double c[3] = {k == 0 ? 0.0 : (k == 1 ? t[2] : -t[1]), k == 0 ? -t[2] : (k == 1 ? 0.0 : t[0]),
+                       k == 0 ? t[1] : (k == 1 ? -t[0] : 0.0)};
+  const double nrm = sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+  const double b1[3] = {c[0] / nrm, c[1] / nrm, c[2] / nrm};
+  const double b2[3] = {t[1] * b1[2] - t[2] * b1[1], t[2] * b1[0] - t[0] * b1[2], t[0] * b1[1] - t[1] * b1[0]};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) st->b1[i] = b1[i], st->b2[i] = b2[i];
+  double out[9];
+  rp_cross(t, R, out);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) st->E[i] = out[i];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double e[3] = {j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0};
+    double M[9];
+    rp_cross(e, R, M);
+    rp_cross(t, M, out);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) st->dE[j][i] = out[i];
+  }
+  rp_cross(b1, R, out);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) st->dE[3][i] = out[i];
+  rp_cross(b2, R, out);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) st->dE[4][i] = out[i];
+}
+
+__global__ __launch_bounds__(64) void rp_init_kernel(const double* __restrict__ R_in, const double* __restrict__ t_in,
+                                                     const int32_t* __restrict__ found, RpState* __restrict__ st) {
+  if (threadIdx.x != 0) return;
+  bool ok = found == nullptr || found[0] != 0;
+  double R[9], t[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    R[i] = R_in[i];
+    ok = ok && isfinite(R[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    t[i] = t_in[i];
+    ok = ok && isfinite(t[i]);
+  }
+  const double nrm = sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+  ok = ok && nrm > 0.0 && nrm < INFINITY;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) st->R[i] = ok ? R[i] : 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) st->t[i] = ok ? t[i] / nrm : 0.0;
+  st->valid = ok ? 1 : 0;
+  st->done = ok ? 0 : 1;
+  st->trial = 0;
+  st->kept = 0, st->kept_total = 0, st->kept_last = 0, st->rounds_run = 0, st->skipped = 0;
+  for (int r = 0; r < RP_MAX_ROUNDS; ++r) st->count[r] = 0;
+  if (ok) {
+    rp_derive(st);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) st->E[i] = 0.0;
+  }
+}
+
+// The round's mask and its count.  first: the caller's mask (NULL: every point); later rounds: the Sampson inliers of the
+// current E that lie in front of both cameras under the current (R, t).
+__global__ __launch_bounds__(RS_COUNT_THREADS) void rp_mask_kernel(const double* __restrict__ xn, int n, const uint8_t* __restrict__ mask_in,
+                                                                   int first, float thr, double dist, int round, RpState* __restrict__ st,
+                                                                   uint8_t* __restrict__ mask_out) {
+  const int valid = st->valid;   // uniform
+  double E[9], R[9], t[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) E[i] = st->E[i], R[i] = st->R[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t[i] = st->t[i];
+  const int base = blockIdx.x * RS_CHUNK;
+  int wc = 0;
+#pragma unroll 1
+  for (int s = 0; s < RS_COUNT_STEPS; ++s) {
+    const int p = base + s * RS_COUNT_THREADS + threadIdx.x;
+    bool in = false;
+    if (p < n && valid) {
+      if (first) {
+        in = mask_in == nullptr || mask_in[p] != 0;
+      } else {
+        const double* q = xn + (size_t)p * 4;
+        in = EsModel::inlier(E, {xn}, p, thr) && (es_in_front(R, t, q[0], q[1], q[2], q[3], dist) & 1) != 0;
+      }
+    }
+    if (p < n) mask_out[p] = in ? 1 : 0;
+    wc += __popcll(__ballot(in));
+  }
+  if ((threadIdx.x & 63) == 0 && wc > 0) atomicAdd(&st->count[round], wc);
+}
+
+// One masked point's terms at the state st, added to acc: J^T J (15), J^T r (5), r^2; a point with g = 0 or a residual that is
+// not finite adds 1 to acc[21] and nothing else.  r = d / sqrt(g) with a = E x1h, b = E^T x2h, d = x2h . a,
+// g = a0^2 + a1^2 + b0^2 + b1^2; its derivative by the quotient rule.
+__device__ __forceinline__ void rp_terms(const RpState* __restrict__ st, double x1, double y1, double x2, double y2, double* acc) {
+  const double* e = st->E;
+  const double a0 = e[0] * x1 + e[1] * y1 + e[2], a1 = e[3] * x1 + e[4] * y1 + e[5], a2 = e[6] * x1 + e[7] * y1 + e[8];
+  const double b0 = e[0] * x2 + e[3] * y2 + e[6], b1 = e[1] * x2 + e[4] * y2 + e[7];
+  const double d = x2 * a0 + y2 * a1 + a2;
+  const double g = a0 * a0 + a1 * a1 + b0 * b0 + b1 * b1;
+  const double s = sqrt(g), r = d / s;
+  if (!(g > 0.0) || !isfinite(r)) {
+    acc[21] += 1.0;
+    return;
+  }
+  double J[RP_PARAMS];
+#pragma unroll
+  for (int k = 0; k < RP_PARAMS; ++k) {
+    const double* q = st->dE[k];
+    const double da0 = q[0] * x1 + q[1] * y1 + q[2], da1 = q[3] * x1 + q[4] * y1 + q[5], da2 = q[6] * x1 + q[7] * y1 + q[8];
+    const double db0 = q[0] * x2 + q[3] * y2 + q[6], db1 = q[1] * x2 + q[4] * y2 + q[7];
+    const double dd = x2 * da0 + y2 * da1 + da2;
+    const double dg = 2.0 * (a0 * da0 + a1 * da1 + b0 * db0 + b1 * db1);
+    J[k] = dd / s - d * dg / (2.0 * s * g);
+  }
+#pragma unroll
+  for (int i = 0; i < RP_PARAMS; ++i) {
+#pragma unroll
+    for (int j = i; j < RP_PARAMS; ++j) acc[rp_tri(i, j)] += J[i] * J[j];
+    acc[15 + i] += J[i] * r;
+  }
+  acc[20] += r * r;
+}
+
+__global__ __launch_bounds__(RS_COUNT_THREADS) void rp_accum_kernel(const double* __restrict__ xn, int n, const uint8_t* __restrict__ mask,
+                                                                    const RpState* __restrict__ st, double* __restrict__ parts) {
+  __shared__ double sh[RS_COUNT_THREADS / 64][RP_SUMS];
+  if (st->done) return;   // uniform
+  double acc[RP_SUMS];
+#pragma unroll
+  for (int i = 0; i < RP_SUMS; ++i) acc[i] = 0.0;
+  const int base = blockIdx.x * RS_CHUNK;
+#pragma unroll 1
+  for (int s = 0; s < RS_COUNT_STEPS; ++s) {   // every thread: its points in ascending order
+    const int p = base + s * RS_COUNT_THREADS + threadIdx.x;
+    if (p < n && mask[p]) {
+      const double* q = xn + (size_t)p * 4;
+      rp_terms(st, q[0], q[1], q[2], q[3], acc);
+    }
+  }
+  // every wavefront: a fixed butterfly (each lane ends with the same bits), then the 4 wavefronts in order
+#pragma unroll
+  for (int i = 0; i < RP_SUMS; ++i) {
+    double a = acc[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a = a + __shfl_xor(a, off);
+    acc[i] = a;
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < RP_SUMS; ++i) sh[threadIdx.x >> 6][i] = acc[i];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < RP_SUMS) {
+    double a = sh[0][threadIdx.x];
+    for (int w = 1; w < RS_COUNT_THREADS / 64; ++w) a = a + sh[w][threadIdx.x];
+    parts[(size_t)blockIdx.x * RP_SUMS + threadIdx.x] = a;
+  }
+}
+
+// the sums of the accumulate before it: judges the step on trial, takes the next one;
+// last: the round's last launch (no further step is taken; the state is made ready for the next round);
+// final: the call's last launch (writes R_out, t_out, E_out and info)
+__global__ __launch_bounds__(64) void rp_finish_kernel(int chunks, int round, int last, int final, const double* __restrict__ parts,
+                                                       RpState* __restrict__ st, double* __restrict__ R_out, double* __restrict__ t_out,
+                                                       double* __restrict__ E_out, int32_t* __restrict__ info) {
+  __shared__ double sums[RP_SUMS];
+  __shared__ double S5[RP_PARAMS * (RP_PARAMS + 1)];
+  __shared__ int P5[RP_PARAMS];
+  const int tid = threadIdx.x;
+  const bool active = !st->done;   // uniform; read before anything below writes it
+  if (active && tid < RP_SUMS) {
+    double a = 0.0;
+    for (int c = 0; c < chunks; ++c) a = a + parts[(size_t)c * RP_SUMS + tid];   // the chunks in chunk order
+    sums[tid] = a;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  const int valid = st->valid;
+  if (active) {
+    const double err = sums[20];
+    bool go_on = true;
+    if (st->trial) {
+      if (err < st->err_prev) {
+        st->kept = st->kept + 1;
+        st->skipped = (int)sums[21];
+      } else {   // not smaller (or NaN): undo the step, the round's refinement ends
+        for (int i = 0; i < 9; ++i) st->R[i] = st->Rprev[i];
+        for (int i = 0; i < 3; ++i) st->t[i] = st->tprev[i];
+        rp_derive(st);
+        go_on = false;
+      }
+      st->trial = 0;
+    } else {
+      st->skipped = (int)sums[21];   // the round's first evaluation
+    }
+    if (go_on && !last) {
+      bool solved = false;
+      double d[RP_PARAMS];
+      if (st->count[round] >= ES_MODEL) {
+        for (int i = 0; i < RP_PARAMS; ++i) {
+          for (int j = i; j < RP_PARAMS; ++j) S5[i * (RP_PARAMS + 1) + j] = S5[j * (RP_PARAMS + 1) + i] = sums[rp_tri(i, j)];
+          S5[i * (RP_PARAMS + 1) + RP_PARAMS] = -sums[15 + i];
+        }
+        solved = rs_solve<RP_PARAMS, 1>(S5, P5, d);
+      }
+      if (solved) {
+        for (int i = 0; i < 9; ++i) st->Rprev[i] = st->R[i];
+        for (int i = 0; i < 3; ++i) st->tprev[i] = st->t[i];
+        st->err_prev = err;
+        double R[9];
+        for (int i = 0; i < 9; ++i) R[i] = st->R[i];
+        rodrigues_rotate(d, R);
+        for (int i = 0; i < 9; ++i) st->R[i] = R[i];
+        const double x = (st->t[0] + d[3] * st->b1[0]) + d[4] * st->b2[0], y = (st->t[1] + d[3] * st->b1[1]) + d[4] * st->b2[1],
+                     z = (st->t[2] + d[3] * st->b1[2]) + d[4] * st->b2[2];
+        const double nrm = sqrt((x * x + y * y) + z * z);
+        st->t[0] = x / nrm, st->t[1] = y / nrm, st->t[2] = z / nrm;
+        rp_derive(st);
+        st->trial = 1;
+      } else {
+        go_on = false;   // fewer than 5 points, or a singular system
+      }
+    }
+    if (!go_on || last) st->done = 1;
+  }
+  if (last && valid) {   // the round is over: its steps counted, the flag lowered for the next one
+    st->kept_total = st->kept_total + st->kept;
+    st->kept_last = st->kept;
+    st->rounds_run = st->rounds_run + 1;
+    st->kept = 0;
+    st->trial = 0;
+    st->done = 0;
+  }
+  if (final) {
+    double e[9], ss = 0.0;
+    for (int i = 0; i < 9; ++i) {
+      e[i] = st->E[i];
+      ss += e[i] * e[i];
+    }
+    const double nrm = sqrt(ss);
+    for (int i = 0; i < 9; ++i) e[i] = e[i] / nrm;
+    const bool negative = rs_negative9(e);
+    for (int i = 0; i < 9; ++i) {
+      R_out[i] = valid ? st->R[i] : 0.0;
+      E_out[i] = valid ? (negative ? -e[i] : e[i]) : 0.0;
+    }
+    for (int i = 0; i < 3; ++i) t_out[i] = valid ? st->t[i] : 0.0;
+    info[0] = valid;
+    info[1] = st->count[round];
+    info[2] = st->rounds_run;
+    info[3] = st->kept_total;
+    info[4] = st->kept_last;
+    info[5] = st->skipped;
+    info[6] = 0;
+    info[7] = 0;
+  }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -818,6 +1134,21 @@ bool es_camera(const double* K, EsCam* c) {
   c->fx = K[0], c->s = K[1], c->cx = K[2], c->fy = K[4], c->cy = K[5];
   const bool finite = isfinite(c->fx) && isfinite(c->fy) && isfinite(c->cx) && isfinite(c->cy) && isfinite(c->s);
   return finite && c->fx != 0.0 && c->fy != 0.0;
+}
+
+// the scratch of cotr_refine_pose: the normalised pairs xn [n, 4], the state, the partial sums [chunks, RP_SUMS]
+struct RpPlan {
+  size_t state, parts, bytes;
+  int chunks;
+};
+
+RpPlan rp_plan(int n) {
+  RpPlan l;
+  l.chunks = (n + RS_CHUNK - 1) / RS_CHUNK;
+  l.state = align_up((size_t)n * 4 * sizeof(double));
+  l.parts = l.state + align_up(sizeof(RpState));
+  l.bytes = l.parts + align_up((size_t)l.chunks * RP_SUMS * sizeof(double));
+  return l;
 }
 
 }  // namespace
@@ -885,6 +1216,58 @@ int cotr_recover_pose(const double* E, const double* pts1, const double* pts2, i
   hipLaunchKernelGGL(es_front_kernel, dim3((unsigned)chunks), dim3(RS_COUNT_THREADS), 0, s, pts1, pts2, n, k1, k2, mask_in, distance_thresh, st);
   hipLaunchKernelGGL(es_pose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pts1, pts2, n, k1, k2, mask_in, distance_thresh, st, R_out,
                      t_out, mask_out, info_out);
+  return launched();
+}
+
+int cotr_refine_pose_scratch_bytes(int n, size_t* bytes) {
+  if (!bytes) return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose_scratch_bytes: bytes is NULL");
+  if (n < ES_MODEL || n > RS_MAX_POINTS) return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: n must be in [5, 2^24]");
+  *bytes = rp_plan(n).bytes;
+  return COTR_OK;
+}
+
+int cotr_refine_pose(const double* R_in, const double* t_in, const double* pts1, const double* pts2, int n, const double* K1, const double* K2,
+                     double threshold, double distance_thresh, int rounds, int refine_iters, const uint8_t* mask_in, const int32_t* found,
+                     double* R_out, double* t_out, double* E_out, uint8_t* mask_out, int32_t* info_out, void* scratch, size_t scratch_bytes,
+                     cotr_stream stream) {
+  if (n < ES_MODEL || n > RS_MAX_POINTS) return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: n must be in [5, 2^24]");
+  if (!(threshold > 0.0) || !(threshold < INFINITY)) return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: threshold must be finite and > 0");
+  if (!(distance_thresh > 0.0) || !(distance_thresh < INFINITY))
+    return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: distance_thresh must be finite and > 0");
+  if (rounds < 1 || rounds > RP_MAX_ROUNDS) return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: rounds must be in [1, 8]");
+  if (refine_iters < 0 || refine_iters > RP_MAX_REFINE) return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: refine_iters must be in [0, 64]");
+  if (!R_in || !t_in || !pts1 || !pts2 || !K1 || !K2 || !R_out || !t_out || !E_out || !mask_out || !info_out || !scratch)
+    return handleless_fail(COTR_ERR_ARG,
+                           "cotr_refine_pose: R_in, t_in, pts1, pts2, K1, K2, R_out, t_out, E_out, mask_out, info_out and scratch must not be NULL");
+  EsCam k1, k2;
+  if (!es_camera(K1, &k1) || !es_camera(K2, &k2))
+    return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: the camera matrices must be finite with focal lengths that are not 0");
+  const double focal = (k1.fx + k1.fy + k2.fx + k2.fy) / 4.0;
+  const double thr = threshold / focal;
+  if (!(thr * thr > 0.0) || !(thr * thr < INFINITY))
+    return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: the threshold over the mean focal length must be finite and not 0");
+  if (!aligned(R_in, 8) || !aligned(t_in, 8) || !aligned(pts1, 8) || !aligned(pts2, 8) || !aligned(R_out, 8) || !aligned(t_out, 8) ||
+      !aligned(E_out, 8) || !aligned(info_out, 4) || !aligned(found, 4) || !aligned(scratch, 16))
+    return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: doubles must be 8-byte, ints 4-byte and scratch 16-byte aligned");
+  const RpPlan l = rp_plan(n);
+  if (scratch_bytes < l.bytes) return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: scratch is smaller than cotr_refine_pose_scratch_bytes");
+  char* base = static_cast<char*>(scratch);
+  double* xn = reinterpret_cast<double*>(base);
+  RpState* st = reinterpret_cast<RpState*>(base + l.state);
+  double* parts = reinterpret_cast<double*>(base + l.parts);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(es_normalise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pts1, pts2, n, k1, k2, xn);
+  hipLaunchKernelGGL(rp_init_kernel, dim3(1), dim3(64), 0, s, R_in, t_in, found, st);
+  for (int r = 0; r < rounds; ++r) {
+    hipLaunchKernelGGL(rp_mask_kernel, dim3((unsigned)l.chunks), dim3(RS_COUNT_THREADS), 0, s, xn, n, mask_in, r == 0, (float)(thr * thr),
+                       distance_thresh, r, st, mask_out);
+    // pair j judges step j - 1 and takes step j; the round's last one takes none
+    for (int j = 0; j <= refine_iters; ++j) {
+      hipLaunchKernelGGL(rp_accum_kernel, dim3((unsigned)l.chunks), dim3(RS_COUNT_THREADS), 0, s, xn, n, mask_out, st, parts);
+      hipLaunchKernelGGL(rp_finish_kernel, dim3(1), dim3(64), 0, s, l.chunks, r, j == refine_iters, r == rounds - 1 && j == refine_iters, parts,
+                         st, R_out, t_out, E_out, info_out);
+    }
+  }
   return launched();
 }
 

@@ -28,6 +28,7 @@
 #include "camera.h"
 #include "handleless.h"
 #include "ransac.h"
+#include "rodrigues.h"
 
 using namespace cotr_detail;
 
@@ -402,23 +403,6 @@ __global__ __launch_bounds__(RS_COUNT_THREADS) void pn_accum_kernel(const double
   }
 }
 
-// R <- exp([w]x) R by Rodrigues' formula
-__device__ void pn_rotate(const double* w, double* R) {
-  const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2], th = sqrt(th2);
-  const double a = th > 1e-8 ? sin(th) / th : 1.0, b = th > 1e-8 ? (1.0 - cos(th)) / th2 : 0.5;
-  const double W[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
-  double E[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      const double ww = (W[i * 3] * W[j] + W[i * 3 + 1] * W[3 + j]) + W[i * 3 + 2] * W[6 + j];
-      E[i * 3 + j] = ((i == j ? 1.0 : 0.0) + a * W[i * 3 + j]) + b * ww;
-    }
-  double out[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) out[i * 3 + j] = (E[i * 3] * R[j] + E[i * 3 + 1] * R[3 + j]) + E[i * 3 + 2] * R[6 + j];
-  for (int i = 0; i < 9; ++i) R[i] = out[i];
-}
-
 // the sums of the accumulate before it: judges the step on trial, takes the next one;
 // last: the chain's last launch (no further step is taken; writes R_out, t_out and info[4])
 __global__ __launch_bounds__(64) void pn_finish_kernel(int chunks, int last, const double* __restrict__ parts, PnState* __restrict__ st,
@@ -461,7 +445,7 @@ __global__ __launch_bounds__(64) void pn_finish_kernel(int chunks, int last, con
         st->err_prev = err;
         double R[9];
         for (int i = 0; i < 9; ++i) R[i] = st->R[i];
-        pn_rotate(d, R);
+        rodrigues_rotate(d, R);
         for (int i = 0; i < 9; ++i) st->R[i] = R[i];
         for (int i = 0; i < 3; ++i) st->t[i] = st->t[i] + d[3 + i];
         st->trial = 1;

@@ -15,11 +15,13 @@ least-squares refit on the inliers), ``paste_by_homography`` the robust form of 
 ``ZoomEngine.homography`` the robust form of the whole demo.  ``find_essential_mat`` and ``recover_pose`` are
 ``cv2.findEssentialMat(..., cv2.RANSAC)`` (five-point RANSAC) and ``cv2.recoverPose`` on the device, ``ransac_essential`` the
 former with device tensors, ``relative_pose`` both as one device sequence and ``ZoomEngine.relative_pose`` the pose after
-demo_wbs.py's correspondences.  ``solve_pnp_ransac`` is ``cv2.solvePnPRansac(..., flags=cv2.SOLVEPNP_P3P)`` on the device (P3P RANSAC,
+demo_wbs.py's correspondences; ``refine_relative_pose`` refits such a pose on its inliers (Gauss-Newton on the Sampson error,
+the inliers re-counted between rounds), ``refine_pose_tensors`` the same with device tensors, and ``relative_pose(...,
+refine_rounds=4)`` runs it third in the same device sequence.  ``solve_pnp_ransac`` is ``cv2.solvePnPRansac(..., flags=cv2.SOLVEPNP_P3P)`` on the device (P3P RANSAC,
 then a Gauss-Newton refit on the inliers), ``ransac_pnp`` the same with device tensors, ``lift_pixels`` the 3D points of pixels of
 a depth map, ``rodrigues`` ``cv2.Rodrigues``, and ``localize`` / ``ZoomEngine.localize`` the metric pose of a new image against a
 posed RGB-D capture."""
-from .essential import find_essential_mat, ransac_essential, recover_pose, relative_pose
+from .essential import find_essential_mat, ransac_essential, recover_pose, refine_pose_tensors, refine_relative_pose, relative_pose
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .homography import find_homography, paste_by_homography, ransac_homography
 from .pnp import lift_pixels, localize, ransac_pnp, rodrigues, solve_pnp_ransac
@@ -31,4 +33,5 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'mutual_matches', 'find_fundamental_mat', 'filter_guided_matches', 'warp_by_map', 'warp_perspective',
            'get_perspective_transform', 'warp_by_corr', 'paste_by_corners', 'find_homography', 'ransac_homography',
            'paste_by_homography', 'find_essential_mat', 'ransac_essential', 'recover_pose', 'relative_pose',
+           'refine_pose_tensors', 'refine_relative_pose',
            'lift_pixels', 'ransac_pnp', 'solve_pnp_ransac', 'rodrigues', 'localize']

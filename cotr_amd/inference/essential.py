@@ -8,7 +8,9 @@ cotr_amd/csrc/essential.hip (``cotr_ransac_essential``, ``cotr_recover_pose``) o
 ``relative_pose`` enqueues both back to back with no host round trip between them.  The rules are the library's own
 (DESIGN.md 3h-3): they follow the structure of OpenCV's estimator - 5-point samples, up to 10 candidates per sample, Sampson
 error, adaptive iteration count, no refit, the four (R, t) in its order - with the F path's counter-based sampler, and claim
-no bit-compatibility with it.  No CPU fallback."""
+no bit-compatibility with it.  ``refine_relative_pose`` / ``refine_pose_tensors`` (``cotr_refine_pose``) refit a
+pose on its inliers, which cv2's pair does not do: Gauss-Newton on the Sampson error over (R, unit t), the inliers re-counted
+between rounds; ``relative_pose(..., refine_rounds=4)`` enqueues it third.  No CPU fallback."""
 import ctypes
 
 import numpy as np
@@ -39,6 +41,12 @@ def _pairs(points1, points2):
 
 def _check_ransac(K1, K2, threshold, confidence, max_iters):
     _ransac.check_ransac(threshold, confidence, max_iters, MAX_ITERS)
+    _check_threshold(K1, K2, threshold)
+
+
+def _check_threshold(K1, K2, threshold):
+    if not (threshold > 0 and np.isfinite(threshold)):
+        raise ValueError(f'the RANSAC threshold must be finite and > 0, got {threshold}')
     thr = threshold / ((K1[0] + K1[4] + K2[0] + K2[4]) / 4.0) if (K1[0] + K1[4] + K2[0] + K2[4]) != 0 else np.inf
     if not (thr * thr > 0 and np.isfinite(thr * thr)):
         raise ValueError('the RANSAC threshold over the mean focal length must be finite and not 0')
@@ -138,22 +146,110 @@ def recover_pose(E, points1, points2, camera_matrix1, camera_matrix2=None, mask=
     return int(info[0]), r['R'].cpu().numpy(), r['t'].cpu().numpy().reshape(3, 1), r['mask'].cpu().numpy().astype(np.uint8).reshape(-1, 1)
 
 
+MAX_ROUNDS = 8
+MAX_REFINE = 64
+
+
+def _no_cpu_tensors(*xs):
+    if any(torch.is_tensor(x) and not x.is_cuda for x in xs):
+        raise _lib.CotrHipError('the pose refit runs on an MI355X only (HIP kernels, no CPU fallback): got a CPU tensor; '
+                                'pass a numpy array or move the tensor with .cuda()')
+
+
+def _check_refine(rounds, refine_iters, what='rounds'):
+    if not 1 <= rounds <= MAX_ROUNDS:
+        raise ValueError(f'{what} must be in [1, {MAX_ROUNDS}], got {rounds}')
+    if not 0 <= refine_iters <= MAX_REFINE:
+        raise ValueError(f'refine_iters must be in [0, {MAX_REFINE}], got {refine_iters}')
+
+
+def _enqueue_refine(lib, R, t, p1, p2, n, k1, k2, threshold, distance_thresh, rounds, refine_iters, mask, found, device):
+    nbytes = ctypes.c_size_t()
+    check_op(lib.cotr_refine_pose_scratch_bytes(n, ctypes.byref(nbytes)), 'cotr_refine_pose_scratch_bytes')
+    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    R_out = torch.empty(9, dtype=torch.float64, device=device)
+    t_out = torch.empty(3, dtype=torch.float64, device=device)
+    E_out = torch.empty(9, dtype=torch.float64, device=device)
+    mask_out = torch.empty(n, dtype=torch.uint8, device=device)
+    info = torch.empty(8, dtype=torch.int32, device=device)
+    check_op(lib.cotr_refine_pose(ptr(R), ptr(t), ptr(p1), ptr(p2), n, k1, k2, float(threshold), float(distance_thresh), int(rounds),
+                                  int(refine_iters), ptr(mask), ptr(found), ptr(R_out), ptr(t_out), ptr(E_out), ptr(mask_out), ptr(info),
+                                  ptr(scratch), nbytes.value, _lib.current_stream_ptr()), 'cotr_refine_pose')
+    return dict(R=R_out.view(3, 3), t=t_out, E=E_out.view(3, 3), mask=mask_out.bool(), info=info)
+
+
+def refine_pose_tensors(R, t, points1, points2, K1, K2=None, mask=None, threshold=1.0, distance_thresh=50.0, rounds=4, refine_iters=10,
+                        found=None, device=None):
+    """One ``cotr_refine_pose`` call on the current stream: the pose (R [3,3], t [3]) refitted on the
+    correspondences by undamped Gauss-Newton on the Sampson error over (R, unit t); round 1 fits on ``mask`` (None: every
+    point), each later round on the Sampson inliers of the current pose (``threshold`` in pixels) that lie in front of both
+    cameras within ``distance_thresh`` -> dict of device tensors: R float64 [3,3], t float64 [3] (unit length), E float64
+    [3,3] (= [t]x R at unit Frobenius norm), mask bool [n] (what the last round fitted on), info int32 [8] = (found, points in
+    mask, rounds run, steps kept in total, steps kept in the last round, points skipped, 0, 0).  ``found``: a device int32
+    tensor whose first entry 0 means there is no pose to refine (every output 0), as do a non-finite pose and t = 0."""
+    p1, p2, n = _pairs(points1, points2)
+    k1 = _camera(K1, 'K1')
+    k2 = k1 if K2 is None else _camera(K2, 'K2')
+    _check_threshold(k1, k2, threshold)
+    _check_distance(distance_thresh)
+    _check_refine(rounds, refine_iters)
+    r = R if torch.is_tensor(R) else torch.from_numpy(np.ascontiguousarray(np.asarray(R, dtype=np.float64)))
+    tt = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64)))
+    if r.numel() != 9:
+        raise ValueError(f'R must be [3, 3], got shape {tuple(r.shape)}')
+    if tt.numel() != 3:
+        raise ValueError(f't must have 3 entries, got shape {tuple(tt.shape)}')
+    m = None
+    if mask is not None:
+        m = mask if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask)))
+        if m.numel() != n:
+            raise ValueError(f'mask must have one entry per correspondence, got {m.numel()} for {n}')
+    _no_cpu_tensors(R, t, points1, points2, mask, found)
+    device = _device(device)
+    r, tt = on(r.to(dtype=torch.float64).reshape(9), device), on(tt.to(dtype=torch.float64).reshape(3), device)
+    p1, p2 = on(p1, device), on(p2, device)
+    if m is not None:
+        m = (on(m, device).reshape(n) != 0).to(torch.uint8)
+    if found is not None:
+        found = on(found, device).to(torch.int32).reshape(-1)
+    with torch.cuda.device(device):
+        return _enqueue_refine(_lib.load_library(), r, tt, p1, p2, n, k1, k2, threshold, distance_thresh, rounds, refine_iters, m, found, device)
+
+
+def refine_relative_pose(R, t, points1, points2, K1, K2=None, mask=None, **kw):
+    """A relative pose refitted on its correspondences (``refine_pose_tensors``; ``kw``: threshold (1.0), distance_thresh (50),
+    rounds (4), refine_iters (10)) -> (R float64 [3,3], t float64 [3,1] of unit length, mask uint8 [n,1]: the points the last
+    round fitted on), x2 ~ R x1 + t."""
+    r = refine_pose_tensors(R, t, points1, points2, K1, K2, mask, **kw)
+    return r['R'].cpu().numpy(), r['t'].cpu().numpy().reshape(3, 1), r['mask'].cpu().numpy().astype(np.uint8).reshape(-1, 1)
+
+
 def relative_pose_tensors(points1, points2, K1, K2=None, threshold=1.0, confidence=0.999, max_iters=1000, seed=0,
-                          distance_thresh=50.0, device=None):
+                          distance_thresh=50.0, device=None, refine_rounds=0, refine_iters=10):
     """``cotr_ransac_essential`` then ``cotr_recover_pose`` enqueued back to back on the current stream: the second reads the
     first's E, mask and found flag on the device, so no host round trip lies between them -> dict of device tensors: E,
-    R, t, mask (the inliers in front of both cameras), info (the RANSAC's), pose_info."""
+    R, t, mask (the inliers in front of both cameras), info (the RANSAC's), pose_info.  With ``refine_rounds`` > 0
+    ``cotr_refine_pose`` follows third in the same sequence, reading R, t, the pose mask and the found flag on the device: R,
+    t, E and mask are then the refit's, with refine_info beside them and the unrefined ones as R_ransac, t_ransac, E_ransac,
+    mask_ransac."""
     p1, p2, n = _pairs(points1, points2)
     k1 = _camera(K1, 'K1')
     k2 = k1 if K2 is None else _camera(K2, 'K2')
     _check_ransac(k1, k2, threshold, confidence, max_iters)
     _check_distance(distance_thresh)
+    if refine_rounds != 0:
+        _check_refine(refine_rounds, refine_iters, 'refine_rounds')
     device = _device(device)
     p1, p2 = on(p1, device), on(p2, device)
     lib = _lib.load_library()
     with torch.cuda.device(device):
         r = _enqueue_essential(lib, p1, p2, n, k1, k2, threshold, confidence, max_iters, seed, False, device)
         q = _enqueue_pose(lib, r['E'], p1, p2, n, k1, k2, distance_thresh, r['mask_u8'], r['info'], device)
+        if refine_rounds != 0:
+            f = _enqueue_refine(lib, q['R'], q['t'], p1, p2, n, k1, k2, threshold, distance_thresh, refine_rounds, refine_iters,
+                                q['mask'].to(torch.uint8), r['info'], device)
+            return dict(E=f['E'], R=f['R'], t=f['t'], mask=f['mask'], info=r['info'], pose_info=q['info'], refine_info=f['info'],
+                        E_ransac=r['E'], R_ransac=q['R'], t_ransac=q['t'], mask_ransac=q['mask'])
     return dict(E=r['E'], R=q['R'], t=q['t'], mask=q['mask'], info=r['info'], pose_info=q['info'])
 
 
@@ -161,7 +257,9 @@ def relative_pose(points1, points2, K1, K2=None, **kw):
     """The relative pose of two calibrated views from their correspondences: ``find_essential_mat`` then ``recover_pose``
     with its mask, as one device sequence -> (R float64 [3,3], t float64 [3,1] of unit length, mask uint8 [n,1]: the
     inliers in front of both cameras), x2 ~ R x1 + t, or (None, None, None) when no model is found.  ``kw``: threshold (1.0),
-    confidence (0.999), max_iters (1000), seed (0), distance_thresh (50)."""
+    confidence (0.999), max_iters (1000), seed (0), distance_thresh (50), refine_rounds (0; above 0: that many rounds of the
+    refit of ``refine_pose_tensors`` follow in the same sequence, and the mask is what the last round fitted on),
+    refine_iters (10)."""
     r = relative_pose_tensors(points1, points2, K1, K2, **kw)
     if not r['info'].cpu().numpy()[0]:
         return None, None, None

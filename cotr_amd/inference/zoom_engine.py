@@ -701,7 +701,8 @@ class ZoomEngine:
         on them with the camera matrices ``K_a``, ``K_b`` [3,3] -> (R float64 [3,3], t float64 [3,1] of unit length with
         x_b ~ R x_a + t, corrs [K, 4], mask uint8 [K, 1]: the inliers in front of both cameras); R, t and mask are None when
         no model is found.  ``ransac_kw``: threshold (1.0), confidence (0.999), max_iters (1000), seed (0), distance_thresh
-        (50).  Fewer than 5 correspondences: ValueError."""
+        (50), refine_rounds (0; above 0 the pose is refitted on its inliers in that many rounds), refine_iters
+        (10).  Fewer than 5 correspondences: ValueError."""
         from .essential import relative_pose
         if queries_a is None:
             corrs = self.cotr_corr_multiscale(img_a, img_b, zoom_ins, converge_iters, max_corrs=max_corrs)

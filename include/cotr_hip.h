@@ -550,6 +550,38 @@ int cotr_recover_pose(const double* E, const double* pts1, const double* pts2, i
                       double distance_thresh, const uint8_t* mask_in, const int32_t* found, double* R_out, double* t_out,
                       uint8_t* mask_out, int32_t* info_out, void* scratch, size_t scratch_bytes, cotr_stream stream);
 
+/* ---- the refit of a relative pose on its inliers (cotr_amd/csrc/essential.hip; rules in DESIGN.md 3h-5) ------------------
+ * Undamped Gauss-Newton on the Sampson error over (R, unit t), with the inliers re-counted between rounds: what the
+ * homography and PnP estimators end with, for the pose of cotr_ransac_essential + cotr_recover_pose.
+ *
+ * K1, K2, pts1, pts2, mask_in, found: as for cotr_recover_pose (K1, K2 on the HOST, the rest DEVICE pointers; mask_in NULL:
+ *   every point; found NULL: 1).  R_in [9], t_in [3] float64 DEVICE: the pose to start from, e.g. R_out, t_out of
+ *   cotr_recover_pose.  -> R_out [9], t_out [3] (unit length), E_out [9] = [t]x R at unit Frobenius norm with the first
+ *   entry of largest magnitude positive, mask_out [n] uint8 (the mask the last round fitted on; must not overlap mask_in),
+ *   info_out [8] int32 = {found, points in mask_out, rounds run, steps kept in total, steps kept in the last round, points
+ *   skipped at the returned pose, 0, 0}.
+ * The points are rounded to float32 and normalised by the rule above.  State: a rotation R, t = t_in / |t_in|,
+ *   E = [t]x R.  Residual of a masked point: r = d / sqrt(g) with a = E x1h, b = E^T x2h, d = x2 a0 + y2 a1 + a2,
+ *   g = a0^2 + a1^2 + b0^2 + b1^2 (r^2: the Sampson error); a point with g = 0 or a residual that is not finite adds
+ *   nothing and is counted.  Five parameters: R <- exp([w]x) R and t <- (t + u b1 + v b2) / |...| with b1 = e_k x t
+ *   normalised (k: the first index of smallest |t_k|) and b2 = t x b1; the Jacobian is exact.  A step solves
+ *   J^T J delta = -J^T r by full-pivot elimination and is kept only if the summed squared error falls; the first step not
+ *   kept, or a singular system, ends the round; no damping.  Round 1 fits on mask_in; each later round first takes as
+ *   its mask the points with float(Sampson error) <= float(thr^2) under the current E (thr as for cotr_ransac_essential)
+ *   whose least-squares depths under the current (R, t) lie in (0, distance_thresh), then fits again.  A round with fewer
+ *   than 5 points in its mask takes no step.  refine_iters = 0 with rounds = 1: R_out = R_in and t_out = t_in / |t_in|
+ *   bit for bit.  found = 0, a non-finite R_in or t_in, or t_in = 0: every output is 0.
+ *   5 <= n <= 2^24, threshold > 0 finite, distance_thresh > 0 finite, 1 <= rounds <= 8, 0 <= refine_iters <= 64.
+ *   scratch: DEVICE, 16-byte aligned, at least cotr_refine_pose_scratch_bytes(n) bytes.
+ * Stream-ordered, 2 + rounds (1 + 2 (refine_iters + 1)) launches whatever the data, no host waits and no allocation
+ * (capturable); integer atomics only, sums in a fixed order: the same input gives the same bits.  Bad arguments are
+ * checked before any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_refine_pose_scratch_bytes(int n, size_t* bytes);
+int cotr_refine_pose(const double* R_in, const double* t_in, const double* pts1, const double* pts2, int n, const double* K1,
+                     const double* K2, double threshold, double distance_thresh, int rounds, int refine_iters,
+                     const uint8_t* mask_in, const int32_t* found, double* R_out, double* t_out, double* E_out, uint8_t* mask_out,
+                     int32_t* info_out, void* scratch, size_t scratch_bytes, cotr_stream stream);
+
 /* ---- absolute pose: P3P RANSAC with a refit, and the lift of pixels through a depth map (cotr_amd/csrc/pnp.hip) ----------
  * The structure of cv2.solvePnPRansac(object, image, K, None, flags=cv2.SOLVEPNP_P3P) on the device, by rules of the
  * library's own (no bit-compatibility with OpenCV is claimed).  x_cam = R X + t.
