@@ -33,6 +33,7 @@
 #include <stdint.h>
 
 #include "handleless.h"
+#include "pinhole.h"
 #include "ransac.h"
 #include "rodrigues.h"
 
@@ -46,12 +47,6 @@ using namespace cotr_detail;
 #define ES_QR_SWEEPS 30        // QR sweeps allowed per eigenvalue
 #define ES_DOUBLES 222         // per-sample LDS: the 10 x 20 system, 10 real roots, 12 of small systems
 #define ES_INTS 15             // the sample, a column permutation
-#define ES_HD __host__ __device__
-
-// fx, fy, cx, cy, skew of an upper-triangular camera matrix
-struct EsCam {
-  double fx, fy, cx, cy, s;
-};
 
 // ---- polynomials in (x, y, z, w = 1) --------------------------------------------------------------------------------
 // a linear one has 4 coefficients (x, y, z, 1), a quadratic one 10 (pairs i <= j at es_q2), a cubic one 20, in the column
@@ -598,14 +593,7 @@ ES_HD int es_five_point(const double* x1, const double* y1, const double* x2, co
 #undef P_
 
 // ---- points and errors ----------------------------------------------------------------------------------------------
-// y = (v - cy) / fy, then x = (u - cx - s y) / fx, of the pixel rounded to float32
-ES_HD __forceinline__ void es_normalise(const EsCam& k, double u, double v, double* x, double* y) {
-  u = (double)(float)u, v = (double)(float)v;
-  const double yy = (v - k.cy) / k.fy;
-  *x = (u - k.cx - k.s * yy) / k.fx;
-  *y = yy;
-}
-
+// (EsCam and es_normalise, the pixel -> normalised coordinates rule: pinhole.h)
 // Sampson error of the normalised pair (x1, y1) -> (x2, y2)
 ES_HD __forceinline__ float es_error(const double* e, double x1, double y1, double x2, double y2) {
   const double a0 = e[0] * x1 + e[1] * y1 + e[2], a1 = e[3] * x1 + e[4] * y1 + e[5], a2 = e[6] * x1 + e[7] * y1 + e[8];

@@ -20,11 +20,15 @@ the inliers re-counted between rounds), ``refine_pose_tensors`` the same with de
 refine_rounds=4)`` runs it third in the same device sequence.  ``solve_pnp_ransac`` is ``cv2.solvePnPRansac(..., flags=cv2.SOLVEPNP_P3P)`` on the device (P3P RANSAC,
 then a Gauss-Newton refit on the inliers), ``ransac_pnp`` the same with device tensors, ``lift_pixels`` the 3D points of pixels of
 a depth map, ``rodrigues`` ``cv2.Rodrigues``, and ``localize`` / ``ZoomEngine.localize`` the metric pose of a new image against a
-posed RGB-D capture."""
+posed RGB-D capture.  ``triangulate_views`` triangulates correspondences seen in 2 to 32 posed views in one device call (the views
+of a point that agree are voted on, the point is refitted on its reprojection error), ``triangulate_points`` is its two-view form
+after ``relative_pose`` or ``localize``, ``stack_views`` shapes one query set matched against several images for it, and
+``ZoomEngine.reconstruct`` is demo_reconstruction.py up to its viewer."""
 from .essential import find_essential_mat, ransac_essential, recover_pose, refine_pose_tensors, refine_relative_pose, relative_pose
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .homography import find_homography, paste_by_homography, ransac_homography
 from .pnp import lift_pixels, localize, ransac_pnp, rodrigues, solve_pnp_ransac
+from .structure import reconstruct_tensors, stack_views, triangulate_points, triangulate_points_tensors, triangulate_views
 from .triangulate import delaunay, triangulate_corr
 from .warp import get_perspective_transform, paste_by_corners, warp_by_corr, warp_by_map, warp_perspective
 from .zoom_engine import FasterSparseEngine, RefineResult, SparseEngine, ZoomEngine, patch_boxes
@@ -34,4 +38,5 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'get_perspective_transform', 'warp_by_corr', 'paste_by_corners', 'find_homography', 'ransac_homography',
            'paste_by_homography', 'find_essential_mat', 'ransac_essential', 'recover_pose', 'relative_pose',
            'refine_pose_tensors', 'refine_relative_pose',
-           'lift_pixels', 'ransac_pnp', 'solve_pnp_ransac', 'rodrigues', 'localize']
+           'lift_pixels', 'ransac_pnp', 'solve_pnp_ransac', 'rodrigues', 'localize',
+           'triangulate_views', 'triangulate_points', 'triangulate_points_tensors', 'stack_views', 'reconstruct_tensors']

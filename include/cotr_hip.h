@@ -623,6 +623,46 @@ int cotr_ransac_pnp(const double* object_points, const double* image_points, int
                     uint8_t* mask_out, int32_t* info_out, double* hyp_pose, int32_t* hyp_count, int32_t* hyp_samples,
                     void* scratch, size_t scratch_bytes, cotr_stream stream);
 
+/* ---- structure from known cameras: robust N-view triangulation (cotr_amd/csrc/structure.hip; rules in DESIGN.md 3h-6) ----
+ * n correspondences seen in V posed views -> their 3D points, the views each point was fitted on, and the per-point
+ * figures a reconstruction filters on.  The rules are the library's own.
+ *
+ * DEVICE pointers: points [V][n][2] float64 (x, y) in pixels, view-major, rounded to float32 first; visible [V][n] uint8
+ *   or NULL (every view sees every point); cams [V][5] float64 (fx, fy, cx, cy, skew); poses [V][12] float64, the
+ *   world-to-camera [R | t] row-major (x_cam = R X + t); found int32 or NULL: when found[0] is 0 every output is 0.
+ * A view whose camera or pose has an entry that is not finite, a focal length of 0 or a centre c = -R^T t that is not
+ *   finite sees no point.  Ray of a point in a view: d = R^T (x, y, 1) normalised, (x, y) by the rule of
+ *   cotr_ransac_essential.  S: the visible views of the point whose rounded coordinates are finite, ascending; fewer than
+ *   two: the point has too few views.
+ * Ray least squares over a set of views: (sum I - d d^T) X = sum (I - d d^T) c, summed ascending, solved by cofactors; a
+ *   determinant that is 0 or not finite, or a coordinate that is not finite: degenerate.
+ * robust = 1: every pair i < j of S in lexicographic order is triangulated by that rule and counts the views of S with depth
+ *   > 0 and float(squared reprojection error) <= float(threshold^2); the first pair with the largest count gives U, its
+ *   inlier views; a count below 2: too few views.  robust = 0: U = S.
+ * Fit: X = ray least squares over U, then up to refine_iters undamped Gauss-Newton steps on the summed squared pixel error
+ *   over U (analytic Jacobian, the 3 x 3 system by cofactors); none unless every view of U has depth > 0 at the start; a
+ *   step is kept only if the error falls and every view of U keeps depth > 0; the first step not kept, or a degenerate
+ *   system, ends the fit.
+ * rule = 1 (V = 2, robust = 0, refine_iters = 0 only): X = c_a + s d_a, the point of ray A nearest ray B,
+ *   s = (d_a.w - (d_a.d_b)(d_b.w)) / (1 - (d_a.d_b)^2), w = c_b - c_a; a denominator of 0: degenerate.
+ * -> X_out [n][3] float64 (NaN: not solved), used_out [V][n] uint8 (U; 0 when not solved), quality_out [n][5] float64 over
+ *   U at X = {mean squared reprojection error, largest, smallest depth, largest depth, smallest cosine between two rays}
+ *   (NaN when not solved), mask_out [n] uint8 = solved, every depth in (0, distance_thresh), every float(error) <=
+ *   float(threshold^2) and the smallest cosine <= max_cos; info_out [8] int32 = {found, points in mask_out, points with too
+ *   few views, degenerate points, solved points dropped by depth, by error (depth passed), by parallax (both passed), steps
+ *   kept in total}.
+ * 2 <= V <= 32, 1 <= n <= 2^24, threshold > 0 finite with a squared float32 that is finite and not 0, -1 <= max_cos <= 1,
+ *   distance_thresh > 0 finite, 0 <= refine_iters <= 64, robust and rule 0 or 1.  points and scratch 16-byte aligned;
+ *   scratch: DEVICE, at least cotr_triangulate_views_scratch_bytes(V, n) bytes.
+ * Stream-ordered, 2 launches whatever the data, no host waits and no allocation (capturable); a thread per point sums in a
+ * fixed order and the counters are integer atomics: the same input gives the same bits.  Bad arguments are checked before
+ * any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_triangulate_views_scratch_bytes(int V, int n, size_t* bytes);
+int cotr_triangulate_views(const double* points, const uint8_t* visible, const double* cams, const double* poses, int V, int n,
+                           const int32_t* found, double threshold, double max_cos, double distance_thresh, int refine_iters,
+                           int robust, int rule, double* X_out, uint8_t* used_out, double* quality_out, uint8_t* mask_out,
+                           int32_t* info_out, void* scratch, size_t scratch_bytes, cotr_stream stream);
+
 /* ---- warps of 8-bit images: cv2.remap / cv2.warpPerspective, INTER_LINEAR, BORDER_CONSTANT 0 (cotr_amd/csrc/warp.hip) ----
  * The last host step of demo_single_pair.py:43 (image B warped by triangulate_corr's dense map) and of
  * demo_homography.py:46-49 (a picture pasted through four corners).  Rule in DESIGN.md 3i: OpenCV's 8-bit bilinear remap.
