@@ -160,6 +160,10 @@ _PROTOS = {
     'cotr_triangulate_views': (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_double,
                                               ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int] +
                                [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_void_p]),
+    'cotr_bundle_adjust_scratch_bytes': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'cotr_bundle_adjust': (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 6 +
+                           [ctypes.c_size_t, ctypes.c_void_p]),
     'cotr_warp_map': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4),
     'cotr_warp_perspective': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                              ctypes.c_int] + [ctypes.c_void_p] * 4),

@@ -11,33 +11,15 @@
 #include <stdint.h>
 
 #include "handleless.h"
-#include "pinhole.h"
+#include "view_table.h"
 
 using namespace cotr_detail;
 
-#define TV_MAX_VIEWS 32
 #define TV_MAX_POINTS (1 << 24)
 #define TV_MAX_REFINE 64
 #define TV_THREADS 64
-// a row of the view table: fx fy cx cy skew | R (9, row-major) | t (3) | c (3) | valid (1.0 or 0.0) | 3 unused
-#define TV_ROW 24
-#define TV_R 5
-#define TV_T 14
-#define TV_C 17
-#define TV_OK 20
 
-// ---- per-view arithmetic (w: the view's row of the table) -----------------------------------------------------------------
-struct TvPixel {
-  double u, v;   // rounded to float32
-  bool finite;
-};
-
-__device__ __forceinline__ TvPixel tv_pixel(const double* __restrict__ points, size_t N, int v, size_t p) {
-  const double2 q = *reinterpret_cast<const double2*>(points + ((size_t)v * N + p) * 2);
-  const float uf = (float)q.x, vf = (float)q.y;
-  return {(double)uf, (double)vf, isfinite(uf) && isfinite(vf)};
-}
-
+// ---- per-view arithmetic (w: the view's row of the table; the pixel, the projection and the solve are in view_table.h) -----
 // d = R^T (x, y, 1) / |R^T (x, y, 1)| with (x, y) the normalised pixel
 __device__ __forceinline__ void tv_ray(const double* w, const TvPixel& q, double* d) {
   const EsCam k = {w[0], w[1], w[2], w[3], w[4]};
@@ -64,37 +46,6 @@ __device__ __forceinline__ void tv_accum(const double* w, const TvPixel& q, doub
   acc[6] += c[0] - d[0] * dc;
   acc[7] += c[1] - d[1] * dc;
   acc[8] += c[2] - d[2] * dc;
-}
-
-// The symmetric 3 x 3 system m (00 01 02 11 12 22) x = b by cofactors, branch-free up to the verdict: false when the
-// determinant is 0 or not finite, or a coordinate is not finite.
-__device__ __forceinline__ bool tv_solve(const double* m, const double* b, double* x) {
-  const double c00 = m[3] * m[5] - m[4] * m[4], c01 = m[2] * m[4] - m[1] * m[5], c02 = m[1] * m[4] - m[2] * m[3];
-  const double c11 = m[0] * m[5] - m[2] * m[2], c12 = m[1] * m[2] - m[0] * m[4], c22 = m[0] * m[3] - m[1] * m[1];
-  const double det = (m[0] * c00 + m[1] * c01) + m[2] * c02;
-  x[0] = ((c00 * b[0] + c01 * b[1]) + c02 * b[2]) / det;
-  x[1] = ((c01 * b[0] + c11 * b[1]) + c12 * b[2]) / det;
-  x[2] = ((c02 * b[0] + c12 * b[1]) + c22 * b[2]) / det;
-  return det != 0.0 && isfinite(det) && isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);
-}
-
-// X in the view: depth z, normalised (xn, yn), squared pixel distance e to the observation, residual (du, dv)
-struct TvProj {
-  double z, xn, yn, du, dv, e;
-};
-
-__device__ __forceinline__ TvProj tv_project(const double* w, const TvPixel& q, const double* X) {
-  const double* R = w + TV_R;
-  const double* t = w + TV_T;
-  TvProj r;
-  const double p0 = ((R[0] * X[0] + R[1] * X[1]) + R[2] * X[2]) + t[0];
-  const double p1 = ((R[3] * X[0] + R[4] * X[1]) + R[5] * X[2]) + t[1];
-  r.z = ((R[6] * X[0] + R[7] * X[1]) + R[8] * X[2]) + t[2];
-  r.xn = p0 / r.z, r.yn = p1 / r.z;
-  r.du = ((w[0] * r.xn + w[4] * r.yn) + w[2]) - q.u;
-  r.dv = (w[1] * r.yn + w[3]) - q.v;
-  r.e = r.du * r.du + r.dv * r.dv;
-  return r;
 }
 
 // ---- per-point loops over a set of views (a bit mask), ascending ----------------------------------------------------------
@@ -150,40 +101,6 @@ __device__ void tv_normal(const TvPoint& c, uint32_t set, const double* X, doubl
 }
 
 // ---- kernels --------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void tv_prepare_kernel(const double* __restrict__ cams, const double* __restrict__ poses, int V,
-                                                        const int32_t* __restrict__ found, double* __restrict__ tab,
-                                                        int32_t* __restrict__ info) {
-  const int v = threadIdx.x;
-  if (v < 8) info[v] = v == 0 ? (found ? (found[0] != 0) : 1) : 0;
-  if (v >= V) return;
-  double* w = tab + v * TV_ROW;
-  const double* k = cams + v * 5;
-  const double* P = poses + v * 12;
-  bool ok = true;
-  for (int i = 0; i < 5; ++i) {
-    w[i] = k[i];
-    ok = ok && isfinite(k[i]);
-  }
-  ok = ok && k[0] != 0.0 && k[1] != 0.0;
-  double t[3];
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) {
-      w[TV_R + r * 3 + c] = P[r * 4 + c];
-      ok = ok && isfinite(P[r * 4 + c]);
-    }
-    t[r] = P[r * 4 + 3];
-    w[TV_T + r] = t[r];
-    ok = ok && isfinite(t[r]);
-  }
-  for (int c = 0; c < 3; ++c) {
-    const double cc = -((P[c] * t[0] + P[4 + c] * t[1]) + P[8 + c] * t[2]);
-    w[TV_C + c] = cc;
-    ok = ok && isfinite(cc);
-  }
-  w[TV_OK] = ok ? 1.0 : 0.0;
-  w[21] = w[22] = w[23] = 0.0;
-}
-
 __global__ __launch_bounds__(TV_THREADS) void tv_points_kernel(const double* __restrict__ points, const uint8_t* __restrict__ visible,
                                                                int V, int n, const double* __restrict__ tab_in,
                                                                const int32_t* __restrict__ found, float thr, double max_cos, double dist,

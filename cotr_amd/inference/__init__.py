@@ -23,7 +23,10 @@ a depth map, ``rodrigues`` ``cv2.Rodrigues``, and ``localize`` / ``ZoomEngine.lo
 posed RGB-D capture.  ``triangulate_views`` triangulates correspondences seen in 2 to 32 posed views in one device call (the views
 of a point that agree are voted on, the point is refitted on its reprojection error), ``triangulate_points`` is its two-view form
 after ``relative_pose`` or ``localize``, ``stack_views`` shapes one query set matched against several images for it, and
-``ZoomEngine.reconstruct`` is demo_reconstruction.py up to its viewer."""
+``ZoomEngine.reconstruct`` is demo_reconstruction.py up to its viewer.  ``bundle_adjust`` refines the poses of such views and
+their points together (Levenberg-Marquardt by the Schur complement, one device call), ``bundle_adjust_tensors`` the same with device
+tensors, and ``reconstruct(..., bundle_rounds=2)`` runs it after the triangulation."""
+from .bundle import bundle_adjust, bundle_adjust_tensors
 from .essential import find_essential_mat, ransac_essential, recover_pose, refine_pose_tensors, refine_relative_pose, relative_pose
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .homography import find_homography, paste_by_homography, ransac_homography
@@ -39,4 +42,5 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'paste_by_homography', 'find_essential_mat', 'ransac_essential', 'recover_pose', 'relative_pose',
            'refine_pose_tensors', 'refine_relative_pose',
            'lift_pixels', 'ransac_pnp', 'solve_pnp_ransac', 'rodrigues', 'localize',
-           'triangulate_views', 'triangulate_points', 'triangulate_points_tensors', 'stack_views', 'reconstruct_tensors']
+           'triangulate_views', 'triangulate_points', 'triangulate_points_tensors', 'stack_views', 'reconstruct_tensors',
+           'bundle_adjust', 'bundle_adjust_tensors']

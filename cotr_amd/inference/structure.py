@@ -239,11 +239,17 @@ def _colours(img_a, img_b, pa, pb, device):
     return torch.where(inside[:, None], col, torch.zeros_like(col)), inside
 
 
-def reconstruct_tensors(corrs, img_a, img_b, K_a, K_b, c2w_a=None, c2w_b=None, rule='rays', pose_kw=None, device=None, **kw):
+def reconstruct_tensors(corrs, img_a, img_b, K_a, K_b, c2w_a=None, c2w_b=None, rule='rays', pose_kw=None, device=None, bundle_rounds=0,
+                        **kw):
     """What follows the correspondences [n,4] of two images: with both camera-to-world poses the demo's triangulation
     (``rule='demo'`` for its own formula), without them ``relative_pose_tensors(**pose_kw)`` and the triangulation in A's frame
     as one device sequence -> dict of device tensors: X [n,3], mask bool [n] (also 0 where a floored coordinate falls
-    outside its image), colors float64 [n,3], and the rest of ``triangulate_views``' dict (with pose: the pose dict)."""
+    outside its image), colors float64 [n,3], and the rest of ``triangulate_views``' dict (with pose: the pose dict).
+    ``bundle_rounds`` > 0: ``bundle_adjust_tensors`` follows the triangulation as one more call of the same
+    device sequence, with that many rounds, view 0 fixed, the observations ``used`` of the points in ``mask`` and the found
+    flag chained; X is then the adjusted points, ``poses`` [2,3,4] the adjusted world-to-camera poses and ``bundle`` the rest of
+    its dict.  With only view 0 fixed nothing pins the scale: the damping leaves it where the input put it, and the translation
+    of view 1 is no longer of unit length.  0 (the default): the outputs are those of the triangulation alone, bit for bit."""
     from .essential import relative_pose_tensors
     c = _tensor(corrs).to(dtype=torch.float64)
     if c.dim() != 2 or c.shape[1] != 4:
@@ -253,6 +259,8 @@ def reconstruct_tensors(corrs, img_a, img_b, K_a, K_b, c2w_a=None, c2w_b=None, r
     for img, what in ((img_a, 'img_a'), (img_b, 'img_b')):
         if len(img.shape) != 3 or img.shape[2] != 3:
             raise ValueError(f'{what} must be [H, W, 3], got shape {tuple(img.shape)}')
+    if int(bundle_rounds) != bundle_rounds or bundle_rounds < 0:
+        raise ValueError(f'bundle_rounds must be an integer >= 0, got {bundle_rounds}')
     device = _device(device)
     c = c.to(device)
     pa, pb = c[:, :2].contiguous(), c[:, 2:].contiguous()
@@ -261,10 +269,21 @@ def reconstruct_tensors(corrs, img_a, img_b, K_a, K_b, c2w_a=None, c2w_b=None, r
     with torch.cuda.device(device):
         if c2w_a is not None:
             r = triangulate_points_tensors(pa, pb, K_a, K_b, c2w1=c2w_a, c2w2=c2w_b, rule=rule, device=device, **kw)
+            spec = _check_two_view_poses(None, None, c2w_a, c2w_b)
         else:
             pose = relative_pose_tensors(pa, pb, K_a, K_b, device=device, **dict(dict(refine_rounds=4), **(pose_kw or {})))
             r = triangulate_points_tensors(pa, pb, K_a, K_b, R=pose['R'], t=pose['t'], found=pose['info'], rule=rule, device=device, **kw)
             r['pose'] = pose
+            spec = ('rt', pose['R'], pose['t'])
+        if bundle_rounds > 0:
+            from .bundle import bundle_adjust_tensors
+            k_a = _k5(K_a, 'K_a')
+            ba = bundle_adjust_tensors(torch.stack([pa, pb], dim=0), np.array([k_a, k_a if K_b is None else _k5(K_b, 'K_b')]),
+                                       _two_view_poses(spec, device), r['X'], visible=r['used'] & r['mask'][None], fixed_views=(0,),
+                                       rounds=int(bundle_rounds), found=r['info'], device=device,
+                                       **{k: v for k, v in kw.items() if k in ('threshold', 'distance_thresh')})
+            r['X'], r['poses'] = ba['X'], ba['poses']
+            r['bundle'] = dict(used=ba['used'], stats=ba['stats'], info=ba['info'])
         r['colors'], inside = _colours(img_a, img_b, pa, pb, device)
         r['mask'] = r['mask'] & inside
     r['corrs'] = c

@@ -735,7 +735,7 @@ class ZoomEngine:
         return c2w_b, corrs, mask
 
     def reconstruct(self, img_a, img_b, K_a, K_b, c2w_a=None, c2w_b=None, queries_a=None, zoom_ins=np.linspace(0.5, 0.0625, 4),
-                    converge_iters=1, max_corrs=1000, rule='rays', pose_kw=None, **structure_kw):
+                    converge_iters=1, max_corrs=1000, rule='rays', pose_kw=None, bundle_rounds=0, **structure_kw):
         """demo_reconstruction.py up to its viewer: ``cotr_corr_multiscale`` from A into B (from ``queries_a`` [N, 2] with
         force=True, or from the engine's own grid when None), then ``reconstruct_tensors`` on them: with both camera-to-world
         poses the points are triangulated in their world frame (``rule='demo'``: the demo's own formula), without poses
@@ -743,7 +743,8 @@ class ZoomEngine:
         device sequence -> dict of device tensors: X float64 [K,3], mask bool [K], colors float64 [K,3] (the mean of the two
         images at the floored coordinates over 255; 0 and mask 0 where one falls outside its image), corrs float64 [K,4], and
         the rest of ``triangulate_views``' dict.  ``structure_kw``: threshold (4.0), min_angle (1.5), distance_thresh (50),
-        refine_iters (10), robust (True)."""
+        refine_iters (10), robust (True).  ``bundle_rounds`` > 0: the bundle adjustment of ``reconstruct_tensors`` follows in the
+        same device sequence (X adjusted, ``poses`` added; the scale stays where the input put it)."""
         from .structure import reconstruct_tensors
         if queries_a is None:
             corrs = self.cotr_corr_multiscale(img_a, img_b, zoom_ins, converge_iters, max_corrs=max_corrs)
@@ -751,6 +752,8 @@ class ZoomEngine:
             queries_a = np.asarray(queries_a)
             corrs = self.cotr_corr_multiscale(img_a, img_b, zoom_ins, converge_iters, max_corrs=max_corrs, queries_a=queries_a,
                                               force=True)
+        if bundle_rounds:
+            structure_kw = dict(structure_kw, bundle_rounds=bundle_rounds)
         return reconstruct_tensors(np.asarray(corrs), img_a, img_b, K_a, K_b, c2w_a, c2w_b, rule=rule, pose_kw=pose_kw, **structure_kw)
 
     @staticmethod

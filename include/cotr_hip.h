@@ -663,6 +663,49 @@ int cotr_triangulate_views(const double* points, const uint8_t* visible, const d
                            int robust, int rule, double* X_out, uint8_t* used_out, double* quality_out, uint8_t* mask_out,
                            int32_t* info_out, void* scratch, size_t scratch_bytes, cotr_stream stream);
 
+/* ---- bundle adjustment: poses and points refined together (cotr_amd/csrc/bundle.hip; rules in DESIGN.md 3h-7) ----
+ * Levenberg-Marquardt on the summed squared pixel error over the poses of the views that are not fixed and the points, the
+ * points eliminated by the Schur complement.  The intrinsics are not optimised.  The rules are the library's own.
+ *
+ * DEVICE pointers: points, visible, cams, poses_in (the world-to-camera poses to start from), found: as for
+ *   cotr_triangulate_views, with its view validity and its projection (z, xn, yn, du, dv, e); X_in [n][3] float64, the
+ *   points to start from.  fixed_views: HOST uint8 [V] (read before the call returns), not 0: the view's pose is held; NULL:
+ *   view 0 alone.
+ * Eligible observation (v, p): the view is valid, sees the point, both rounded coordinates are finite, X of p is finite.
+ * The set of round 1: the eligible observations with z > 0 at the input state; of a later round: those with z in (0,
+ *   distance_thresh) and float(e) <= float(threshold^2) at the current state.  A view that is not fixed with fewer than 4
+ *   observations in the set is frozen for the round (its pose stays, its observations leave the set); after that a point
+ *   with fewer than 2 observations is a landmark for the round (its X stays, its observations still constrain the views).
+ *   No free view left, or no observation: the round takes no step.
+ * Parameters: per free view R <- exp([w]x) R (Rodrigues, as cotr_ransac_pnp) and t <- t + dt; per point X <- X + dX;
+ *   exact Jacobians Jc (2 x 6) and Jp (2 x 3) per observation.  An iteration at damping lambda: V_p = sum Jp^T Jp,
+ *   g_p = sum Jp^T r, U_v = sum Jc^T Jc, g_v = sum Jc^T r, W_vp = Jc^T Jp; the diagonals of U_v and V_p times (1 + lambda);
+ *   V_p* inverted by the cofactor rule of cotr_triangulate_views (a determinant that is 0 or not finite: a landmark for this
+ *   iteration); S_vw = [v = w] U_v* - sum_p W_vp V_p*^-1 W_wp^T, b_v = g_v - sum_p W_vp V_p*^-1 g_p; S dc = b by Cholesky (a
+ *   pivot <= 0 or not finite rejects the step); dX_p = V_p*^-1 (g_p - sum_v W_vp^T dc_v); the candidate is the state minus
+ *   the steps and is kept only if its summed e over the set is strictly smaller (a NaN rejects) and every observation of
+ *   the set keeps z > 0.  Kept: lambda <- max(lambda / 10, 1e-12); rejected: lambda <- 10 lambda.  A round starts at lambda0
+ *   and ends after iters iterations or when lambda exceeds 1e12.
+ * -> poses_out [V][12], X_out [n][3] float64 (views and points that never moved: the input bit for bit), used_out [V][n]
+ *   uint8 (the last round's set), stats_out [4] float64 = {cost of round 1's set at the input state, cost of the last
+ *   round's set at the output state, the last lambda, 0}, info_out [8] int32 = {found, observations in the last set, free
+ *   views of the last round, views frozen, landmarks, steps kept in total, steps rejected in total, rounds run}; found[0] =
+ *   0: every output is 0.
+ * 2 <= V <= 32, 1 <= n <= 2^20, 1 <= rounds <= 8, 0 <= iters <= 64, 1e-12 <= lambda0 <= 1e12, threshold as for
+ *   cotr_triangulate_views, distance_thresh > 0 finite, at least one view fixed and one not.  points and scratch 16-byte
+ *   aligned; scratch: DEVICE, at least cotr_bundle_adjust_scratch_bytes(V, n) bytes (O(n + chunks V^2): the Jacobians are
+ *   recomputed where needed, not stored).
+ * Stream-ordered, 3 + rounds (3 + 5 iters) launches whatever the data (rejected iterations and those after a round's end
+ * cost their launches and change nothing), no host waits and no allocation (capturable); integer atomics only, every
+ * floating-point sum in a fixed order: the same input gives the same bits.  Bad arguments are checked before any HIP call:
+ * COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_bundle_adjust_scratch_bytes(int V, int n, size_t* bytes);
+int cotr_bundle_adjust(const double* points, const uint8_t* visible, const double* cams, const double* poses_in,
+                       const double* X_in, const uint8_t* fixed_views, int V, int n, const int32_t* found, double threshold,
+                       double distance_thresh, int rounds, int iters, double lambda0, double* poses_out, double* X_out,
+                       uint8_t* used_out, double* stats_out, int32_t* info_out, void* scratch, size_t scratch_bytes,
+                       cotr_stream stream);
+
 /* ---- warps of 8-bit images: cv2.remap / cv2.warpPerspective, INTER_LINEAR, BORDER_CONSTANT 0 (cotr_amd/csrc/warp.hip) ----
  * The last host step of demo_single_pair.py:43 (image B warped by triangulate_corr's dense map) and of
  * demo_homography.py:46-49 (a picture pasted through four corners).  Rule in DESIGN.md 3i: OpenCV's 8-bit bilinear remap.
