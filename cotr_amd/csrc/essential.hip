@@ -20,10 +20,11 @@
 //   per round:
 //   3. rp_mask_kernel       per 2048-point chunk: the round's mask (round 1: mask_in; later: Sampson inliers of E in front
 //                           under (R, t)) and its integer count
-//   4. refine_iters + 1 pairs of rp_accum_kernel (per chunk: 22 sums over the mask, every thread over its points in order,
-//      every wavefront in a fixed tree, the 4 wavefronts in order -> scratch) and rp_finish_kernel (one workgroup: the chunks
-//      in chunk order, then: accept or undo the last step, take the next; the round's last takes none, the call's last writes
-//      the outputs).  A device-side flag idles the rest of a round's chain; its length never depends on the data.
+//   4. refine_iters + 1 pairs of rf_accum_kernel<RpTerms> (per chunk: 22 sums over the mask, every thread over its points in
+//      order, every wavefront in a fixed tree, the 4 wavefronts in order -> scratch) and rp_finish_kernel (one workgroup: the
+//      chunks in chunk order, then rf_step: accept or undo the last step, take the next; the round's last takes none, the
+//      call's last writes the outputs); refit.h's frame.  A device-side flag idles the rest of a round's chain; its length
+//      never depends on the data.
 // No floating-point atomics: the same input gives the same bits.  No host waits, no allocation: capturable.
 // Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -35,7 +36,7 @@
 #include "handleless.h"
 #include "pinhole.h"
 #include "ransac.h"
-#include "rodrigues.h"
+#include "refit.h"
 
 using namespace cotr_detail;
 
@@ -809,22 +810,33 @@ __global__ __launch_bounds__(256) void es_pose_kernel(const double* __restrict__
 #define RP_MAX_ROUNDS 8
 #define RP_MAX_REFINE 64
 
-// index of (i, j), i <= j, in the row-major upper triangle of a 5 x 5 matrix
-__host__ __device__ constexpr int rp_tri(int i, int j) { return i * 5 - i * (i - 1) / 2 + (j - i); }
+struct RpState;
+__device__ void rp_derive(RpState* __restrict__ st);
 
-// in scratch
-struct RpState {
-  double R[9], t[3];           // current pose, |t| = 1
+// in scratch (the pose: |t| = 1; done, kept: of this round), and the model of refit.h's step
+struct RpState : RfPose {
   double E[9];                 // [t]x R
   double dE[RP_PARAMS][9];     // its derivative in the five directions
   double b1[3], b2[3];         // the tangent basis at t
-  double Rprev[9], tprev[3];   // the pose before the step on trial
-  double err_prev;             // squared error at the previous pose
   int valid;                   // found, and R_in, t_in finite with t_in != 0
-  int done;                    // nothing more to accumulate in this round
-  int trial;                   // R, t are a step whose error is not known yet
-  int kept, kept_total, kept_last, rounds_run, skipped;
+  int kept_total, kept_last, rounds_run, skipped;
   int count[RP_MAX_ROUNDS];    // points in each round's mask
+
+  static constexpr int PARAMS = RP_PARAMS;
+  static __device__ __forceinline__ bool solvable(const RpState* st, int round) { return st->count[round] >= ES_MODEL; }
+  static __device__ __forceinline__ void evaluated(RpState* st, const double* sums) { st->skipped = (int)sums[21]; }
+  static __device__ __forceinline__ void restore(RpState* st) {
+    RfPose::restore(st);
+    rp_derive(st);
+  }
+  static __device__ __forceinline__ void apply(RpState* st, const double* d) {
+    rotate(st, d);
+    const double x = (st->t[0] + d[3] * st->b1[0]) + d[4] * st->b2[0], y = (st->t[1] + d[3] * st->b1[1]) + d[4] * st->b2[1],
+                 z = (st->t[2] + d[3] * st->b1[2]) + d[4] * st->b2[2];
+    const double nrm = sqrt((x * x + y * y) + z * z);
+    st->t[0] = x / nrm, st->t[1] = y / nrm, st->t[2] = z / nrm;
+    rp_derive(st);
+  }
 };
 
 // out = [v]x M
@@ -967,114 +979,35 @@ __device__ __forceinline__ void rp_terms(const RpState* __restrict__ st, double 
 #pragma unroll
   for (int i = 0; i < RP_PARAMS; ++i) {
 #pragma unroll
-    for (int j = i; j < RP_PARAMS; ++j) acc[rp_tri(i, j)] += J[i] * J[j];
+    for (int j = i; j < RP_PARAMS; ++j) acc[rf_tri<RP_PARAMS>(i, j)] += J[i] * J[j];
     acc[15 + i] += J[i] * r;
   }
   acc[20] += r * r;
 }
 
-__global__ __launch_bounds__(RS_COUNT_THREADS) void rp_accum_kernel(const double* __restrict__ xn, int n, const uint8_t* __restrict__ mask,
-                                                                    const RpState* __restrict__ st, double* __restrict__ parts) {
-  __shared__ double sh[RS_COUNT_THREADS / 64][RP_SUMS];
-  if (st->done) return;   // uniform
-  double acc[RP_SUMS];
-#pragma unroll
-  for (int i = 0; i < RP_SUMS; ++i) acc[i] = 0.0;
-  const int base = blockIdx.x * RS_CHUNK;
-#pragma unroll 1
-  for (int s = 0; s < RS_COUNT_STEPS; ++s) {   // every thread: its points in ascending order
-    const int p = base + s * RS_COUNT_THREADS + threadIdx.x;
-    if (p < n && mask[p]) {
-      const double* q = xn + (size_t)p * 4;
-      rp_terms(st, q[0], q[1], q[2], q[3], acc);
-    }
+struct RpTerms {
+  static constexpr int SUMS = RP_SUMS, STRIDE = RP_SUMS;
+  using Points = EsModel::Points;
+  using State = RpState;
+  static __device__ __forceinline__ void terms(const RpState* __restrict__ st, const Points& pts, int p, double* acc) {
+    const double* q = pts.xn + (size_t)p * 4;
+    rp_terms(st, q[0], q[1], q[2], q[3], acc);
   }
-  // every wavefront: a fixed butterfly (each lane ends with the same bits), then the 4 wavefronts in order
-#pragma unroll
-  for (int i = 0; i < RP_SUMS; ++i) {
-    double a = acc[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a = a + __shfl_xor(a, off);
-    acc[i] = a;
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < RP_SUMS; ++i) sh[threadIdx.x >> 6][i] = acc[i];
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < RP_SUMS) {
-    double a = sh[0][threadIdx.x];
-    for (int w = 1; w < RS_COUNT_THREADS / 64; ++w) a = a + sh[w][threadIdx.x];
-    parts[(size_t)blockIdx.x * RP_SUMS + threadIdx.x] = a;
-  }
-}
+};
 
-// the sums of the accumulate before it: judges the step on trial, takes the next one;
+// the sums of the accumulate before it: judges the step on trial, takes the next one (fewer than 5 points in the round's mask:
+// none);
 // last: the round's last launch (no further step is taken; the state is made ready for the next round);
 // final: the call's last launch (writes R_out, t_out, E_out and info)
-__global__ __launch_bounds__(64) void rp_finish_kernel(int chunks, int round, int last, int final, const double* __restrict__ parts,
-                                                       RpState* __restrict__ st, double* __restrict__ R_out, double* __restrict__ t_out,
+__global__ __launch_bounds__(64) void rp_finish_kernel(int chunks, const double* __restrict__ parts, RpState* __restrict__ st, int round,
+                                                       int last, int final, double* __restrict__ R_out, double* __restrict__ t_out,
                                                        double* __restrict__ E_out, int32_t* __restrict__ info) {
   __shared__ double sums[RP_SUMS];
-  __shared__ double S5[RP_PARAMS * (RP_PARAMS + 1)];
-  __shared__ int P5[RP_PARAMS];
-  const int tid = threadIdx.x;
   const bool active = !st->done;   // uniform; read before anything below writes it
-  if (active && tid < RP_SUMS) {
-    double a = 0.0;
-    for (int c = 0; c < chunks; ++c) a = a + parts[(size_t)c * RP_SUMS + tid];   // the chunks in chunk order
-    sums[tid] = a;
-  }
-  __syncthreads();
-  if (tid != 0) return;
+  rf_reduce<RP_SUMS>(parts, chunks, active ? RP_SUMS : 0, sums);
+  if (threadIdx.x != 0) return;
   const int valid = st->valid;
-  if (active) {
-    const double err = sums[20];
-    bool go_on = true;
-    if (st->trial) {
-      if (err < st->err_prev) {
-        st->kept = st->kept + 1;
-        st->skipped = (int)sums[21];
-      } else {   // not smaller (or NaN): undo the step, the round's refinement ends
-        for (int i = 0; i < 9; ++i) st->R[i] = st->Rprev[i];
-        for (int i = 0; i < 3; ++i) st->t[i] = st->tprev[i];
-        rp_derive(st);
-        go_on = false;
-      }
-      st->trial = 0;
-    } else {
-      st->skipped = (int)sums[21];   // the round's first evaluation
-    }
-    if (go_on && !last) {
-      bool solved = false;
-      double d[RP_PARAMS];
-      if (st->count[round] >= ES_MODEL) {
-        for (int i = 0; i < RP_PARAMS; ++i) {
-          for (int j = i; j < RP_PARAMS; ++j) S5[i * (RP_PARAMS + 1) + j] = S5[j * (RP_PARAMS + 1) + i] = sums[rp_tri(i, j)];
-          S5[i * (RP_PARAMS + 1) + RP_PARAMS] = -sums[15 + i];
-        }
-        solved = rs_solve<RP_PARAMS, 1>(S5, P5, d);
-      }
-      if (solved) {
-        for (int i = 0; i < 9; ++i) st->Rprev[i] = st->R[i];
-        for (int i = 0; i < 3; ++i) st->tprev[i] = st->t[i];
-        st->err_prev = err;
-        double R[9];
-        for (int i = 0; i < 9; ++i) R[i] = st->R[i];
-        rodrigues_rotate(d, R);
-        for (int i = 0; i < 9; ++i) st->R[i] = R[i];
-        const double x = (st->t[0] + d[3] * st->b1[0]) + d[4] * st->b2[0], y = (st->t[1] + d[3] * st->b1[1]) + d[4] * st->b2[1],
-                     z = (st->t[2] + d[3] * st->b1[2]) + d[4] * st->b2[2];
-        const double nrm = sqrt((x * x + y * y) + z * z);
-        st->t[0] = x / nrm, st->t[1] = y / nrm, st->t[2] = z / nrm;
-        rp_derive(st);
-        st->trial = 1;
-      } else {
-        go_on = false;   // fewer than 5 points, or a singular system
-      }
-    }
-    if (!go_on || last) st->done = 1;
-  }
+  if (active) rf_step(st, sums, last, round);
   if (last && valid) {   // the round is over: its steps counted, the flag lowered for the next one
     st->kept_total = st->kept_total + st->kept;
     st->kept_last = st->kept;
@@ -1116,28 +1049,8 @@ const RsEntry ES_ENTRY = {"cotr_ransac_essential", "E_out", ES_MODEL, "", ES_SLO
 // after the frame's candidates and counts: the normalised pairs xn [n, 4]
 size_t es_scratch_bytes(const RsPlan& l, int n) { return l.bytes + align_up((size_t)n * 4 * sizeof(double)); }
 
-// the camera of an upper-triangular K (row-major 9 doubles, on the host); false unless fx and fy are finite and non-zero and
-// the rest is finite
-bool es_camera(const double* K, EsCam* c) {
-  c->fx = K[0], c->s = K[1], c->cx = K[2], c->fy = K[4], c->cy = K[5];
-  const bool finite = isfinite(c->fx) && isfinite(c->fy) && isfinite(c->cx) && isfinite(c->cy) && isfinite(c->s);
-  return finite && c->fx != 0.0 && c->fy != 0.0;
-}
-
 // the scratch of cotr_refine_pose: the normalised pairs xn [n, 4], the state, the partial sums [chunks, RP_SUMS]
-struct RpPlan {
-  size_t state, parts, bytes;
-  int chunks;
-};
-
-RpPlan rp_plan(int n) {
-  RpPlan l;
-  l.chunks = (n + RS_CHUNK - 1) / RS_CHUNK;
-  l.state = align_up((size_t)n * 4 * sizeof(double));
-  l.parts = l.state + align_up(sizeof(RpState));
-  l.bytes = l.parts + align_up((size_t)l.chunks * RP_SUMS * sizeof(double));
-  return l;
-}
+RfPlan rp_plan(int n) { return rf_plan(align_up((size_t)n * 4 * sizeof(double)), sizeof(RpState), n, RP_SUMS); }
 
 }  // namespace
 
@@ -1237,12 +1150,11 @@ int cotr_refine_pose(const double* R_in, const double* t_in, const double* pts1,
   if (!aligned(R_in, 8) || !aligned(t_in, 8) || !aligned(pts1, 8) || !aligned(pts2, 8) || !aligned(R_out, 8) || !aligned(t_out, 8) ||
       !aligned(E_out, 8) || !aligned(info_out, 4) || !aligned(found, 4) || !aligned(scratch, 16))
     return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: doubles must be 8-byte, ints 4-byte and scratch 16-byte aligned");
-  const RpPlan l = rp_plan(n);
+  const RfPlan l = rp_plan(n);
   if (scratch_bytes < l.bytes) return handleless_fail(COTR_ERR_ARG, "cotr_refine_pose: scratch is smaller than cotr_refine_pose_scratch_bytes");
   char* base = static_cast<char*>(scratch);
   double* xn = reinterpret_cast<double*>(base);
   RpState* st = reinterpret_cast<RpState*>(base + l.state);
-  double* parts = reinterpret_cast<double*>(base + l.parts);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(es_normalise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pts1, pts2, n, k1, k2, xn);
   hipLaunchKernelGGL(rp_init_kernel, dim3(1), dim3(64), 0, s, R_in, t_in, found, st);
@@ -1250,11 +1162,9 @@ int cotr_refine_pose(const double* R_in, const double* t_in, const double* pts1,
     hipLaunchKernelGGL(rp_mask_kernel, dim3((unsigned)l.chunks), dim3(RS_COUNT_THREADS), 0, s, xn, n, mask_in, r == 0, (float)(thr * thr),
                        distance_thresh, r, st, mask_out);
     // pair j judges step j - 1 and takes step j; the round's last one takes none
-    for (int j = 0; j <= refine_iters; ++j) {
-      hipLaunchKernelGGL(rp_accum_kernel, dim3((unsigned)l.chunks), dim3(RS_COUNT_THREADS), 0, s, xn, n, mask_out, st, parts);
-      hipLaunchKernelGGL(rp_finish_kernel, dim3(1), dim3(64), 0, s, l.chunks, r, j == refine_iters, r == rounds - 1 && j == refine_iters, parts,
-                         st, R_out, t_out, E_out, info_out);
-    }
+    for (int j = 0; j <= refine_iters; ++j)
+      rf_enqueue_pair<RpTerms>(s, l, scratch, {xn}, n, mask_out, rp_finish_kernel, r, (int)(j == refine_iters),
+                               (int)(r == rounds - 1 && j == refine_iters), R_out, t_out, E_out, info_out);
   }
   return launched();
 }

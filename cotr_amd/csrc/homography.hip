@@ -8,12 +8,12 @@
 //   3. rs_select_kernel<4, 1>   the sequential selection loop replayed on the counts
 //   4. rs_mask_kernel<HgModel>  the chosen candidate's mask, H_ransac, and (the model's tail) the refit's state
 //      (2 - 4: ransac.h's frame on the model HgModel, as are the sampler, the normalisation and the elimination of 1)
-//   5. the refit chain, pairs of hg_accum_kernel<STAGE> (per 2048-point chunk: up to 45 sums over the mask, every thread
-//      over its points in order, every wavefront in a fixed tree, the 4 wavefronts in order -> scratch) and
-//      hg_finish_kernel (one workgroup: the chunks in chunk order, then the stage's small serial problem):
+//   5. the refit chain, pairs of rf_accum_kernel<HgTerms<STAGE>> (per 2048-point chunk: up to 45 sums over the mask, every
+//      thread over its points in order, every wavefront in a fixed tree, the 4 wavefronts in order -> scratch) and
+//      hg_finish_kernel (one workgroup: the chunks in chunk order, then the stage's small serial problem); refit.h's frame:
 //        CENTROID, DISTANCE          the Hartley normalisation of the inliers
 //        DLT                         L^T L (45 sums) -> the eigenvector of the smallest eigenvalue by cyclic Jacobi
-//        GN x (refine_iters + 1)     (none with refine_iters = 0) J^T J, J^T r, squared error (45 sums) -> accept or undo the last step, take the next
+//        GN x (refine_iters + 1)     (none with refine_iters = 0) J^T J, J^T r, squared error (45 sums) -> rf_step: accept or undo the last step, take the next
 //      A device-side flag ends the chain's work early; its length never depends on the data.
 // No floating-point atomics: the same input gives the same bits.  No host waits, no allocation: capturable.
 // Compiled with -ffp-contract=off.
@@ -25,6 +25,7 @@
 
 #include "handleless.h"
 #include "ransac.h"
+#include "refit.h"
 
 using namespace cotr_detail;
 
@@ -36,16 +37,25 @@ using namespace cotr_detail;
 enum { HG_CENTROID = 0, HG_DISTANCE = 1, HG_DLT = 2, HG_GN = 3 };
 
 // the refit's state, in scratch; written by the mask kernel's tail (done, status, kept, trial) and by the finish kernels
-struct HgState {
+// and the model of refit.h's step: the 8 free entries of Hn
+struct HgState : RfCore {
   double c1x, c1y, s1, c2x, c2y, s2;   // T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]] of each point set
   double cnt;                          // number of inliers, as a sum over the mask
   double h[9];                         // current Hn (normalised frame); h[8] = 1 while refining
   double hprev[9];                     // Hn before the step on trial
-  double err_prev;                     // squared error at hprev
-  int done;                            // nothing more to accumulate
   int status;                          // 0 DLT + refine, 1 DLT only, 2 none
-  int kept;                            // Gauss-Newton steps kept
-  int trial;                           // h is a step whose error is not known yet
+
+  static constexpr int PARAMS = 8;
+  static __device__ __forceinline__ void judged(HgState* st) { st->status = 0; }
+  static __device__ __forceinline__ void save(HgState* st) {
+    for (int i = 0; i < 9; ++i) st->hprev[i] = st->h[i];
+  }
+  static __device__ __forceinline__ void restore(HgState* st) {
+    for (int i = 0; i < 9; ++i) st->h[i] = st->hprev[i];
+  }
+  static __device__ __forceinline__ void apply(HgState* st, const double* d) {
+    for (int i = 0; i < 8; ++i) st->h[i] = st->h[i] + d[i];
+  }
 };
 
 // ---- the model of ransac.h's frame: one candidate per 4-point sample; the tail starts the refit's state -------------------
@@ -194,14 +204,6 @@ __global__ __launch_bounds__(RS_SOLVE_THREADS) void hg_solve_kernel(const double
 }
 
 // ---- the refit -----------------------------------------------------------------------------------------------------
-template <int STAGE>
-struct HgSums {
-  static constexpr int N = STAGE == HG_CENTROID ? 5 : STAGE == HG_DISTANCE ? 2 : HG_SUMS;
-};
-
-// index of (i, j), i <= j, in the row-major upper triangle of an N x N matrix
-__host__ __device__ constexpr int hg_tri(int N, int i, int j) { return i * N - i * (i - 1) / 2 + (j - i); }
-
 // One inlier's terms, added to acc: every stage reads the point rounded to float32.
 template <int STAGE>
 __device__ __forceinline__ void hg_terms(const HgState* __restrict__ st, double x, double y, double u, double v, double* acc) {
@@ -222,7 +224,7 @@ __device__ __forceinline__ void hg_terms(const HgState* __restrict__ st, double 
 #pragma unroll
     for (int i = 0; i < 9; ++i)
 #pragma unroll
-      for (int j = i; j < 9; ++j) acc[hg_tri(9, i, j)] += r1[i] * r1[j] + r2[i] * r2[j];
+      for (int j = i; j < 9; ++j) acc[rf_tri<9>(i, j)] += r1[i] * r1[j] + r2[i] * r2[j];
     return;
   }
   // HG_GN: residual and Jacobian of the 8 free entries at st->h (h[8] = 1)
@@ -236,51 +238,23 @@ __device__ __forceinline__ void hg_terms(const HgState* __restrict__ st, double 
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
 #pragma unroll
-    for (int j = i; j < 8; ++j) acc[hg_tri(8, i, j)] += j1[i] * j1[j] + j2[i] * j2[j];
+    for (int j = i; j < 8; ++j) acc[rf_tri<8>(i, j)] += j1[i] * j1[j] + j2[i] * j2[j];
     acc[36 + i] += j1[i] * rx + j2[i] * ry;
   }
   acc[44] += rx * rx + ry * ry;
 }
 
 template <int STAGE>
-__global__ __launch_bounds__(RS_COUNT_THREADS) void hg_accum_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2, int n,
-                                                                    const uint8_t* __restrict__ mask, const HgState* __restrict__ st,
-                                                                    double* __restrict__ parts) {
-  constexpr int NS = HgSums<STAGE>::N;
-  __shared__ double sh[RS_COUNT_THREADS / 64][HG_SUMS];
-  if (st->done) return;   // uniform
-  double acc[NS];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) acc[k] = 0.0;
-  const int base = blockIdx.x * RS_CHUNK;
-#pragma unroll 1
-  for (int s = 0; s < RS_COUNT_STEPS; ++s) {   // every thread: its points in ascending order
-    const int p = base + s * RS_COUNT_THREADS + threadIdx.x;
-    if (p < n && mask[p]) {
-      const double x = f32r(pts1[(size_t)p * 2]), y = f32r(pts1[(size_t)p * 2 + 1]);
-      const double u = f32r(pts2[(size_t)p * 2]), v = f32r(pts2[(size_t)p * 2 + 1]);
-      hg_terms<STAGE>(st, x, y, u, v, acc);
-    }
+struct HgTerms {
+  static constexpr int SUMS = STAGE == HG_CENTROID ? 5 : STAGE == HG_DISTANCE ? 2 : HG_SUMS, STRIDE = HG_SUMS;
+  using Points = RsPixelPairs;
+  using State = HgState;
+  static __device__ __forceinline__ void terms(const HgState* __restrict__ st, const Points& pts, int p, double* acc) {
+    const double x = f32r(pts.pts1[(size_t)p * 2]), y = f32r(pts.pts1[(size_t)p * 2 + 1]);
+    const double u = f32r(pts.pts2[(size_t)p * 2]), v = f32r(pts.pts2[(size_t)p * 2 + 1]);
+    hg_terms<STAGE>(st, x, y, u, v, acc);
   }
-  // every wavefront: a fixed butterfly (each lane ends with the same bits), then the 4 wavefronts in order
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    double a = acc[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a = a + __shfl_xor(a, off);
-    acc[k] = a;
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < NS; ++k) sh[threadIdx.x >> 6][k] = acc[k];
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < NS) {
-    double a = sh[0][threadIdx.x];
-    for (int w = 1; w < RS_COUNT_THREADS / 64; ++w) a = a + sh[w][threadIdx.x];
-    parts[(size_t)blockIdx.x * HG_SUMS + threadIdx.x] = a;
-  }
-}
+};
 
 // the eigenvector of the smallest eigenvalue of the symmetric 9 x 9 a (destroyed), by cyclic Jacobi (ransac.h) -> e[9]
 __device__ void hg_jacobi9(double (*a)[9], double (*v)[9], double* e) {
@@ -293,23 +267,15 @@ __device__ void hg_jacobi9(double (*a)[9], double (*v)[9], double* e) {
 
 // stage: which sums the accumulate before it made;
 // last: the chain's last launch (no further step is taken; writes H_out and info[4..7])
-__global__ __launch_bounds__(64) void hg_finish_kernel(int stage, int chunks, int last, const double* __restrict__ parts,
-                                                       HgState* __restrict__ st, const double* __restrict__ Hc,
-                                                       double* __restrict__ H_out, int32_t* __restrict__ info) {
+__global__ __launch_bounds__(64) void hg_finish_kernel(int chunks, const double* __restrict__ parts, HgState* __restrict__ st, int stage,
+                                                       int last, const double* __restrict__ Hc, double* __restrict__ H_out,
+                                                       int32_t* __restrict__ info) {
   __shared__ double sums[HG_SUMS];
   __shared__ double A[9][9], Vv[9][9];
-  __shared__ double S8[72];
-  __shared__ int P8[8];
-  const int tid = threadIdx.x;
   const bool active = !st->done;   // uniform; read before anything below writes it
   const int ns = stage == HG_CENTROID ? 5 : stage == HG_DISTANCE ? 2 : HG_SUMS;
-  if (active && tid < ns) {
-    double a = 0.0;
-    for (int c = 0; c < chunks; ++c) a = a + parts[(size_t)c * HG_SUMS + tid];   // the chunks in chunk order
-    sums[tid] = a;
-  }
-  __syncthreads();
-  if (tid != 0) return;
+  rf_reduce<HG_SUMS>(parts, chunks, active ? ns : 0, sums);
+  if (threadIdx.x != 0) return;
   if (active) {
     if (stage == HG_CENTROID) {
       const double cnt = sums[4];
@@ -324,7 +290,7 @@ __global__ __launch_bounds__(64) void hg_finish_kernel(int stage, int chunks, in
       }
     } else if (stage == HG_DLT) {
       for (int i = 0; i < 9; ++i)
-        for (int j = i; j < 9; ++j) A[i][j] = A[j][i] = sums[hg_tri(9, i, j)];
+        for (int j = i; j < 9; ++j) A[i][j] = A[j][i] = sums[rf_tri<9>(i, j)];
       double e[9];
       hg_jacobi9(A, Vv, e);
       double ss = 0.0;
@@ -341,34 +307,7 @@ __global__ __launch_bounds__(64) void hg_finish_kernel(int stage, int chunks, in
         if (!refine || last) st->done = 1;
       }
     } else {   // HG_GN
-      const double err = sums[44];
-      bool go_on = true;
-      if (st->trial) {
-        if (err < st->err_prev) {
-          st->kept = st->kept + 1;
-        } else {   // not smaller (or NaN): undo the step, the refinement ends
-          for (int i = 0; i < 9; ++i) st->h[i] = st->hprev[i];
-          go_on = false;
-        }
-        st->trial = 0;
-      }
-      st->status = 0;
-      if (go_on && !last) {
-        for (int i = 0; i < 8; ++i) {
-          for (int j = i; j < 8; ++j) S8[i * 9 + j] = S8[j * 9 + i] = sums[hg_tri(8, i, j)];
-          S8[i * 9 + 8] = -sums[36 + i];
-        }
-        double d[8];
-        if (rs_solve<8, 1>(S8, P8, d)) {
-          for (int i = 0; i < 9; ++i) st->hprev[i] = st->h[i];
-          st->err_prev = err;
-          for (int i = 0; i < 8; ++i) st->h[i] = st->h[i] + d[i];
-          st->trial = 1;
-        } else {
-          go_on = false;   // singular system
-        }
-      }
-      if (!go_on || last) st->done = 1;
+      rf_step(st, sums, last);
     }
   }
   if (last) {
@@ -396,28 +335,7 @@ namespace {
 const RsEntry HG_ENTRY = {"cotr_ransac_homography", "H_out", HG_MODEL, "", HgModel::SLOTS, RS_MAX_ITERS};
 
 // after the frame's candidates and counts: the refit's state, then its partial sums [chunks, HG_SUMS]
-struct HgPlan {
-  RsPlan rs;
-  size_t state, parts, bytes;
-  int chunks;
-};
-
-HgPlan hg_plan(int n, int max_iters) {
-  HgPlan l;
-  l.rs = rs_plan(HG_ENTRY, max_iters);
-  l.chunks = (n + RS_CHUNK - 1) / RS_CHUNK;
-  l.state = l.rs.bytes;
-  l.parts = l.state + align_up(sizeof(HgState));
-  l.bytes = l.parts + align_up((size_t)l.chunks * HG_SUMS * sizeof(double));
-  return l;
-}
-
-template <int STAGE>
-void hg_pair(hipStream_t s, const HgPlan& l, int last, const double* pts1, const double* pts2, int n, const uint8_t* mask, HgState* st,
-             double* parts, const double* Hc, double* H_out, int32_t* info) {
-  hipLaunchKernelGGL(hg_accum_kernel<STAGE>, dim3((unsigned)l.chunks), dim3(RS_COUNT_THREADS), 0, s, pts1, pts2, n, mask, st, parts);
-  hipLaunchKernelGGL(hg_finish_kernel, dim3(1), dim3(64), 0, s, STAGE, l.chunks, last, parts, st, Hc, H_out, info);
-}
+RfPlan hg_plan(const RsPlan& rs, int n) { return rf_plan(rs.bytes, sizeof(HgState), n, HG_SUMS); }
 
 }  // namespace
 
@@ -425,7 +343,7 @@ extern "C" {
 
 int cotr_ransac_homography_scratch_bytes(int n, int max_iters, size_t* bytes) {
   if (const int rc = rs_scratch_bytes(HG_ENTRY, n, max_iters, bytes)) return rc;
-  *bytes = hg_plan(n, max_iters).bytes;
+  *bytes = hg_plan(rs_plan(HG_ENTRY, max_iters), n).bytes;
   return COTR_OK;
 }
 
@@ -433,28 +351,32 @@ int cotr_ransac_homography(const double* pts1, const double* pts2, int n, double
                            int refine_iters, uint64_t seed, double* H_out, uint8_t* mask_out, int32_t* info_out, double* H_ransac,
                            double* hyp_H, int32_t* hyp_count, int32_t* hyp_samples, void* scratch, size_t scratch_bytes,
                            cotr_stream stream) {
-  const HgPlan l = hg_plan(n, max_iters);
+  const RsPlan rs = rs_plan(HG_ENTRY, max_iters);
+  const RfPlan l = hg_plan(rs, n);
   if (const int rc = rs_check_call(HG_ENTRY, n, max_iters, threshold, confidence, pts1, pts2, H_out, mask_out, info_out, hyp_H, hyp_count,
                                    hyp_samples, scratch, scratch_bytes, l.bytes))
     return rc;
   if (refine_iters < 0 || refine_iters > HG_MAX_REFINE) return rs_fail(HG_ENTRY, "refine_iters must be in [0, 64]");
   if (!aligned(H_ransac, 8)) return rs_fail(HG_ENTRY, "H_ransac must be 8-byte aligned");
   char* base = static_cast<char*>(scratch);
-  const double* Hc = reinterpret_cast<const double*>(base + l.rs.candidates);
+  const double* Hc = reinterpret_cast<const double*>(base + rs.candidates);
   HgState* st = reinterpret_cast<HgState*>(base + l.state);
-  double* parts = reinterpret_cast<double*>(base + l.parts);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const auto solve = [&](double* cand, int* count) {
     hipLaunchKernelGGL(hg_solve_kernel, dim3((unsigned)((max_iters + RS_SOLVE_THREADS - 1) / RS_SOLVE_THREADS)), dim3(RS_SOLVE_THREADS), 0, s,
                        pts1, pts2, n, max_iters, seed, cand, count, hyp_H, hyp_samples);
   };
-  rs_enqueue<HgModel>(s, solve, {pts1, pts2}, n, max_iters, confidence, (float)(threshold * threshold), l.rs, scratch, H_ransac, mask_out,
+  rs_enqueue<HgModel>(s, solve, {pts1, pts2}, n, max_iters, confidence, (float)(threshold * threshold), rs, scratch, H_ransac, mask_out,
                       info_out, hyp_count, {st});
-  hg_pair<HG_CENTROID>(s, l, 0, pts1, pts2, n, mask_out, st, parts, Hc, H_out, info_out);
-  hg_pair<HG_DISTANCE>(s, l, 0, pts1, pts2, n, mask_out, st, parts, Hc, H_out, info_out);
+  const RsPixelPairs pts = {pts1, pts2};
+  const auto pair = [&](auto terms, int stage, int last) {
+    rf_enqueue_pair<decltype(terms)>(s, l, scratch, pts, n, mask_out, hg_finish_kernel, stage, last, Hc, H_out, info_out);
+  };
+  pair(HgTerms<HG_CENTROID>(), HG_CENTROID, 0);
+  pair(HgTerms<HG_DISTANCE>(), HG_DISTANCE, 0);
   // refine_iters = 0: the DLT's finish is the last launch (status 1); else pair j judges step j - 1 and takes step j
-  hg_pair<HG_DLT>(s, l, refine_iters == 0, pts1, pts2, n, mask_out, st, parts, Hc, H_out, info_out);
-  for (int j = 0; refine_iters > 0 && j <= refine_iters; ++j) hg_pair<HG_GN>(s, l, j == refine_iters, pts1, pts2, n, mask_out, st, parts, Hc, H_out, info_out);
+  pair(HgTerms<HG_DLT>(), HG_DLT, refine_iters == 0);
+  for (int j = 0; refine_iters > 0 && j <= refine_iters; ++j) pair(HgTerms<HG_GN>(), HG_GN, j == refine_iters);
   return launched();
 }
 }  // extern "C"

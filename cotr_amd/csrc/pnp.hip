@@ -12,10 +12,10 @@
 //   3. rs_select_kernel<4, 1>   the sequential selection loop replayed on the counts
 //   4. rs_mask_kernel<PnModel>  the chosen candidate's mask; (the model's tail) R_out, t_out, info[4..7], the refit's state
 //      (2 - 4: ransac.h's frame on the model PnModel, as is the sampler of 1)
-//   5. the refit chain, pairs of pn_accum_kernel (per 2048-point chunk: 29 sums over the mask, every thread over its points
-//      in order, every wavefront in a fixed tree, the 4 wavefronts in order -> scratch) and pn_finish_kernel (one
-//      workgroup: the chunks in chunk order, then: accept or undo the last step, take the next).  A device-side flag ends
-//      the chain's work early; its length never depends on the data.
+//   5. the refit chain, pairs of rf_accum_kernel<PnTerms> (per 2048-point chunk: 29 sums over the mask, every thread over
+//      its points in order, every wavefront in a fixed tree, the 4 wavefronts in order -> scratch) and pn_finish_kernel (one
+//      workgroup: the chunks in chunk order, then rf_step: accept or undo the last step, take the next); refit.h's frame.
+//      A device-side flag ends the chain's work early; its length never depends on the data.
 // A candidate is 9 doubles: rows 1 and 2 of R, then t; row 3 is their cross product wherever the candidate is used.
 // No floating-point atomics: the same input gives the same bits.  No host waits, no allocation: capturable.
 // Compiled with -ffp-contract=off.
@@ -27,8 +27,9 @@
 
 #include "camera.h"
 #include "handleless.h"
+#include "pinhole.h"
 #include "ransac.h"
-#include "rodrigues.h"
+#include "refit.h"
 
 using namespace cotr_detail;
 
@@ -40,11 +41,6 @@ using namespace cotr_detail;
 #define PN_VMAX 1e8            // the depth ratios looked at: (0, PN_VMAX)
 #define PN_SAMPLE_TOL 1e-18    // (1e-9 px)^2: a solution must put its three sample points back this close
 
-// fx, skew, cx, fy, cy of an upper-triangular camera matrix
-struct PnCam {
-  double fx, s, cx, fy, cy;
-};
-
 // ---- a candidate ------------------------------------------------------------------------------------------------------
 // m[9] = rows 1 and 2 of R, t -> the camera-space point of X (row 3 of R: the cross product of the two)
 RS_HD __forceinline__ void pn_transform(const double* m, double X, double Y, double Z, double* x, double* y, double* z) {
@@ -55,14 +51,14 @@ RS_HD __forceinline__ void pn_transform(const double* m, double X, double Y, dou
 }
 
 // the pixel of the camera-space point (x, y, z)
-RS_HD __forceinline__ void pn_project(const PnCam& k, double x, double y, double z, double* u, double* v) {
+RS_HD __forceinline__ void pn_project(const EsCam& k, double x, double y, double z, double* u, double* v) {
   const double xn = x / z, yn = y / z;
   *u = (k.fx * xn + k.s * yn) + k.cx;
   *v = k.fy * yn + k.cy;
 }
 
 // squared reprojection error of X against the pixel (u, v); false unless X lies in front of the camera
-RS_HD __forceinline__ bool pn_error(const double* m, const PnCam& k, double X, double Y, double Z, double u, double v, double* err) {
+RS_HD __forceinline__ bool pn_error(const double* m, const EsCam& k, double X, double Y, double Z, double u, double v, double* err) {
   double x, y, z, pu, pv;
   pn_transform(m, X, Y, Z, &x, &y, &z);
   if (!(z > 0.0)) return false;   // also for NaN
@@ -72,22 +68,24 @@ RS_HD __forceinline__ bool pn_error(const double* m, const PnCam& k, double X, d
   return true;
 }
 
-// the model of ransac.h's frame: one candidate per 4-point sample; the tail writes the chosen pose and starts the refit
-struct PnState {
-  double R[9], t[3];           // current pose
-  double Rprev[9], tprev[3];   // the pose before the step on trial
-  double err_prev;             // squared error at the previous pose
-  int done;                    // nothing more to accumulate
-  int kept;                    // Gauss-Newton steps kept
-  int trial;                   // R, t are a step whose error is not known yet
+// the refit's state, in scratch, and the model of refit.h's step: exp([w]x) R, t + dt
+struct PnState : RfPose {
+  static constexpr int PARAMS = 6;
+  // no inlier behind the camera
+  static __device__ __forceinline__ bool acceptable(const PnState*, const double* sums) { return sums[28] == 0.0; }
+  static __device__ __forceinline__ void apply(PnState* st, const double* d) {
+    rotate(st, d);
+    for (int i = 0; i < 3; ++i) st->t[i] = st->t[i] + d[3 + i];
+  }
 };
 
+// the model of ransac.h's frame: one candidate per 4-point sample; the tail writes the chosen pose and starts the refit
 struct PnModel {
   static constexpr int MODEL = PN_MODEL, SLOTS = 1;
   struct Points {
     const double* __restrict__ obj;
     const double* __restrict__ img;
-    double fx, s, cx, fy, cy;
+    EsCam k;
   };
   struct Tail {
     const double* cand;
@@ -100,9 +98,8 @@ struct PnModel {
   static __device__ __forceinline__ bool inlier(const double* m, const Points& pts, int p, float thr) {
     const double* X = pts.obj + (size_t)p * 3;
     const double u = f32r(pts.img[(size_t)p * 2]), v = f32r(pts.img[(size_t)p * 2 + 1]);
-    const PnCam k = {pts.fx, pts.s, pts.cx, pts.fy, pts.cy};
     double err;
-    if (!pn_error(m, k, X[0], X[1], X[2], u, v, &err)) return false;
+    if (!pn_error(m, pts.k, X[0], X[1], X[2], u, v, &err)) return false;
     return (float)err <= thr;   // false for NaN
   }
 
@@ -160,7 +157,7 @@ RS_HD __forceinline__ double pn_clamp(double x, double lo, double hi) { return x
 // orthonormal frame of the object triangle to that of the triangle s_k f_k, and it must put the three sample points back
 // within 1e-9 px.  Of the solutions with the fourth point in front of the camera, the one with the smallest squared
 // reprojection error there (the first of equal ones) -> best[9]; false when there is none.
-RS_HD __forceinline__ bool pn_p3p(const double* Xo, const double* px, const double* py, const PnCam& k, double* best) {
+RS_HD __forceinline__ bool pn_p3p(const double* Xo, const double* px, const double* py, const EsCam& k, double* best) {
   // the object triangle: edges, collinearity, frame
   const double e1x = Xo[3] - Xo[0], e1y = Xo[4] - Xo[1], e1z = Xo[5] - Xo[2];
   const double e2x = Xo[6] - Xo[0], e2y = Xo[7] - Xo[1], e2z = Xo[8] - Xo[2];
@@ -291,7 +288,7 @@ RS_HD __forceinline__ bool pn_p3p(const double* Xo, const double* px, const doub
 }
 
 __global__ __launch_bounds__(RS_SOLVE_THREADS) void pn_solve_kernel(const double* __restrict__ obj, const double* __restrict__ img, int n,
-                                                                    PnCam k, int max_iters, uint64_t seed, double* __restrict__ Pc,
+                                                                    EsCam k, int max_iters, uint64_t seed, double* __restrict__ Pc,
                                                                     int* __restrict__ count, double* __restrict__ hyp_pose,
                                                                     int32_t* __restrict__ hyp_samples) {
   __shared__ int shI[PN_MODEL * RS_SOLVE_THREADS];   // the sample: the sampler indexes it at run time
@@ -332,13 +329,10 @@ __global__ __launch_bounds__(RS_SOLVE_THREADS) void pn_solve_kernel(const double
 }
 
 // ---- the refit ------------------------------------------------------------------------------------------------------------
-// index of (i, j), i <= j, in the row-major upper triangle of a 6 x 6 matrix
-__host__ __device__ constexpr int pn_tri(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
-
 // One inlier's terms at the pose of st, added to acc: J^T J (21), J^T r (6), the squared error, and 1 for a point that is
 // not in front of the camera (which adds nothing else).  The step is exp([w]x) R, t + dt: with P = R X the Jacobian of the
 // camera-space point is [-[P]x | I].
-__device__ __forceinline__ void pn_terms(const PnState* __restrict__ st, const PnCam& k, const double* X, double u, double v, double* acc) {
+__device__ __forceinline__ void pn_terms(const PnState* __restrict__ st, const EsCam& k, const double* X, double u, double v, double* acc) {
   const double* R = st->R;
   const double Px = (R[0] * X[0] + R[1] * X[1]) + R[2] * X[2], Py = (R[3] * X[0] + R[4] * X[1]) + R[5] * X[2],
                Pz = (R[6] * X[0] + R[7] * X[1]) + R[8] * X[2];
@@ -360,101 +354,32 @@ __device__ __forceinline__ void pn_terms(const PnState* __restrict__ st, const P
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
 #pragma unroll
-    for (int j = i; j < 6; ++j) acc[pn_tri(i, j)] += j1[i] * j1[j] + j2[i] * j2[j];
+    for (int j = i; j < 6; ++j) acc[rf_tri<6>(i, j)] += j1[i] * j1[j] + j2[i] * j2[j];
     acc[21 + i] += j1[i] * ru + j2[i] * rv;
   }
   acc[27] += ru * ru + rv * rv;
 }
 
-__global__ __launch_bounds__(RS_COUNT_THREADS) void pn_accum_kernel(const double* __restrict__ obj, const double* __restrict__ img, int n,
-                                                                    PnCam k, const uint8_t* __restrict__ mask,
-                                                                    const PnState* __restrict__ st, double* __restrict__ parts) {
-  __shared__ double sh[RS_COUNT_THREADS / 64][PN_SUMS];
-  if (st->done) return;   // uniform
-  double acc[PN_SUMS];
-#pragma unroll
-  for (int i = 0; i < PN_SUMS; ++i) acc[i] = 0.0;
-  const int base = blockIdx.x * RS_CHUNK;
-#pragma unroll 1
-  for (int s = 0; s < RS_COUNT_STEPS; ++s) {   // every thread: its points in ascending order
-    const int p = base + s * RS_COUNT_THREADS + threadIdx.x;
-    if (p < n && mask[p]) {
-      const double X[3] = {obj[(size_t)p * 3], obj[(size_t)p * 3 + 1], obj[(size_t)p * 3 + 2]};
-      pn_terms(st, k, X, f32r(img[(size_t)p * 2]), f32r(img[(size_t)p * 2 + 1]), acc);
-    }
+// the object point as it is, the pixel rounded to float32
+struct PnTerms {
+  static constexpr int SUMS = PN_SUMS, STRIDE = PN_SUMS;
+  using Points = PnModel::Points;
+  using State = PnState;
+  static __device__ __forceinline__ void terms(const PnState* __restrict__ st, const Points& pts, int p, double* acc) {
+    const double X[3] = {pts.obj[(size_t)p * 3], pts.obj[(size_t)p * 3 + 1], pts.obj[(size_t)p * 3 + 2]};
+    pn_terms(st, pts.k, X, f32r(pts.img[(size_t)p * 2]), f32r(pts.img[(size_t)p * 2 + 1]), acc);
   }
-  // every wavefront: a fixed butterfly (each lane ends with the same bits), then the 4 wavefronts in order
-#pragma unroll
-  for (int i = 0; i < PN_SUMS; ++i) {
-    double a = acc[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a = a + __shfl_xor(a, off);
-    acc[i] = a;
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < PN_SUMS; ++i) sh[threadIdx.x >> 6][i] = acc[i];
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < PN_SUMS) {
-    double a = sh[0][threadIdx.x];
-    for (int w = 1; w < RS_COUNT_THREADS / 64; ++w) a = a + sh[w][threadIdx.x];
-    parts[(size_t)blockIdx.x * PN_SUMS + threadIdx.x] = a;
-  }
-}
+};
 
 // the sums of the accumulate before it: judges the step on trial, takes the next one;
 // last: the chain's last launch (no further step is taken; writes R_out, t_out and info[4])
-__global__ __launch_bounds__(64) void pn_finish_kernel(int chunks, int last, const double* __restrict__ parts, PnState* __restrict__ st,
+__global__ __launch_bounds__(64) void pn_finish_kernel(int chunks, const double* __restrict__ parts, PnState* __restrict__ st, int last,
                                                        double* __restrict__ R_out, double* __restrict__ t_out, int32_t* __restrict__ info) {
   __shared__ double sums[PN_SUMS];
-  __shared__ double S6[42];
-  __shared__ int P6[6];
-  const int tid = threadIdx.x;
   const bool active = !st->done;   // uniform; read before anything below writes it
-  if (active && tid < PN_SUMS) {
-    double a = 0.0;
-    for (int c = 0; c < chunks; ++c) a = a + parts[(size_t)c * PN_SUMS + tid];   // the chunks in chunk order
-    sums[tid] = a;
-  }
-  __syncthreads();
-  if (tid != 0) return;
-  if (active) {
-    const double err = sums[27];
-    const bool front = sums[28] == 0.0;
-    bool go_on = true;
-    if (st->trial) {
-      if (front && err < st->err_prev) {
-        st->kept = st->kept + 1;
-      } else {   // not smaller (or NaN), or an inlier behind the camera: undo the step, the refinement ends
-        for (int i = 0; i < 9; ++i) st->R[i] = st->Rprev[i];
-        for (int i = 0; i < 3; ++i) st->t[i] = st->tprev[i];
-        go_on = false;
-      }
-      st->trial = 0;
-    }
-    if (go_on && !last) {
-      for (int i = 0; i < 6; ++i) {
-        for (int j = i; j < 6; ++j) S6[i * 7 + j] = S6[j * 7 + i] = sums[pn_tri(i, j)];
-        S6[i * 7 + 6] = -sums[21 + i];
-      }
-      double d[6];
-      if (rs_solve<6, 1>(S6, P6, d)) {
-        for (int i = 0; i < 9; ++i) st->Rprev[i] = st->R[i];
-        for (int i = 0; i < 3; ++i) st->tprev[i] = st->t[i];
-        st->err_prev = err;
-        double R[9];
-        for (int i = 0; i < 9; ++i) R[i] = st->R[i];
-        rodrigues_rotate(d, R);
-        for (int i = 0; i < 9; ++i) st->R[i] = R[i];
-        for (int i = 0; i < 3; ++i) st->t[i] = st->t[i] + d[3 + i];
-        st->trial = 1;
-      } else {
-        go_on = false;   // singular system
-      }
-    }
-    if (!go_on || last) st->done = 1;
-  }
+  rf_reduce<PN_SUMS>(parts, chunks, active ? PN_SUMS : 0, sums);
+  if (threadIdx.x != 0) return;
+  if (active) rf_step(st, sums, last);
   if (last) {
     const int found = info[0];
     for (int i = 0; i < 9; ++i) R_out[i] = found ? st->R[i] : 0.0;
@@ -466,7 +391,7 @@ __global__ __launch_bounds__(64) void pn_finish_kernel(int chunks, int last, con
 // ---- the lift -------------------------------------------------------------------------------------------------------------
 // One thread per point: the depth at the pixel the point falls in (ties to even), X = z K^-1 (x, y, 1) with the point as
 // it is, then c2w (rows as in camera.h) when given; three NaN outside the map or without a finite depth > 0.
-__global__ __launch_bounds__(256) void pn_lift_kernel(const float* __restrict__ depth, int H, int W, PnCam k, const double* __restrict__ c2w,
+__global__ __launch_bounds__(256) void pn_lift_kernel(const float* __restrict__ depth, int H, int W, EsCam k, const double* __restrict__ c2w,
                                                       const double* __restrict__ pts, int n, double* __restrict__ out) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
@@ -495,29 +420,7 @@ namespace {
 const RsEntry PN_ENTRY = {"cotr_ransac_pnp", "R_out", PN_MODEL, "", PnModel::SLOTS, RS_MAX_ITERS};
 
 // after the frame's candidates and counts: the refit's state, then its partial sums [chunks, PN_SUMS]
-struct PnPlan {
-  RsPlan rs;
-  size_t state, parts, bytes;
-  int chunks;
-};
-
-PnPlan pn_plan(int n, int max_iters) {
-  PnPlan l;
-  l.rs = rs_plan(PN_ENTRY, max_iters);
-  l.chunks = (n + RS_CHUNK - 1) / RS_CHUNK;
-  l.state = l.rs.bytes;
-  l.parts = l.state + align_up(sizeof(PnState));
-  l.bytes = l.parts + align_up((size_t)l.chunks * PN_SUMS * sizeof(double));
-  return l;
-}
-
-// the camera of an upper-triangular K (row-major 9 doubles, on the host); false unless fx and fy are finite and non-zero and
-// the rest is finite
-bool pn_camera(const double* K, PnCam* c) {
-  c->fx = K[0], c->s = K[1], c->cx = K[2], c->fy = K[4], c->cy = K[5];
-  const bool finite = isfinite(c->fx) && isfinite(c->fy) && isfinite(c->cx) && isfinite(c->cy) && isfinite(c->s);
-  return finite && c->fx != 0.0 && c->fy != 0.0;
-}
+RfPlan pn_plan(const RsPlan& rs, int n) { return rf_plan(rs.bytes, sizeof(PnState), n, PN_SUMS); }
 
 }  // namespace
 
@@ -528,8 +431,8 @@ int cotr_lift_pixels(const float* depth, int H, int W, const double* K, const do
   if (H < 1 || W < 1 || (long long)H * W > MAX_PIXELS) return handleless_fail(COTR_ERR_ARG, "cotr_lift_pixels: H and W must be >= 1 with at most 2^28 pixels");
   if (n < 1 || n > RS_MAX_POINTS) return handleless_fail(COTR_ERR_ARG, "cotr_lift_pixels: n must be in [1, 2^24]");
   if (!depth || !K || !points || !out) return handleless_fail(COTR_ERR_ARG, "cotr_lift_pixels: depth, K, points and out must not be NULL");
-  PnCam k;
-  if (!pn_camera(K, &k)) return handleless_fail(COTR_ERR_ARG, "cotr_lift_pixels: the camera matrix must be finite with focal lengths that are not 0");
+  EsCam k;
+  if (!es_camera(K, &k)) return handleless_fail(COTR_ERR_ARG, "cotr_lift_pixels: the camera matrix must be finite with focal lengths that are not 0");
   if (!aligned(depth, 4) || !aligned(c2w, 8) || !aligned(points, 8) || !aligned(out, 8))
     return handleless_fail(COTR_ERR_ARG, "cotr_lift_pixels: floats must be 4-byte and doubles 8-byte aligned");
   hipLaunchKernelGGL(pn_lift_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), depth, H, W, k, c2w,
@@ -539,41 +442,39 @@ int cotr_lift_pixels(const float* depth, int H, int W, const double* K, const do
 
 int cotr_ransac_pnp_scratch_bytes(int n, int max_iters, size_t* bytes) {
   if (const int rc = rs_scratch_bytes(PN_ENTRY, n, max_iters, bytes)) return rc;
-  *bytes = pn_plan(n, max_iters).bytes;
+  *bytes = pn_plan(rs_plan(PN_ENTRY, max_iters), n).bytes;
   return COTR_OK;
 }
 
 int cotr_ransac_pnp(const double* object_points, const double* image_points, int n, const double* K, double threshold, double confidence,
                     int max_iters, uint64_t seed, int refine_iters, double* R_out, double* t_out, uint8_t* mask_out, int32_t* info_out,
                     double* hyp_pose, int32_t* hyp_count, int32_t* hyp_samples, void* scratch, size_t scratch_bytes, cotr_stream stream) {
-  const PnPlan l = pn_plan(n, max_iters);
+  const RsPlan rs = rs_plan(PN_ENTRY, max_iters);
+  const RfPlan l = pn_plan(rs, n);
   if (const int rc = rs_check_call(PN_ENTRY, n, max_iters, threshold, confidence, object_points, image_points, R_out, mask_out, info_out,
                                    hyp_pose, hyp_count, hyp_samples, scratch, scratch_bytes, l.bytes))
     return rc;
   if (!K || !t_out) return rs_fail(PN_ENTRY, "K and t_out must not be NULL");
   if (!aligned(t_out, 8)) return rs_fail(PN_ENTRY, "t_out must be 8-byte aligned");
   if (refine_iters < 0 || refine_iters > PN_MAX_REFINE) return rs_fail(PN_ENTRY, "refine_iters must be in [0, 64]");
-  PnCam k;
-  if (!pn_camera(K, &k)) return rs_fail(PN_ENTRY, "the camera matrix must be finite with focal lengths that are not 0");
+  EsCam k;
+  if (!es_camera(K, &k)) return rs_fail(PN_ENTRY, "the camera matrix must be finite with focal lengths that are not 0");
   const float thr = (float)(threshold * threshold);
   if (!(thr > 0.0f) || !(thr < INFINITY)) return rs_fail(PN_ENTRY, "the squared threshold must be a finite float32 that is not 0");
   char* base = static_cast<char*>(scratch);
-  const double* Pc = reinterpret_cast<const double*>(base + l.rs.candidates);
+  const double* Pc = reinterpret_cast<const double*>(base + rs.candidates);
   PnState* st = reinterpret_cast<PnState*>(base + l.state);
-  double* parts = reinterpret_cast<double*>(base + l.parts);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const auto solve = [&](double* cand, int* count) {
     hipLaunchKernelGGL(pn_solve_kernel, dim3((unsigned)((max_iters + RS_SOLVE_THREADS - 1) / RS_SOLVE_THREADS)), dim3(RS_SOLVE_THREADS), 0, s,
                        object_points, image_points, n, k, max_iters, seed, cand, count, hyp_pose, hyp_samples);
   };
-  rs_enqueue<PnModel>(s, solve, {object_points, image_points, k.fx, k.s, k.cx, k.fy, k.cy}, n, max_iters, confidence, thr, l.rs, scratch,
-                      nullptr, mask_out, info_out, hyp_count, {Pc, info_out, R_out, t_out, st});
+  const PnModel::Points pts = {object_points, image_points, k};
+  rs_enqueue<PnModel>(s, solve, pts, n, max_iters, confidence, thr, rs, scratch, nullptr, mask_out, info_out, hyp_count,
+                      {Pc, info_out, R_out, t_out, st});
   // pair j judges step j - 1 and takes step j; the last one takes none
-  for (int j = 0; refine_iters > 0 && j <= refine_iters; ++j) {
-    hipLaunchKernelGGL(pn_accum_kernel, dim3((unsigned)l.chunks), dim3(RS_COUNT_THREADS), 0, s, object_points, image_points, n, k, mask_out, st,
-                       parts);
-    hipLaunchKernelGGL(pn_finish_kernel, dim3(1), dim3(64), 0, s, l.chunks, j == refine_iters, parts, st, R_out, t_out, info_out);
-  }
+  for (int j = 0; refine_iters > 0 && j <= refine_iters; ++j)
+    rf_enqueue_pair<PnTerms>(s, l, scratch, pts, n, mask_out, pn_finish_kernel, (int)(j == refine_iters), R_out, t_out, info_out);
   return launched();
 }
 

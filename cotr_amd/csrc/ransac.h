@@ -5,8 +5,9 @@
 //   inlier(m, pts, p, thr)   whether point p is an inlier of the candidate m[9]
 //   Tail, tail(t, found)     what thread 0 of the mask kernel does besides, with its arguments
 // and a solve kernel of its own that fills the SLOTS * max_iters slots (a slot without a candidate: NaN, count -1).  Shared
-// here: the counter-based sampler, the sample's Hartley normalisation, the full-pivot elimination with its solve and
-// null-vector forms, the scaling rule of a 3 x 3 result, rs_count_kernel<M>, OpenCV's iteration update, the kernel that
+// here: the counter-based sampler, the wavefront sum of the refits (refit.h), the sample's Hartley normalisation, the
+// full-pivot elimination with its solve and null-vector forms, the scaling rule of a 3 x 3 result, rs_count_kernel<M>,
+// OpenCV's iteration update, the kernel that
 // replays the sequential selection loop on the counts, rs_mask_kernel<M>, the cyclic Jacobi iteration of the symmetric
 // eigenproblems, and on the host the scratch prefix, the argument checks and the launch sequence.  Rules in DESIGN.md 3h.
 // Included by translation units compiled with -ffp-contract=off.
@@ -40,6 +41,13 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
 }
 
 __device__ __forceinline__ double f32r(double v) { return (double)(float)v; }
+
+// the sum over a wavefront by a fixed butterfly: every lane ends with the same bits
+__device__ __forceinline__ double rs_wave_sum(double a) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) a = a + __shfl_xor(a, off);
+  return a;
+}
 
 // Sample of iteration it: draw d is splitmix64(splitmix64(seed) ^ (it << 6 | d)), index (z >> 32) % n; duplicates are
 // rejected; the first MODEL distinct indices of at most RS_MAX_DRAWS draws go to s[k * stride].  Returns how many it got.
