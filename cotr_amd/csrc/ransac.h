@@ -1,5 +1,5 @@
 // The frame of the RANSAC estimators (guided.hip: fundamental matrix, homography.hip: homography, essential.hip: essential
-// matrix).  A model is a struct M with
+// matrix, pnp.hip: absolute pose, rigid3d.hip: 3D-3D registration).  A model is a struct M with
 //   MODEL, SLOTS      sample size, candidate slots per iteration (slot = SLOTS * it + k)
 //   Points            what its kernels read the correspondences from, passed to them by value
 //   inlier(m, pts, p, thr)   whether point p is an inlier of the candidate m[9]

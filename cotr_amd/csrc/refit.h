@@ -1,5 +1,6 @@
 // The frame of the Gauss-Newton refits on the inliers (homography.hip, pnp.hip, essential.hip: cotr_refine_pose): pairs of
 // rf_accum_kernel<T> and the estimator's own finish kernel, which is rf_reduce + rf_step + its epilogue.  Rules in DESIGN.md 3h.
+// rigid3d.hip uses the accumulate / reduce half alone, with two terms policies a round: its refit is a closed form, not a step.
 // A terms policy T is a struct with
 //   SUMS, STRIDE      the sums one launch makes, the row length of the per-chunk sums `parts` (>= SUMS)
 //   Points, State     what the kernel reads the points from (by value), the refit's state in scratch

@@ -25,12 +25,16 @@ of a point that agree are voted on, the point is refitted on its reprojection er
 after ``relative_pose`` or ``localize``, ``stack_views`` shapes one query set matched against several images for it, and
 ``ZoomEngine.reconstruct`` is demo_reconstruction.py up to its viewer.  ``bundle_adjust`` refines the poses of such views and
 their points together (Levenberg-Marquardt by the Schur complement, one device call), ``bundle_adjust_tensors`` the same with device
-tensors, and ``reconstruct(..., bundle_rounds=2)`` runs it after the triangulation."""
+tensors, and ``reconstruct(..., bundle_rounds=2)`` runs it after the triangulation.  ``register_points`` is the robust absolute
+orientation of 3D-3D correspondences (3-point RANSAC on Horn's closed form, a closed-form refit on the inliers; a similarity with
+``with_scale=True``), ``ransac_rigid3d`` the same with device tensors, and ``register_captures`` / ``ZoomEngine.register`` the
+metric pose of one RGB-D capture against another from both depth maps."""
 from .bundle import bundle_adjust, bundle_adjust_tensors
 from .essential import find_essential_mat, ransac_essential, recover_pose, refine_pose_tensors, refine_relative_pose, relative_pose
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .homography import find_homography, paste_by_homography, ransac_homography
 from .pnp import lift_pixels, localize, ransac_pnp, rodrigues, solve_pnp_ransac
+from .rigid3d import ransac_rigid3d, register_captures, register_captures_tensors, register_points
 from .structure import reconstruct_tensors, stack_views, triangulate_points, triangulate_points_tensors, triangulate_views
 from .triangulate import delaunay, triangulate_corr
 from .warp import get_perspective_transform, paste_by_corners, warp_by_corr, warp_by_map, warp_perspective
@@ -43,4 +47,5 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'refine_pose_tensors', 'refine_relative_pose',
            'lift_pixels', 'ransac_pnp', 'solve_pnp_ransac', 'rodrigues', 'localize',
            'triangulate_views', 'triangulate_points', 'triangulate_points_tensors', 'stack_views', 'reconstruct_tensors',
-           'bundle_adjust', 'bundle_adjust_tensors']
+           'bundle_adjust', 'bundle_adjust_tensors',
+           'ransac_rigid3d', 'register_points', 'register_captures', 'register_captures_tensors']

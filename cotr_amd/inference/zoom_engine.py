@@ -734,6 +734,25 @@ class ZoomEngine:
         c2w_b, mask = localize(corrs[:, :2], corrs[:, 2:], cap_a, K_b, **ransac_kw)
         return c2w_b, corrs, mask
 
+    def register(self, cap_a, cap_b, queries_a=None, zoom_ins=np.linspace(0.5, 0.0625, 4), converge_iters=1, max_corrs=1000, **ransac_kw):
+        """The metric pose of the RGB-D capture ``cap_b`` against the posed RGB-D capture ``cap_a`` (``cotr_amd.data.Capture``:
+        image, depth, K, c2w; the pose of ``cap_b`` is not read): ``cotr_corr_multiscale`` from A's image into B's (from
+        ``queries_a`` [N, 2] with force=True, or from the engine's own grid when None), then ``register_captures`` on them: both
+        sides lifted through their depth maps, 3-point RANSAC on the rigid motion between the two clouds and its refit ->
+        (c2w_b float64 [4,4] in the world frame of ``cap_a``, corrs [K, 4], mask uint8 [K, 1]: the inliers); c2w_b and mask are
+        None when no model is found.  ``ransac_kw``: threshold (0.05, in the depth maps' units), confidence (0.99), max_iters
+        (100), seed (0), with_scale (False), rounds (2).  Fewer than 3 correspondences: ValueError."""
+        from .rigid3d import register_captures
+        if queries_a is None:
+            corrs = self.cotr_corr_multiscale(cap_a.image, cap_b.image, zoom_ins, converge_iters, max_corrs=max_corrs)
+        else:
+            queries_a = np.asarray(queries_a)
+            corrs = self.cotr_corr_multiscale(cap_a.image, cap_b.image, zoom_ins, converge_iters, max_corrs=max_corrs, queries_a=queries_a,
+                                              force=True)
+        corrs = np.asarray(corrs)
+        c2w_b, mask = register_captures(corrs[:, :2], corrs[:, 2:], cap_a, cap_b, **ransac_kw)
+        return c2w_b, corrs, mask
+
     def reconstruct(self, img_a, img_b, K_a, K_b, c2w_a=None, c2w_b=None, queries_a=None, zoom_ins=np.linspace(0.5, 0.0625, 4),
                     converge_iters=1, max_corrs=1000, rule='rays', pose_kw=None, bundle_rounds=0, **structure_kw):
         """demo_reconstruction.py up to its viewer: ``cotr_corr_multiscale`` from A into B (from ``queries_a`` [N, 2] with

@@ -623,6 +623,40 @@ int cotr_ransac_pnp(const double* object_points, const double* image_points, int
                     uint8_t* mask_out, int32_t* info_out, double* hyp_pose, int32_t* hyp_count, int32_t* hyp_samples,
                     void* scratch, size_t scratch_bytes, cotr_stream stream);
 
+/* ---- 3D-3D registration: rigid and similarity RANSAC with a closed-form refit (cotr_amd/csrc/rigid3d.hip) ----------------
+ * Robust absolute orientation (Kabsch / Horn / Umeyama) of n corresponding 3D points, by rules of the library's own
+ * (DESIGN.md 3h-8).  y = s R x + t.
+ *
+ * cotr_ransac_rigid3d: src [n,3], dst [n,3] float64 DEVICE pointers, taken as they are -> R_out [9] (row-major), t_out [3],
+ *   scale_out [1] float64, mask_out [n] uint8, info_out [8] int32 = {found, best inlier count, sequential iterations run,
+ *   chosen slot (-1: none), refit rounds run, points in mask_out, 0, 0}; every output is 0 when nothing is found.
+ *   Iteration it draws 3 distinct indices with the sampler of cotr_ransac_fundamental and solves Horn's closed form on the
+ *   three pairs: the centroids, the centred 3 x 3 cross-covariance, the symmetric 4 x 4 matrix N of the quaternion method,
+ *   the eigenvector of its first largest eigenvalue by cyclic Jacobi -> R (a proper rotation by construction); with_scale =
+ *   1: s = sum (R a').b' / sum |a'|^2, finite and > 0; with_scale = 0: s = 1 exactly; t = cb - s R ca.  No candidate: a
+ *   short draw, a NaN among the six points, a sample on a line in src or in dst (|e1 x e2| <= 1e-12 |e1| |e2|), the two
+ *   largest eigenvalues of N not separated (l1 - l2 <= 1e-12 l1).  A candidate is 9 doubles: rows 1 and 2 of s R, then t;
+ *   s = |row 1| and row 3 = (row 1 x row 2) / s (with_scale = 0: s = 1, row 3 = row 1 x row 2).  The candidates are counted
+ *   in parallel and the sequential RANSAC loop is replayed on the counts.  An inlier has float(|s R x + t - y|^2) <=
+ *   float(threshold^2), the threshold in dst's units; a pair with a NaN never is one.  rounds = 0: the outputs are the
+ *   chosen candidate bit for bit (R_out = s R / s) and mask_out its inliers.  rounds > 0: round 1 fits the closed form on
+ *   the RANSAC mask (two passes: the centroids, then the centred moments); each later round first re-counts the inliers of
+ *   the current model among all n points and fits on those.  A round whose mask holds fewer than 3 points or whose moments
+ *   are degenerate is skipped: the model stays and no later round runs.  mask_out is the mask the last executed round
+ *   fitted on.  3 <= n <= 2^24, 1 <= max_iters <= 65536, threshold > 0 finite with a finite non-zero float32 square,
+ *   0 < confidence < 1, with_scale 0 or 1, 0 <= rounds <= 8.
+ *   hyp_model [max_iters][9] float64, hyp_count [max_iters] int32 (-1: no candidate; its entries are NaN), hyp_samples
+ *   [max_iters][3] int32 (-1 past the indices drawn): optional DEVICE outputs (NULL: not written).
+ *   scratch: DEVICE, 16-byte aligned, at least cotr_ransac_rigid3d_scratch_bytes(n, max_iters) bytes.
+ * Stream-ordered, 4 launches with rounds = 0 and 4 + 4 + 6 (rounds - 1) otherwise, whatever the data, no host waits and no
+ * allocation (capturable); integer atomics only, sums in a fixed order: the same input gives the same bits.  Bad arguments
+ * are checked before any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_ransac_rigid3d_scratch_bytes(int n, int max_iters, size_t* bytes);
+int cotr_ransac_rigid3d(const double* src, const double* dst, int n, double threshold, double confidence, int max_iters,
+                        uint64_t seed, int with_scale, int rounds, double* R_out, double* t_out, double* scale_out,
+                        uint8_t* mask_out, int32_t* info_out, double* hyp_model, int32_t* hyp_count, int32_t* hyp_samples,
+                        void* scratch, size_t scratch_bytes, cotr_stream stream);
+
 /* ---- structure from known cameras: robust N-view triangulation (cotr_amd/csrc/structure.hip; rules in DESIGN.md 3h-6) ----
  * n correspondences seen in V posed views -> their 3D points, the views each point was fitted on, and the per-point
  * figures a reconstruction filters on.  The rules are the library's own.
