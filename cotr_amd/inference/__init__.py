@@ -28,11 +28,14 @@ their points together (Levenberg-Marquardt by the Schur complement, one device c
 tensors, and ``reconstruct(..., bundle_rounds=2)`` runs it after the triangulation.  ``register_points`` is the robust absolute
 orientation of 3D-3D correspondences (3-point RANSAC on Horn's closed form, a closed-form refit on the inliers; a similarity with
 ``with_scale=True``), ``ransac_rigid3d`` the same with device tensors, and ``register_captures`` / ``ZoomEngine.register`` the
-metric pose of one RGB-D capture against another from both depth maps."""
+metric pose of one RGB-D capture against another from both depth maps.  ``icp_depth`` refines a rigid motion on every pixel of two
+depth maps (projective association, point-to-plane Gauss-Newton), ``refine_registration`` the same on two captures, and
+``register_captures(..., icp_iters=10)`` runs it behind the sparse registration."""
 from .bundle import bundle_adjust, bundle_adjust_tensors
 from .essential import find_essential_mat, ransac_essential, recover_pose, refine_pose_tensors, refine_relative_pose, relative_pose
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .homography import find_homography, paste_by_homography, ransac_homography
+from .icp import icp_depth, refine_registration
 from .pnp import lift_pixels, localize, ransac_pnp, rodrigues, solve_pnp_ransac
 from .rigid3d import ransac_rigid3d, register_captures, register_captures_tensors, register_points
 from .structure import reconstruct_tensors, stack_views, triangulate_points, triangulate_points_tensors, triangulate_views
@@ -48,4 +51,5 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'lift_pixels', 'ransac_pnp', 'solve_pnp_ransac', 'rodrigues', 'localize',
            'triangulate_views', 'triangulate_points', 'triangulate_points_tensors', 'stack_views', 'reconstruct_tensors',
            'bundle_adjust', 'bundle_adjust_tensors',
-           'ransac_rigid3d', 'register_points', 'register_captures', 'register_captures_tensors']
+           'ransac_rigid3d', 'register_points', 'register_captures', 'register_captures_tensors',
+           'icp_depth', 'refine_registration']

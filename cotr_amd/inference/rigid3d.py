@@ -13,6 +13,7 @@ import torch
 from .. import _lib
 from .._lib import check_op, on, ptr
 from . import _ransac
+from . import icp as _icp
 from ._ransac import _device
 from .essential import _camera
 from .pnp import _check_depth, _enqueue_lift, _image_points, _pose_matrix
@@ -102,11 +103,15 @@ def register_points(src, dst, threshold, confidence=0.99, max_iters=100, seed=0,
 
 
 def register_captures_tensors(points_a, points_b, depth_a, K_a, c2w_a, depth_b, K_b, threshold=0.05, confidence=0.99, max_iters=100, seed=0,
-                              with_scale=False, rounds=2, device=None):
+                              with_scale=False, rounds=2, icp_iters=0, icp_max_dist=None, device=None):
     """Two ``cotr_lift_pixels`` calls (A's pixels through ``c2w_a`` into the world frame, B's into B's camera frame) and
     ``cotr_ransac_rigid3d`` with src = B's points, enqueued back to back on the current stream with no host round trip
     between them -> the dict of ``ransac_rigid3d`` (world = scale R x_b + t) with points_world [n,3] and points_cam_b [n,3]
-    besides.  A point without depth on either side is NaN and never an inlier."""
+    besides.  A point without depth on either side is NaN and never an inlier.  ``icp_iters`` > 0: ``cotr_icp_depth`` on both
+    depth maps is the next call of the same sequence, started from the sparse result and gated by its info[0]
+    (``icp_max_dist``: the association distance, the RANSAC ``threshold`` unless given; the other arguments at the defaults
+    of ``icp_depth``): R and t are then the refined pose, R_sparse and t_sparse the sparse one, icp the dict of ``icp_depth``
+    (all 0 when no model was found).  Not with ``with_scale``."""
     pa, pb = _image_points(points_a, 'points_a'), _image_points(points_b, 'points_b')
     n = pa.shape[0]
     _count(n, pb.shape[0], 'points_a', 'points_b')
@@ -115,6 +120,15 @@ def register_captures_tensors(points_a, points_b, depth_a, K_a, c2w_a, depth_b, 
     ka, kb = _camera(K_a, 'K_a'), _camera(K_b, 'K_b')
     m = _pose_matrix(c2w_a)
     _check(threshold, confidence, max_iters, with_scale, rounds)
+    if not 0 <= icp_iters <= _icp.MAX_ITERS or int(icp_iters) != icp_iters:
+        raise ValueError(f'icp_iters must be an integer in [0, {_icp.MAX_ITERS}], got {icp_iters}')
+    if icp_iters > 0:
+        if with_scale:
+            raise ValueError('icp_iters > 0 refines a rigid motion: not together with with_scale')
+        icp_max_dist = threshold if icp_max_dist is None else icp_max_dist
+        _icp._check_map(depth_a, 'depth_a')
+        _icp._check_map(depth_b, 'depth_b')
+        _icp._check(icp_max_dist, 0.5, 0.05, 1e-6, icp_iters, 1)
     _no_cpu_tensors(points_a, points_b, depth_a, depth_b)
     device = _device(device)
     pa, pb, depth_a, depth_b = on(pa, device), on(pb, device), on(depth_a, device), on(depth_b, device)
@@ -124,6 +138,11 @@ def register_captures_tensors(points_a, points_b, depth_a, K_a, c2w_a, depth_b, 
         world = _enqueue_lift(lib, pa, n, depth_a, ka, m, device)
         cam_b = _enqueue_lift(lib, pb, n, depth_b, kb, None, device)
         r = _enqueue_rigid3d(lib, cam_b, world, n, threshold, confidence, max_iters, seed, with_scale, rounds, False, device)
+        if icp_iters > 0:
+            d = _icp._enqueue_icp(lib, depth_a, ka, depth_b, kb, r['R'], r['t'], m, r['info'], None, icp_max_dist, 0.5, 0.05, 1e-6,
+                                  icp_iters, 1, False, device)
+            r['R_sparse'], r['t_sparse'], r['icp'] = r['R'], r['t'], d
+            r['R'], r['t'] = d['R'], d['t']
     r['points_world'] = world
     r['points_cam_b'] = cam_b
     return r
@@ -136,7 +155,8 @@ def register_captures(points_a, points_b, cap_a, cap_b, **ransac_kw):
     read), and the rigid motion between the two clouds is estimated, as one device sequence -> (c2w_b float64 [4,4] in the
     world frame of ``cap_a``; mask uint8 [n,1]), or (None, None) when no model is found.  ``ransac_kw``: threshold (0.05, in
     the depth maps' units), confidence (0.99), max_iters (100), seed (0), with_scale (False; True keeps the scaled rotation
-    in c2w_b), rounds (2)."""
+    in c2w_b), rounds (2), icp_iters (0; above 0 the pose is refined on both depth maps by that many point-to-plane steps of
+    ``icp_depth`` within the same device sequence), icp_max_dist (the threshold)."""
     r = register_captures_tensors(points_a, points_b, cap_a.depth, cap_a.K, cap_a.c2w, cap_b.depth, cap_b.K, **ransac_kw)
     if not r['info'].cpu().numpy()[0]:
         return None, None

@@ -741,7 +741,8 @@ class ZoomEngine:
         sides lifted through their depth maps, 3-point RANSAC on the rigid motion between the two clouds and its refit ->
         (c2w_b float64 [4,4] in the world frame of ``cap_a``, corrs [K, 4], mask uint8 [K, 1]: the inliers); c2w_b and mask are
         None when no model is found.  ``ransac_kw``: threshold (0.05, in the depth maps' units), confidence (0.99), max_iters
-        (100), seed (0), with_scale (False), rounds (2).  Fewer than 3 correspondences: ValueError."""
+        (100), seed (0), with_scale (False), rounds (2), icp_iters (0; above 0 the dense point-to-plane refinement on both depth
+        maps follows), icp_max_dist (the threshold).  Fewer than 3 correspondences: ValueError."""
         from .rigid3d import register_captures
         if queries_a is None:
             corrs = self.cotr_corr_multiscale(cap_a.image, cap_b.image, zoom_ins, converge_iters, max_corrs=max_corrs)

@@ -657,6 +657,51 @@ int cotr_ransac_rigid3d(const double* src, const double* dst, int n, double thre
                         uint8_t* mask_out, int32_t* info_out, double* hyp_model, int32_t* hyp_count, int32_t* hyp_samples,
                         void* scratch, size_t scratch_bytes, cotr_stream stream);
 
+/* ---- dense registration of two depth maps: point-to-plane ICP (cotr_amd/csrc/icp.hip; rules in DESIGN.md 3h-9) -----------
+ * Projective data association with a point-to-plane Gauss-Newton step, by rules of the library's own.  x_a = R x_b + t.
+ *
+ * cotr_icp_depth: depth_a [Ha,Wa], depth_b [Hb,Wb] float32 DEVICE; K_a, K_b HOST, 9 doubles each as in cotr_lift_pixels;
+ *   R0 [9], t0 [3] float64 DEVICE, the start (they may be the outputs of cotr_ransac_rigid3d); c2w_a [16] float64 DEVICE or
+ *   NULL: NULL, the poses are x_a = R x_b + t in A's camera frame; given, the start and the result map B's camera frame to
+ *   the world frame, and the start is taken into A's camera frame with the rigid inverse (R_a^T, -R_a^T t_a) and the result
+ *   back.  found: int32 DEVICE or NULL; found[0] == 0: every output is 0 (assoc_out -1) and the chain idles.  src_mask
+ *   [Hb,Wb] uint8 DEVICE or NULL: only source pixels whose entry is not 0 may be used.
+ *   Maps, of both captures: the vertex of pixel (x, y) is cotr_lift_pixels' point of (x, y) without c2w, NaN where the
+ *   depth is not finite and > 0.  The normal of an interior pixel is (V(x+1,y) - V(x-1,y)) x (V(x,y+1) - V(x,y-1)) over
+ *   its norm, negated when n . V > 0; it exists only when all five depths are valid, each of the four neighbours has
+ *   |z_nb - z| <= edge z, and the norm is > 0.  Border pixels have none.
+ *   One evaluation at (R, t), over the source pixels x % stride == 0 and y % stride == 0 of B in row-major order: a pixel
+ *   makes a pair when, in this order, it has a normal and src_mask admits it; Y = R X_b + t has Y_z > 0; (rint u, rint v)
+ *   (ties to even) of u = (fx xn + skew yn) + cx, v = fy yn + cy, xn = Y_x / Y_z, yn = Y_y / Y_z through K_a lies inside
+ *   A; A has a normal n_a there; |Y - V_a|^2 <= max_dist^2; (R n_b) . n_a >= normal_cos.  Its residual is r = n_a . (Y -
+ *   V_a), its Jacobian row over (w, dt) of R <- exp([w]x) R, t <- t + dt is ((R X_b) x n_a, n_a).  29 sums in a fixed
+ *   order: the upper triangle of J^T J row-major (21), J^T r (6), sum r^2, the pairs.
+ *   The chain stops and the pose stays when the pairs are fewer than 6 (stop reason 1), a sum is not finite (3), or the
+ *   normal matrix is ill-conditioned (2): its eigenvalues by cyclic Jacobi, l_min <= cond_tol l_max.  Otherwise the step
+ *   -V diag(1 / l) V^T (J^T r) is taken, every time: the pairs change with the pose, so no fall of an error is asked for.
+ *   iters steps at most, iters + 1 evaluations; the last only evaluates.
+ *   -> R_out [9] (row-major), t_out [3] float64; info_out [8] int32 = {ok: ran all its evaluations, steps taken, pairs at
+ *   the returned pose, stop reason (0: ran all), source pixels that have a normal and are admitted by src_mask, pixels of
+ *   A with a normal, 0, 0}; stats_out [2] float64 = {sum r^2, sqrt(sum r^2 / pairs)} at the returned pose.
+ *   Optional DEVICE outputs (NULL: not written): hist_out [iters + 1][32] float64, the 29 sums of every evaluation, then
+ *   l_min, l_max (0 where no step was solved for) and 0; rows after a stop are 0.  assoc_out [n_src] int32, n_src =
+ *   ceil(Hb / stride) ceil(Wb / stride): for the evaluation at the returned pose, the pixel index of A paired with each
+ *   source pixel, or -1.  maps_a_out [Ha Wa][6], maps_b_out [Hb Wb][6] float64: vertex, then normal, of every pixel.
+ *   3 <= H, W and H W <= 2^28 on both sides, 1 <= stride <= 64, 0 <= iters <= 64, max_dist > 0 finite, -1 <= normal_cos
+ *   <= 1, edge > 0 finite, 0 < cond_tol < 1.
+ *   scratch: DEVICE, 16-byte aligned, at least cotr_icp_depth_scratch_bytes(Ha, Wa, Hb, Wb, stride) bytes.
+ * Stream-ordered, 3 + 2 (iters + 1) launches whatever the data (a prologue, the two maps, iters + 1 pairs of accumulate and
+ * finish; the last finish is the epilogue), no host waits and no allocation (capturable); integer atomics only, sums in a
+ * fixed order: the same input gives the same bits.  Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the
+ * message in cotr_raster_last_error(). */
+int cotr_icp_depth_scratch_bytes(int Ha, int Wa, int Hb, int Wb, int stride, size_t* bytes);
+int cotr_icp_depth(const float* depth_a, int Ha, int Wa, const double* K_a, const float* depth_b, int Hb, int Wb,
+                   const double* K_b, const double* R0, const double* t0, const double* c2w_a, const int32_t* found,
+                   const uint8_t* src_mask, double max_dist, double normal_cos, double edge, double cond_tol, int iters,
+                   int stride, double* R_out, double* t_out, int32_t* info_out, double* stats_out, double* hist_out,
+                   int32_t* assoc_out, double* maps_a_out, double* maps_b_out, void* scratch, size_t scratch_bytes,
+                   cotr_stream stream);
+
 /* ---- structure from known cameras: robust N-view triangulation (cotr_amd/csrc/structure.hip; rules in DESIGN.md 3h-6) ----
  * n correspondences seen in V posed views -> their 3D points, the views each point was fitted on, and the per-point
  * figures a reconstruction filters on.  The rules are the library's own.
