@@ -5,16 +5,13 @@ device and stream: Levenberg-Marquardt on the summed squared pixel error, the po
 observation set re-selected between rounds.  It follows ``triangulate_views`` (its ``X`` and ``used`` are the natural ``X`` and
 ``visible`` here) as one more call of the same device sequence; ``bundle_adjust`` is the same with host arrays back.  No CPU
 fallback."""
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib
 from .._lib import check_op, on, ptr
-from ._ransac import _device
-from .essential import _check_distance
-from .structure import _cam_rows, _no_cpu_tensors, _pose_rows, _tensor, _view_points
+from . import _args
+from ._args import F64, I32, U8
 
 MAX_POINTS = 1 << 20
 MAX_ROUNDS = 8
@@ -42,33 +39,21 @@ def _fixed(fixed_views, V):
 
 
 def _check(threshold, distance_thresh, rounds, iters, lambda0):
-    if not (threshold > 0 and np.isfinite(threshold)):
-        raise ValueError(f'threshold must be finite and > 0, got {threshold}')
-    with np.errstate(over='ignore', under='ignore'):
-        sq = np.float32(float(threshold) * float(threshold))
-    if not (sq > 0 and np.isfinite(sq)):
-        raise ValueError(f'the squared threshold must be a finite float32 that is not 0, got threshold {threshold}')
-    _check_distance(distance_thresh)
-    if int(rounds) != rounds or not 1 <= int(rounds) <= MAX_ROUNDS:
-        raise ValueError(f'rounds must be an integer in [1, {MAX_ROUNDS}], got {rounds}')
-    if int(iters) != iters or not 0 <= int(iters) <= MAX_ITERS:
-        raise ValueError(f'iters must be an integer in [0, {MAX_ITERS}], got {iters}')
+    _args.check_positive('threshold', threshold)
+    _args.check_sq_float32(threshold)
+    _args.check_distance(distance_thresh)
+    _args.check_int_range('rounds', rounds, 1, MAX_ROUNDS)
+    _args.check_int_range('iters', iters, 0, MAX_ITERS)
     if not 1e-12 <= lambda0 <= 1e12:
         raise ValueError(f'lambda0 must be in [1e-12, 1e12], got {lambda0}')
 
 
 def _enqueue(lib, pts, vis, cams, rows, X, fixed, V, N, found, threshold, distance_thresh, rounds, iters, lambda0, device):
-    nbytes = ctypes.c_size_t()
-    check_op(lib.cotr_bundle_adjust_scratch_bytes(V, N, ctypes.byref(nbytes)), 'cotr_bundle_adjust_scratch_bytes')
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    poses = torch.empty((V, 12), dtype=torch.float64, device=device)
-    Xo = torch.empty((N, 3), dtype=torch.float64, device=device)
-    used = torch.empty((V, N), dtype=torch.uint8, device=device)
-    stats = torch.empty(4, dtype=torch.float64, device=device)
-    info = torch.empty(8, dtype=torch.int32, device=device)
+    scratch, nbytes = _args.scratch(lib, 'cotr_bundle_adjust_scratch_bytes', V, N, device=device)
+    poses, Xo, used, stats, info = _args.empty(device, ((V, 12), F64), ((N, 3), F64), ((V, N), U8), (4, F64), (8, I32))
     check_op(lib.cotr_bundle_adjust(ptr(pts), ptr(vis), ptr(cams), ptr(rows), ptr(X), fixed.ctypes.data, V, N, ptr(found), float(threshold),
                                     float(distance_thresh), int(rounds), int(iters), float(lambda0), ptr(poses), ptr(Xo), ptr(used),
-                                    ptr(stats), ptr(info), ptr(scratch), nbytes.value, _lib.current_stream_ptr()), 'cotr_bundle_adjust')
+                                    ptr(stats), ptr(info), ptr(scratch), nbytes, _lib.current_stream_ptr()), 'cotr_bundle_adjust')
     return dict(poses=poses.reshape(V, 3, 4), X=Xo, used=used.bool(), stats=stats, info=info)
 
 
@@ -85,28 +70,20 @@ def bundle_adjust_tensors(points, cameras, poses, X, visible=None, fixed_views=(
     observations in front of their camera; each later round re-selects those within ``threshold`` px and ``distance_thresh``
     at the current state.  ``iters`` Levenberg-Marquardt iterations per round from damping ``lambda0``.  The intrinsics are
     not optimised.  ``found``: a device int32 tensor whose first entry 0 zeroes every output."""
-    pts, V, N = _view_points(points)
+    pts, V, N = _args.view_points(points)
     if N > MAX_POINTS:
         raise ValueError(f'between 1 and 2^20 points, got {N}')
-    cams = _cam_rows(cameras, V)
-    rows = _pose_rows(poses, V)
-    Xt = _tensor(X).to(dtype=torch.float64)
+    cams, rows = _args.cam_rows(cameras, V), _args.pose_rows(poses, V)
+    Xt = _args.tensor(X).to(dtype=torch.float64)
     if tuple(Xt.shape) != (N, 3):
         raise ValueError(f'X must be [N, 3] = [{N}, 3], got shape {tuple(Xt.shape)}')
-    vis = None
-    if visible is not None:
-        vis = _tensor(visible, None)
-        if tuple(vis.shape) != (V, N):
-            raise ValueError(f'visible must be [V, N] = [{V}, {N}], got shape {tuple(vis.shape)}')
+    vis = _args.visible(visible, V, N)
     fixed = _fixed(fixed_views, V)
     _check(threshold, distance_thresh, rounds, iters, lambda0)
-    _no_cpu_tensors(points, cameras, poses, X, visible, found)
-    device = _device(device)
+    _args.no_cpu_tensors('the triangulation runs', points, cameras, poses, X, visible, found)   # (the wording of structure.py, whose call this follows)
+    device = _args.device(device)
     pts, cams, rows, Xt = on(pts, device, 16), on(cams, device), on(rows, device), on(Xt, device)
-    if vis is not None:
-        vis = (on(vis, device) != 0).to(torch.uint8)
-    if found is not None:
-        found = on(found, device).to(torch.int32).reshape(-1)
+    vis, found = _args.mask_u8(vis, (V, N), device), _args.found_i32(found, device)
     with torch.cuda.device(device):
         return _enqueue(_lib.load_library(), pts, vis, cams, rows, Xt, fixed, V, N, found, threshold, distance_thresh, rounds, iters, lambda0,
                         device)

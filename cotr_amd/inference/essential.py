@@ -11,32 +11,22 @@ error, adaptive iteration count, no refit, the four (R, t) in its order - with t
 no bit-compatibility with it.  ``refine_relative_pose`` / ``refine_pose_tensors`` (``cotr_refine_pose``) refit a
 pose on its inliers, which cv2's pair does not do: Gauss-Newton on the Sampson error over (R, unit t), the inliers re-counted
 between rounds; ``relative_pose(..., refine_rounds=4)`` enqueues it third.  No CPU fallback."""
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib
 from .._lib import check_op, on, ptr
-from . import _ransac
-from ._ransac import _device
+from . import _args, _ransac
+from ._args import F64, I32, U8
 
 MAX_ITERS = 6553
-_K9 = ctypes.c_double * 9
 
 
-def _camera(K, what):
-    """[3,3] upper-triangular camera matrix -> 9 host doubles; finite, focal lengths not 0"""
-    k = np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float64)
-    if k.shape != (3, 3):
-        raise ValueError(f'{what} must be [3, 3], got shape {k.shape}')
-    if not np.isfinite(k[[0, 0, 0, 1, 1], [0, 1, 2, 1, 2]]).all() or k[0, 0] == 0 or k[1, 1] == 0:
-        raise ValueError(f'{what} must be finite with focal lengths that are not 0')
-    return _K9(*k.reshape(9))
-
-
-def _pairs(points1, points2):
-    return _ransac.pairs(points1, points2, 5, 'an essential matrix needs at least 5 correspondences')
+def _views(points1, points2, K1, K2):
+    """-> (points1, points2, n, k1, k2): the pair of point sets and the two cameras (K2 = K1 when None)"""
+    p1, p2, n = _ransac.pairs(points1, points2, 5, 'an essential matrix needs at least 5 correspondences')
+    k1 = _args.camera(K1, 'K1')
+    return p1, p2, n, k1, k1 if K2 is None else _args.camera(K2, 'K2')
 
 
 def _check_ransac(K1, K2, threshold, confidence, max_iters):
@@ -45,16 +35,21 @@ def _check_ransac(K1, K2, threshold, confidence, max_iters):
 
 
 def _check_threshold(K1, K2, threshold):
-    if not (threshold > 0 and np.isfinite(threshold)):
-        raise ValueError(f'the RANSAC threshold must be finite and > 0, got {threshold}')
+    _args.check_positive('the RANSAC threshold', threshold)
     thr = threshold / ((K1[0] + K1[4] + K2[0] + K2[4]) / 4.0) if (K1[0] + K1[4] + K2[0] + K2[4]) != 0 else np.inf
     if not (thr * thr > 0 and np.isfinite(thr * thr)):
         raise ValueError('the RANSAC threshold over the mean focal length must be finite and not 0')
 
 
+def _mask(mask, n):
+    m = None if mask is None else _args.tensor(mask, None)
+    if m is not None and m.numel() != n:
+        raise ValueError(f'mask must have one entry per correspondence, got {m.numel()} for {n}')
+    return m
+
+
 def _enqueue_essential(lib, p1, p2, n, k1, k2, threshold, confidence, max_iters, seed, hypotheses, device):
-    scratch, E, mask, out = _ransac.outputs(lib.cotr_ransac_essential_scratch_bytes, 'cotr_ransac_essential_scratch_bytes', n,
-                                            max_iters, 5, 10, 8, 'hyp_E', hypotheses, device)
+    scratch, E, mask, out = _ransac.outputs(lib, 'cotr_ransac_essential_scratch_bytes', n, max_iters, 5, 10, 8, 'hyp_E', hypotheses, device)
     check_op(lib.cotr_ransac_essential(ptr(p1), ptr(p2), n, k1, k2, float(threshold), float(confidence), int(max_iters),
                                        _ransac.seed64(seed), ptr(E), ptr(mask), ptr(out['info']), ptr(out.get('hyp_E')),
                                        ptr(out.get('hyp_count')), ptr(out.get('samples')), ptr(scratch), scratch.numel(),
@@ -65,15 +60,10 @@ def _enqueue_essential(lib, p1, p2, n, k1, k2, threshold, confidence, max_iters,
 
 
 def _enqueue_pose(lib, E, p1, p2, n, k1, k2, distance_thresh, mask, found, device):
-    nbytes = ctypes.c_size_t()
-    check_op(lib.cotr_recover_pose_scratch_bytes(n, ctypes.byref(nbytes)), 'cotr_recover_pose_scratch_bytes')
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    R = torch.empty(9, dtype=torch.float64, device=device)
-    t = torch.empty(3, dtype=torch.float64, device=device)
-    mask_out = torch.empty(n, dtype=torch.uint8, device=device)
-    info = torch.empty(8, dtype=torch.int32, device=device)
+    scratch, nbytes = _args.scratch(lib, 'cotr_recover_pose_scratch_bytes', n, device=device)
+    R, t, mask_out, info = _args.empty(device, (9, F64), (3, F64), (n, U8), (8, I32))
     check_op(lib.cotr_recover_pose(ptr(E), ptr(p1), ptr(p2), n, k1, k2, float(distance_thresh), ptr(mask), ptr(found), ptr(R), ptr(t),
-                                   ptr(mask_out), ptr(info), ptr(scratch), nbytes.value, _lib.current_stream_ptr()), 'cotr_recover_pose')
+                                   ptr(mask_out), ptr(info), ptr(scratch), nbytes, _lib.current_stream_ptr()), 'cotr_recover_pose')
     return dict(R=R.view(3, 3), t=t, mask=mask_out.bool(), info=info)
 
 
@@ -85,11 +75,9 @@ def ransac_essential(points1, points2, K1, K2=None, threshold=1.0, confidence=0.
     int32 [max_iters, 5], hyp_E float64 [10 * max_iters, 9] and hyp_count int32 [10 * max_iters] (the tables tests check).
     K1, K2 [3,3] upper-triangular camera matrices (K2 = K1 when None); threshold in pixels.  Nothing found: E = 0, mask = 0,
     info[0] = 0."""
-    p1, p2, n = _pairs(points1, points2)
-    k1 = _camera(K1, 'K1')
-    k2 = k1 if K2 is None else _camera(K2, 'K2')
+    p1, p2, n, k1, k2 = _views(points1, points2, K1, K2)
     _check_ransac(k1, k2, threshold, confidence, max_iters)
-    device = _device(device)
+    device = _args.device(device)
     p1, p2 = on(p1, device), on(p2, device)
     with torch.cuda.device(device):
         out = _enqueue_essential(_lib.load_library(), p1, p2, n, k1, k2, threshold, confidence, max_iters, seed, hypotheses, device)
@@ -102,37 +90,21 @@ def find_essential_mat(points1, points2, camera_matrix1, camera_matrix2=None, pr
     the rules of DESIGN.md 3h-3 -> (E float64 [3,3], mask uint8 [n,1]) as cv2 shapes them, or (None, None) when no model is
     found."""
     r = ransac_essential(points1, points2, camera_matrix1, camera_matrix2, threshold, prob, max_iters, seed)
-    if not r['info'].cpu().numpy()[0]:
+    if not _args.found_flag(r):
         return None, None
-    return r['E'].cpu().numpy(), r['mask'].cpu().numpy().astype(np.uint8).reshape(-1, 1)
-
-
-def _check_distance(distance_thresh):
-    if not (distance_thresh > 0 and np.isfinite(distance_thresh)):
-        raise ValueError(f'distance_thresh must be finite and > 0, got {distance_thresh}')
+    return r['E'].cpu().numpy(), _args.mask_column(r['mask'])
 
 
 def pose_of_essential(E, points1, points2, K1, K2=None, mask=None, distance_thresh=50.0, device=None):
     """One ``cotr_recover_pose`` call on the current stream -> dict of device tensors: R float64 [3,3], t float64 [3] (unit
     length; x2 ~ R x1 + t), mask bool [n] (``mask`` and in front of both cameras), info int32 [8] = (points in front, chosen
     candidate, the four counts, 0, 0)."""
-    p1, p2, n = _pairs(points1, points2)
-    k1 = _camera(K1, 'K1')
-    k2 = k1 if K2 is None else _camera(K2, 'K2')
-    _check_distance(distance_thresh)
-    e = E if torch.is_tensor(E) else torch.from_numpy(np.ascontiguousarray(np.asarray(E, dtype=np.float64)))
-    if e.numel() != 9:
-        raise ValueError(f'E must be [3, 3], got shape {tuple(e.shape)}')
-    m = None
-    if mask is not None:
-        m = mask if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask)))
-        if m.numel() != n:
-            raise ValueError(f'mask must have one entry per correspondence, got {m.numel()} for {n}')
-    device = _device(device)
-    e = on(e.to(dtype=torch.float64).reshape(9), device)
-    p1, p2 = on(p1, device), on(p2, device)
-    if m is not None:
-        m = (on(m, device).reshape(n) != 0).to(torch.uint8)
+    p1, p2, n, k1, k2 = _views(points1, points2, K1, K2)
+    _args.check_distance(distance_thresh)
+    e = _args.flat(E, 'E', 9)
+    m = _mask(mask, n)
+    device = _args.device(device)
+    e, p1, p2, m = on(e, device), on(p1, device), on(p2, device), _args.mask_u8(m, n, device)
     with torch.cuda.device(device):
         return _enqueue_pose(_lib.load_library(), e, p1, p2, n, k1, k2, distance_thresh, m, None, device)
 
@@ -142,39 +114,24 @@ def recover_pose(E, points1, points2, camera_matrix1, camera_matrix2=None, mask=
     (with a second camera matrix when the two views differ) -> (n_good, R float64 [3,3], t float64 [3,1], mask uint8 [n,1])
     as cv2 shapes them."""
     r = pose_of_essential(E, points1, points2, camera_matrix1, camera_matrix2, mask, distance_thresh)
-    info = r['info'].cpu().numpy()
-    return int(info[0]), r['R'].cpu().numpy(), r['t'].cpu().numpy().reshape(3, 1), r['mask'].cpu().numpy().astype(np.uint8).reshape(-1, 1)
+    return int(_args.found_flag(r)), r['R'].cpu().numpy(), r['t'].cpu().numpy().reshape(3, 1), _args.mask_column(r['mask'])
 
 
 MAX_ROUNDS = 8
 MAX_REFINE = 64
 
 
-def _no_cpu_tensors(*xs):
-    if any(torch.is_tensor(x) and not x.is_cuda for x in xs):
-        raise _lib.CotrHipError('the pose refit runs on an MI355X only (HIP kernels, no CPU fallback): got a CPU tensor; '
-                                'pass a numpy array or move the tensor with .cuda()')
-
-
 def _check_refine(rounds, refine_iters, what='rounds'):
-    if not 1 <= rounds <= MAX_ROUNDS:
-        raise ValueError(f'{what} must be in [1, {MAX_ROUNDS}], got {rounds}')
-    if not 0 <= refine_iters <= MAX_REFINE:
-        raise ValueError(f'refine_iters must be in [0, {MAX_REFINE}], got {refine_iters}')
+    _args.check_int_range(what, rounds, 1, MAX_ROUNDS, integer=False)
+    _args.check_int_range('refine_iters', refine_iters, 0, MAX_REFINE, integer=False)
 
 
 def _enqueue_refine(lib, R, t, p1, p2, n, k1, k2, threshold, distance_thresh, rounds, refine_iters, mask, found, device):
-    nbytes = ctypes.c_size_t()
-    check_op(lib.cotr_refine_pose_scratch_bytes(n, ctypes.byref(nbytes)), 'cotr_refine_pose_scratch_bytes')
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    R_out = torch.empty(9, dtype=torch.float64, device=device)
-    t_out = torch.empty(3, dtype=torch.float64, device=device)
-    E_out = torch.empty(9, dtype=torch.float64, device=device)
-    mask_out = torch.empty(n, dtype=torch.uint8, device=device)
-    info = torch.empty(8, dtype=torch.int32, device=device)
+    scratch, nbytes = _args.scratch(lib, 'cotr_refine_pose_scratch_bytes', n, device=device)
+    R_out, t_out, E_out, mask_out, info = _args.empty(device, (9, F64), (3, F64), (9, F64), (n, U8), (8, I32))
     check_op(lib.cotr_refine_pose(ptr(R), ptr(t), ptr(p1), ptr(p2), n, k1, k2, float(threshold), float(distance_thresh), int(rounds),
                                   int(refine_iters), ptr(mask), ptr(found), ptr(R_out), ptr(t_out), ptr(E_out), ptr(mask_out), ptr(info),
-                                  ptr(scratch), nbytes.value, _lib.current_stream_ptr()), 'cotr_refine_pose')
+                                  ptr(scratch), nbytes, _lib.current_stream_ptr()), 'cotr_refine_pose')
     return dict(R=R_out.view(3, 3), t=t_out, E=E_out.view(3, 3), mask=mask_out.bool(), info=info)
 
 
@@ -187,31 +144,16 @@ def refine_pose_tensors(R, t, points1, points2, K1, K2=None, mask=None, threshol
     [3,3] (= [t]x R at unit Frobenius norm), mask bool [n] (what the last round fitted on), info int32 [8] = (found, points in
     mask, rounds run, steps kept in total, steps kept in the last round, points skipped, 0, 0).  ``found``: a device int32
     tensor whose first entry 0 means there is no pose to refine (every output 0), as do a non-finite pose and t = 0."""
-    p1, p2, n = _pairs(points1, points2)
-    k1 = _camera(K1, 'K1')
-    k2 = k1 if K2 is None else _camera(K2, 'K2')
+    p1, p2, n, k1, k2 = _views(points1, points2, K1, K2)
     _check_threshold(k1, k2, threshold)
-    _check_distance(distance_thresh)
+    _args.check_distance(distance_thresh)
     _check_refine(rounds, refine_iters)
-    r = R if torch.is_tensor(R) else torch.from_numpy(np.ascontiguousarray(np.asarray(R, dtype=np.float64)))
-    tt = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64)))
-    if r.numel() != 9:
-        raise ValueError(f'R must be [3, 3], got shape {tuple(r.shape)}')
-    if tt.numel() != 3:
-        raise ValueError(f't must have 3 entries, got shape {tuple(tt.shape)}')
-    m = None
-    if mask is not None:
-        m = mask if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask)))
-        if m.numel() != n:
-            raise ValueError(f'mask must have one entry per correspondence, got {m.numel()} for {n}')
-    _no_cpu_tensors(R, t, points1, points2, mask, found)
-    device = _device(device)
-    r, tt = on(r.to(dtype=torch.float64).reshape(9), device), on(tt.to(dtype=torch.float64).reshape(3), device)
-    p1, p2 = on(p1, device), on(p2, device)
-    if m is not None:
-        m = (on(m, device).reshape(n) != 0).to(torch.uint8)
-    if found is not None:
-        found = on(found, device).to(torch.int32).reshape(-1)
+    r, tt = _args.flat(R, 'R', 9), _args.flat(t, 't', 3, 'have 3 entries')
+    m = _mask(mask, n)
+    _args.no_cpu_tensors('the pose refit runs', R, t, points1, points2, mask, found)
+    device = _args.device(device)
+    r, tt, p1, p2 = on(r, device), on(tt, device), on(p1, device), on(p2, device)
+    m, found = _args.mask_u8(m, n, device), _args.found_i32(found, device)
     with torch.cuda.device(device):
         return _enqueue_refine(_lib.load_library(), r, tt, p1, p2, n, k1, k2, threshold, distance_thresh, rounds, refine_iters, m, found, device)
 
@@ -221,7 +163,7 @@ def refine_relative_pose(R, t, points1, points2, K1, K2=None, mask=None, **kw):
     rounds (4), refine_iters (10)) -> (R float64 [3,3], t float64 [3,1] of unit length, mask uint8 [n,1]: the points the last
     round fitted on), x2 ~ R x1 + t."""
     r = refine_pose_tensors(R, t, points1, points2, K1, K2, mask, **kw)
-    return r['R'].cpu().numpy(), r['t'].cpu().numpy().reshape(3, 1), r['mask'].cpu().numpy().astype(np.uint8).reshape(-1, 1)
+    return r['R'].cpu().numpy(), r['t'].cpu().numpy().reshape(3, 1), _args.mask_column(r['mask'])
 
 
 def relative_pose_tensors(points1, points2, K1, K2=None, threshold=1.0, confidence=0.999, max_iters=1000, seed=0,
@@ -232,14 +174,12 @@ def relative_pose_tensors(points1, points2, K1, K2=None, threshold=1.0, confiden
     ``cotr_refine_pose`` follows third in the same sequence, reading R, t, the pose mask and the found flag on the device: R,
     t, E and mask are then the refit's, with refine_info beside them and the unrefined ones as R_ransac, t_ransac, E_ransac,
     mask_ransac."""
-    p1, p2, n = _pairs(points1, points2)
-    k1 = _camera(K1, 'K1')
-    k2 = k1 if K2 is None else _camera(K2, 'K2')
+    p1, p2, n, k1, k2 = _views(points1, points2, K1, K2)
     _check_ransac(k1, k2, threshold, confidence, max_iters)
-    _check_distance(distance_thresh)
+    _args.check_distance(distance_thresh)
     if refine_rounds != 0:
         _check_refine(refine_rounds, refine_iters, 'refine_rounds')
-    device = _device(device)
+    device = _args.device(device)
     p1, p2 = on(p1, device), on(p2, device)
     lib = _lib.load_library()
     with torch.cuda.device(device):
@@ -261,6 +201,6 @@ def relative_pose(points1, points2, K1, K2=None, **kw):
     refit of ``refine_pose_tensors`` follow in the same sequence, and the mask is what the last round fitted on),
     refine_iters (10)."""
     r = relative_pose_tensors(points1, points2, K1, K2, **kw)
-    if not r['info'].cpu().numpy()[0]:
+    if not _args.found_flag(r):
         return None, None, None
-    return r['R'].cpu().numpy(), r['t'].cpu().numpy().reshape(3, 1), r['mask'].cpu().numpy().astype(np.uint8).reshape(-1, 1)
+    return r['R'].cpu().numpy(), r['t'].cpu().numpy().reshape(3, 1), _args.mask_column(r['mask'])

@@ -6,41 +6,34 @@ After its two ``cotr_corr_multiscale`` calls the reference demo matches every pr
 third one ``cotr_ransac_fundamental`` call (cotr_amd/csrc/guided.hip; rules in DESIGN.md 3h), on the current device and
 stream.  The RANSAC follows the structure of OpenCV 3.4's FM_RANSAC with a counter-based sampler of its own: same
 distribution of samples, different draws.  cv2's 7-point LMedS fallback below 15 points is not provided.  No CPU fallback."""
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib
 from .._lib import check_op, on, ptr
-from . import _ransac
-from ._ransac import _device, _points
+from . import _args, _ransac
 
 
 def nearest_mutual(pred_ab, kp_b, pred_ba, kp_a, device=None):
     """idx_ab [Na] (nearest kp_b of every pred_ab row), idx_ba [Nb] (nearest kp_a of every pred_ba row), int32, and the
     mutual flags [Na] bool (idx_ba[idx_ab[i]] == i), as device tensors; one ``cotr_nearest_mutual`` call on the current
     stream.  pred_ab and kp_a are [Na, 2], pred_ba and kp_b [Nb, 2]."""
-    pred_ab, kp_b, pred_ba, kp_a = (_points(p, w) for p, w in ((pred_ab, 'pred_ab'), (kp_b, 'kp_b'), (pred_ba, 'pred_ba'),
-                                                                (kp_a, 'kp_a')))
+    pred_ab, kp_b, pred_ba, kp_a = (_args.points(p, w) for p, w in ((pred_ab, 'pred_ab'), (kp_b, 'kp_b'), (pred_ba, 'pred_ba'),
+                                                                     (kp_a, 'kp_a')))
     na, nb = kp_a.shape[0], kp_b.shape[0]
     if pred_ab.shape[0] != na or pred_ba.shape[0] != nb:
         raise ValueError(f'pred_ab must have one row per kp_a ({na}) and pred_ba one per kp_b ({nb}), got '
                          f'{pred_ab.shape[0]} and {pred_ba.shape[0]}')
     if na == 0 or nb == 0:
         raise ValueError('nearest keypoints need at least one keypoint on each side')
-    device = _device(device)
+    device = _args.device(device)
     pred_ab, kp_b, pred_ba, kp_a = (on(t, device) for t in (pred_ab, kp_b, pred_ba, kp_a))
     lib = _lib.load_library()
-    nbytes = ctypes.c_size_t()
-    check_op(lib.cotr_nearest_mutual_scratch_bytes(na, nb, ctypes.byref(nbytes)), 'cotr_nearest_mutual_scratch_bytes')
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    idx_ab = torch.empty(na, dtype=torch.int32, device=device)
-    idx_ba = torch.empty(nb, dtype=torch.int32, device=device)
-    mutual = torch.empty(na, dtype=torch.uint8, device=device)
+    scratch, nbytes = _args.scratch(lib, 'cotr_nearest_mutual_scratch_bytes', na, nb, device=device)
+    idx_ab, idx_ba, mutual = _args.empty(device, (na, _args.I32), (nb, _args.I32), (na, _args.U8))
     with torch.cuda.device(device):
         check_op(lib.cotr_nearest_mutual(ptr(pred_ab), ptr(kp_b), ptr(pred_ba), ptr(kp_a), na, nb, ptr(idx_ab), ptr(idx_ba),
-                                         ptr(mutual), ptr(scratch), nbytes.value, _lib.current_stream_ptr()), 'cotr_nearest_mutual')
+                                         ptr(mutual), ptr(scratch), nbytes, _lib.current_stream_ptr()), 'cotr_nearest_mutual')
     return idx_ab, idx_ba, mutual.bool()
 
 
@@ -64,11 +57,10 @@ def ransac_fundamental(points1, points2, threshold=3.0, confidence=0.99, max_ite
     p1, p2, n = _ransac.pairs(points1, points2, 15, 'find_fundamental_mat needs at least 15 correspondences for RANSAC '
                               '(cv2\'s 7-point / LMedS fallback below 15 points is not provided)')
     _ransac.check_ransac(threshold, confidence, max_iters)
-    device = _device(device)
+    device = _args.device(device)
     p1, p2 = on(p1, device), on(p2, device)
     lib = _lib.load_library()
-    scratch, F, mask, out = _ransac.outputs(lib.cotr_ransac_fundamental_scratch_bytes, 'cotr_ransac_fundamental_scratch_bytes', n,
-                                            max_iters, 7, 3, 4, 'hyp_F', hypotheses, device)
+    scratch, F, mask, out = _ransac.outputs(lib, 'cotr_ransac_fundamental_scratch_bytes', n, max_iters, 7, 3, 4, 'hyp_F', hypotheses, device)
     with torch.cuda.device(device):
         check_op(lib.cotr_ransac_fundamental(ptr(p1), ptr(p2), n, float(threshold), float(confidence), int(max_iters),
                                              _ransac.seed64(seed), ptr(F), ptr(mask), ptr(out['info']), ptr(out.get('hyp_F')),
@@ -84,10 +76,9 @@ def find_fundamental_mat(points1, points2, ransac_reproj_threshold=3.0, confiden
     rule of DESIGN.md 3h -> (F float64 [3,3], mask uint8 [n,1]) as cv2 shapes them, or (None, None) when no model is
     found.  Fewer than 15 points: ValueError (cv2 would switch to its 7-point / LMedS fallback, not provided here)."""
     r = ransac_fundamental(points1, points2, ransac_reproj_threshold, confidence, max_iters, seed)
-    info = r['info'].cpu().numpy()
-    if not info[0]:
+    if not _args.found_flag(r):
         return None, None
-    return r['F'].cpu().numpy(), r['mask'].cpu().numpy().astype(np.uint8).reshape(-1, 1)
+    return r['F'].cpu().numpy(), _args.mask_column(r['mask'])
 
 
 def filter_guided_matches(corrs_a_b, corrs_b_a, kp_a, kp_b, ransac_threshold=5.0, confidence=0.999999, seed=0):

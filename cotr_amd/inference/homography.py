@@ -11,8 +11,7 @@ import torch
 
 from .. import _lib
 from .._lib import check_op, on, ptr
-from . import _ransac
-from ._ransac import _device
+from . import _args, _ransac
 
 MAX_REFINE = 64
 
@@ -26,13 +25,11 @@ def ransac_homography(points1, points2, threshold=3.0, confidence=0.995, max_ite
     [max_iters, 9] and hyp_count int32 [max_iters] (the tables tests check).  Nothing found: H = 0, mask = 0, info[0] = 0."""
     p1, p2, n = _ransac.pairs(points1, points2, 4, 'a homography needs at least 4 correspondences')
     _ransac.check_ransac(threshold, confidence, max_iters)
-    if not 0 <= refine_iters <= MAX_REFINE:
-        raise ValueError(f'refine_iters must be in [0, {MAX_REFINE}], got {refine_iters}')
-    device = _device(device)
+    _args.check_int_range('refine_iters', refine_iters, 0, MAX_REFINE, integer=False)
+    device = _args.device(device)
     p1, p2 = on(p1, device), on(p2, device)
     lib = _lib.load_library()
-    scratch, H, mask, out = _ransac.outputs(lib.cotr_ransac_homography_scratch_bytes, 'cotr_ransac_homography_scratch_bytes', n,
-                                            max_iters, 4, 1, 8, 'hyp_H', hypotheses, device)
+    scratch, H, mask, out = _ransac.outputs(lib, 'cotr_ransac_homography_scratch_bytes', n, max_iters, 4, 1, 8, 'hyp_H', hypotheses, device)
     H_ransac = torch.empty(9, dtype=torch.float64, device=device)
     with torch.cuda.device(device):
         check_op(lib.cotr_ransac_homography(ptr(p1), ptr(p2), n, float(threshold), float(confidence), int(max_iters), int(refine_iters),
@@ -56,10 +53,9 @@ def find_homography(src, dst, ransac_reproj_threshold=3.0, max_iters=2000, confi
     rules of DESIGN.md 3h-2 -> (H float64 [3,3] mapping src to dst, mask uint8 [n,1]) as cv2 shapes them, or (None, None)
     when no model is found."""
     r = ransac_homography(src, dst, ransac_reproj_threshold, confidence, max_iters, seed)
-    info = r['info'].cpu().numpy()
-    if not info[0]:
+    if not _args.found_flag(r):
         return None, None
-    return r['H'].cpu().numpy(), r['mask'].cpu().numpy().astype(np.uint8).reshape(-1, 1)
+    return r['H'].cpu().numpy(), _args.mask_column(r['mask'])
 
 
 def paste_by_homography(picture, pts_picture, pts_b, img_b, as_tensor=False, **ransac_kw):
@@ -70,9 +66,9 @@ def paste_by_homography(picture, pts_picture, pts_b, img_b, as_tensor=False, **r
     host, with no estimator call (``ransac_kw`` is checked as ``find_homography`` checks it and then has no effect), so the
     picture's four corners give what ``paste_by_corners`` gives.  Then the one ``cotr_warp_perspective`` launch of
     ``paste_by_corners``, ``img_b`` as the background.  No model found: ValueError."""
-    from .warp import _check_image, get_perspective_transform, warp_perspective
-    _check_image(picture, 'picture')
-    Hb, Wb, _ = _check_image(img_b, 'img_b')
+    from .warp import check_image, get_perspective_transform, warp_perspective
+    check_image(picture, 'picture')
+    Hb, Wb, _ = check_image(img_b, 'img_b')
     pp = np.asarray(pts_picture.cpu() if torch.is_tensor(pts_picture) else pts_picture)
     pb = np.asarray(pts_b.cpu() if torch.is_tensor(pts_b) else pts_b)
     if pp.ndim != 2 or pp.shape[1] != 2 or pb.shape != pp.shape:

@@ -6,53 +6,34 @@ sparse correspondences.
 on two ``cotr_amd.data.Capture`` with host results, and ``register_captures(..., icp_iters=10)`` (rigid3d.py) enqueues it behind
 the sparse registration as one device sequence.  The model is x_a = R x_b + t; the rules are the library's own (DESIGN.md
 3h-9).  No CPU fallback."""
-import ctypes
-
-import numpy as np
 import torch
 
 from .. import _lib
 from .._lib import check_op, on, ptr
-from ._ransac import _device
-from .essential import _camera
-from .pnp import _check_depth, _pose_matrix
+from . import _args
+from ._args import F64, I32
 
 MAX_ITERS = 64
 MAX_STRIDE = 64
+NORMAL_COS, EDGE, COND_TOL = 0.5, 0.05, 1e-6   # the defaults of icp_depth, and what register_captures(icp_iters=...) runs it with
 STOP_REASONS = ('ran all', 'too few pairs', 'ill-conditioned', 'not finite')
 
 
-def _no_cpu_tensors(*xs):
-    if any(torch.is_tensor(x) and not x.is_cuda for x in xs):
-        raise _lib.CotrHipError('the dense registration runs on an MI355X only (HIP kernels, no CPU fallback): got a CPU tensor; '
-                                'pass a numpy array or move the tensor with .cuda()')
-
-
-def _check_map(depth, what):
-    _check_depth(depth)
-    if depth.shape[0] < 3 or depth.shape[1] < 3:
-        raise ValueError(f'{what}: a map of at least 3 x 3 pixels, got {depth.shape[0]} x {depth.shape[1]}')
-
-
-def _check(max_dist, normal_cos, edge, cond_tol, iters, stride):
-    if not (max_dist > 0 and np.isfinite(max_dist)):
-        raise ValueError(f'max_dist must be finite and > 0, got {max_dist}')
+def check(max_dist, normal_cos=NORMAL_COS, edge=EDGE, cond_tol=COND_TOL, iters=10, stride=1):
+    _args.check_positive('max_dist', max_dist)
     if not -1 <= normal_cos <= 1:
         raise ValueError(f'normal_cos must be in [-1, 1], got {normal_cos}')
-    if not (edge > 0 and np.isfinite(edge)):
-        raise ValueError(f'edge must be finite and > 0, got {edge}')
+    _args.check_positive('edge', edge)
     if not 0 < cond_tol < 1:
         raise ValueError(f'cond_tol must be in (0, 1), got {cond_tol}')
-    if not 0 <= iters <= MAX_ITERS or int(iters) != iters:
-        raise ValueError(f'iters must be an integer in [0, {MAX_ITERS}], got {iters}')
-    if not 1 <= stride <= MAX_STRIDE or int(stride) != stride:
-        raise ValueError(f'stride must be an integer in [1, {MAX_STRIDE}], got {stride}')
+    _args.check_int_range('iters', iters, 0, MAX_ITERS)
+    _args.check_int_range('stride', stride, 1, MAX_STRIDE)
 
 
 def _pose(R0, t0):
     """-> R [9], t [3] float64 tensors, where they were"""
     def take(x, shape, what):
-        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64)))
+        t = _args.tensor(x)
         if tuple(t.shape) not in shape:
             raise ValueError(f'{what} must have shape {" or ".join(str(list(s)) for s in shape)}, got {list(t.shape)}')
         return t.to(dtype=torch.float64).reshape(-1)
@@ -62,7 +43,7 @@ def _pose(R0, t0):
 def _source_mask(src_mask, depth_b):
     if src_mask is None:
         return None
-    m = src_mask if torch.is_tensor(src_mask) else torch.from_numpy(np.ascontiguousarray(src_mask))
+    m = _args.tensor(src_mask, None)
     if tuple(m.shape) != tuple(depth_b.shape):
         raise ValueError(f'src_mask must have the shape of depth_b {list(depth_b.shape)}, got {list(m.shape)}')
     if m.dtype not in (torch.bool, torch.uint8):
@@ -75,28 +56,23 @@ def _enqueue_icp(lib, depth_a, ka, depth_b, kb, R0, t0, c2w_a, found, src_mask, 
     """every tensor on ``device`` already, every argument checked -> the dict of ``icp_depth``"""
     (Ha, Wa), (Hb, Wb) = (int(v) for v in depth_a.shape), (int(v) for v in depth_b.shape)
     iters, stride = int(iters), int(stride)
-    nbytes = ctypes.c_size_t()
-    check_op(lib.cotr_icp_depth_scratch_bytes(Ha, Wa, Hb, Wb, stride, ctypes.byref(nbytes)), 'cotr_icp_depth_scratch_bytes')
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    R = torch.empty(9, dtype=torch.float64, device=device)
-    out = dict(t=torch.empty(3, dtype=torch.float64, device=device), info=torch.empty(8, dtype=torch.int32, device=device),
-               stats=torch.empty(2, dtype=torch.float64, device=device))
+    scratch, nbytes = _args.scratch(lib, 'cotr_icp_depth_scratch_bytes', Ha, Wa, Hb, Wb, stride, device=device)
+    R, t, info, stats = _args.empty(device, (9, F64), (3, F64), (8, I32), (2, F64))
+    out = dict(t=t, info=info, stats=stats)
     if tables:
         n_src = -(-Hb // stride) * -(-Wb // stride)
-        out['hist'] = torch.empty((iters + 1, 32), dtype=torch.float64, device=device)
-        out['assoc'] = torch.empty(n_src, dtype=torch.int32, device=device)
-        out['maps_a'] = torch.empty((Ha, Wa, 6), dtype=torch.float64, device=device)
-        out['maps_b'] = torch.empty((Hb, Wb, 6), dtype=torch.float64, device=device)
+        out['hist'], out['assoc'], out['maps_a'], out['maps_b'] = _args.empty(device, ((iters + 1, 32), F64), (n_src, I32), ((Ha, Wa, 6), F64),
+                                                                              ((Hb, Wb, 6), F64))
     check_op(lib.cotr_icp_depth(ptr(depth_a), Ha, Wa, ka, ptr(depth_b), Hb, Wb, kb, ptr(R0), ptr(t0), ptr(c2w_a), ptr(found), ptr(src_mask),
                                 float(max_dist), float(normal_cos), float(edge), float(cond_tol), iters, stride, ptr(R), ptr(out['t']),
                                 ptr(out['info']), ptr(out['stats']), ptr(out.get('hist')), ptr(out.get('assoc')), ptr(out.get('maps_a')),
-                                ptr(out.get('maps_b')), ptr(scratch), scratch.numel(), _lib.current_stream_ptr()), 'cotr_icp_depth')
+                                ptr(out.get('maps_b')), ptr(scratch), nbytes, _lib.current_stream_ptr()), 'cotr_icp_depth')
     out['R'] = R.view(3, 3)
     return out
 
 
-def icp_depth(depth_a, K_a, depth_b, K_b, R0, t0, max_dist, normal_cos=0.5, edge=0.05, cond_tol=1e-6, iters=10, stride=1, c2w_a=None,
-              src_mask=None, tables=False, device=None):
+def icp_depth(depth_a, K_a, depth_b, K_b, R0, t0, max_dist, normal_cos=NORMAL_COS, edge=EDGE, cond_tol=COND_TOL, iters=10, stride=1,
+              c2w_a=None, src_mask=None, tables=False, device=None):
     """One ``cotr_icp_depth`` call on the current stream: the rigid motion x_a = R x_b + t between the depth maps ``depth_a``
     [Ha,Wa] and ``depth_b`` [Hb,Wb] (float32, cameras ``K_a``, ``K_b``), refined from the start (``R0`` [3,3], ``t0`` [3]; device
     tensors are read in place) by up to ``iters`` point-to-plane steps on the pairs that projective association finds: a source
@@ -108,18 +84,17 @@ def icp_depth(depth_a, K_a, depth_b, K_b, R0, t0, max_dist, normal_cos=0.5, edge
     largest, 3 not finite), usable source pixels, pixels of A with a normal, 0, 0), stats float64 [2] = (sum r^2, rmse); with
     ``tables=True`` also hist float64 [iters + 1, 32], assoc int32 [n_src], maps_a [Ha,Wa,6] and maps_b [Hb,Wb,6] (the
     tables tests check).  A stop leaves the pose of the evaluation it happened at: at the first one, the start."""
-    _check_map(depth_a, 'depth_a')
-    _check_map(depth_b, 'depth_b')
-    ka, kb = _camera(K_a, 'K_a'), _camera(K_b, 'K_b')
+    _args.check_map(depth_a, 'depth_a')
+    _args.check_map(depth_b, 'depth_b')
+    ka, kb = _args.camera(K_a, 'K_a'), _args.camera(K_b, 'K_b')
     raw = (depth_a, depth_b, R0, t0, src_mask)
     R0, t0 = _pose(R0, t0)
-    m = _pose_matrix(c2w_a)
+    m = _args.pose_matrix(c2w_a)
     sm = _source_mask(src_mask, depth_b)
-    _check(max_dist, normal_cos, edge, cond_tol, iters, stride)
-    _no_cpu_tensors(*raw)
-    device = _device(device)
-    depth_a, depth_b, R0, t0 = on(depth_a, device), on(depth_b, device), on(R0, device), on(t0, device)
-    m = None if m is None else on(m.reshape(16), device)
+    check(max_dist, normal_cos, edge, cond_tol, iters, stride)
+    _args.no_cpu_tensors('the dense registration runs', *raw)
+    device = _args.device(device)
+    depth_a, depth_b, R0, t0, m = on(depth_a, device), on(depth_b, device), on(R0, device), on(t0, device), _args.pose_on(m, device)
     sm = None if sm is None else on(sm, device)
     with torch.cuda.device(device):
         return _enqueue_icp(_lib.load_library(), depth_a, ka, depth_b, kb, R0, t0, m, None, sm, max_dist, normal_cos, edge, cond_tol, iters,
@@ -131,13 +106,11 @@ def refine_registration(cap_a, cap_b, c2w_b, max_dist=0.05, **kw):
     ``cotr_amd.data.Capture``; the c2w of ``cap_b`` is not read), refined on both depth maps by ``icp_depth`` -> (c2w_b float64
     [4,4], info: dict(ok, steps, pairs, stop (one of STOP_REASONS), source_pixels, target_pixels, sum_r2, rmse)).  ``kw``:
     normal_cos, edge, cond_tol, iters, stride, src_mask.  A stop at the first evaluation returns the pose given."""
-    start = _pose_matrix(c2w_b)
+    start = _args.pose_matrix(c2w_b)
     if start is None:
         raise ValueError('c2w_b must be a finite [4, 4] matrix, got None')
     r = icp_depth(cap_a.depth, cap_a.K, cap_b.depth, cap_b.K, start[:3, :3], start[:3, 3], max_dist, c2w_a=cap_a.c2w, **kw)
     info, stats = r['info'].cpu().numpy(), r['stats'].cpu().numpy()
-    c2w = np.eye(4)
-    c2w[:3, :3] = r['R'].cpu().numpy()
-    c2w[:3, 3] = r['t'].cpu().numpy()
+    c2w = _args.c2w_from(r['R'], r['t'])
     return c2w, dict(ok=bool(info[0]), steps=int(info[1]), pairs=int(info[2]), stop=STOP_REASONS[int(info[3])], source_pixels=int(info[4]),
                      target_pixels=int(info[5]), sum_r2=float(stats[0]), rmse=float(stats[1]))

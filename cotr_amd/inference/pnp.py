@@ -16,76 +16,17 @@ import torch
 
 from .. import _lib
 from .._lib import check_op, on, ptr
-from . import _ransac
-from ._ransac import _device
-from .essential import _camera
+from . import _args, _ransac
 
 MAX_REFINE = 64
-
-
-def _no_cpu_tensors(*xs):
-    if any(torch.is_tensor(x) and not x.is_cuda for x in xs):
-        raise _lib.CotrHipError('the absolute-pose estimator runs on an MI355X only (HIP kernels, no CPU fallback): got a CPU tensor; '
-                                'pass a numpy array or move the tensor with .cuda()')
-
-
-def _object_points(p, n=None):
-    """[N,3] float64 tensor, where it was"""
-    t = p if torch.is_tensor(p) else torch.from_numpy(np.ascontiguousarray(np.asarray(p, dtype=np.float64)))
-    if t.dim() == 3 and t.shape[1] == 1:   # cv2's [N,1,3]
-        t = t[:, 0]
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f'object_points must be [N, 3], got shape {tuple(t.shape)}')
-    if n is not None and t.shape[0] != n:
-        raise ValueError(f'object_points and image_points must have the same length, got {t.shape[0]} and {n}')
-    return t.to(dtype=torch.float64)
-
-
-def _image_points(p, what='image_points'):
-    if not torch.is_tensor(p):
-        p = np.asarray(p, dtype=np.float64)
-    if p.ndim == 3 and p.shape[1] == 1:   # cv2's [N,1,2]
-        p = p[:, 0]
-    return _ransac._points(p, what)
-
-
-def _pairs(object_points, image_points):
-    img = _image_points(image_points)
-    n = img.shape[0]
-    obj = _object_points(object_points, n)
-    if n < 4:
-        raise ValueError(f'an absolute pose needs at least 4 correspondences, got {n}')
-    if n > _ransac.MAX_POINTS:
-        raise ValueError(f'at most 2^24 correspondences, got {n}')
-    return obj, img, n
+_TOO_FEW = 'an absolute pose needs at least 4 correspondences'
+_SUBJECT = 'the absolute-pose estimator runs'
 
 
 def _check(threshold, confidence, max_iters, refine_iters):
     _ransac.check_ransac(threshold, confidence, max_iters)
-    with np.errstate(over='ignore', under='ignore'):
-        sq = np.float32(float(threshold) * float(threshold))
-    if not (sq > 0 and np.isfinite(sq)):
-        raise ValueError(f'the squared RANSAC threshold must be a finite float32 that is not 0, got threshold {threshold}')
-    if not 0 <= int(refine_iters) <= MAX_REFINE or int(refine_iters) != refine_iters:
-        raise ValueError(f'refine_iters must be an integer in [0, {MAX_REFINE}], got {refine_iters}')
-
-
-def _check_depth(depth):
-    if (torch.is_tensor(depth) and depth.dtype != torch.float32) or (not torch.is_tensor(depth) and np.asarray(depth).dtype != np.float32):
-        raise ValueError(f'depth must be float32, got {depth.dtype if hasattr(depth, "dtype") else type(depth)}')
-    if len(depth.shape) != 2 or depth.shape[0] < 1 or depth.shape[1] < 1:
-        raise ValueError(f'depth must be [H, W], got shape {tuple(depth.shape)}')
-    if int(depth.shape[0]) * int(depth.shape[1]) > 1 << 28:
-        raise ValueError(f'depth: at most 2^28 pixels, got {depth.shape[0]} x {depth.shape[1]}')
-
-
-def _pose_matrix(c2w):
-    if c2w is None:
-        return None
-    m = np.asarray(c2w.cpu() if torch.is_tensor(c2w) else c2w, dtype=np.float64)
-    if m.shape != (4, 4) or not np.isfinite(m).all():
-        raise ValueError(f'c2w must be a finite [4, 4] matrix, got shape {m.shape}')
-    return np.ascontiguousarray(m)
+    _args.check_sq_float32(threshold, ransac=True)
+    _args.check_int_range('refine_iters', refine_iters, 0, MAX_REFINE)
 
 
 def _enqueue_lift(lib, pts, n, depth, k, c2w, device):
@@ -96,9 +37,7 @@ def _enqueue_lift(lib, pts, n, depth, k, c2w, device):
 
 
 def _enqueue_pnp(lib, obj, img, n, k, threshold, confidence, max_iters, seed, refine_iters, hypotheses, device):
-    scratch, _, mask, out = _ransac.outputs(lib.cotr_ransac_pnp_scratch_bytes, 'cotr_ransac_pnp_scratch_bytes', n, max_iters, 4, 1, 8,
-                                            'hyp_pose', hypotheses, device)
-    R = torch.empty(9, dtype=torch.float64, device=device)
+    scratch, R, mask, out = _ransac.outputs(lib, 'cotr_ransac_pnp_scratch_bytes', n, max_iters, 4, 1, 8, 'hyp_pose', hypotheses, device)
     t = torch.empty(3, dtype=torch.float64, device=device)
     check_op(lib.cotr_ransac_pnp(ptr(obj), ptr(img), n, k, float(threshold), float(confidence), int(max_iters), _ransac.seed64(seed),
                                  int(refine_iters), ptr(R), ptr(t), ptr(mask), ptr(out['info']), ptr(out.get('hyp_pose')),
@@ -115,17 +54,16 @@ def lift_pixels(points, depth, K, c2w=None, device=None):
     float32 with the camera matrix ``K`` -> device tensor float64 [n,3]: the depth read at the pixel the point falls in
     (``np.round``: ties to even), X = z K^-1 (x, y, 1) of the unrounded point, in world coordinates when the camera-to-world
     pose ``c2w`` [4,4] is given.  Three NaN for a point outside the map or without a finite depth > 0."""
-    pts = _image_points(points, 'points')
+    pts = _args.points(points, 'points', cv2=True)
     n = pts.shape[0]
     if n < 1 or n > _ransac.MAX_POINTS:
         raise ValueError(f'points: between 1 and 2^24 of them, got {n}')
-    _check_depth(depth)
-    k = _camera(K, 'K')
-    m = _pose_matrix(c2w)
-    _no_cpu_tensors(points, depth)
-    device = _device(device)
-    pts, depth = on(pts, device), on(depth, device)
-    m = None if m is None else on(m.reshape(16), device)
+    _args.check_depth(depth)
+    k = _args.camera(K, 'K')
+    m = _args.pose_matrix(c2w)
+    _args.no_cpu_tensors(_SUBJECT, points, depth)
+    device = _args.device(device)
+    pts, depth, m = on(pts, device), on(depth, device), _args.pose_on(m, device)
     with torch.cuda.device(device):
         return _enqueue_lift(_lib.load_library(), pts, n, depth, k, m, device)
 
@@ -139,11 +77,13 @@ def ransac_pnp(object_points, image_points, K, threshold=8.0, confidence=0.99, m
     [max_iters, 9] (rows 1 and 2 of R, then t) and hyp_count int32 [max_iters] (the tables tests check).  K [3,3]
     upper-triangular; threshold in pixels.  An object point with a NaN is never an inlier.  Nothing found: R = 0, t = 0,
     mask = 0, info[0] = 0."""
-    obj, img, n = _pairs(object_points, image_points)
-    k = _camera(K, 'K')
+    img, obj = _args.points(image_points, 'image_points', cv2=True), _args.points(object_points, 'object_points', 3, cv2=True)
+    n = img.shape[0]
+    _args.count_pairs(obj.shape[0], n, 4, _TOO_FEW, 'object_points', 'image_points')
+    k = _args.camera(K, 'K')
     _check(threshold, confidence, max_iters, refine_iters)
-    _no_cpu_tensors(object_points, image_points)
-    device = _device(device)
+    _args.no_cpu_tensors(_SUBJECT, object_points, image_points)
+    device = _args.device(device)
     obj, img = on(obj, device), on(img, device)
     with torch.cuda.device(device):
         return _enqueue_pnp(_lib.load_library(), obj, img, n, k, threshold, confidence, max_iters, seed, refine_iters, hypotheses, device)
@@ -194,7 +134,7 @@ def solve_pnp_ransac(object_points, image_points, camera_matrix, dist_coeffs=Non
     if dist_coeffs is not None and np.any(np.asarray(dist_coeffs, dtype=np.float64) != 0):
         raise ValueError('dist_coeffs must be None or zero: lens distortion is not modelled')
     r = ransac_pnp(object_points, image_points, camera_matrix, reprojection_error, confidence, iterations_count, seed, refine_iters)
-    if not r['info'].cpu().numpy()[0]:
+    if not _args.found_flag(r):
         return False, None, None, None
     inl = np.flatnonzero(r['mask'].cpu().numpy()).astype(np.int32).reshape(-1, 1)
     return True, rodrigues(r['R'].cpu().numpy()), r['t'].cpu().numpy().reshape(3, 1), inl
@@ -205,22 +145,16 @@ def localize_tensors(points_a, points_b, depth_a, K_a, c2w_a, K_b, threshold=8.0
     """``cotr_lift_pixels`` then ``cotr_ransac_pnp`` enqueued back to back on the current stream: the second reads the
     first's points on the device, so no host round trip lies between them -> the dict of ``ransac_pnp`` with
     object_points [n,3] besides."""
-    pa, pb = _image_points(points_a, 'points_a'), _image_points(points_b, 'points_b')
+    pa, pb = _args.points(points_a, 'points_a', cv2=True), _args.points(points_b, 'points_b', cv2=True)
     n = pa.shape[0]
-    if pb.shape[0] != n:
-        raise ValueError(f'points_a and points_b must have the same length, got {n} and {pb.shape[0]}')
-    if n < 4:
-        raise ValueError(f'an absolute pose needs at least 4 correspondences, got {n}')
-    if n > _ransac.MAX_POINTS:
-        raise ValueError(f'at most 2^24 correspondences, got {n}')
-    _check_depth(depth_a)
-    ka, kb = _camera(K_a, 'K_a'), _camera(K_b, 'K_b')
-    m = _pose_matrix(c2w_a)
+    _args.count_pairs(n, pb.shape[0], 4, _TOO_FEW, 'points_a', 'points_b')
+    _args.check_depth(depth_a)
+    ka, kb = _args.camera(K_a, 'K_a'), _args.camera(K_b, 'K_b')
+    m = _args.pose_matrix(c2w_a)
     _check(threshold, confidence, max_iters, refine_iters)
-    _no_cpu_tensors(points_a, points_b, depth_a)
-    device = _device(device)
-    pa, pb, depth_a = on(pa, device), on(pb, device), on(depth_a, device)
-    m = None if m is None else on(m.reshape(16), device)
+    _args.no_cpu_tensors(_SUBJECT, points_a, points_b, depth_a)
+    device = _args.device(device)
+    pa, pb, depth_a, m = on(pa, device), on(pb, device), on(depth_a, device), _args.pose_on(m, device)
     lib = _lib.load_library()
     with torch.cuda.device(device):
         obj = _enqueue_lift(lib, pa, n, depth_a, ka, m, device)
@@ -237,10 +171,6 @@ def localize(points_a, points_b, cap_a, K_b, **ransac_kw):
     None) when no pose is found.  ``ransac_kw``: threshold (8.0), confidence (0.99), max_iters (100), seed (0), refine_iters
     (10)."""
     r = localize_tensors(points_a, points_b, cap_a.depth, cap_a.K, cap_a.c2w, K_b, **ransac_kw)
-    if not r['info'].cpu().numpy()[0]:
+    if not _args.found_flag(r):
         return None, None
-    R, t = r['R'].cpu().numpy(), r['t'].cpu().numpy()
-    c2w = np.eye(4)
-    c2w[:3, :3] = R.T
-    c2w[:3, 3] = -(R.T @ t)
-    return c2w, r['mask'].cpu().numpy().astype(np.uint8).reshape(-1, 1)
+    return _args.c2w_from(r['R'], r['t'], invert=True), _args.mask_column(r['mask'])

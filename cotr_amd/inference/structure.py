@@ -8,88 +8,26 @@ camera-to-world matrices, ``stack_views`` shapes the correspondences of one quer
 ``reconstruct_tensors`` is what ``ZoomEngine.reconstruct`` runs after its correspondences: the last lines of
 demo_reconstruction.py (``rule='demo'``: the point on ray A nearest ray B; colours: the mean of the two images at the
 floored coordinates over 255) without its viewer.  No CPU fallback."""
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib
 from .._lib import check_op, on, ptr
-from . import _ransac
-from ._ransac import _device
-from .essential import _camera, _check_distance
+from . import _args, _ransac
+from ._args import F64, I32, MAX_VIEWS, U8  # noqa: F401 (MAX_VIEWS: the limit of this module's calls)
 
-MAX_VIEWS = 32
 MAX_REFINE = 64
 RULES = {'rays': 0, 'demo': 1}
-
-
-def _no_cpu_tensors(*xs):
-    if any(torch.is_tensor(x) and not x.is_cuda for x in xs):
-        raise _lib.CotrHipError('the triangulation runs on an MI355X only (HIP kernels, no CPU fallback): got a CPU tensor; '
-                                'pass a numpy array or move the tensor with .cuda()')
-
-
-def _tensor(x, dtype=np.float64):
-    return x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dtype)))
-
-
-def _view_points(points):
-    t = _tensor(points)
-    if t.dim() != 3 or t.shape[2] != 2:
-        raise ValueError(f'points must be [V, N, 2], got shape {tuple(t.shape)}')
-    V, N = int(t.shape[0]), int(t.shape[1])
-    if not 2 <= V <= MAX_VIEWS:
-        raise ValueError(f'between 2 and {MAX_VIEWS} views, got {V}')
-    if not 1 <= N <= _ransac.MAX_POINTS:
-        raise ValueError(f'between 1 and 2^24 points, got {N}')
-    return t.to(dtype=torch.float64), V, N
-
-
-def _cam_rows(cameras, V):
-    """[V,3,3] camera matrices, one [3,3] for every view, or [V,5] rows (fx, fy, cx, cy, skew) -> [V,5] float64 tensor"""
-    if torch.is_tensor(cameras) and cameras.is_cuda:
-        c = cameras.to(dtype=torch.float64)
-        if c.dim() == 3 and tuple(c.shape[1:]) == (3, 3):
-            c = torch.stack([c[:, 0, 0], c[:, 1, 1], c[:, 0, 2], c[:, 1, 2], c[:, 0, 1]], dim=1)
-    else:
-        k = np.asarray(cameras.cpu() if torch.is_tensor(cameras) else cameras, dtype=np.float64)
-        if k.shape == (3, 3):
-            k = np.broadcast_to(k, (V, 3, 3))
-        if k.ndim == 3 and k.shape[1:] == (3, 3):
-            k = np.stack([k[:, 0, 0], k[:, 1, 1], k[:, 0, 2], k[:, 1, 2], k[:, 0, 1]], axis=1)
-        if k.ndim == 2 and k.shape[1] == 5 and (not np.isfinite(k).all() or (k[:, :2] == 0).any()):
-            raise ValueError('cameras must be finite with focal lengths that are not 0')
-        c = torch.from_numpy(np.ascontiguousarray(k))
-    if c.dim() != 2 or tuple(c.shape) != (V, 5):
-        raise ValueError(f'cameras must be [V, 3, 3], [3, 3] or [V, 5] for {V} views, got shape {tuple(np.shape(cameras))}')
-    return c
-
-
-def _pose_rows(poses, V):
-    """[V,3,4] or [V,4,4] world-to-camera matrices, or [V,12] -> [V,12] float64 tensor"""
-    t = _tensor(poses).to(dtype=torch.float64)
-    if t.dim() == 3 and tuple(t.shape[1:]) == (4, 4):
-        t = t[:, :3]
-    if t.dim() == 3 and tuple(t.shape[1:]) == (3, 4):
-        t = t.reshape(t.shape[0], 12)
-    if t.dim() != 2 or tuple(t.shape) != (V, 12):
-        raise ValueError(f'poses must be [V, 3, 4], [V, 4, 4] or [V, 12] for {V} views, got shape {tuple(np.shape(poses))}')
-    return t
+_SUBJECT = 'the triangulation runs'
 
 
 def _check(threshold, min_angle, distance_thresh, refine_iters, robust, rule, V):
-    if not (threshold > 0 and np.isfinite(threshold)):
-        raise ValueError(f'threshold must be finite and > 0, got {threshold}')
-    with np.errstate(over='ignore', under='ignore'):
-        sq = np.float32(float(threshold) * float(threshold))
-    if not (sq > 0 and np.isfinite(sq)):
-        raise ValueError(f'the squared threshold must be a finite float32 that is not 0, got threshold {threshold}')
+    _args.check_positive('threshold', threshold)
+    _args.check_sq_float32(threshold)
     if not 0 <= min_angle <= 180:
         raise ValueError(f'min_angle must be in [0, 180] degrees, got {min_angle}')
-    _check_distance(distance_thresh)
-    if not 0 <= int(refine_iters) <= MAX_REFINE or int(refine_iters) != refine_iters:
-        raise ValueError(f'refine_iters must be an integer in [0, {MAX_REFINE}], got {refine_iters}')
+    _args.check_distance(distance_thresh)
+    _args.check_int_range('refine_iters', refine_iters, 0, MAX_REFINE)
     if rule not in RULES:
         raise ValueError(f"rule must be 'rays' or 'demo', got {rule!r}")
     if rule == 'demo' and (V != 2 or robust or refine_iters != 0):
@@ -97,17 +35,11 @@ def _check(threshold, min_angle, distance_thresh, refine_iters, robust, rule, V)
 
 
 def _enqueue(lib, pts, vis, cams, poses, V, N, found, threshold, max_cos, distance_thresh, refine_iters, robust, rule, device):
-    nbytes = ctypes.c_size_t()
-    check_op(lib.cotr_triangulate_views_scratch_bytes(V, N, ctypes.byref(nbytes)), 'cotr_triangulate_views_scratch_bytes')
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    X = torch.empty((N, 3), dtype=torch.float64, device=device)
-    used = torch.empty((V, N), dtype=torch.uint8, device=device)
-    quality = torch.empty((N, 5), dtype=torch.float64, device=device)
-    mask = torch.empty(N, dtype=torch.uint8, device=device)
-    info = torch.empty(8, dtype=torch.int32, device=device)
+    scratch, nbytes = _args.scratch(lib, 'cotr_triangulate_views_scratch_bytes', V, N, device=device)
+    X, used, quality, mask, info = _args.empty(device, ((N, 3), F64), ((V, N), U8), ((N, 5), F64), (N, U8), (8, I32))
     check_op(lib.cotr_triangulate_views(ptr(pts), ptr(vis), ptr(cams), ptr(poses), V, N, ptr(found), float(threshold), float(max_cos),
                                         float(distance_thresh), int(refine_iters), int(bool(robust)), RULES[rule], ptr(X), ptr(used),
-                                        ptr(quality), ptr(mask), ptr(info), ptr(scratch), nbytes.value, _lib.current_stream_ptr()),
+                                        ptr(quality), ptr(mask), ptr(info), ptr(scratch), nbytes, _lib.current_stream_ptr()),
              'cotr_triangulate_views')
     return dict(X=X, used=used.bool(), quality=quality, mask=mask.bool(), info=info)
 
@@ -126,22 +58,13 @@ def triangulate_views(points, cameras, poses, visible=None, threshold=4.0, min_a
     kept).  ``refine_iters``: the most Gauss-Newton steps on the pixel error after the ray least squares.  ``rule='demo'``
     (two views, robust=False, refine_iters=0): the point on ray A nearest ray B.  ``found``: a device int32 tensor whose
     first entry 0 zeroes every output (the flag ``relative_pose_tensors`` returns as info)."""
-    pts, V, N = _view_points(points)
-    cams = _cam_rows(cameras, V)
-    rows = _pose_rows(poses, V)
-    vis = None
-    if visible is not None:
-        vis = _tensor(visible, None)
-        if tuple(vis.shape) != (V, N):
-            raise ValueError(f'visible must be [V, N] = [{V}, {N}], got shape {tuple(vis.shape)}')
+    pts, V, N = _args.view_points(points)
+    cams, rows, vis = _args.cam_rows(cameras, V), _args.pose_rows(poses, V), _args.visible(visible, V, N)
     _check(threshold, min_angle, distance_thresh, refine_iters, robust, rule, V)
-    _no_cpu_tensors(points, cameras, poses, visible, found)
-    device = _device(device)
+    _args.no_cpu_tensors(_SUBJECT, points, cameras, poses, visible, found)
+    device = _args.device(device)
     pts, cams, rows = on(pts, device, 16), on(cams, device), on(rows, device)
-    if vis is not None:
-        vis = (on(vis, device) != 0).to(torch.uint8)
-    if found is not None:
-        found = on(found, device).to(torch.int32).reshape(-1)
+    vis, found = _args.mask_u8(vis, (V, N), device), _args.found_i32(found, device)
     max_cos = float(np.cos(np.deg2rad(float(min_angle))))
     with torch.cuda.device(device):
         return _enqueue(_lib.load_library(), pts, vis, cams, rows, V, N, found, threshold, max_cos, distance_thresh, refine_iters, robust,
@@ -149,7 +72,7 @@ def triangulate_views(points, cameras, poses, visible=None, threshold=4.0, min_a
 
 
 def _k5(K, what):
-    k = _camera(K, what)
+    k = _args.camera(K, what)
     return [k[0], k[4], k[2], k[5], k[1]]
 
 
@@ -158,12 +81,8 @@ def _check_two_view_poses(R, t, c2w1, c2w2):
     if (R is None) != (t is None) or (c2w1 is None) != (c2w2 is None) or (R is None) == (c2w1 is None):
         raise ValueError('give either R and t (camera 1 at [I | 0]) or c2w1 and c2w2')
     if R is not None:
-        r, tt = _tensor(R).to(dtype=torch.float64), _tensor(t).to(dtype=torch.float64)
-        if r.numel() != 9:
-            raise ValueError(f'R must be [3, 3], got shape {tuple(r.shape)}')
-        if tt.numel() != 3:
-            raise ValueError(f't must have 3 entries, got shape {tuple(tt.shape)}')
-        _no_cpu_tensors(R, t)
+        r, tt = _args.flat(R, 'R', 9), _args.flat(t, 't', 3, 'have 3 entries')
+        _args.no_cpu_tensors(_SUBJECT, R, t)
         return 'rt', r, tt
     rows = []
     for m, what in ((c2w1, 'c2w1'), (c2w2, 'c2w2')):
@@ -195,8 +114,8 @@ def triangulate_points_tensors(points1, points2, K1, K2=None, R=None, t=None, c2
     check = dict(threshold=4.0, min_angle=1.5, distance_thresh=50.0, refine_iters=10, robust=True, rule='rays')
     check.update({k: v for k, v in kw.items() if k in check})
     _check(V=2, **check)
-    _no_cpu_tensors(points1, points2, kw.get('visible'), kw.get('found'))
-    device = _device(device)
+    _args.no_cpu_tensors(_SUBJECT, points1, points2, kw.get('visible'), kw.get('found'))
+    device = _args.device(device)
     poses = _two_view_poses(spec, device)
     pts = torch.stack([p1.to(device), p2.to(device)], dim=0)
     return triangulate_views(pts, np.array([k1, k2]), poses, device=device, **kw)
@@ -205,7 +124,7 @@ def triangulate_points_tensors(points1, points2, K1, K2=None, R=None, t=None, c2
 def triangulate_points(points1, points2, K1, K2=None, R=None, t=None, c2w1=None, c2w2=None, **kw):
     """``triangulate_points_tensors`` with host arrays back -> (X float64 [n,3], mask uint8 [n,1])."""
     r = triangulate_points_tensors(points1, points2, K1, K2, R, t, c2w1, c2w2, **kw)
-    return r['X'].cpu().numpy(), r['mask'].cpu().numpy().astype(np.uint8).reshape(-1, 1)
+    return r['X'].cpu().numpy(), _args.mask_column(r['mask'])
 
 
 def stack_views(corrs_list):
@@ -251,7 +170,7 @@ def reconstruct_tensors(corrs, img_a, img_b, K_a, K_b, c2w_a=None, c2w_b=None, r
     its dict.  With only view 0 fixed nothing pins the scale: the damping leaves it where the input put it, and the translation
     of view 1 is no longer of unit length.  0 (the default): the outputs are those of the triangulation alone, bit for bit."""
     from .essential import relative_pose_tensors
-    c = _tensor(corrs).to(dtype=torch.float64)
+    c = _args.tensor(corrs).to(dtype=torch.float64)
     if c.dim() != 2 or c.shape[1] != 4:
         raise ValueError(f'corrs must be [N, 4], got shape {tuple(c.shape)}')
     if (c2w_a is None) != (c2w_b is None):
@@ -261,7 +180,7 @@ def reconstruct_tensors(corrs, img_a, img_b, K_a, K_b, c2w_a=None, c2w_b=None, r
             raise ValueError(f'{what} must be [H, W, 3], got shape {tuple(img.shape)}')
     if int(bundle_rounds) != bundle_rounds or bundle_rounds < 0:
         raise ValueError(f'bundle_rounds must be an integer >= 0, got {bundle_rounds}')
-    device = _device(device)
+    device = _args.device(device)
     c = c.to(device)
     pa, pb = c[:, :2].contiguous(), c[:, 2:].contiguous()
     if rule == 'demo':

@@ -6,13 +6,12 @@ rasterisation is one ``cotr_raster_mesh`` call on the current device (cotr_amd/c
 in DESIGN.md 3g).  The triangulation is scipy's on the host by default (imported when called); with ``simplices='device'``
 it is one ``cotr_delaunay`` call (cotr_amd/csrc/delaunay.hip; an exact rule of its own) and nothing
 leaves the device.  No CPU fallback."""
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib
 from .._lib import check_op, ptr
+from . import _args
 
 
 def raster_mesh(verts, attrs, tris, H, W, device=None):
@@ -26,14 +25,12 @@ def raster_mesh(verts, attrs, tris, H, W, device=None):
     tris = torch.as_tensor(np.asarray(tris, dtype=np.int32) if not torch.is_tensor(tris) else tris,
                            dtype=torch.int32).to(device).contiguous()
     n_tris = tris.numel() // 3
-    nbytes = ctypes.c_size_t()
-    check_op(lib.cotr_raster_mesh_scratch_bytes(n_tris, H, W, ctypes.byref(nbytes)), 'cotr_raster_mesh_scratch_bytes')
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    scratch, nbytes = _args.scratch(lib, 'cotr_raster_mesh_scratch_bytes', n_tris, H, W, device=device)
     out = torch.empty((H, W, 2), dtype=torch.float32, device=device)
     mask = torch.empty((H, W), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
         check_op(lib.cotr_raster_mesh(ptr(verts), verts.shape[0], ptr(attrs), ptr(tris), n_tris, H, W, ptr(out), ptr(mask), ptr(scratch),
-                                      nbytes.value, _lib.current_stream_ptr()), 'cotr_raster_mesh')
+                                      nbytes, _lib.current_stream_ptr()), 'cotr_raster_mesh')
     return out, mask.bool()
 
 
@@ -58,13 +55,11 @@ def delaunay(points, device=None, as_tensor=False):
         device = points.device if torch.is_tensor(points) and points.is_cuda else torch.device('cuda', torch.cuda.current_device())
     device = torch.device(device)
     verts = torch.as_tensor(points if torch.is_tensor(points) else np.asarray(points), dtype=torch.float32).to(device).contiguous()
-    nbytes = ctypes.c_size_t()
-    check_op(lib.cotr_delaunay_scratch_bytes(n, ctypes.byref(nbytes)), 'cotr_delaunay_scratch_bytes')
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    scratch, nbytes = _args.scratch(lib, 'cotr_delaunay_scratch_bytes', n, device=device)
     tris = torch.empty((lib.cotr_delaunay_max_tris(n), 3), dtype=torch.int32, device=device)
     info = torch.empty(2, dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        check_op(lib.cotr_delaunay(ptr(verts), n, ptr(tris), ptr(info), ptr(scratch), nbytes.value, _lib.current_stream_ptr()),
+        check_op(lib.cotr_delaunay(ptr(verts), n, ptr(tris), ptr(info), ptr(scratch), nbytes, _lib.current_stream_ptr()),
                  'cotr_delaunay')
     if as_tensor:
         return tris, info

@@ -16,27 +16,22 @@ import torch
 
 from .. import _lib
 from .._lib import check_op, on, ptr
+from . import _args
 from .triangulate import triangulate_corr
 
 MAX_SIDE = 16384
 
 
-def _is_tensor_on_cpu(*xs):
-    return any(torch.is_tensor(x) and not x.is_cuda for x in xs)
-
-
 def _pick_device(*xs):
     """the device of the tensors among xs (they must agree), else the current one; every check here runs before an upload"""
-    if _is_tensor_on_cpu(*xs):
-        raise _lib.CotrHipError('the warps run on an MI355X only (HIP kernels, no CPU fallback): got a CPU tensor; '
-                                'pass a numpy array or move the tensor with .cuda()')
+    _args.no_cpu_tensors('the warps run', *xs)
     devs = {x.device for x in xs if torch.is_tensor(x)}
     if len(devs) > 1:
         raise ValueError(f'the tensors of one warp must be on one device, got {sorted(str(d) for d in devs)}')
     return devs.pop() if devs else torch.device('cuda', torch.cuda.current_device())
 
 
-def _check_image(img, what):
+def check_image(img, what):
     """shape and dtype of an image argument -> (H, W, C); ValueError otherwise"""
     dtype = img.dtype
     if dtype not in (np.uint8, torch.uint8):
@@ -66,7 +61,7 @@ def _check_map(map_):
 def _check_background(background, Hd, Wd, C, img_ndim):
     if background is None:
         return
-    shape = _check_image(background, 'background')
+    shape = check_image(background, 'background')
     if shape != (Hd, Wd, C) or len(background.shape) != img_ndim:
         raise ValueError(f'background must have the result\'s shape {(Hd, Wd) + ((C,) if img_ndim == 3 else ())}, '
                          f'got {tuple(background.shape)}')
@@ -92,7 +87,7 @@ def warp_by_map(img, map, background=None, return_cover=False, as_tensor=False):
         background's pixel instead of the border value 0.
     return_cover: also return the bool [Hd, Wd] cover (``cv2.remap(ones) > 0``).
     as_tensor: return device tensors instead of numpy arrays."""
-    Hs, Ws, C = _check_image(img, 'img')
+    Hs, Ws, C = check_image(img, 'img')
     Hd, Wd = _check_map(map)
     _check_background(background, Hd, Wd, C, len(img.shape))
     device = _pick_device(img, map, background)
@@ -134,7 +129,7 @@ def warp_perspective(img, M, dsize, inverse_map=False, background=None, return_c
     inverse_map=True) by the rule of DESIGN.md 3i.  M: 3 x 3, source -> destination as cv2's default; it is inverted on the
     host in float64 (a singular M: ValueError).  dsize = (width, height).  background, return_cover, as_tensor: as in
     ``warp_by_map``."""
-    Hs, Ws, C = _check_image(img, 'img')
+    Hs, Ws, C = check_image(img, 'img')
     if len(dsize) != 2 or int(dsize[0]) != dsize[0] or int(dsize[1]) != dsize[1]:
         raise ValueError(f'dsize must be (width, height), got {dsize}')
     Wd, Hd = int(dsize[0]), int(dsize[1])
@@ -190,8 +185,8 @@ def paste_by_corners(picture, corners_b, img_b, as_tensor=False):
     picture's corners (``picture_corners``: lu, ru, lb, rb) land in ``img_b``, e.g. ``corrs[:, 2:]`` of the demo; rounded to
     float32 as the demo does.  One ``cotr_warp_perspective`` launch with ``img_b`` as the background -> uint8, ``img_b``'s
     shape: the warped picture where it covers, ``img_b`` elsewhere."""
-    _check_image(picture, 'picture')
-    Hb, Wb, _ = _check_image(img_b, 'img_b')
+    check_image(picture, 'picture')
+    Hb, Wb, _ = check_image(img_b, 'img_b')
     corners_b = np.asarray(corners_b.cpu() if torch.is_tensor(corners_b) else corners_b)
     if corners_b.shape != (4, 2):
         raise ValueError(f'corners_b must be [4, 2], got {corners_b.shape}')
@@ -205,8 +200,8 @@ def warp_by_corr(img_a, img_b, corrs, alpha=0.5, as_tensor=False, simplices=None
     [H_a, W_a, 3]).  The dense map stays on the device.  Outside the correspondences' hull the map is 0, so ``warped``
     reads ``img_b`` at (0, 0) there, exactly as the demo's cv2 call does.  simplices: as in ``triangulate_corr``; with 'device', device tensors for the images
     and ``corrs`` and as_tensor=True nothing passes through the host, and the call can be captured into a graph."""
-    _check_image(img_a, 'img_a')
-    _check_image(img_b, 'img_b')
+    check_image(img_a, 'img_a')
+    check_image(img_b, 'img_b')
     device = _pick_device(img_a, img_b)
     with torch.cuda.device(device):
         dense = triangulate_corr(corrs, img_a.shape, img_b.shape, simplices=simplices, as_tensor=True)

@@ -16,7 +16,7 @@ import torch
 from cotr_amd import _lib
 from cotr_amd.data import Capture, depth_corrs
 from cotr_amd.inference import ZoomEngine, icp_depth, refine_registration, register_captures
-from cotr_amd.inference import icp as icp_mod
+from cotr_amd.inference import _args, icp as icp_mod
 from cotr_amd.inference.rigid3d import register_captures_tensors
 from tests import icp_oracle as io
 from tests import pnp_oracle as po
@@ -144,7 +144,7 @@ def test_against_the_scene_at_96x128():
 def _device_args(sc):
     cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()   # noqa: E731
     return dict(depth_a=cu(sc['depth_a']), depth_b=cu(sc['depth_b']), R0=cu(sc['R0'].reshape(9)), t0=cu(sc['t0']),
-                ka=icp_mod._camera(sc['K_a'], 'K_a'), kb=icp_mod._camera(sc['K_b'], 'K_b'))
+                ka=_args.camera(sc['K_a'], 'K_a'), kb=_args.camera(sc['K_b'], 'K_b'))
 
 
 def _enqueue(a, found, iters=ITERS, tables=True):

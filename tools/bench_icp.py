@@ -21,7 +21,8 @@ import numpy as np
 import torch
 
 from cotr_amd import _lib
-from cotr_amd.inference.icp import _camera, icp_depth
+from cotr_amd.inference._args import camera
+from cotr_amd.inference.icp import icp_depth
 from tests import icp_oracle as io
 
 
@@ -45,7 +46,7 @@ def bench(H, W, a, steps=10, max_dist=0.25):
     sc = io.scene(H, W, H, W)
     cu = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()   # noqa: E731
     da, db, R0, t0 = cu(sc['depth_a']), cu(sc['depth_b']), cu(sc['R0'].reshape(9)), cu(sc['t0'])
-    ka, kb = _camera(sc['K_a'], 'K_a'), _camera(sc['K_b'], 'K_b')
+    ka, kb = camera(sc['K_a'], 'K_a'), camera(sc['K_b'], 'K_b')
     lib = _lib.load_library()
     nb = ctypes.c_size_t()
     assert lib.cotr_icp_depth_scratch_bytes(H, W, H, W, 1, ctypes.byref(nb)) == 0
