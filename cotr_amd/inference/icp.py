@@ -101,6 +101,14 @@ def icp_depth(depth_a, K_a, depth_b, K_b, R0, t0, max_dist, normal_cos=NORMAL_CO
                             stride, tables, device)
 
 
+def host_result(r):
+    """the dict of ``icp_depth`` -> (c2w float64 [4,4], info dict) on the host, as ``refine_registration`` returns them"""
+    info, stats = r['info'].cpu().numpy(), r['stats'].cpu().numpy()
+    c2w = _args.c2w_from(r['R'], r['t'])
+    return c2w, dict(ok=bool(info[0]), steps=int(info[1]), pairs=int(info[2]), stop=STOP_REASONS[int(info[3])], source_pixels=int(info[4]),
+                     target_pixels=int(info[5]), sum_r2=float(stats[0]), rmse=float(stats[1]))
+
+
 def refine_registration(cap_a, cap_b, c2w_b, max_dist=0.05, **kw):
     """The pose ``c2w_b`` [4,4] of the RGB-D capture ``cap_b`` in the world frame of the posed capture ``cap_a`` (both
     ``cotr_amd.data.Capture``; the c2w of ``cap_b`` is not read), refined on both depth maps by ``icp_depth`` -> (c2w_b float64
@@ -109,8 +117,4 @@ def refine_registration(cap_a, cap_b, c2w_b, max_dist=0.05, **kw):
     start = _args.pose_matrix(c2w_b)
     if start is None:
         raise ValueError('c2w_b must be a finite [4, 4] matrix, got None')
-    r = icp_depth(cap_a.depth, cap_a.K, cap_b.depth, cap_b.K, start[:3, :3], start[:3, 3], max_dist, c2w_a=cap_a.c2w, **kw)
-    info, stats = r['info'].cpu().numpy(), r['stats'].cpu().numpy()
-    c2w = _args.c2w_from(r['R'], r['t'])
-    return c2w, dict(ok=bool(info[0]), steps=int(info[1]), pairs=int(info[2]), stop=STOP_REASONS[int(info[3])], source_pixels=int(info[4]),
-                     target_pixels=int(info[5]), sum_r2=float(stats[0]), rmse=float(stats[1]))
+    return host_result(icp_depth(cap_a.depth, cap_a.K, cap_b.depth, cap_b.K, start[:3, :3], start[:3, 3], max_dist, c2w_a=cap_a.c2w, **kw))

@@ -1,0 +1,251 @@
+"""A fused model of registered RGB-D captures on the device: a truncated signed distance (TSDF) volume that averages their
+depth maps, and the raycast of that volume from a pose - the model half of KinectFusion, whose tracking half is ``icp_depth``.
+
+``TsdfVolume`` holds the two float32 tensors [Nz,Ny,Nx] and the scalars; ``integrate_depths`` is ``cotr_tsdf_integrate``
+(cotr_amd/csrc/tsdf.hip) with device tensors, ``fuse_captures`` the same on ``cotr_amd.data.Capture``s; ``raycast_volume`` is
+``cotr_tsdf_raycast``: a float32 depth map (and normals) of the kind ``icp_depth`` reads, so ``track_capture`` - a raycast at
+the predicted pose and ``icp_depth`` against it, one device sequence - is frame-to-model tracking with no ICP code of its own.
+The rules are the library's own.  No CPU fallback."""
+import ctypes
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .._lib import check_op, on, ptr
+from . import _args, icp
+from ._args import F64, I32
+from .icp import _enqueue_icp
+
+MAX_CAPTURES = 32
+MAX_VOXELS = 1 << 28
+MAX_STEPS = 1 << 16
+D3 = ctypes.c_double * 3
+
+
+class TsdfVolume:
+    """``dims`` = (Nx, Ny, Nz) voxels of side ``voxel``; ``origin``: the world position of the centre of voxel (0, 0, 0).
+    ``tsdf`` and ``weight``: float32 device tensors [Nz,Ny,Nx], 1 and 0 when fresh.  ``trunc``: the truncation distance (3 voxels
+    unless given); ``max_weight``: where a voxel's weight stops growing, so that the model keeps following the captures."""
+
+    def __init__(self, origin, voxel, dims, trunc=None, max_weight=64.0, device=None):
+        o = np.asarray(origin, dtype=np.float64)
+        if o.shape != (3,) or not np.isfinite(o).all():
+            raise ValueError(f'origin must be 3 finite numbers, got {origin}')
+        _args.check_positive('voxel', voxel)
+        if len(dims) != 3:
+            raise ValueError(f'dims must be (Nx, Ny, Nz), got {dims}')
+        for name, v in zip(('Nx', 'Ny', 'Nz'), dims):
+            _args.check_int_range(name, v, 2, MAX_VOXELS)
+        if int(dims[0]) * int(dims[1]) * int(dims[2]) > MAX_VOXELS:
+            raise ValueError(f'dims: at most 2^28 voxels, got {dims[0]} x {dims[1]} x {dims[2]}')
+        trunc = 3.0 * voxel if trunc is None else trunc
+        _args.check_positive('trunc', trunc)
+        if not max_weight > 0:
+            raise ValueError(f'max_weight must be > 0, got {max_weight}')
+        self.origin, self.voxel, self.dims = o, float(voxel), tuple(int(v) for v in dims)
+        self.trunc, self.max_weight = float(trunc), float(max_weight)
+        self.device = _args.device(device)
+        Nx, Ny, Nz = self.dims
+        self.tsdf, self.weight = _args.empty(self.device, ((Nz, Ny, Nx), torch.float32), ((Nz, Ny, Nx), torch.float32))
+        self.reset()
+
+    def reset(self):
+        self.tsdf.fill_(1.0)
+        self.weight.zero_()
+        return self
+
+    def corners(self):
+        """the centres of the 8 corner voxels, [8, 3]"""
+        far = self.origin + self.voxel * (np.asarray(self.dims, np.float64) - 1)
+        return np.array([[(self.origin, far)[b >> a & 1][a] for a in range(3)] for b in range(8)])
+
+
+def _volume_args(volume):
+    Nx, Ny, Nz = volume.dims
+    return ptr(volume.tsdf), ptr(volume.weight), Nx, Ny, Nz, D3(*volume.origin), volume.voxel
+
+
+def _check_volume(volume):
+    if not isinstance(volume, TsdfVolume):
+        raise ValueError(f'volume must be a TsdfVolume, got {type(volume).__name__}')
+
+
+def _pose_rows(c2ws, n):
+    """[n,4,4] camera-to-world: a device tensor as it is, anything else through ``_args.pose_matrix`` -> float64 [n,16], where it was"""
+    if torch.is_tensor(c2ws) and c2ws.is_cuda:
+        if c2ws.dtype != F64 or c2ws.numel() != n * 16:
+            raise ValueError(f'c2ws on the device must be float64 [{n}, 4, 4], got {c2ws.dtype} {list(c2ws.shape)}')
+        return c2ws.reshape(n, 16)
+    if len(c2ws) != n:
+        raise ValueError(f'c2ws must hold one [4, 4] matrix for each of the {n} depth maps, got {len(c2ws)}')
+    return torch.from_numpy(np.stack([_args.pose_matrix(m) for m in c2ws]).reshape(n, 16))
+
+
+def _enqueue_integrate(lib, volume, depths, ks, c2ws, found, weights):
+    """every tensor on the volume's device already, every argument checked, at most 32 maps -> info int32 [n,4]"""
+    n, H, W = (int(v) for v in depths.shape)
+    info, = _args.empty(volume.device, ((n, 4), I32))
+    K = (ctypes.c_double * (9 * n))(*[v for k in ks for v in k])
+    w = None if weights is None else (ctypes.c_double * n)(*weights)
+    check_op(lib.cotr_tsdf_integrate(*_volume_args(volume), volume.trunc, ptr(depths), n, H, W, K, ptr(c2ws), ptr(found), w, volume.max_weight,
+                                     ptr(info), _lib.current_stream_ptr()), 'cotr_tsdf_integrate')
+    return info
+
+
+def integrate_depths(volume, depths, Ks, c2ws, found=None, weights=None):
+    """``cotr_tsdf_integrate`` on the current stream: the depth maps ``depths`` float32 [n,H,W] with the cameras ``Ks`` [n,3,3]
+    (host; one [3,3] serves every map) and the camera-to-world poses ``c2ws`` [n,4,4] (float64; device tensors are read in
+    place) are averaged into ``volume`` in the order 0 .. n-1.  ``found`` int [n]: a map whose entry is 0 is skipped (a device
+    tensor is read in place); ``weights`` [n] > 0: the weight of each map's observations (1).  More than 32 maps go in calls of
+    32.  -> info int32 device tensor [n,4] = (integrated, voxels updated, voxels whose pixel held a valid depth, 0)."""
+    _check_volume(volume)
+    if len(depths.shape) != 3 or depths.shape[0] < 1:
+        raise ValueError(f'depths must be [n, H, W] with n >= 1, got shape {tuple(depths.shape)}')
+    _args.check_depth(depths[0])
+    n = int(depths.shape[0])
+    k = np.asarray(Ks.cpu() if torch.is_tensor(Ks) else Ks, dtype=np.float64)
+    if k.shape == (3, 3):
+        k = np.broadcast_to(k, (n, 3, 3))
+    if k.shape != (n, 3, 3):
+        raise ValueError(f'Ks must be [{n}, 3, 3] or [3, 3], got shape {k.shape}')
+    ks = [_args.camera(m, 'Ks') for m in k]
+    rows = _pose_rows(c2ws, n)
+    if weights is not None:
+        weights = [float(v) for v in np.asarray(weights, dtype=np.float64).reshape(-1)]
+        if len(weights) != n:
+            raise ValueError(f'weights must be [{n}], got {len(weights)}')
+        for v in weights:
+            _args.check_positive('weights', v)
+    if found is not None and not torch.is_tensor(found):
+        found = np.asarray(found)
+    if found is not None and int(np.prod(tuple(found.shape))) != n:
+        raise ValueError(f'found must be [{n}], got shape {tuple(found.shape)}')
+    _args.no_cpu_tensors('the TSDF volume runs', depths, c2ws, found)
+    device = volume.device
+    depths, rows, found = on(depths, device), on(rows, device), _args.found_i32(found, device)
+    with torch.cuda.device(device):
+        lib = _lib.load_library()
+        infos = [_enqueue_integrate(lib, volume, depths[a:a + MAX_CAPTURES], ks[a:a + MAX_CAPTURES], rows[a:a + MAX_CAPTURES],
+                                    None if found is None else found[a:a + MAX_CAPTURES], None if weights is None else weights[a:a + MAX_CAPTURES])
+                 for a in range(0, n, MAX_CAPTURES)]
+    return infos[0] if len(infos) == 1 else torch.cat(infos)
+
+
+def fuse_captures(caps, volume=None, origin=None, voxel=None, dims=None, weights=None, **kw):
+    """The posed RGB-D captures ``caps`` (``cotr_amd.data.Capture``: image, depth, K, c2w; the image is not read) averaged into
+    ``volume``, or into a fresh ``TsdfVolume(origin, voxel, dims, **kw)`` (``kw``: trunc, max_weight, device), in list order;
+    neighbours of one depth-map size share a call.  -> (volume, one dict(integrated, updated, valid) per capture)."""
+    caps = list(caps)
+    if not caps:
+        raise ValueError('fuse_captures needs at least one capture')
+    for cap in caps:
+        _args.check_depth(cap.depth)
+        _args.camera(cap.K, 'K')
+        if _args.pose_matrix(cap.c2w) is None:
+            raise ValueError('c2w must be a finite [4, 4] matrix, got None')
+    if weights is not None and len(weights) != len(caps):
+        raise ValueError(f'weights must be [{len(caps)}], got {len(weights)}')
+    _args.no_cpu_tensors('the TSDF volume runs', *[cap.depth for cap in caps])
+    if volume is None:
+        if origin is None or voxel is None or dims is None:
+            raise ValueError('fuse_captures needs a volume, or origin, voxel and dims for a fresh one')
+        volume = TsdfVolume(origin, voxel, dims, **kw)
+    elif kw or origin is not None or voxel is not None or dims is not None:
+        raise ValueError('origin, voxel, dims, trunc, max_weight and device describe a fresh volume: give them or a volume, not both')
+    _check_volume(volume)
+    infos, a = [], 0
+    while a < len(caps):
+        b = a + 1
+        while b < len(caps) and b - a < MAX_CAPTURES and tuple(caps[b].depth.shape) == tuple(caps[a].depth.shape):
+            b += 1
+        depths = torch.stack([on(cap.depth, volume.device) for cap in caps[a:b]])
+        infos.append(integrate_depths(volume, depths, np.stack([np.asarray(cap.K, np.float64) for cap in caps[a:b]]),
+                                      [cap.c2w for cap in caps[a:b]], weights=None if weights is None else weights[a:b]))
+        a = b
+    rows = torch.cat(infos).cpu().numpy()
+    return volume, [dict(integrated=bool(r[0]), updated=int(r[1]), valid=int(r[2])) for r in rows]
+
+
+def _enqueue_raycast(lib, volume, k, c2w, found, H, W, near, far, step, normals):
+    """``c2w`` float64 [16] and ``found`` on the volume's device already, every argument checked -> the dict of ``raycast_volume``"""
+    depth, info = _args.empty(volume.device, ((H, W), torch.float32), (4, I32))
+    out = dict(depth=depth, info=info)
+    if normals:
+        out['normals'], = _args.empty(volume.device, ((H, W, 3), F64))
+    check_op(lib.cotr_tsdf_raycast(*_volume_args(volume), k, ptr(c2w), ptr(found), H, W, float(near), float(far), float(step), ptr(depth),
+                                   ptr(out.get('normals')), ptr(info), _lib.current_stream_ptr()), 'cotr_tsdf_raycast')
+    return out
+
+
+def _ray_args(volume, c2w, shape, near, far, step):
+    """-> (the pose as float64 [16] where it was, H, W, near, far, step) with the defaults filled in and every rule checked"""
+    _check_volume(volume)
+    if len(shape) != 2:
+        raise ValueError(f'shape must be (H, W), got {shape}')
+    H, W = shape
+    _args.check_int_range('H', H, 1, 1 << 28)
+    _args.check_int_range('W', W, 1, 1 << 28)
+    if int(H) * int(W) > 1 << 28:
+        raise ValueError(f'shape: at most 2^28 pixels, got {H} x {W}')
+    near = 0.0 if near is None else near
+    step = volume.trunc / 2 if step is None else step
+    if not (near >= 0 and np.isfinite(near)):
+        raise ValueError(f'near must be finite and >= 0, got {near}')
+    _args.check_positive('step', step)
+    if torch.is_tensor(c2w) and c2w.is_cuda:
+        if c2w.dtype != F64 or c2w.numel() != 16:
+            raise ValueError(f'c2w on the device must be float64 [4, 4], got {c2w.dtype} {list(c2w.shape)}')
+        if far is None:
+            raise ValueError('far must be given when c2w is a device tensor: its default is worked out from the pose on the host')
+        pose = c2w.reshape(16)
+    else:
+        m = _args.pose_matrix(c2w)
+        if m is None:
+            raise ValueError('c2w must be a finite [4, 4] matrix, got None')
+        if far is None:
+            far = float(np.linalg.norm(volume.corners() - m[:3, 3], axis=1).max())
+            far = max(far, near + step)
+        pose = torch.from_numpy(m.reshape(16))
+    if not (far > near and np.isfinite(far)):
+        raise ValueError(f'far must be finite and > near, got {far}')
+    if np.ceil((far - near) / step) > MAX_STEPS:
+        raise ValueError(f'at most 65536 steps from near to far, got {np.ceil((far - near) / step):.0f}')
+    return pose, int(H), int(W), float(near), float(far), float(step)
+
+
+def raycast_volume(volume, K, c2w, shape, near=None, far=None, step=None, normals=False):
+    """``cotr_tsdf_raycast`` on the current stream: ``volume`` seen from the camera-to-world pose ``c2w`` [4,4] (float64; a
+    device tensor is read in place) through the camera ``K`` [3,3] at ``shape`` = (H, W): every ray walks from ``near`` (0) to
+    ``far`` in steps of ``step`` (half the truncation distance) to the first crossing from in front of the surface to behind
+    it.  ``far`` defaults to the largest distance from the camera centre to a corner of the volume, worked out on the host: it
+    must be given with a device ``c2w``.  -> dict of device tensors: depth float32 [H,W] (0 where no surface is hit: a valid
+    input of ``icp_depth``, ``lift_pixels`` and ``integrate_depths``), info int32 [4] = (ok, pixels hit, rays ended at a back
+    face, 0), with ``normals=True`` normals float64 [H,W,3] in the camera frame (NaN where there is none)."""
+    k = _args.camera(K, 'K')
+    pose, H, W, near, far, step = _ray_args(volume, c2w, shape, near, far, step)
+    _args.no_cpu_tensors('the TSDF volume runs', c2w)
+    with torch.cuda.device(volume.device):
+        return _enqueue_raycast(_lib.load_library(), volume, k, on(pose, volume.device), None, H, W, near, far, step, normals)
+
+
+def track_capture(volume, cap, c2w0, max_dist=0.05, near=None, far=None, step=None, normal_cos=icp.NORMAL_COS, edge=icp.EDGE,
+                  cond_tol=icp.COND_TOL, iters=10, stride=1):
+    """Frame-to-model tracking: ``volume`` is raycast at the predicted pose ``c2w0`` [4,4] with the camera and map size of the
+    RGB-D capture ``cap`` (its c2w is not read), and ``icp_depth`` refines ``c2w0`` with that map as A and ``cap.depth`` as B, in
+    one device sequence -> (c2w float64 [4,4], info) as ``refine_registration`` returns them."""
+    _args.check_map(cap.depth, 'cap.depth')
+    k = _args.camera(cap.K, 'K')
+    start = _args.pose_matrix(c2w0)
+    pose, H, W, near, far, step = _ray_args(volume, start, tuple(cap.depth.shape), near, far, step)
+    icp.check(max_dist, normal_cos, edge, cond_tol, iters, stride)
+    _args.no_cpu_tensors('the TSDF volume runs', cap.depth)
+    device = volume.device
+    with torch.cuda.device(device):
+        lib = _lib.load_library()
+        pose = on(pose, device)
+        model = _enqueue_raycast(lib, volume, k, pose, None, H, W, near, far, step, False)
+        R0, t0 = on(np.ascontiguousarray(start[:3, :3]).reshape(9), device), on(np.ascontiguousarray(start[:3, 3]), device)
+        r = _enqueue_icp(lib, model['depth'], k, on(cap.depth, device), k, R0, t0, pose, None, None, max_dist, normal_cos, edge, cond_tol, iters,
+                         stride, False, device)
+    return icp.host_result(r)

@@ -754,6 +754,18 @@ class ZoomEngine:
         c2w_b, mask = register_captures(corrs[:, :2], corrs[:, 2:], cap_a, cap_b, **ransac_kw)
         return c2w_b, corrs, mask
 
+    def fuse(self, caps, volume, icp_iters=10, **register_kw):
+        """A small reconstruction: the RGB-D captures ``caps[1:]`` (``cotr_amd.data.Capture``; their c2w is not read) are placed
+        against the posed capture ``caps[0]`` by ``register`` (``register_kw``, with the dense refinement of ``icp_iters`` steps),
+        and every capture that was placed is averaged into the ``TsdfVolume`` ``volume`` by ``fuse_captures``, in list order ->
+        (volume, poses: one c2w float64 [4,4] per capture, None where none was found, found: one bool per capture)."""
+        from .tsdf import fuse_captures
+        caps = list(caps)
+        poses = [np.asarray(caps[0].c2w, dtype=np.float64)] + [self.register(caps[0], cap, icp_iters=icp_iters, **register_kw)[0] for cap in caps[1:]]
+        found = [p is not None for p in poses]
+        fuse_captures([cap._replace(c2w=p) for cap, p in zip(caps, poses) if p is not None], volume)
+        return volume, poses, found
+
     def reconstruct(self, img_a, img_b, K_a, K_b, c2w_a=None, c2w_b=None, queries_a=None, zoom_ins=np.linspace(0.5, 0.0625, 4),
                     converge_iters=1, max_corrs=1000, rule='rays', pose_kw=None, bundle_rounds=0, **structure_kw):
         """demo_reconstruction.py up to its viewer: ``cotr_corr_multiscale`` from A into B (from ``queries_a`` [N, 2] with

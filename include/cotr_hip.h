@@ -702,6 +702,53 @@ int cotr_icp_depth(const float* depth_a, int Ha, int Wa, const double* K_a, cons
                    int32_t* assoc_out, double* maps_a_out, double* maps_b_out, void* scratch, size_t scratch_bytes,
                    cotr_stream stream);
 
+/* ---- a fused model of posed depth maps: TSDF integration and raycast (cotr_amd/csrc/tsdf.hip; rules in DESIGN.md 3h-11) ---
+ * A truncated signed distance volume that averages registered depth maps, and the depth map of its zero crossing seen from
+ * a pose: the map cotr_icp_depth tracks the next capture against.  The rules are the library's own.
+ *
+ * The volume: tsdf, weight float32 [Nz][Ny][Nx] DEVICE, x fastest, owned by the caller; a fresh volume has tsdf = 1 and
+ *   weight = 0.  origin: HOST, 3 doubles, the world position of the centre of voxel (0, 0, 0); voxel > 0: the voxel's side.
+ *   2 <= Nx, Ny, Nz and Nx Ny Nz <= 2^28.  Storage is float32; every intermediate below is float64, and no product is
+ *   contracted into an FMA.
+ * cotr_tsdf_integrate: depths [n][H][W] float32 DEVICE, 1 <= n <= 32, 1 <= H, W and H W <= 2^28; Ks HOST [n][9], each as K
+ *   in cotr_lift_pixels; c2w [n][16] float64 DEVICE, row-major camera-to-world [R | t] (it may be built from the outputs of
+ *   cotr_icp_depth without a host trip); found int32 DEVICE [n] or NULL: a capture whose entry is 0 is skipped; obs_weight
+ *   HOST [n] or NULL (every w = 1): each finite and > 0; trunc > 0 finite; max_weight > 0.
+ *   One thread owns a voxel and takes the captures in the order 0 .. n-1, so the result is the same bits as n calls of one
+ *   capture each; the volume is read once and written once whatever n is.  Voxel (i, j, k), capture c:
+ *   P = origin + voxel (i, j, k) (each origin_a + voxel * index); D = P - t; Y = R^T D, each component (R_0a D_0 + R_1a D_1)
+ *   + R_2a D_2.  Skipped unless Y_z > 0.  xn = Y_x / Y_z, yn = Y_y / Y_z, u = (fx xn + skew yn) + cx, v = fy yn + cy (the rule
+ *   of cotr_icp_depth); skipped unless (rint u, rint v) (ties to even) lies inside the map.  z: the depth there; skipped
+ *   unless it is finite and > 0.  sdf = z - Y_z; skipped when sdf < -trunc.  d = min(1, sdf / trunc);
+ *   tsdf <- float32((double(tsdf) double(weight) + d w) / (double(weight) + w)), then
+ *   weight <- float32(min(double(weight) + w, max_weight)).
+ *   -> info_out int32 [n][4] = {integrated (0 when found skipped it), voxels updated, voxels whose pixel held a valid
+ *   depth, 0}.
+ * cotr_tsdf_raycast: K HOST; c2w [16] float64 DEVICE; found int32 DEVICE [1] or NULL: found[0] == 0: every output is 0.
+ *   1 <= H, W and H W <= 2^28; near >= 0, far > near, step > 0, all finite, S = ceil((far - near) / step) <= 65536.
+ *   One thread owns a pixel (x, y).  yn = (y - cy) / fy, xn = (x - cx - skew yn) / fx (cotr_lift_pixels' rule at the pixel
+ *   centre), m = sqrt((xn^2 + yn^2) + 1), the direction in the camera frame c = (xn / m, yn / m, 1 / m) and in the world
+ *   d_a = (R_a0 c_0 + R_a1 c_1) + R_a2 c_2.  Sample k = 0 .. S lies at s_k = near + k step (a product, not a running sum),
+ *   p = t + s_k d.  A sample at p: g = (p - origin) / voxel, i0 = floor(g); valid iff 0 <= i0 <= N - 2 on each axis and all 8
+ *   corners i0 + {0, 1}^3 have weight > 0; its value f is the trilinear blend of their tsdf with fr = g - i0, every blend
+ *   a + fr (b - a), along x, then y, then z.  The first k whose previous sample is valid with f_prev > 0 and whose own is
+ *   valid with f <= 0 is a hit at s* = s_(k-1) + step (f_prev / (f_prev - f)).  A valid f_prev < 0 followed by a valid f > 0
+ *   is a back face: the ray ends with no hit.  An invalid sample resets "previous".
+ *   -> depth_out float32 [H][W] = s* c_2, 0 where there is no hit: a valid input of cotr_icp_depth, cotr_lift_pixels and
+ *   cotr_tsdf_integrate.  normal_out float64 [H][W][3] DEVICE or NULL, in the camera frame: at p* = t + s* d the gradient
+ *   G_a = f(p* + voxel e_a) - f(p* - voxel e_a) from six more samples, L = sqrt((G_0^2 + G_1^2) + G_2^2), n_a = ((R_0a G_0 +
+ *   R_1a G_1) + R_2a G_2) / L; three NaN where there is no hit, one of the six samples is invalid or L is not > 0.
+ *   info_out int32 [4] = {ok (found), pixels hit, rays ended at a back face, 0}.
+ * Stream-ordered, 2 launches each whatever the data (a prologue that sets info_out, then the volume or the image), no host
+ * waits and no allocation (capturable); integer atomics only: the same input gives the same bits.  Bad arguments are checked
+ * before any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_tsdf_integrate(float* tsdf, float* weight, int Nx, int Ny, int Nz, const double* origin, double voxel, double trunc,
+                        const float* depths, int n, int H, int W, const double* Ks, const double* c2w, const int32_t* found,
+                        const double* obs_weight, double max_weight, int32_t* info_out, cotr_stream stream);
+int cotr_tsdf_raycast(const float* tsdf, const float* weight, int Nx, int Ny, int Nz, const double* origin, double voxel,
+                      const double* K, const double* c2w, const int32_t* found, int H, int W, double near, double far,
+                      double step, float* depth_out, double* normal_out, int32_t* info_out, cotr_stream stream);
+
 /* ---- structure from known cameras: robust N-view triangulation (cotr_amd/csrc/structure.hip; rules in DESIGN.md 3h-6) ----
  * n correspondences seen in V posed views -> their 3D points, the views each point was fitted on, and the per-point
  * figures a reconstruction filters on.  The rules are the library's own.
