@@ -18,12 +18,30 @@
 //                               g = (p - origin) / voxel is monotone), so the samples inside the box are one run of k and every
 //                               sample after it is invalid by the rule itself.  The hit and back-face counts: a ballot and one
 //                               integer atomic per wavefront.
+// cotr_tsdf_mesh (marching tetrahedra on the Kuhn split of every cell): 4 launches to count, 1 or 2 more to write:
+//   1. ts_begin_kernel          info = {found, 0, 0, 0}
+//   2. ms_classify_kernel       one thread per voxel: the cell above it is valid, and the inside bits of its 8 corners (2 B a voxel
+//                               of scratch).  A lane reads its column of 4 voxels and takes the column at x + 1 from the next lane.
+//   3. ms_count_kernel          one thread per voxel, blocks of 512 voxels: the 7 live bits of the voxel's edges from the codes of the
+//                               (at most 4) cells that hold each, the triangles of its cell, and the scan of both counts inside the
+//                               block (packed in one int: wave shuffles, wave totals through LDS) -> a 4 B record a voxel (written only
+//                               where the block holds a vertex) and the block's two totals.  Valid cells: ballots summed in a register
+//                               of each wavefront, four LDS slots, one integer atomic per workgroup into info.  2 and 3 run on at most
+//                               2048 workgroups that walk the blocks: one walk covers 2048 * 512 = 2^20 voxels.
+//   4. ms_scan_kernel           one workgroup of 1024: the exclusive scan of the block totals, both carried together; the counts.
+//   5. ms_emit_kernel           (a capacity above 0) a workgroup whose block has neither vertex nor triangle leaves; a thread writes
+//                               the vertices (and normals) of its voxel's live edges and the triangles of its cell: a vertex index
+//                               is the scanned base of the edge's voxel + the live bits below the edge's code.
+//   6. ms_pad_kernel            (cap_tris above 0) -1 into the triangle rows past the count.
+// Every position comes from the scan, none from an atomic.
 // Integer atomics only: the same input gives the same bits.  No host waits, no allocation: capturable.  Compiled with
 // -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
+
+#include <algorithm>
 
 #include "handleless.h"
 #include "pinhole.h"
@@ -122,10 +140,15 @@ struct TsRay {
   double near, step;
 };
 
-// the grid coordinates of p; false unless floor of each lies in [0, N - 2]
+// the validity of a sample at grid coordinates q, before its corners are looked at: floor of each lies in [0, N - 2]
+__device__ __forceinline__ bool ts_in_box(const TsGrid& g, const double* q) {
+  return q[0] >= 0.0 && q[0] < (double)(g.Nx - 1) && q[1] >= 0.0 && q[1] < (double)(g.Ny - 1) && q[2] >= 0.0 && q[2] < (double)(g.Nz - 1);
+}
+
+// the grid coordinates of p; false unless they lie in the box
 __device__ __forceinline__ bool ts_grid(const TsGrid& g, double px, double py, double pz, double* q) {
   q[0] = (px - g.ox) / g.voxel, q[1] = (py - g.oy) / g.voxel, q[2] = (pz - g.oz) / g.voxel;
-  return q[0] >= 0.0 && q[0] < (double)(g.Nx - 1) && q[1] >= 0.0 && q[1] < (double)(g.Ny - 1) && q[2] >= 0.0 && q[2] < (double)(g.Nz - 1);
+  return ts_in_box(g, q);
 }
 
 // the trilinear value at grid coordinates inside the box; false unless all 8 corners have been observed
@@ -229,6 +252,305 @@ __global__ __launch_bounds__(256) void ts_raycast_kernel(const float* __restrict
   }
 }
 
+// ---- the mesh -------------------------------------------------------------------------------------------------------------
+#define MS_THREADS 256
+#define MS_ROUNDS 2
+#define MS_BLOCK (MS_THREADS * MS_ROUNDS)   // voxels a workgroup of ms_count_kernel and ms_emit_kernel walks
+#define MS_BLOCK_SHIFT 9
+#define MS_SCAN_THREADS 1024                // block totals a pass of ms_scan_kernel takes: one pass covers 2^19 voxels
+#define MS_MAX_VOXELS (1 << 27)
+#define MS_GRID 2048                        // workgroups of a pass over the voxels: 8 on each of the 256 CUs, each walks every 2048th block
+// a voxel's record: its 7 live bits, then the vertices (12 bits) and the triangles (13 bits) of the voxels before it in its block
+static_assert(MS_BLOCK == 1 << MS_BLOCK_SHIFT && (MS_BLOCK - 1) * 7 < (1 << 12) && (MS_BLOCK - 1) * 12 < (1 << 13), "the record is 7 + 12 + 13 bits");
+
+// tetrahedron m of the Kuhn split: corners 0, k1, k2, 7 of the cell (corner b = x + 2 y + 4 z), the permutations of the axes in
+// lexicographic order
+__device__ __forceinline__ constexpr int ms_k1(int m) { return 1 << (m >> 1); }
+__device__ __forceinline__ constexpr int ms_k2(int m) { return ms_k1(m) | 1 << (m == 0 ? 1 : m == 1 ? 2 : m == 2 ? 0 : m == 3 ? 2 : m == 4 ? 0 : 1); }
+// bit 2 S + n: triangle n of sign pattern S leaves with its second and third vertex swapped.  One word for the even
+// permutations and one for the odd: a reflection of the tetrahedron turns every triangle over.
+__device__ __forceinline__ constexpr unsigned ms_swap(int m) { return (m == 0 || m == 3 || m == 4) ? 0x10710c10u : 0x070c71c4u; }
+
+__device__ __forceinline__ unsigned ms_pattern(unsigned C, int m) {
+  return (C & 1u) | ((C >> ms_k1(m)) & 1u) << 1 | ((C >> ms_k2(m)) & 1u) << 2 | ((C >> 7) & 1u) << 3;
+}
+
+// observed (bit 0) and inside (bit 1) of the voxels (j, k), (j + 1, k), (j, k + 1), (j + 1, k + 1) of column idx, two bits each;
+// a voxel past the volume reads as unobserved
+__device__ __forceinline__ unsigned ms_column(const float* __restrict__ tsdf, const float* __restrict__ weight, const TsGrid& g, int idx, int j, int k) {
+  const int sy = g.Nx, sz = g.Nx * g.Ny;
+  const bool hy = j < g.Ny - 1, hz = k < g.Nz - 1;
+  unsigned c = (weight[idx] > 0.0f ? 1u : 0u) | (tsdf[idx] <= 0.0f ? 2u : 0u);
+  if (hy) c |= ((weight[idx + sy] > 0.0f ? 1u : 0u) | (tsdf[idx + sy] <= 0.0f ? 2u : 0u)) << 2;
+  if (hz) c |= ((weight[idx + sz] > 0.0f ? 1u : 0u) | (tsdf[idx + sz] <= 0.0f ? 2u : 0u)) << 4;
+  if (hy && hz) c |= ((weight[idx + sz + sy] > 0.0f ? 1u : 0u) | (tsdf[idx + sz + sy] <= 0.0f ? 2u : 0u)) << 6;
+  return c;
+}
+
+// code[v] of the cell whose low corner is voxel v: 0x100 | the inside bits of its 8 corners when it is valid, else 0
+__global__ __launch_bounds__(MS_THREADS) void ms_classify_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, TsGrid g,
+                                                                 int nblk, uint16_t* __restrict__ code) {
+  const int total = g.Nx * g.Ny * g.Nz, lane = threadIdx.x & 63;
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {   // uniform: every lane of a wavefront reaches the shuffle
+    const int idx = blk * MS_THREADS + threadIdx.x;
+    const bool in = idx < total;
+    const int row = idx / g.Nx, i = idx - row * g.Nx, k = row / g.Ny, j = row - k * g.Ny;
+    const bool has_x = in && i < g.Nx - 1;
+    const unsigned mine = in ? ms_column(tsdf, weight, g, idx, j, k) : 0u;
+    unsigned next = __shfl_down(mine, 1, 64);   // the next lane holds the column at x + 1; the last lane reads it
+    if (lane == 63) next = has_x ? ms_column(tsdf, weight, g, idx + 1, j, k) : 0u;
+    unsigned c = 0;
+    if (has_x && j < g.Ny - 1 && k < g.Nz - 1 && (mine & next & 0x55u) == 0x55u) c = 0x100u | ((mine >> 1) & 0x55u) | (next & 0xAAu);
+    if (in) code[idx] = (uint16_t)c;
+  }
+}
+
+// edge (corner a, corner b) of a cell crosses and the cell is valid
+__device__ __forceinline__ unsigned ms_cross(unsigned C, int a, int b) { return (C >> 8) & ((C >> a) ^ (C >> b)) & 1u; }
+
+// the cell is valid with corners on both sides: only such a cell has a crossing edge
+__device__ __forceinline__ unsigned ms_cut(unsigned C) { return (C >> 8) & ((((C & 0xffu) + 1u) & 0xfeu) != 0u ? 1u : 0u); }
+
+__device__ __forceinline__ int ms_triangles(unsigned C) {
+  if (!(C & 0x100u)) return 0;
+  int n = 0;
+#pragma unroll
+  for (int m = 0; m < 6; ++m) {
+    const int pc = __popc(ms_pattern(C, m));
+    n += (pc == 0 || pc == 4) ? 0 : (pc == 2 ? 2 : 1);
+  }
+  return n;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void ms_count_kernel(const uint16_t* __restrict__ code, TsGrid g, const int32_t* __restrict__ found,
+                                                              int nblk, uint32_t* __restrict__ rec, int2* __restrict__ totals,
+                                                              int32_t* __restrict__ info) {
+  __shared__ int wave_sum[MS_ROUNDS * 4];
+  __shared__ int wave_cells[4];
+  const bool on = found ? found[0] != 0 : true;   // uniform
+  const int total = g.Nx * g.Ny * g.Nz, sy = g.Nx, sz = g.Nx * g.Ny;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int cells = 0;               // the valid cells of this wavefront's voxels over the whole walk: the same in all of its lanes
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {   // uniform
+    unsigned live[MS_ROUNDS];
+    int packed[MS_ROUNDS], incl[MS_ROUNDS];   // vertices in the low half, triangles in the high half: at most 3584 and 6144 a block
+#pragma unroll
+    for (int r = 0; r < MS_ROUNDS; ++r) {
+      const int idx = (blk * MS_ROUNDS + r) * MS_THREADS + threadIdx.x;
+      unsigned lv = 0;
+      int nt = 0;
+      bool valid = false;
+      if (idx < total && on) {
+        const int row = idx / g.Nx, i = idx - row * g.Nx, k = row / g.Ny, j = row - k * g.Ny;
+        const bool lx = i > 0, ly = j > 0, lz = k > 0;
+        // the cells that hold an edge of this voxel: its own and those one step down along the axes the edge does not run along
+        const unsigned C0 = code[idx], Cx = lx ? code[idx - 1] : 0u, Cy = ly ? code[idx - sy] : 0u, Cz = lz ? code[idx - sz] : 0u;
+        const unsigned Cxy = lx && ly ? code[idx - 1 - sy] : 0u, Cxz = lx && lz ? code[idx - 1 - sz] : 0u, Cyz = ly && lz ? code[idx - sy - sz] : 0u;
+        // most voxels lie away from the surface: no cell around them is cut, so none of their edges is live
+        if (ms_cut(C0) | ms_cut(Cx) | ms_cut(Cy) | ms_cut(Cz) | ms_cut(Cxy) | ms_cut(Cxz) | ms_cut(Cyz)) {
+          lv = (ms_cross(C0, 0, 1) | ms_cross(Cy, 2, 3) | ms_cross(Cz, 4, 5) | ms_cross(Cyz, 6, 7)) |
+               (ms_cross(C0, 0, 2) | ms_cross(Cx, 1, 3) | ms_cross(Cz, 4, 6) | ms_cross(Cxz, 5, 7)) << 1 |
+               (ms_cross(C0, 0, 3) | ms_cross(Cz, 4, 7)) << 2 |
+               (ms_cross(C0, 0, 4) | ms_cross(Cx, 1, 5) | ms_cross(Cy, 2, 6) | ms_cross(Cxy, 3, 7)) << 3 |
+               (ms_cross(C0, 0, 5) | ms_cross(Cy, 2, 7)) << 4 | (ms_cross(C0, 0, 6) | ms_cross(Cx, 1, 7)) << 5 | ms_cross(C0, 0, 7) << 6;
+          nt = ms_triangles(C0);
+        }
+        valid = (C0 & 0x100u) != 0;
+      }
+      live[r] = lv;
+      packed[r] = __popc(lv) | nt << 16;
+      int inc = packed[r];
+      if (__ballot(inc != 0) != 0ull) {   // uniform
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+          const int t = __shfl_up(inc, d, 64);
+          if (lane >= d) inc += t;
+        }
+      }
+      incl[r] = inc;
+      if (lane == 63) wave_sum[r * 4 + wave] = inc;
+      cells += __popcll(__ballot(valid));
+    }
+    __syncthreads();
+    int all = 0;
+#pragma unroll
+    for (int q = 0; q < MS_ROUNDS * 4; ++q) all += wave_sum[q];
+    // a block with no vertex has no triangle either (a cut tetrahedron cuts an edge at q0, which its own voxel owns) and nobody
+    // reads its records: ms_emit_kernel takes them as 0
+    if (all != 0) {
+#pragma unroll
+      for (int r = 0; r < MS_ROUNDS; ++r) {
+        int before = 0;
+#pragma unroll
+        for (int q = 0; q < MS_ROUNDS * 4; ++q) before += q < r * 4 + wave ? wave_sum[q] : 0;
+        const int idx = (blk * MS_ROUNDS + r) * MS_THREADS + threadIdx.x;
+        const int ex = before + incl[r] - packed[r];
+        if (idx < total) rec[idx] = live[r] | (unsigned)(ex & 0xffff) << 7 | (unsigned)(ex >> 16) << 19;
+      }
+    }
+    if (threadIdx.x == 0) totals[blk] = make_int2(all & 0xffff, all >> 16);
+    __syncthreads();   // wave_sum is written again
+  }
+  if (lane == 0) wave_cells[wave] = cells;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int n = (wave_cells[0] + wave_cells[1]) + (wave_cells[2] + wave_cells[3]);
+    if (n > 0) atomicAdd(&info[3], n);   // the call's only atomic
+  }
+}
+
+// one workgroup: bases[b] = the vertices and triangles of the blocks before b, and both counts into info
+__global__ __launch_bounds__(MS_SCAN_THREADS) void ms_scan_kernel(const int2* __restrict__ totals, int nblk, int2* __restrict__ bases,
+                                                                  int32_t* __restrict__ info) {
+  __shared__ int2 wave_sum[MS_SCAN_THREADS / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int cx = 0, cy = 0;
+  for (int base = 0; base < nblk; base += MS_SCAN_THREADS) {
+    const int b = base + threadIdx.x;
+    const int2 c = b < nblk ? totals[b] : make_int2(0, 0);
+    int ix = c.x, iy = c.y;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int tx = __shfl_up(ix, d, 64), ty = __shfl_up(iy, d, 64);
+      if (lane >= d) ix += tx, iy += ty;
+    }
+    if (lane == 63) wave_sum[wave] = make_int2(ix, iy);
+    __syncthreads();
+    int bx = 0, by = 0, tx = 0, ty = 0;
+#pragma unroll
+    for (int q = 0; q < MS_SCAN_THREADS / 64; ++q) {
+      const int2 w = wave_sum[q];
+      bx += q < wave ? w.x : 0, by += q < wave ? w.y : 0;
+      tx += w.x, ty += w.y;
+    }
+    if (b < nblk) bases[b] = make_int2(cx + bx + ix - c.x, cy + by + iy - c.y);
+    cx += tx, cy += ty;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) info[1] = cx, info[2] = cy;
+}
+
+// the value at grid coordinates q by ts_trilinear's rule; false outside the box or at an unobserved corner
+__device__ __forceinline__ bool ms_sample(const float* __restrict__ tsdf, const float* __restrict__ weight, const TsGrid& g, double qx, double qy,
+                                          double qz, double* f) {
+  const double q[3] = {qx, qy, qz};
+  return ts_in_box(g, q) && ts_trilinear(tsdf, weight, g, q, f);
+}
+
+// the triangles of one tetrahedron with sign pattern S (1 .. 14) from the vertices on its six edges, rows `row` on
+__device__ __forceinline__ int ms_tetrahedron(unsigned S, unsigned swap, int e01, int e02, int e03, int e12, int e13, int e23,
+                                              int32_t* __restrict__ tris, int row, int cap) {
+  int A, B, C, D = -1;       // (A, B, C), then with a second triangle (A, C, D)
+  switch (S) {
+    case 1: case 14: A = e01, B = e02, C = e03; break;
+    case 2: case 13: A = e01, B = e12, C = e13; break;
+    case 4: case 11: A = e02, B = e12, C = e23; break;
+    case 8: case 7: A = e03, B = e13, C = e23; break;
+    case 3: A = e02, B = e03, C = e13, D = e12; break;
+    case 5: A = e01, B = e03, C = e23, D = e12; break;
+    case 9: A = e01, B = e02, C = e23, D = e13; break;
+    case 6: A = e01, B = e13, C = e23, D = e02; break;
+    case 10: A = e01, B = e12, C = e23, D = e03; break;
+    default: A = e02, B = e12, C = e13, D = e03; break;   // 12
+  }
+  const bool two = __popc(S) == 2;
+  const unsigned sw = swap >> (2 * S);
+  if (row < cap) {
+    int32_t* t = tris + (size_t)row * 3;
+    t[0] = A, t[1] = (sw & 1u) ? C : B, t[2] = (sw & 1u) ? B : C;
+  }
+  if (two && row + 1 < cap) {
+    int32_t* t = tris + (size_t)(row + 1) * 3;
+    t[0] = A, t[1] = (sw & 2u) ? D : C, t[2] = (sw & 2u) ? C : D;
+  }
+  return two ? 2 : 1;
+}
+
+// A workgroup whose block holds no vertex and no triangle leaves at once.  tsdf is read a second time here, at the two ends of
+// the live edges only (and around them for the normals): a pass that kept the values of every voxel for this one would write
+// 4 B a voxel to spare 8 B a vertex.
+__global__ __launch_bounds__(MS_THREADS) void ms_emit_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, TsGrid g,
+                                                             const uint16_t* __restrict__ code, const uint32_t* __restrict__ rec,
+                                                             int nblk, const int2* __restrict__ totals, const int2* __restrict__ bases,
+                                                             double* __restrict__ verts, double* __restrict__ normals, int cap_verts,
+                                                             int32_t* __restrict__ tris, int cap_tris) {
+  const int total = g.Nx * g.Ny * g.Nz, sy = g.Nx, sz = g.Nx * g.Ny;
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    if (totals[blk].x == 0) continue;   // no vertex, so no triangle
+    const int2 base = bases[blk];
+#pragma unroll 1
+    for (int r = 0; r < MS_ROUNDS; ++r) {
+      const int idx = (blk * MS_ROUNDS + r) * MS_THREADS + threadIdx.x;
+      if (idx >= total) continue;
+      const unsigned me = rec[idx], live = me & 127u;
+      const int row = idx / g.Nx, i = idx - row * g.Nx, k = row / g.Ny, j = row - k * g.Ny;
+      if (live && cap_verts > 0) {
+        const int first = base.x + (int)((me >> 7) & 4095u);
+        const double fa = (double)tsdf[idx];
+#pragma unroll
+        for (int d = 1; d < 8; ++d) {
+          const int slot = first + __popc(live & ((1u << (d - 1)) - 1u));
+          if (!((live >> (d - 1)) & 1u) || slot >= cap_verts) continue;   // beyond the capacity: counted, not written
+          const double fb = (double)tsdf[idx + (d & 1) + ((d >> 1) & 1) * sy + (d >> 2) * sz];
+          const double t = fa / (fa - fb);
+          const double gx = (d & 1) ? (double)i + t : (double)i, gy = (d & 2) ? (double)j + t : (double)j, gz = (d & 4) ? (double)k + t : (double)k;
+          double* v = verts + (size_t)slot * 3;
+          v[0] = g.ox + g.voxel * gx, v[1] = g.oy + g.voxel * gy, v[2] = g.oz + g.voxel * gz;
+          if (normals) {
+            double fp[3], fm[3];
+            bool ok = ms_sample(tsdf, weight, g, gx + 1.0, gy, gz, &fp[0]) && ms_sample(tsdf, weight, g, gx - 1.0, gy, gz, &fm[0]);
+            ok = ok && ms_sample(tsdf, weight, g, gx, gy + 1.0, gz, &fp[1]) && ms_sample(tsdf, weight, g, gx, gy - 1.0, gz, &fm[1]);
+            ok = ok && ms_sample(tsdf, weight, g, gx, gy, gz + 1.0, &fp[2]) && ms_sample(tsdf, weight, g, gx, gy, gz - 1.0, &fm[2]);
+            double n0 = NAN, n1 = NAN, n2 = NAN;
+            if (ok) {
+              const double Gx = fp[0] - fm[0], Gy = fp[1] - fm[1], Gz = fp[2] - fm[2];
+              const double len = sqrt((Gx * Gx + Gy * Gy) + Gz * Gz);
+              if (len > 0.0) n0 = Gx / len, n1 = Gy / len, n2 = Gz / len;   // false for NaN
+            }
+            double* n = normals + (size_t)slot * 3;
+            n[0] = n0, n[1] = n1, n[2] = n2;
+          }
+        }
+      }
+      if (cap_tris <= 0) continue;
+      const unsigned C = code[idx];
+      if (!(C & 0x100u) || (C & 0xffu) == 0u || (C & 0xffu) == 0xffu) continue;
+      // the first vertex and the live bits of the 7 corners that own an edge of this cell
+      int cb[7];
+      unsigned lv[7];
+#pragma unroll
+      for (int c = 0; c < 7; ++c) {
+        const int u = idx + (c & 1) + ((c >> 1) & 1) * sy + (c >> 2) * sz;
+        const int ub = u >> MS_BLOCK_SHIFT;
+        const bool mine = ub == blk;
+        const unsigned ru = c == 0 ? me : (mine || totals[ub].x != 0) ? rec[u] : 0u;   // a block without vertices wrote no records
+        const int bu = mine ? base.x : bases[ub].x;
+        cb[c] = bu + (int)((ru >> 7) & 4095u);
+        lv[c] = ru & 127u;
+      }
+      int out = base.y + (int)(me >> 19);
+#pragma unroll
+      for (int m = 0; m < 6; ++m) {
+        const unsigned S = ms_pattern(C, m);
+        if (S == 0u || S == 15u) continue;
+        constexpr int k0 = 0, k3 = 7;
+        const int k1 = ms_k1(m), k2 = ms_k2(m);
+        // the vertex on edge (corner a, corner b): the owner's first vertex + its live edges below dcode b - a
+#define MS_EDGE(a, b) (cb[a] + __popc(lv[a] & ((1u << ((b) - (a) - 1)) - 1u)))
+        out += ms_tetrahedron(S, ms_swap(m), MS_EDGE(k0, k1), MS_EDGE(k0, k2), MS_EDGE(k0, k3), MS_EDGE(k1, k2), MS_EDGE(k1, k3), MS_EDGE(k2, k3),
+                              tris, out, cap_tris);
+#undef MS_EDGE
+      }
+    }
+  }
+}
+
+// the rows of tris past the count
+__global__ __launch_bounds__(MS_THREADS) void ms_pad_kernel(int32_t* __restrict__ tris, int cap_tris, const int32_t* __restrict__ info) {
+  const size_t e = (size_t)blockIdx.x * MS_THREADS + threadIdx.x;
+  if (e < (size_t)cap_tris * 3 && e >= (size_t)info[2] * 3) tris[e] = -1;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -310,6 +632,83 @@ int cotr_tsdf_raycast(const float* tsdf, const float* weight, int Nx, int Ny, in
   const unsigned tiles = (unsigned)((W + 15) / 16) * (unsigned)((H + 15) / 16);
   hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, 1, info_out);
   hipLaunchKernelGGL(ts_raycast_kernel, dim3(tiles), dim3(256), 0, s, tsdf, weight, g, ray, c2w, found, depth_out, normal_out, info_out);
+  return launched();
+}
+
+}  // extern "C"
+
+namespace {
+
+struct MsScratch {
+  size_t code, rec, totals, bases, bytes;
+  int nblk;
+};
+
+MsScratch ms_layout(int Nx, int Ny, int Nz) {
+  const size_t total = (size_t)Nx * Ny * Nz;
+  MsScratch L;
+  L.nblk = (int)((total + MS_BLOCK - 1) / MS_BLOCK);
+  L.code = 0;
+  L.rec = L.code + align_up(total * sizeof(uint16_t));
+  L.totals = L.rec + align_up(total * sizeof(uint32_t));
+  L.bases = L.totals + align_up((size_t)L.nblk * sizeof(int2));
+  L.bytes = L.bases + align_up((size_t)L.nblk * sizeof(int2));
+  return L;
+}
+
+const char* MS_DIMS = "Nx, Ny and Nz must be >= 2 with at most 2^27 voxels";
+
+// each dimension first: the product of three ints can wrap a 64-bit integer
+bool ms_dims_ok(int Nx, int Ny, int Nz) {
+  return Nx >= 2 && Ny >= 2 && Nz >= 2 && Nx <= MS_MAX_VOXELS && Ny <= MS_MAX_VOXELS && Nz <= MS_MAX_VOXELS &&
+         (long long)Nx * Ny <= MS_MAX_VOXELS && (long long)Nx * Ny * Nz <= MS_MAX_VOXELS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cotr_tsdf_mesh_scratch_bytes(int Nx, int Ny, int Nz, size_t* bytes) {
+  static const char* fn = "cotr_tsdf_mesh_scratch_bytes";
+  if (!bytes) return ts_fail(fn, "bytes must not be NULL");
+  if (!ms_dims_ok(Nx, Ny, Nz)) return ts_fail(fn, MS_DIMS);
+  *bytes = ms_layout(Nx, Ny, Nz).bytes;
+  return COTR_OK;
+}
+
+int cotr_tsdf_mesh(const float* tsdf, const float* weight, int Nx, int Ny, int Nz, const double* origin, double voxel, const int32_t* found,
+                   double* verts_out, int cap_verts, double* normals_out, int32_t* tris_out, int cap_tris, int32_t* info_out, void* scratch,
+                   size_t scratch_bytes, cotr_stream stream) {
+  static const char* fn = "cotr_tsdf_mesh";
+  TsGrid g;
+  if (!ms_dims_ok(Nx, Ny, Nz)) return ts_fail(fn, MS_DIMS);
+  if (const char* msg = ts_check_volume(tsdf, weight, Nx, Ny, Nz, origin, voxel, &g)) return ts_fail(fn, msg);
+  if (cap_verts < 0 || cap_tris < 0) return ts_fail(fn, "cap_verts and cap_tris must be >= 0");
+  if ((cap_verts > 0 && !verts_out) || (cap_tris > 0 && !tris_out) || !info_out)
+    return ts_fail(fn, "verts_out, tris_out (with a capacity above 0) and info_out must not be NULL");
+  if (!aligned(found, 4) || !aligned(verts_out, 8) || !aligned(normals_out, 8) || !aligned(tris_out, 4) || !aligned(info_out, 4))
+    return ts_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
+  const MsScratch L = ms_layout(Nx, Ny, Nz);
+  if (!scratch || scratch_bytes < L.bytes || !aligned(scratch, 16))
+    return ts_fail(fn, "scratch must be 16-byte aligned and hold cotr_tsdf_mesh_scratch_bytes(Nx, Ny, Nz) bytes");
+  char* base = static_cast<char*>(scratch);
+  uint16_t* code = reinterpret_cast<uint16_t*>(base + L.code);
+  uint32_t* rec = reinterpret_cast<uint32_t*>(base + L.rec);
+  int2* totals = reinterpret_cast<int2*>(base + L.totals);
+  int2* bases = reinterpret_cast<int2*>(base + L.bases);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int total = Nx * Ny * Nz;
+  hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, 1, info_out);
+  const int nrun = (total + MS_THREADS - 1) / MS_THREADS;
+  hipLaunchKernelGGL(ms_classify_kernel, dim3((unsigned)std::min(nrun, MS_GRID)), dim3(MS_THREADS), 0, s, tsdf, weight, g, nrun, code);
+  hipLaunchKernelGGL(ms_count_kernel, dim3((unsigned)std::min(L.nblk, MS_GRID)), dim3(MS_THREADS), 0, s, code, g, found, L.nblk, rec, totals, info_out);
+  hipLaunchKernelGGL(ms_scan_kernel, dim3(1), dim3(MS_SCAN_THREADS), 0, s, totals, L.nblk, bases, info_out);
+  if (cap_verts > 0 || cap_tris > 0)   // the blocks with a surface are few and heavy: a workgroup each, so that they spread over the CUs
+    hipLaunchKernelGGL(ms_emit_kernel, dim3((unsigned)L.nblk), dim3(MS_THREADS), 0, s, tsdf, weight, g, code, rec, L.nblk, totals, bases, verts_out,
+                       cap_verts > 0 ? normals_out : nullptr, cap_verts, tris_out, cap_tris);
+  if (cap_tris > 0)
+    hipLaunchKernelGGL(ms_pad_kernel, dim3((unsigned)(((size_t)cap_tris * 3 + MS_THREADS - 1) / MS_THREADS)), dim3(MS_THREADS), 0, s, tris_out, cap_tris,
+                       info_out);
   return launched();
 }
 

@@ -32,8 +32,9 @@ metric pose of one RGB-D capture against another from both depth maps.  ``icp_de
 depth maps (projective association, point-to-plane Gauss-Newton), ``refine_registration`` the same on two captures, and
 ``register_captures(..., icp_iters=10)`` runs it behind the sparse registration.  ``TsdfVolume`` is a truncated signed distance volume on
 the device, ``integrate_depths`` averages posed depth maps into it and ``fuse_captures`` posed captures, ``raycast_volume`` is the depth
-map (and normals) of its surface seen from a pose, ``track_capture`` ``icp_depth`` against such a map (frame-to-model tracking), and
-``ZoomEngine.fuse`` registers a list of captures against the first and fuses those it placed."""
+map (and normals) of its surface seen from a pose, ``track_capture`` ``icp_depth`` against such a map (frame-to-model tracking),
+``extract_mesh`` its surface as an indexed triangle mesh (``write_ply`` puts it into a file), and ``ZoomEngine.fuse`` registers a list
+of captures against the first and fuses those it placed."""
 from .bundle import bundle_adjust, bundle_adjust_tensors
 from .essential import find_essential_mat, ransac_essential, recover_pose, refine_pose_tensors, refine_relative_pose, relative_pose
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
@@ -43,7 +44,7 @@ from .pnp import lift_pixels, localize, ransac_pnp, rodrigues, solve_pnp_ransac
 from .rigid3d import ransac_rigid3d, register_captures, register_captures_tensors, register_points
 from .structure import reconstruct_tensors, stack_views, triangulate_points, triangulate_points_tensors, triangulate_views
 from .triangulate import delaunay, triangulate_corr
-from .tsdf import TsdfVolume, fuse_captures, integrate_depths, raycast_volume, track_capture
+from .tsdf import TsdfVolume, extract_mesh, fuse_captures, integrate_depths, raycast_volume, track_capture, write_ply
 from .warp import get_perspective_transform, paste_by_corners, warp_by_corr, warp_by_map, warp_perspective
 from .zoom_engine import FasterSparseEngine, RefineResult, SparseEngine, ZoomEngine, patch_boxes
 
@@ -57,4 +58,4 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'bundle_adjust', 'bundle_adjust_tensors',
            'ransac_rigid3d', 'register_points', 'register_captures', 'register_captures_tensors',
            'icp_depth', 'refine_registration',
-           'TsdfVolume', 'integrate_depths', 'fuse_captures', 'raycast_volume', 'track_capture']
+           'TsdfVolume', 'integrate_depths', 'fuse_captures', 'raycast_volume', 'track_capture', 'extract_mesh', 'write_ply']

@@ -5,7 +5,8 @@ depth maps, and the raycast of that volume from a pose - the model half of Kinec
 (cotr_amd/csrc/tsdf.hip) with device tensors, ``fuse_captures`` the same on ``cotr_amd.data.Capture``s; ``raycast_volume`` is
 ``cotr_tsdf_raycast``: a float32 depth map (and normals) of the kind ``icp_depth`` reads, so ``track_capture`` - a raycast at
 the predicted pose and ``icp_depth`` against it, one device sequence - is frame-to-model tracking with no ICP code of its own.
-The rules are the library's own.  No CPU fallback."""
+``extract_mesh`` is ``cotr_tsdf_mesh``: the volume's surface as an indexed triangle mesh (marching tetrahedra),
+which ``write_ply`` puts into a file.  The rules are the library's own.  No CPU fallback."""
 import ctypes
 
 import numpy as np
@@ -19,6 +20,7 @@ from .icp import _enqueue_icp
 
 MAX_CAPTURES = 32
 MAX_VOXELS = 1 << 28
+MAX_MESH_VOXELS = 1 << 27
 MAX_STEPS = 1 << 16
 D3 = ctypes.c_double * 3
 
@@ -227,6 +229,79 @@ def raycast_volume(volume, K, c2w, shape, near=None, far=None, step=None, normal
     _args.no_cpu_tensors('the TSDF volume runs', c2w)
     with torch.cuda.device(volume.device):
         return _enqueue_raycast(_lib.load_library(), volume, k, on(pose, volume.device), None, H, W, near, far, step, normals)
+
+
+def _check_mesh_volume(volume):
+    _check_volume(volume)
+    Nx, Ny, Nz = volume.dims
+    if Nx * Ny * Nz > MAX_MESH_VOXELS:
+        raise ValueError(f'extract_mesh: at most 2^27 voxels (12 triangles a cell in an int32), got {Nx} x {Ny} x {Nz}')
+
+
+def _enqueue_mesh(lib, volume, found, max_verts, max_tris, normals, scratch=None):
+    """``found`` on the volume's device already, every argument checked -> (verts [max_verts,3], tris [max_tris,3], normals or
+    None, info int32 [4]), device tensors; ``scratch``: what ``_args.scratch`` returned for this volume, to use it again"""
+    device = volume.device
+    buf, nbytes = scratch if scratch is not None else _args.scratch(lib, 'cotr_tsdf_mesh_scratch_bytes', *volume.dims, device=device)
+    verts, tris, info = _args.empty(device, ((max_verts, 3), F64), ((max_tris, 3), I32), (4, I32))
+    nrm = _args.empty(device, ((max_verts, 3), F64))[0] if normals else None
+    check_op(lib.cotr_tsdf_mesh(*_volume_args(volume), ptr(found), ptr(verts) if max_verts else None, max_verts, ptr(nrm) if max_verts else None,
+                                ptr(tris) if max_tris else None, max_tris, ptr(info), ptr(buf), nbytes, _lib.current_stream_ptr()), 'cotr_tsdf_mesh')
+    return verts, tris, nrm, info
+
+
+def extract_mesh(volume, max_verts=None, max_tris=None, normals=False):
+    """``cotr_tsdf_mesh`` on the current stream: the surface of ``volume`` (at most 2^27 voxels) as an indexed triangle mesh by
+    marching tetrahedra, closed and oriented outwards (towards tsdf > 0) wherever the cells around it have been
+    observed.  With ``max_verts`` and ``max_tris`` both given it is one capturable call with no host wait: the tensors come
+    back padded to the capacities (what lies beyond one is counted in ``info`` but not written; the rows of ``tris`` past the
+    count are -1, those of ``verts`` and ``normals`` are not written) and ``info`` stays on the device.  With both ``None`` a first
+    call only counts, the two counts are read on the host (the one host wait) and a second call writes tensors of exactly that
+    size.  -> (verts float64 [V,3] in the world frame, tris int32 [T,3], normals float64 [V,3] (NaN where the volume around the
+    vertex is not observed) or None, info int32 device tensor [4] = (ok, vertices, triangles, valid cells))."""
+    _check_mesh_volume(volume)
+    if (max_verts is None) != (max_tris is None):
+        raise ValueError('max_verts and max_tris go together: give both for one capturable call, or neither for an exact mesh')
+    if max_verts is not None:
+        _args.check_int_range('max_verts', max_verts, 0, (1 << 31) - 1)
+        _args.check_int_range('max_tris', max_tris, 0, (1 << 31) - 1)
+    with torch.cuda.device(volume.device):
+        lib = _lib.load_library()
+        if max_verts is not None:
+            return _enqueue_mesh(lib, volume, None, int(max_verts), int(max_tris), normals)
+        scratch = _args.scratch(lib, 'cotr_tsdf_mesh_scratch_bytes', *volume.dims, device=volume.device)
+        counts = _enqueue_mesh(lib, volume, None, 0, 0, False, scratch)[3].cpu().numpy()   # the host wait
+        return _enqueue_mesh(lib, volume, None, int(counts[1]), int(counts[2]), normals, scratch)
+
+
+def write_ply(path, verts, tris, normals=None):
+    """A binary little-endian PLY file of the mesh ``extract_mesh`` returned (tensors or arrays): float64 x, y, z (and nx, ny,
+    nz) per vertex, a uchar count and three int32 indices per face.  Triangle rows of -1 (the padding of a fixed capacity) are
+    dropped; with padded vertices pass ``verts[:V]``.  A host helper: device tensors are copied first."""
+    host = lambda a: a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)   # noqa: E731
+    v, t = np.ascontiguousarray(host(verts), dtype='<f8'), np.asarray(host(tris))
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError(f'verts must be [V, 3], got shape {v.shape}')
+    if t.ndim != 2 or t.shape[1] != 3 or t.dtype.kind not in 'iu':
+        raise ValueError(f'tris must be integers [T, 3], got {t.dtype} {t.shape}')
+    t = t[(t != -1).all(1)]
+    if len(t) and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError(f'tris refers to vertices outside [0, {len(v)})')
+    cols = [v]
+    if normals is not None:
+        n = np.ascontiguousarray(host(normals), dtype='<f8')
+        if n.shape != v.shape:
+            raise ValueError(f'normals must be [V, 3] like verts, got shape {n.shape}')
+        cols.append(n)
+    faces = np.empty(len(t), dtype=[('n', 'u1'), ('v', '<i4', (3,))])
+    faces['n'], faces['v'] = 3, t
+    header = ['ply', 'format binary_little_endian 1.0', f'element vertex {len(v)}'] + [f'property double {c}' for c in 'xyz']
+    header += [f'property double n{c}' for c in 'xyz'] if normals is not None else []
+    header += [f'element face {len(t)}', 'property list uchar int vertex_indices', 'end_header']
+    with open(path, 'wb') as f:
+        f.write(('\n'.join(header) + '\n').encode('ascii'))
+        f.write(np.ascontiguousarray(np.hstack(cols)).tobytes())
+        f.write(faces.tobytes())
 
 
 def track_capture(volume, cap, c2w0, max_dist=0.05, near=None, far=None, step=None, normal_cos=icp.NORMAL_COS, edge=icp.EDGE,

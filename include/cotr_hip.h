@@ -749,6 +749,45 @@ int cotr_tsdf_raycast(const float* tsdf, const float* weight, int Nx, int Ny, in
                       const double* K, const double* c2w, const int32_t* found, int H, int W, double near, double far,
                       double step, float* depth_out, double* normal_out, int32_t* info_out, cotr_stream stream);
 
+/* ---- the surface of a TSDF volume as an indexed triangle mesh (cotr_amd/csrc/tsdf.hip; rules in DESIGN.md 3h-12) ----------
+ * Marching tetrahedra on the Kuhn split of every cell: no case table to trust, no ambiguous face, closed and consistently
+ * oriented meshes by construction, about twice the triangles of marching cubes.  The rule is the library's own.
+ *
+ * The volume is the one of cotr_tsdf_integrate, here with 2 <= Nx, Ny, Nz and Nx Ny Nz <= 2^27 (12 triangles a cell in an
+ *   int32).  A corner is inside iff tsdf <= 0 (the raycast's hit rule).  Cell c = (i, j, k), 0 <= i <= Nx - 2 and likewise j, k,
+ *   is valid iff its 8 corners all have weight > 0.
+ * Tetrahedra: cell c is split into T_0 .. T_5, one for each permutation p of the axes in lexicographic order (xyz, xzy, yxz,
+ *   yzx, zxy, zyx): q0 = c, q1 = q0 + e_p1, q2 = q1 + e_p2, q3 = c + (1, 1, 1).  Every tetrahedron edge is (v, v + d) with d in
+ *   {0, 1}^3 \ {0}, and every face diagonal runs from the face's low corner to its high corner, so neighbouring cells agree.
+ * Vertices: edge (v, d) crosses iff exactly one end is inside and is live iff it crosses and some valid cell contains it.
+ *   Each live edge carries one vertex: with fa, fb the float32 values at v and v + d as doubles, t = fa / (fa - fb); grid
+ *   coordinate g_a = v_a + t where d_a = 1, else v_a; world coordinate p_a = origin_a + voxel * g_a.  Vertices are numbered in
+ *   the order of (linear index of v with x fastest, dcode = dx + 2 dy + 4 dz).  Every vertex is referenced by a triangle.
+ * Triangles: the valid cells in linear order, in each T_0 .. T_5.  S: the inside vertices among q0 .. q3; E_ab (a < b): the
+ *   vertex on edge (q_a, q_b).  0 or 4 inside: nothing.  1 inside, {a}, or 3 inside with {a} outside: with b < c < d the
+ *   others, (E_ab, E_ac, E_ad).  2 inside {a, b}, a < b, with {c, d} outside, c < d: (E_ac, E_ad, E_bd), then (E_ac, E_bd,
+ *   E_bc).  Each triangle is written so, or with its second and third vertex swapped, whichever makes (B - A) x (C - A) point
+ *   to the outside (tsdf > 0): that depends on the tetrahedron and S alone.  Triangles of no area (a corner value of exactly
+ *   0) are kept: the counts are combinatorial.
+ * Normals (normals_out not NULL): at the vertex's grid coordinates g, G_a = f(g + e_a) - f(g - e_a), f the trilinear value
+ *   of cotr_tsdf_raycast with its validity (0 <= floor <= N - 2 on each axis, all 8 corners observed); n = G / sqrt((G_0^2 +
+ *   G_1^2) + G_2^2), in the world frame; three NaN where one of the six samples is invalid or the length is not > 0.
+ * cotr_tsdf_mesh: found int32 DEVICE [1] or NULL: found[0] == 0: every count is 0, every written row of tris_out is -1 and
+ *   verts_out, normals_out are not touched.  verts_out float64 [cap_verts][3] DEVICE (NULL with cap_verts = 0); normals_out
+ *   float64 [cap_verts][3] DEVICE or NULL; tris_out int32 [cap_tris][3] DEVICE (NULL with cap_tris = 0).  Capacities as in
+ *   cotr_depth_corrs: a vertex or triangle beyond its capacity is counted, not written; the rows of tris_out past the count
+ *   are -1; a triangle that refers to a vertex beyond cap_verts is written all the same.  Both capacities 0: the call only
+ *   counts.  info_out int32 [4] DEVICE = {ok (found), vertices, triangles, valid cells}.  scratch: DEVICE, 16-byte aligned,
+ *   cotr_tsdf_mesh_scratch_bytes(Nx, Ny, Nz) bytes (6 a voxel).
+ * Stream-ordered; 4 launches, one more with a capacity above 0 and one more with cap_tris above 0, whatever the data; no
+ * host waits and no allocation (capturable).  Every output position comes from a scan; integer atomics only, and only for
+ * info_out: the same input gives the same bytes.  Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the
+ * message in cotr_raster_last_error(). */
+int cotr_tsdf_mesh_scratch_bytes(int Nx, int Ny, int Nz, size_t* bytes);
+int cotr_tsdf_mesh(const float* tsdf, const float* weight, int Nx, int Ny, int Nz, const double* origin, double voxel,
+                   const int32_t* found, double* verts_out, int cap_verts, double* normals_out, int32_t* tris_out, int cap_tris,
+                   int32_t* info_out, void* scratch, size_t scratch_bytes, cotr_stream stream);
+
 /* ---- structure from known cameras: robust N-view triangulation (cotr_amd/csrc/structure.hip; rules in DESIGN.md 3h-6) ----
  * n correspondences seen in V posed views -> their 3D points, the views each point was fitted on, and the per-point
  * figures a reconstruction filters on.  The rules are the library's own.
