@@ -74,25 +74,19 @@ struct BaScratch {
 static BaScratch ba_layout(void* base, int V, int n) {
   BaScratch l;
   const size_t N = (size_t)n, chunks = (N + RS_CHUNK - 1) / RS_CHUNK, pairs = (size_t)V * (V + 1) / 2;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* q = p ? p + off : nullptr;
-    off += align_up(bytes);
-    return q;
-  };
-  l.tab = reinterpret_cast<double*>(take(2 * BA_TAB * sizeof(double)));
-  l.st = reinterpret_cast<BaState*>(take(sizeof(BaState)));
-  l.cnt = reinterpret_cast<int*>(take(BA_COUNTERS * sizeof(int)));
-  l.dc = reinterpret_cast<double*>(take(192 * sizeof(double)));
-  l.X = reinterpret_cast<double*>(take(2 * N * 3 * sizeof(double)));
-  l.set = reinterpret_cast<uint32_t*>(take(N * sizeof(uint32_t)));
-  l.lm = reinterpret_cast<uint8_t*>(take(N));
-  l.moves = reinterpret_cast<uint8_t*>(take(N));
-  l.pt = reinterpret_cast<double*>(take(N * 9 * sizeof(double)));
-  l.cparts = reinterpret_cast<double*>(take((N + BA_THREADS - 1) / BA_THREADS * sizeof(double)));
-  l.parts = reinterpret_cast<double*>(take(pairs * chunks * BA_SUMS * sizeof(double)));
-  l.bytes = off;
+  Carver c(base);
+  l.tab = c.take<double>(2 * BA_TAB);
+  l.st = c.take<BaState>(1);
+  l.cnt = c.take<int>(BA_COUNTERS);
+  l.dc = c.take<double>(192);
+  l.X = c.take<double>(2 * N * 3);
+  l.set = c.take<uint32_t>(N);
+  l.lm = c.take<uint8_t>(N);
+  l.moves = c.take<uint8_t>(N);
+  l.pt = c.take<double>(N * 9);
+  l.cparts = c.take<double>((N + BA_THREADS - 1) / BA_THREADS);
+  l.parts = c.take<double>(pairs * chunks * BA_SUMS);
+  l.bytes = c.bytes;
   return l;
 }
 
@@ -643,11 +637,11 @@ __global__ __launch_bounds__(BA_THREADS) void ba_finish_kernel(int V, int n, con
 // ---- host side ------------------------------------------------------------------------------------------------------------
 namespace {
 
-int ba_fail(const char* msg) { return handleless_fail(COTR_ERR_ARG, msg); }
+const char* const BA_FN = "cotr_bundle_adjust";
 
 const char* ba_check_shape(int V, int n) {
-  if (V < 2 || V > TV_MAX_VIEWS) return "cotr_bundle_adjust: V must be in [2, 32]";
-  if (n < 1 || n > BA_MAX_POINTS) return "cotr_bundle_adjust: n must be in [1, 2^20]";
+  if (V < 2 || V > TV_MAX_VIEWS) return "V must be in [2, 32]";
+  if (n < 1 || n > BA_MAX_POINTS) return "n must be in [1, 2^20]";
   return nullptr;
 }
 
@@ -658,8 +652,8 @@ extern "C" {
 // per point: two copies of X, the set, two flags, the 9 doubles of ba_points; per 256 points a cost; per 2048-point chunk, for each of the
 // V (V + 1) / 2 view pairs, 64 sums (the Jacobians are recomputed where they are needed instead of being stored: O(n + chunks pairs))
 int cotr_bundle_adjust_scratch_bytes(int V, int n, size_t* bytes) {
-  if (!bytes) return ba_fail("cotr_bundle_adjust_scratch_bytes: bytes is NULL");
-  if (const char* msg = ba_check_shape(V, n)) return ba_fail(msg);
+  if (!bytes) return arg_fail("cotr_bundle_adjust_scratch_bytes", "bytes is NULL");
+  if (const char* msg = ba_check_shape(V, n)) return arg_fail(BA_FN, msg);
   *bytes = ba_layout(nullptr, V, n).bytes;
   return COTR_OK;
 }
@@ -668,14 +662,14 @@ int cotr_bundle_adjust(const double* points, const uint8_t* visible, const doubl
                        const uint8_t* fixed_views, int V, int n, const int32_t* found, double threshold, double distance_thresh, int rounds,
                        int iters, double lambda0, double* poses_out, double* X_out, uint8_t* used_out, double* stats_out, int32_t* info_out,
                        void* scratch, size_t scratch_bytes, cotr_stream stream) {
-  if (const char* msg = ba_check_shape(V, n)) return ba_fail(msg);
-  if (!(threshold > 0.0) || !(threshold < INFINITY)) return ba_fail("cotr_bundle_adjust: threshold must be finite and > 0");
+  if (const char* msg = ba_check_shape(V, n)) return arg_fail(BA_FN, msg);
+  if (!(threshold > 0.0) || !(threshold < INFINITY)) return arg_fail(BA_FN, "threshold must be finite and > 0");
   const float thr = (float)(threshold * threshold);
-  if (!(thr > 0.0f) || !(thr < INFINITY)) return ba_fail("cotr_bundle_adjust: the squared threshold must be a finite float32 that is not 0");
-  if (!(distance_thresh > 0.0) || !(distance_thresh < INFINITY)) return ba_fail("cotr_bundle_adjust: distance_thresh must be finite and > 0");
-  if (rounds < 1 || rounds > BA_MAX_ROUNDS) return ba_fail("cotr_bundle_adjust: rounds must be in [1, 8]");
-  if (iters < 0 || iters > BA_MAX_ITERS) return ba_fail("cotr_bundle_adjust: iters must be in [0, 64]");
-  if (!(lambda0 >= BA_LAMBDA_MIN) || !(lambda0 <= BA_LAMBDA_MAX)) return ba_fail("cotr_bundle_adjust: lambda0 must be in [1e-12, 1e12]");
+  if (!(thr > 0.0f) || !(thr < INFINITY)) return arg_fail(BA_FN, "the squared threshold must be a finite float32 that is not 0");
+  if (!(distance_thresh > 0.0) || !(distance_thresh < INFINITY)) return arg_fail(BA_FN, "distance_thresh must be finite and > 0");
+  if (rounds < 1 || rounds > BA_MAX_ROUNDS) return arg_fail(BA_FN, "rounds must be in [1, 8]");
+  if (iters < 0 || iters > BA_MAX_ITERS) return arg_fail(BA_FN, "iters must be in [0, 64]");
+  if (!(lambda0 >= BA_LAMBDA_MIN) || !(lambda0 <= BA_LAMBDA_MAX)) return arg_fail(BA_FN, "lambda0 must be in [1e-12, 1e12]");
   uint32_t fixed = 1u;
   if (fixed_views) {
     fixed = 0;
@@ -683,15 +677,15 @@ int cotr_bundle_adjust(const double* points, const uint8_t* visible, const doubl
       if (fixed_views[v]) fixed |= 1u << v;
   }
   const uint32_t all = V == 32 ? 0xffffffffu : (1u << V) - 1u;
-  if (fixed == 0) return ba_fail("cotr_bundle_adjust: at least one view must be fixed");
-  if (fixed == all) return ba_fail("cotr_bundle_adjust: at least one view must not be fixed");
+  if (fixed == 0) return arg_fail(BA_FN, "at least one view must be fixed");
+  if (fixed == all) return arg_fail(BA_FN, "at least one view must not be fixed");
   if (!points || !cams || !poses_in || !X_in || !poses_out || !X_out || !used_out || !stats_out || !info_out || !scratch)
-    return ba_fail("cotr_bundle_adjust: points, cams, poses_in, X_in, poses_out, X_out, used_out, stats_out, info_out and scratch must not be NULL");
+    return arg_fail(BA_FN, "points, cams, poses_in, X_in, poses_out, X_out, used_out, stats_out, info_out and scratch must not be NULL");
   if (!aligned(points, 16) || !aligned(cams, 8) || !aligned(poses_in, 8) || !aligned(X_in, 8) || !aligned(poses_out, 8) || !aligned(X_out, 8) ||
       !aligned(stats_out, 8) || !aligned(info_out, 4) || !aligned(found, 4) || !aligned(scratch, 16))
-    return ba_fail("cotr_bundle_adjust: points and scratch must be 16-byte, other doubles 8-byte and ints 4-byte aligned");
+    return arg_fail(BA_FN, "points and scratch must be 16-byte, other doubles 8-byte and ints 4-byte aligned");
   const BaScratch l = ba_layout(scratch, V, n);
-  if (scratch_bytes < l.bytes) return ba_fail("cotr_bundle_adjust: scratch is smaller than cotr_bundle_adjust_scratch_bytes");
+  if (scratch_bytes < l.bytes) return arg_fail(BA_FN, "scratch is smaller than cotr_bundle_adjust_scratch_bytes");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int chunks = (n + RS_CHUNK - 1) / RS_CHUNK;
   const unsigned blocks = (unsigned)((n + BA_THREADS - 1) / BA_THREADS);

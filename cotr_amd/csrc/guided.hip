@@ -316,7 +316,9 @@ namespace {
 
 struct NnPlan {
   int qblocks[2], splits[2], chunk[2];
-  size_t pd, pj, bytes;
+  double* pd;   // [splits[0] na + splits[1] nb] the partial minima of both directions
+  int* pj;      // and the indices they belong to
+  size_t bytes;
 };
 
 void nn_split(int nq, int nk, int* qblocks, int* splits, int* chunk) {
@@ -328,14 +330,15 @@ void nn_split(int nq, int nk, int* qblocks, int* splits, int* chunk) {
   *splits = (nk + *chunk - 1) / *chunk;
 }
 
-NnPlan nn_plan(int na, int nb) {
+NnPlan nn_plan(void* base, int na, int nb) {
   NnPlan l;
+  Carver c(base);
   nn_split(na, nb, &l.qblocks[0], &l.splits[0], &l.chunk[0]);
   nn_split(nb, na, &l.qblocks[1], &l.splits[1], &l.chunk[1]);
   const size_t parts = (size_t)l.splits[0] * na + (size_t)l.splits[1] * nb;
-  l.pd = 0;
-  l.pj = align_up(parts * sizeof(double));
-  l.bytes = l.pj + align_up(parts * sizeof(int));
+  l.pd = c.take<double>(parts);
+  l.pj = c.take<int>(parts);
+  l.bytes = c.bytes;
   return l;
 }
 
@@ -354,7 +357,7 @@ extern "C" {
 int cotr_nearest_mutual_scratch_bytes(int na, int nb, size_t* bytes) {
   if (!bytes) return handleless_fail(COTR_ERR_ARG, "cotr_nearest_mutual_scratch_bytes: bytes is NULL");
   if (const char* e = nn_check_shape(na, nb)) return handleless_fail(COTR_ERR_ARG, e);
-  *bytes = nn_plan(na, nb).bytes;
+  *bytes = nn_plan(nullptr, na, nb).bytes;
   return COTR_OK;
 }
 
@@ -366,15 +369,12 @@ int cotr_nearest_mutual(const double* pred_ab, const double* kp_b, const double*
   if (!aligned(pred_ab, 8) || !aligned(kp_b, 8) || !aligned(pred_ba, 8) || !aligned(kp_a, 8) || !aligned(idx_ab, 4) ||
       !aligned(idx_ba, 4) || !aligned(scratch, 16))
     return handleless_fail(COTR_ERR_ARG, "cotr_nearest_mutual: points must be 8-byte, indices 4-byte and scratch 16-byte aligned");
-  const NnPlan l = nn_plan(na, nb);
+  const NnPlan l = nn_plan(scratch, na, nb);
   if (scratch_bytes < l.bytes) return handleless_fail(COTR_ERR_ARG, "scratch is smaller than cotr_nearest_mutual_scratch_bytes");
-  char* base = static_cast<char*>(scratch);
-  double* pd = reinterpret_cast<double*>(base + l.pd);
-  int* pj = reinterpret_cast<int*>(base + l.pj);
   NnArgs a;
-  a.dir[0] = NnDir{pred_ab, kp_b, pd, pj, idx_ab, na, nb, l.qblocks[0], l.splits[0], l.chunk[0]};
+  a.dir[0] = NnDir{pred_ab, kp_b, l.pd, l.pj, idx_ab, na, nb, l.qblocks[0], l.splits[0], l.chunk[0]};
   const size_t off = (size_t)l.splits[0] * na;
-  a.dir[1] = NnDir{pred_ba, kp_a, pd + off, pj + off, idx_ba, nb, na, l.qblocks[1], l.splits[1], l.chunk[1]};
+  a.dir[1] = NnDir{pred_ba, kp_a, l.pd + off, l.pj + off, idx_ba, nb, na, l.qblocks[1], l.splits[1], l.chunk[1]};
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(nn_partial_kernel, dim3(l.qblocks[0] + l.qblocks[1], max(l.splits[0], l.splits[1])), dim3(NN_THREADS), 0, s, a);
   hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)(((size_t)na + nb + 255) / 256)), dim3(256), 0, s, a);

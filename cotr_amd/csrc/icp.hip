@@ -21,7 +21,6 @@
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "handleless.h"
 #include "pinhole.h"
@@ -308,32 +307,31 @@ __global__ __launch_bounds__(64) void ic_finish_kernel(int chunks, const double*
 // ---- host side ------------------------------------------------------------------------------------------------------------
 namespace {
 
-int ic_fail(const char* what) {
-  char msg[256];
-  snprintf(msg, sizeof msg, "cotr_icp_depth: %s", what);
-  return handleless_fail(COTR_ERR_ARG, msg);
-}
+int ic_fail(const char* what) { return arg_fail("cotr_icp_depth", what); }
 
 // the state, the per-chunk sums [chunks, IC_SUMS], A's vertices and normals [Ha Wa, 3] each, B's, the source mask [n_src]
 struct IcPlan {
   RfPlan rf;
-  size_t va, na, vb, nb, smask, bytes;
+  double *va, *na, *vb, *nb;
+  uint8_t* smask;
+  size_t bytes;
   int ws, hs, n_src;
 };
 
-IcPlan ic_plan(int Ha, int Wa, int Hb, int Wb, int stride) {
+IcPlan ic_plan(void* base, int Ha, int Wa, int Hb, int Wb, int stride) {
   IcPlan l;
   l.ws = (Wb + stride - 1) / stride;
   l.hs = (Hb + stride - 1) / stride;
   l.n_src = l.ws * l.hs;
   l.rf = rf_plan(0, sizeof(IcState), l.n_src, IC_SUMS);
-  const size_t a = align_up((size_t)Ha * Wa * 3 * sizeof(double)), b = align_up((size_t)Hb * Wb * 3 * sizeof(double));
-  l.va = l.rf.bytes;
-  l.na = l.va + a;
-  l.vb = l.na + a;
-  l.nb = l.vb + b;
-  l.smask = l.nb + b;
-  l.bytes = l.smask + align_up((size_t)l.n_src);
+  const size_t a = (size_t)Ha * Wa * 3, b = (size_t)Hb * Wb * 3;
+  Carver c(base, l.rf.bytes);
+  l.va = c.take<double>(a);
+  l.na = c.take<double>(a);
+  l.vb = c.take<double>(b);
+  l.nb = c.take<double>(b);
+  l.smask = c.take<uint8_t>(l.n_src);
+  l.bytes = c.bytes;
   return l;
 }
 
@@ -351,7 +349,7 @@ extern "C" {
 int cotr_icp_depth_scratch_bytes(int Ha, int Wa, int Hb, int Wb, int stride, size_t* bytes) {
   if (const int rc = ic_check_shape(Ha, Wa, Hb, Wb, stride)) return rc;
   if (!bytes) return ic_fail("bytes must not be NULL");
-  *bytes = ic_plan(Ha, Wa, Hb, Wb, stride).bytes;
+  *bytes = ic_plan(nullptr, Ha, Wa, Hb, Wb, stride).bytes;
   return COTR_OK;
 }
 
@@ -374,24 +372,18 @@ int cotr_icp_depth(const float* depth_a, int Ha, int Wa, const double* K_a, cons
       !aligned(R_out, 8) || !aligned(t_out, 8) || !aligned(info_out, 4) || !aligned(stats_out, 8) || !aligned(hist_out, 8) ||
       !aligned(assoc_out, 4) || !aligned(maps_a_out, 8) || !aligned(maps_b_out, 8) || !aligned(scratch, 16))
     return ic_fail("floats and int32 must be 4-byte, doubles 8-byte and scratch 16-byte aligned");
-  const IcPlan l = ic_plan(Ha, Wa, Hb, Wb, stride);
+  const IcPlan l = ic_plan(scratch, Ha, Wa, Hb, Wb, stride);
   if (scratch_bytes < l.bytes) return ic_fail("scratch is smaller than cotr_icp_depth_scratch_bytes asks for");
-  char* base = static_cast<char*>(scratch);
-  IcState* st = reinterpret_cast<IcState*>(base + l.rf.state);
-  double* Va = reinterpret_cast<double*>(base + l.va);
-  double* Na = reinterpret_cast<double*>(base + l.na);
-  double* Vb = reinterpret_cast<double*>(base + l.vb);
-  double* Nb = reinterpret_cast<double*>(base + l.nb);
-  uint8_t* smask = reinterpret_cast<uint8_t*>(base + l.smask);
+  IcState* st = reinterpret_cast<IcState*>(static_cast<char*>(scratch) + l.rf.state);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(ic_begin_kernel, dim3(1), dim3(64), 0, s, R0, t0, c2w_a, found, st);
   hipLaunchKernelGGL(ic_map_kernel, dim3((unsigned)((Ha * Wa + 255) / 256)), dim3(256), 0, s, depth_a, Ha, Wa, ka, edge, 0, 1, Wa,
-                     (const uint8_t*)nullptr, Va, Na, maps_a_out, (uint8_t*)nullptr, (int32_t*)nullptr, st);
+                     (const uint8_t*)nullptr, l.va, l.na, maps_a_out, (uint8_t*)nullptr, (int32_t*)nullptr, st);
   hipLaunchKernelGGL(ic_map_kernel, dim3((unsigned)((Hb * Wb + 255) / 256)), dim3(256), 0, s, depth_b, Hb, Wb, kb, edge, 1, stride, l.ws,
-                     src_mask, Vb, Nb, maps_b_out, smask, assoc_out, st);
-  const IcPoints pts = {Va, Na, Vb, Nb, assoc_out, ka, Ha, Wa, Wb, stride, l.ws, max_dist * max_dist, normal_cos};
+                     src_mask, l.vb, l.nb, maps_b_out, l.smask, assoc_out, st);
+  const IcPoints pts = {l.va, l.na, l.vb, l.nb, assoc_out, ka, Ha, Wa, Wb, stride, l.ws, max_dist * max_dist, normal_cos};
   for (int k = 0; k <= iters; ++k)
-    rf_enqueue_pair<IcTerms>(s, l.rf, scratch, pts, l.n_src, smask, ic_finish_kernel, k, (int)(k == iters), cond_tol, R_out, t_out, info_out,
+    rf_enqueue_pair<IcTerms>(s, l.rf, scratch, pts, l.n_src, l.smask, ic_finish_kernel, k, (int)(k == iters), cond_tol, R_out, t_out, info_out,
                              stats_out, hist_out);
   return launched();
 }

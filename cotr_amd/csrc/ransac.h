@@ -404,11 +404,7 @@ inline RsPlan rs_plan(const RsEntry& e, int max_iters) {
   return l;
 }
 
-inline int rs_fail(const RsEntry& e, const char* what, const char* note = "") {
-  char msg[256];
-  snprintf(msg, sizeof msg, "%s: %s%s", e.name, what, note);
-  return handleless_fail(COTR_ERR_ARG, msg);
-}
+inline int rs_fail(const RsEntry& e, const char* what, const char* note = "") { return arg_fail(e.name, what, note); }
 
 inline int rs_check_shape(const RsEntry& e, int n, int max_iters) {
   char what[64];

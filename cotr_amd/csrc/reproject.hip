@@ -6,9 +6,9 @@
 // (u, v) of the target and its depth p.z), then
 //   zt = to_depth[floor(v), floor(u)]                                    keep iff |zt - p.z| < 0.5
 // The kept rows (x, y, u, v) leave in SOURCE order (row-major pixels, or the order of the subset list): what the reference's
-// chained boolean masks return.  The compaction is a scan, not a slot counter, so two runs give the same bytes:
+// chained boolean masks return.  A kept row's slot comes from scan.h, so two runs give the same bytes:
 //   flags   one lane per source pixel: the predicate, a 64-bit wave ballot per wavefront to scratch
-//   scan    one workgroup per item: popcount of each block's four ballots, exclusive scan of the block totals, the count
+//   scan    one workgroup per item: the kept rows of each block (its four ballots) summed over the blocks before it, the count
 //   scatter a kept lane's slot = its block's offset + the popcounts of the ballots before it + that of the lanes below it
 // cotr_depth_valid is the same machinery with the predicate depth > 0 and the pixel index as the row.
 // cotr_crop_depth_nearest is Pillow's NEAREST resize (ImagingScaleAffine): source column of output column j is
@@ -20,6 +20,7 @@
 
 #include "camera.h"
 #include "handleless.h"
+#include "scan.h"
 
 using namespace cotr_detail;
 
@@ -108,30 +109,11 @@ __global__ __launch_bounds__(RP_THREADS) void reproj_scan_kernel(const unsigned 
   const int item = blockIdx.x;
   const RpItem it = load_item(ptrs, shapes, item, max_src);
   const int nb = (it.n_src + RP_THREADS - 1) / RP_THREADS;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int carry = 0;
-  for (int base = 0; base < nb; base += RP_THREADS) {
-    const int b = base + threadIdx.x;
-    const int c = b < nb ? block_kept(ballots + ((size_t)item * nb_max + b) * RP_WAVES) : 0;
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += t;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < RP_WAVES; ++k) {
-      before += k < wave ? wave_sum[k] : 0;
-      total += wave_sum[k];
-    }
-    if (b < nb) offsets[(size_t)item * nb_max + b] = carry + before + incl - c;
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[item] = carry;
+  const size_t first = (size_t)item * nb_max;
+  const int total = cotr_scan::scan_array<RP_WAVES>(
+      nb, wave_sum, [&](int b) { return block_kept(ballots + (first + b) * RP_WAVES); },
+      [&](int b, int before) { offsets[first + b] = before; });
+  if (threadIdx.x == 0) counts[item] = total;
 }
 
 template <bool VALID>

@@ -389,14 +389,16 @@ const RsEntry RG_ENTRY = {"cotr_ransac_rigid3d", "R_out", RG_MODEL, "", RgModel:
 // round [n]
 struct RgPlan {
   RfPlan rf;
-  size_t work, bytes;
+  uint8_t* work;
+  size_t bytes;
 };
 
-RgPlan rg_plan(const RsPlan& rs, int n) {
+RgPlan rg_plan(void* base, const RsPlan& rs, int n) {
   RgPlan l;
   l.rf = rf_plan(rs.bytes, sizeof(RgState), n, RG_STRIDE);
-  l.work = l.rf.bytes;
-  l.bytes = l.work + align_up((size_t)n);
+  Carver c(base, l.rf.bytes);
+  l.work = c.take<uint8_t>(n);
+  l.bytes = c.bytes;
   return l;
 }
 
@@ -406,7 +408,7 @@ extern "C" {
 
 int cotr_ransac_rigid3d_scratch_bytes(int n, int max_iters, size_t* bytes) {
   if (const int rc = rs_scratch_bytes(RG_ENTRY, n, max_iters, bytes)) return rc;
-  *bytes = rg_plan(rs_plan(RG_ENTRY, max_iters), n).bytes;
+  *bytes = rg_plan(nullptr, rs_plan(RG_ENTRY, max_iters), n).bytes;
   return COTR_OK;
 }
 
@@ -414,7 +416,7 @@ int cotr_ransac_rigid3d(const double* src, const double* dst, int n, double thre
                         int with_scale, int rounds, double* R_out, double* t_out, double* scale_out, uint8_t* mask_out, int32_t* info_out,
                         double* hyp_model, int32_t* hyp_count, int32_t* hyp_samples, void* scratch, size_t scratch_bytes, cotr_stream stream) {
   const RsPlan rs = rs_plan(RG_ENTRY, max_iters);
-  const RgPlan l = rg_plan(rs, n);
+  const RgPlan l = rg_plan(scratch, rs, n);
   if (const int rc = rs_check_call(RG_ENTRY, n, max_iters, threshold, confidence, src, dst, R_out, mask_out, info_out, hyp_model, hyp_count,
                                    hyp_samples, scratch, scratch_bytes, l.bytes))
     return rc;
@@ -427,7 +429,6 @@ int cotr_ransac_rigid3d(const double* src, const double* dst, int n, double thre
   char* base = static_cast<char*>(scratch);
   const double* cand = reinterpret_cast<const double*>(base + rs.candidates);
   RgState* st = reinterpret_cast<RgState*>(base + l.rf.state);
-  uint8_t* work = reinterpret_cast<uint8_t*>(base + l.work);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const auto solve = [&](double* c, int* count) {
     hipLaunchKernelGGL(rg_solve_kernel, dim3((unsigned)((max_iters + RS_SOLVE_THREADS - 1) / RS_SOLVE_THREADS)), dim3(RS_SOLVE_THREADS), 0, s, src,
@@ -438,12 +439,12 @@ int cotr_ransac_rigid3d(const double* src, const double* dst, int n, double thre
                       {cand, info_out, R_out, t_out, scale_out, st, with_scale});
   for (int r = 0; r < rounds; ++r) {
     // round 1 fits on the RANSAC mask, a later one on its own re-count
-    const uint8_t* mask = r == 0 ? mask_out : work;
+    const uint8_t* mask = r == 0 ? mask_out : l.work;
     if (r > 0)
-      hipLaunchKernelGGL(rg_mask_kernel, dim3((unsigned)l.rf.chunks), dim3(RS_COUNT_THREADS), 0, s, pts, n, thr, r, st, work);
+      hipLaunchKernelGGL(rg_mask_kernel, dim3((unsigned)l.rf.chunks), dim3(RS_COUNT_THREADS), 0, s, pts, n, thr, r, st, l.work);
     rf_enqueue_pair<RgSums1>(s, l.rf, scratch, pts, n, mask, rg_centroid_kernel, r);
     rf_enqueue_pair<RgSums2>(s, l.rf, scratch, pts, n, mask, rg_fit_kernel, r, R_out, t_out, scale_out, info_out);
-    if (r > 0) hipLaunchKernelGGL(rg_commit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, (const RgState*)st, (const uint8_t*)work, mask_out);
+    if (r > 0) hipLaunchKernelGGL(rg_commit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, (const RgState*)st, (const uint8_t*)l.work, mask_out);
   }
   return launched();
 }

@@ -247,13 +247,13 @@ __global__ __launch_bounds__(TV_THREADS) void tv_points_kernel(const double* __r
 // ---- host side ------------------------------------------------------------------------------------------------------------
 namespace {
 
-int tv_fail(const char* msg) { return handleless_fail(COTR_ERR_ARG, msg); }
-
 size_t tv_scratch_bytes() { return align_up((size_t)TV_MAX_VIEWS * TV_ROW * sizeof(double)); }
 
+const char* const TV_FN = "cotr_triangulate_views";
+
 const char* tv_check_shape(int V, int n) {
-  if (V < 2 || V > TV_MAX_VIEWS) return "cotr_triangulate_views: V must be in [2, 32]";
-  if (n < 1 || n > TV_MAX_POINTS) return "cotr_triangulate_views: n must be in [1, 2^24]";
+  if (V < 2 || V > TV_MAX_VIEWS) return "V must be in [2, 32]";
+  if (n < 1 || n > TV_MAX_POINTS) return "n must be in [1, 2^24]";
   return nullptr;
 }
 
@@ -262,8 +262,8 @@ const char* tv_check_shape(int V, int n) {
 extern "C" {
 
 int cotr_triangulate_views_scratch_bytes(int V, int n, size_t* bytes) {
-  if (!bytes) return tv_fail("cotr_triangulate_views_scratch_bytes: bytes is NULL");
-  if (const char* msg = tv_check_shape(V, n)) return tv_fail(msg);
+  if (!bytes) return arg_fail("cotr_triangulate_views_scratch_bytes", "bytes is NULL");
+  if (const char* msg = tv_check_shape(V, n)) return arg_fail(TV_FN, msg);
   *bytes = tv_scratch_bytes();
   return COTR_OK;
 }
@@ -272,25 +272,25 @@ int cotr_triangulate_views(const double* points, const uint8_t* visible, const d
                            const int32_t* found, double threshold, double max_cos, double distance_thresh, int refine_iters, int robust,
                            int rule, double* X_out, uint8_t* used_out, double* quality_out, uint8_t* mask_out, int32_t* info_out,
                            void* scratch, size_t scratch_bytes, cotr_stream stream) {
-  if (const char* msg = tv_check_shape(V, n)) return tv_fail(msg);
-  if (!(threshold > 0.0) || !(threshold < INFINITY)) return tv_fail("cotr_triangulate_views: threshold must be finite and > 0");
+  if (const char* msg = tv_check_shape(V, n)) return arg_fail(TV_FN, msg);
+  if (!(threshold > 0.0) || !(threshold < INFINITY)) return arg_fail(TV_FN, "threshold must be finite and > 0");
   const float thr = (float)(threshold * threshold);
   if (!(thr > 0.0f) || !(thr < INFINITY))
-    return tv_fail("cotr_triangulate_views: the squared threshold must be a finite float32 that is not 0");
-  if (!(max_cos >= -1.0) || !(max_cos <= 1.0)) return tv_fail("cotr_triangulate_views: max_cos must be in [-1, 1]");
+    return arg_fail(TV_FN, "the squared threshold must be a finite float32 that is not 0");
+  if (!(max_cos >= -1.0) || !(max_cos <= 1.0)) return arg_fail(TV_FN, "max_cos must be in [-1, 1]");
   if (!(distance_thresh > 0.0) || !(distance_thresh < INFINITY))
-    return tv_fail("cotr_triangulate_views: distance_thresh must be finite and > 0");
-  if (refine_iters < 0 || refine_iters > TV_MAX_REFINE) return tv_fail("cotr_triangulate_views: refine_iters must be in [0, 64]");
-  if (robust != 0 && robust != 1) return tv_fail("cotr_triangulate_views: robust must be 0 or 1");
-  if (rule != 0 && rule != 1) return tv_fail("cotr_triangulate_views: rule must be 0 (rays) or 1 (demo)");
+    return arg_fail(TV_FN, "distance_thresh must be finite and > 0");
+  if (refine_iters < 0 || refine_iters > TV_MAX_REFINE) return arg_fail(TV_FN, "refine_iters must be in [0, 64]");
+  if (robust != 0 && robust != 1) return arg_fail(TV_FN, "robust must be 0 or 1");
+  if (rule != 0 && rule != 1) return arg_fail(TV_FN, "rule must be 0 (rays) or 1 (demo)");
   if (rule == 1 && (V != 2 || robust != 0 || refine_iters != 0))
-    return tv_fail("cotr_triangulate_views: rule 1 (demo) takes V = 2, robust = 0 and refine_iters = 0");
+    return arg_fail(TV_FN, "rule 1 (demo) takes V = 2, robust = 0 and refine_iters = 0");
   if (!points || !cams || !poses || !X_out || !used_out || !quality_out || !mask_out || !info_out || !scratch)
-    return tv_fail("cotr_triangulate_views: points, cams, poses, X_out, used_out, quality_out, mask_out, info_out and scratch must not be NULL");
+    return arg_fail(TV_FN, "points, cams, poses, X_out, used_out, quality_out, mask_out, info_out and scratch must not be NULL");
   if (!aligned(points, 16) || !aligned(cams, 8) || !aligned(poses, 8) || !aligned(X_out, 8) || !aligned(quality_out, 8) ||
       !aligned(info_out, 4) || !aligned(found, 4) || !aligned(scratch, 16))
-    return tv_fail("cotr_triangulate_views: points and scratch must be 16-byte, other doubles 8-byte and ints 4-byte aligned");
-  if (scratch_bytes < tv_scratch_bytes()) return tv_fail("cotr_triangulate_views: scratch is smaller than cotr_triangulate_views_scratch_bytes");
+    return arg_fail(TV_FN, "points and scratch must be 16-byte, other doubles 8-byte and ints 4-byte aligned");
+  if (scratch_bytes < tv_scratch_bytes()) return arg_fail(TV_FN, "scratch is smaller than cotr_triangulate_views_scratch_bytes");
   double* tab = static_cast<double*>(scratch);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(tv_prepare_kernel, dim3(1), dim3(64), 0, s, cams, poses, V, found, tab, info_out);

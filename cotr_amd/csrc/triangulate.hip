@@ -17,9 +17,8 @@
 //
 //   0. tri_clear_kernel   ids = 0 (a kernel, not a memset node: the same in every graph the call is captured into)
 //   1. tri_setup_kernel   one thread per triangle: checks, snapping, orientation, bounding box of the samples it can
-//                         cover (clipped to the canvas), cut into 16x16-sample tiles; block-local inclusive scan of the
-//                         tile counts
-//   2. tri_scan_kernel    one workgroup: exclusive scan of the per-block totals, and the total tile count
+//                         cover (clipped to the canvas), cut into 16x16-sample tiles; the tile counts summed inside the block
+//   2. tri_scan_kernel    one workgroup: the block totals summed (both by scan.h), and the total tile count
 //   3. tri_raster_kernel  a fixed grid of wavefronts splits the total tile count into equal contiguous ranges (one
 //                         binary search per wavefront, then a walk), so a sliver spanning the canvas is shared by
 //                         many wavefronts; one 16x16 tile per wavefront step, 4 samples per lane, atomicMax of ids
@@ -30,6 +29,7 @@
 #include <stdint.h>
 
 #include "handleless.h"
+#include "scan.h"
 
 using namespace cotr_detail;
 
@@ -68,27 +68,11 @@ __device__ __forceinline__ long long tile_count(const TriRec& r) {
   return r.ntx == 0 ? 0 : (long long)r.ntx * ((r.i1 - r.i0) / TILE + 1);
 }
 
-// inclusive scan over the 256 threads of a workgroup
-__device__ long long block_scan_256(long long v, long long* sh) {
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {
-    const long long x = tid >= off ? sh[tid - off] : 0;
-    __syncthreads();
-    sh[tid] += x;
-    __syncthreads();
-  }
-  const long long r = sh[tid];
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(SETUP_THREADS) void tri_setup_kernel(const float* __restrict__ verts, int n_verts,
                                                                   const int32_t* __restrict__ tris, int n_tris, int H, int W,
                                                                   TriRec* __restrict__ recs, long long* __restrict__ local,
                                                                   long long* __restrict__ bsum) {
-  __shared__ long long sh[SETUP_THREADS];
+  __shared__ long long sums[SETUP_THREADS / 64];
   const int t = blockIdx.x * SETUP_THREADS + threadIdx.x;
   long long cnt = 0;
   if (t < n_tris) {
@@ -137,26 +121,18 @@ __global__ __launch_bounds__(SETUP_THREADS) void tri_setup_kernel(const float* _
     }
     recs[t] = r;
   }
-  const long long incl = block_scan_256(cnt, sh);
-  if (t < n_tris) local[t] = incl;
-  if (threadIdx.x == SETUP_THREADS - 1) bsum[blockIdx.x] = incl;
+  long long total;
+  const long long before = cotr_scan::block_scan<SETUP_THREADS / 64>(cnt, sums, &total);
+  if (t < n_tris) local[t] = before + cnt;   // inclusive: incl_at reads it
+  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
 // bsum[0..nb) block totals -> exclusive block offsets; bsum[nb] = total tile count
 __global__ __launch_bounds__(256) void tri_scan_kernel(long long* __restrict__ bsum, int nb) {
-  __shared__ long long sh[256];
-  long long carry = 0;
-  for (int base = 0; base < nb; base += 256) {
-    const int b = base + threadIdx.x;
-    const long long v = b < nb ? bsum[b] : 0;
-    const long long incl = block_scan_256(v, sh);
-    if (b < nb) bsum[b] = carry + incl - v;
-    if (threadIdx.x == 255) sh[0] = incl;   // the chunk total
-    __syncthreads();
-    carry += sh[0];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) bsum[nb] = carry;
+  __shared__ long long sums[4];
+  const long long total = cotr_scan::scan_array<4>(
+      nb, sums, [&](int b) { return bsum[b]; }, [&](int b, long long before) { bsum[b] = before; });
+  if (threadIdx.x == 0) bsum[nb] = total;
 }
 
 __device__ __forceinline__ long long incl_at(const long long* local, const long long* boff, int t) {
@@ -240,18 +216,23 @@ __global__ __launch_bounds__(256) void tri_resolve_kernel(const TriRec* __restri
 namespace {
 
 struct Layout {
-  size_t ids, recs, local, bsum, bytes;
+  int* ids;           // [H][W], padded to whole int4
+  TriRec* recs;       // [n_tris]
+  long long* local;   // [n_tris]
+  long long* bsum;    // [nb + 1]
+  size_t bytes;
   int nb;
 };
 
-Layout layout(int n_tris, int H, int W) {
+Layout layout(void* base, int n_tris, int H, int W) {
   Layout l;
+  Carver c(base);
   l.nb = (n_tris + SETUP_THREADS - 1) / SETUP_THREADS;
-  l.ids = 0;
-  l.recs = align_up((size_t)H * W * sizeof(int));
-  l.local = l.recs + align_up((size_t)n_tris * sizeof(TriRec));
-  l.bsum = l.local + align_up((size_t)n_tris * sizeof(long long));
-  l.bytes = l.bsum + align_up(((size_t)l.nb + 1) * sizeof(long long));
+  l.ids = c.take<int>((size_t)H * W);
+  l.recs = c.take<TriRec>(n_tris);
+  l.local = c.take<long long>(n_tris);
+  l.bsum = c.take<long long>((size_t)l.nb + 1);
+  l.bytes = c.bytes;
   return l;
 }
 
@@ -268,7 +249,7 @@ extern "C" {
 int cotr_raster_mesh_scratch_bytes(int n_tris, int H, int W, size_t* bytes) {
   if (!bytes) return handleless_fail(COTR_ERR_ARG, "cotr_raster_mesh_scratch_bytes: bytes is NULL");
   if (const char* e = check_shape(n_tris, H, W)) return handleless_fail(COTR_ERR_ARG, e);
-  *bytes = layout(n_tris, H, W).bytes;
+  *bytes = layout(nullptr, n_tris, H, W).bytes;
   return COTR_OK;
 }
 
@@ -280,22 +261,17 @@ int cotr_raster_mesh(const float* verts, int n_verts, const float* attrs, const 
   if (n_tris > 0 && (!verts || !attrs || !tris)) return handleless_fail(COTR_ERR_ARG, "verts, attrs and tris must not be NULL");
   if (!aligned(scratch, 16) || !aligned(out, 8))
     return handleless_fail(COTR_ERR_ARG, "scratch must be 16-byte and out 8-byte aligned");
-  const Layout l = layout(n_tris, H, W);
+  const Layout l = layout(scratch, n_tris, H, W);
   if (scratch_bytes < l.bytes) return handleless_fail(COTR_ERR_ARG, "scratch is smaller than cotr_raster_mesh_scratch_bytes");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(scratch);
-  int* ids = reinterpret_cast<int*>(base + l.ids);
-  TriRec* recs = reinterpret_cast<TriRec*>(base + l.recs);
-  long long* local = reinterpret_cast<long long*>(base + l.local);
-  long long* bsum = reinterpret_cast<long long*>(base + l.bsum);
   const long long npx = (long long)H * W, n4 = (npx + 3) / 4;   // the ids region is padded to 256 bytes: n4 int4 fit
-  hipLaunchKernelGGL(tri_clear_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<int4*>(ids), n4);
+  hipLaunchKernelGGL(tri_clear_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<int4*>(l.ids), n4);
   if (n_tris > 0) {
-    hipLaunchKernelGGL(tri_setup_kernel, dim3(l.nb), dim3(SETUP_THREADS), 0, s, verts, n_verts, tris, n_tris, H, W, recs, local, bsum);
-    hipLaunchKernelGGL(tri_scan_kernel, dim3(1), dim3(256), 0, s, bsum, l.nb);
-    hipLaunchKernelGGL(tri_raster_kernel, dim3(RASTER_BLOCKS), dim3(256), 0, s, recs, local, bsum, l.nb, n_tris, W, ids);
+    hipLaunchKernelGGL(tri_setup_kernel, dim3(l.nb), dim3(SETUP_THREADS), 0, s, verts, n_verts, tris, n_tris, H, W, l.recs, l.local, l.bsum);
+    hipLaunchKernelGGL(tri_scan_kernel, dim3(1), dim3(256), 0, s, l.bsum, l.nb);
+    hipLaunchKernelGGL(tri_raster_kernel, dim3(RASTER_BLOCKS), dim3(256), 0, s, l.recs, l.local, l.bsum, l.nb, n_tris, W, l.ids);
   }
-  hipLaunchKernelGGL(tri_resolve_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s, recs, ids, attrs, n_tris, H, W,
+  hipLaunchKernelGGL(tri_resolve_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s, l.recs, l.ids, attrs, n_tris, H, W,
                      reinterpret_cast<float2*>(out), mask);
   return launched();
 }

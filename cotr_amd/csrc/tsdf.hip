@@ -23,12 +23,12 @@
 //   2. ms_classify_kernel       one thread per voxel: the cell above it is valid, and the inside bits of its 8 corners (2 B a voxel
 //                               of scratch).  A lane reads its column of 4 voxels and takes the column at x + 1 from the next lane.
 //   3. ms_count_kernel          one thread per voxel, blocks of 512 voxels: the 7 live bits of the voxel's edges from the codes of the
-//                               (at most 4) cells that hold each, the triangles of its cell, and the scan of both counts inside the
-//                               block (packed in one int: wave shuffles, wave totals through LDS) -> a 4 B record a voxel (written only
+//                               (at most 4) cells that hold each, the triangles of its cell, and both counts (packed in one int) summed
+//                               inside the block by scan.h -> a 4 B record a voxel (written only
 //                               where the block holds a vertex) and the block's two totals.  Valid cells: ballots summed in a register
 //                               of each wavefront, four LDS slots, one integer atomic per workgroup into info.  2 and 3 run on at most
 //                               2048 workgroups that walk the blocks: one walk covers 2048 * 512 = 2^20 voxels.
-//   4. ms_scan_kernel           one workgroup of 1024: the exclusive scan of the block totals, both carried together; the counts.
+//   4. ms_scan_kernel           one workgroup of 1024: the block totals summed by scan.h, both carried together; the counts.
 //   5. ms_emit_kernel           (a capacity above 0) a workgroup whose block has neither vertex nor triangle leaves; a thread writes
 //                               the vertices (and normals) of its voxel's live edges and the triangles of its cell: a vertex index
 //                               is the scanned base of the edge's voxel + the live bits below the edge's code.
@@ -39,12 +39,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include <algorithm>
 
 #include "handleless.h"
 #include "pinhole.h"
+#include "scan.h"
 
 using namespace cotr_detail;
 
@@ -359,32 +359,20 @@ __global__ __launch_bounds__(MS_THREADS) void ms_count_kernel(const uint16_t* __
       }
       live[r] = lv;
       packed[r] = __popc(lv) | nt << 16;
-      int inc = packed[r];
-      if (__ballot(inc != 0) != 0ull) {   // uniform
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-          const int t = __shfl_up(inc, d, 64);
-          if (lane >= d) inc += t;
-        }
-      }
-      incl[r] = inc;
-      if (lane == 63) wave_sum[r * 4 + wave] = inc;
+      // a wavefront away from the surface has nothing to scan (uniform)
+      incl[r] = __ballot(packed[r] != 0) != 0ull ? cotr_scan::wave_scan(packed[r]) : packed[r];
+      cotr_scan::wave_sum_put(incl[r], wave_sum, r * 4 + wave);
       cells += __popcll(__ballot(valid));
     }
     __syncthreads();
-    int all = 0;
-#pragma unroll
-    for (int q = 0; q < MS_ROUNDS * 4; ++q) all += wave_sum[q];
+    const int all = cotr_scan::wave_sums_below<MS_ROUNDS * 4>(wave_sum, MS_ROUNDS * 4);
     // a block with no vertex has no triangle either (a cut tetrahedron cuts an edge at q0, which its own voxel owns) and nobody
     // reads its records: ms_emit_kernel takes them as 0
     if (all != 0) {
 #pragma unroll
       for (int r = 0; r < MS_ROUNDS; ++r) {
-        int before = 0;
-#pragma unroll
-        for (int q = 0; q < MS_ROUNDS * 4; ++q) before += q < r * 4 + wave ? wave_sum[q] : 0;
         const int idx = (blk * MS_ROUNDS + r) * MS_THREADS + threadIdx.x;
-        const int ex = before + incl[r] - packed[r];
+        const int ex = cotr_scan::wave_sums_below<MS_ROUNDS * 4>(wave_sum, r * 4 + wave) + incl[r] - packed[r];
         if (idx < total) rec[idx] = live[r] | (unsigned)(ex & 0xffff) << 7 | (unsigned)(ex >> 16) << 19;
       }
     }
@@ -403,31 +391,9 @@ __global__ __launch_bounds__(MS_THREADS) void ms_count_kernel(const uint16_t* __
 __global__ __launch_bounds__(MS_SCAN_THREADS) void ms_scan_kernel(const int2* __restrict__ totals, int nblk, int2* __restrict__ bases,
                                                                   int32_t* __restrict__ info) {
   __shared__ int2 wave_sum[MS_SCAN_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int cx = 0, cy = 0;
-  for (int base = 0; base < nblk; base += MS_SCAN_THREADS) {
-    const int b = base + threadIdx.x;
-    const int2 c = b < nblk ? totals[b] : make_int2(0, 0);
-    int ix = c.x, iy = c.y;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int tx = __shfl_up(ix, d, 64), ty = __shfl_up(iy, d, 64);
-      if (lane >= d) ix += tx, iy += ty;
-    }
-    if (lane == 63) wave_sum[wave] = make_int2(ix, iy);
-    __syncthreads();
-    int bx = 0, by = 0, tx = 0, ty = 0;
-#pragma unroll
-    for (int q = 0; q < MS_SCAN_THREADS / 64; ++q) {
-      const int2 w = wave_sum[q];
-      bx += q < wave ? w.x : 0, by += q < wave ? w.y : 0;
-      tx += w.x, ty += w.y;
-    }
-    if (b < nblk) bases[b] = make_int2(cx + bx + ix - c.x, cy + by + iy - c.y);
-    cx += tx, cy += ty;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) info[1] = cx, info[2] = cy;
+  const int2 all = cotr_scan::scan_array<MS_SCAN_THREADS / 64>(
+      nblk, wave_sum, [&](int b) { return totals[b]; }, [&](int b, int2 before) { bases[b] = before; });
+  if (threadIdx.x == 0) info[1] = all.x, info[2] = all.y;
 }
 
 // the value at grid coordinates q by ts_trilinear's rule; false outside the box or at an unobserved corner
@@ -554,12 +520,6 @@ __global__ __launch_bounds__(MS_THREADS) void ms_pad_kernel(int32_t* __restrict_
 // ---- host side ------------------------------------------------------------------------------------------------------------
 namespace {
 
-int ts_fail(const char* fn, const char* what) {
-  char msg[256];
-  snprintf(msg, sizeof msg, "%s: %s", fn, what);
-  return handleless_fail(COTR_ERR_ARG, msg);
-}
-
 bool ts_finite(double v) { return fabs(v) < INFINITY; }   // false for NaN
 
 // the volume's arguments -> g; the message of the first rule broken, or NULL
@@ -582,26 +542,26 @@ int cotr_tsdf_integrate(float* tsdf, float* weight, int Nx, int Ny, int Nz, cons
                         const double* obs_weight, double max_weight, int32_t* info_out, cotr_stream stream) {
   static const char* fn = "cotr_tsdf_integrate";
   TsGrid g;
-  if (const char* msg = ts_check_volume(tsdf, weight, Nx, Ny, Nz, origin, voxel, &g)) return ts_fail(fn, msg);
-  if (!(trunc > 0.0) || !ts_finite(trunc)) return ts_fail(fn, "trunc must be finite and > 0");
-  if (n < 1 || n > TS_MAX_CAPS) return ts_fail(fn, "n must be in [1, 32]");
-  if (H < 1 || W < 1 || (long long)H * W > MAX_PIXELS) return ts_fail(fn, "H and W must be >= 1 with at most 2^28 pixels");
-  if (!(max_weight > 0.0)) return ts_fail(fn, "max_weight must be > 0");
-  if (!depths || !Ks || !c2w || !info_out) return ts_fail(fn, "depths, Ks, c2w and info_out must not be NULL");
+  if (const char* msg = ts_check_volume(tsdf, weight, Nx, Ny, Nz, origin, voxel, &g)) return arg_fail(fn, msg);
+  if (!(trunc > 0.0) || !ts_finite(trunc)) return arg_fail(fn, "trunc must be finite and > 0");
+  if (n < 1 || n > TS_MAX_CAPS) return arg_fail(fn, "n must be in [1, 32]");
+  if (H < 1 || W < 1 || (long long)H * W > MAX_PIXELS) return arg_fail(fn, "H and W must be >= 1 with at most 2^28 pixels");
+  if (!(max_weight > 0.0)) return arg_fail(fn, "max_weight must be > 0");
+  if (!depths || !Ks || !c2w || !info_out) return arg_fail(fn, "depths, Ks, c2w and info_out must not be NULL");
   TsCaps caps;
   for (int c = 0; c < TS_MAX_CAPS; ++c) {
     caps.k[c] = {1.0, 1.0, 0.0, 0.0, 0.0};
     caps.w[c] = 1.0;
   }
   for (int c = 0; c < n; ++c) {
-    if (!es_camera(Ks + c * 9, &caps.k[c])) return ts_fail(fn, "the camera matrices must be finite with focal lengths that are not 0");
+    if (!es_camera(Ks + c * 9, &caps.k[c])) return arg_fail(fn, "the camera matrices must be finite with focal lengths that are not 0");
     if (obs_weight) {
-      if (!(obs_weight[c] > 0.0) || !ts_finite(obs_weight[c])) return ts_fail(fn, "every obs_weight must be finite and > 0");
+      if (!(obs_weight[c] > 0.0) || !ts_finite(obs_weight[c])) return arg_fail(fn, "every obs_weight must be finite and > 0");
       caps.w[c] = obs_weight[c];
     }
   }
   if (!aligned(depths, 4) || !aligned(c2w, 8) || !aligned(found, 4) || !aligned(info_out, 4))
-    return ts_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
+    return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int total = Nx * Ny * Nz, per_group = 256 * TS_ROWS;
   hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, n, info_out);
@@ -615,18 +575,18 @@ int cotr_tsdf_raycast(const float* tsdf, const float* weight, int Nx, int Ny, in
                       double* normal_out, int32_t* info_out, cotr_stream stream) {
   static const char* fn = "cotr_tsdf_raycast";
   TsGrid g;
-  if (const char* msg = ts_check_volume(tsdf, weight, Nx, Ny, Nz, origin, voxel, &g)) return ts_fail(fn, msg);
-  if (H < 1 || W < 1 || (long long)H * W > MAX_PIXELS) return ts_fail(fn, "H and W must be >= 1 with at most 2^28 pixels");
-  if (!(near >= 0.0) || !ts_finite(near)) return ts_fail(fn, "near must be finite and >= 0");
-  if (!(far > near) || !ts_finite(far)) return ts_fail(fn, "far must be finite and > near");
-  if (!(step > 0.0) || !ts_finite(step)) return ts_fail(fn, "step must be finite and > 0");
+  if (const char* msg = ts_check_volume(tsdf, weight, Nx, Ny, Nz, origin, voxel, &g)) return arg_fail(fn, msg);
+  if (H < 1 || W < 1 || (long long)H * W > MAX_PIXELS) return arg_fail(fn, "H and W must be >= 1 with at most 2^28 pixels");
+  if (!(near >= 0.0) || !ts_finite(near)) return arg_fail(fn, "near must be finite and >= 0");
+  if (!(far > near) || !ts_finite(far)) return arg_fail(fn, "far must be finite and > near");
+  if (!(step > 0.0) || !ts_finite(step)) return arg_fail(fn, "step must be finite and > 0");
   const double steps = ceil((far - near) / step);
-  if (!(steps <= (double)TS_MAX_STEPS)) return ts_fail(fn, "ceil((far - near) / step) must be at most 65536");
-  if (!K || !c2w || !depth_out || !info_out) return ts_fail(fn, "K, c2w, depth_out and info_out must not be NULL");
+  if (!(steps <= (double)TS_MAX_STEPS)) return arg_fail(fn, "ceil((far - near) / step) must be at most 65536");
+  if (!K || !c2w || !depth_out || !info_out) return arg_fail(fn, "K, c2w, depth_out and info_out must not be NULL");
   TsRay ray;
-  if (!es_camera(K, &ray.k)) return ts_fail(fn, "the camera matrix must be finite with focal lengths that are not 0");
+  if (!es_camera(K, &ray.k)) return arg_fail(fn, "the camera matrix must be finite with focal lengths that are not 0");
   if (!aligned(c2w, 8) || !aligned(found, 4) || !aligned(depth_out, 4) || !aligned(normal_out, 8) || !aligned(info_out, 4))
-    return ts_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
+    return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
   ray.H = H, ray.W = W, ray.steps = (int)steps, ray.near = near, ray.step = step;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned tiles = (unsigned)((W + 15) / 16) * (unsigned)((H + 15) / 16);
@@ -640,19 +600,23 @@ int cotr_tsdf_raycast(const float* tsdf, const float* weight, int Nx, int Ny, in
 namespace {
 
 struct MsScratch {
-  size_t code, rec, totals, bases, bytes;
+  uint16_t* code;          // [voxels]
+  uint32_t* rec;           // [voxels]
+  int2 *totals, *bases;    // [nblk]
+  size_t bytes;
   int nblk;
 };
 
-MsScratch ms_layout(int Nx, int Ny, int Nz) {
+MsScratch ms_layout(void* base, int Nx, int Ny, int Nz) {
   const size_t total = (size_t)Nx * Ny * Nz;
   MsScratch L;
+  Carver c(base);
   L.nblk = (int)((total + MS_BLOCK - 1) / MS_BLOCK);
-  L.code = 0;
-  L.rec = L.code + align_up(total * sizeof(uint16_t));
-  L.totals = L.rec + align_up(total * sizeof(uint32_t));
-  L.bases = L.totals + align_up((size_t)L.nblk * sizeof(int2));
-  L.bytes = L.bases + align_up((size_t)L.nblk * sizeof(int2));
+  L.code = c.take<uint16_t>(total);
+  L.rec = c.take<uint32_t>(total);
+  L.totals = c.take<int2>(L.nblk);
+  L.bases = c.take<int2>(L.nblk);
+  L.bytes = c.bytes;
   return L;
 }
 
@@ -670,9 +634,9 @@ extern "C" {
 
 int cotr_tsdf_mesh_scratch_bytes(int Nx, int Ny, int Nz, size_t* bytes) {
   static const char* fn = "cotr_tsdf_mesh_scratch_bytes";
-  if (!bytes) return ts_fail(fn, "bytes must not be NULL");
-  if (!ms_dims_ok(Nx, Ny, Nz)) return ts_fail(fn, MS_DIMS);
-  *bytes = ms_layout(Nx, Ny, Nz).bytes;
+  if (!bytes) return arg_fail(fn, "bytes must not be NULL");
+  if (!ms_dims_ok(Nx, Ny, Nz)) return arg_fail(fn, MS_DIMS);
+  *bytes = ms_layout(nullptr, Nx, Ny, Nz).bytes;
   return COTR_OK;
 }
 
@@ -681,30 +645,25 @@ int cotr_tsdf_mesh(const float* tsdf, const float* weight, int Nx, int Ny, int N
                    size_t scratch_bytes, cotr_stream stream) {
   static const char* fn = "cotr_tsdf_mesh";
   TsGrid g;
-  if (!ms_dims_ok(Nx, Ny, Nz)) return ts_fail(fn, MS_DIMS);
-  if (const char* msg = ts_check_volume(tsdf, weight, Nx, Ny, Nz, origin, voxel, &g)) return ts_fail(fn, msg);
-  if (cap_verts < 0 || cap_tris < 0) return ts_fail(fn, "cap_verts and cap_tris must be >= 0");
+  if (!ms_dims_ok(Nx, Ny, Nz)) return arg_fail(fn, MS_DIMS);
+  if (const char* msg = ts_check_volume(tsdf, weight, Nx, Ny, Nz, origin, voxel, &g)) return arg_fail(fn, msg);
+  if (cap_verts < 0 || cap_tris < 0) return arg_fail(fn, "cap_verts and cap_tris must be >= 0");
   if ((cap_verts > 0 && !verts_out) || (cap_tris > 0 && !tris_out) || !info_out)
-    return ts_fail(fn, "verts_out, tris_out (with a capacity above 0) and info_out must not be NULL");
+    return arg_fail(fn, "verts_out, tris_out (with a capacity above 0) and info_out must not be NULL");
   if (!aligned(found, 4) || !aligned(verts_out, 8) || !aligned(normals_out, 8) || !aligned(tris_out, 4) || !aligned(info_out, 4))
-    return ts_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
-  const MsScratch L = ms_layout(Nx, Ny, Nz);
+    return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
+  const MsScratch L = ms_layout(scratch, Nx, Ny, Nz);
   if (!scratch || scratch_bytes < L.bytes || !aligned(scratch, 16))
-    return ts_fail(fn, "scratch must be 16-byte aligned and hold cotr_tsdf_mesh_scratch_bytes(Nx, Ny, Nz) bytes");
-  char* base = static_cast<char*>(scratch);
-  uint16_t* code = reinterpret_cast<uint16_t*>(base + L.code);
-  uint32_t* rec = reinterpret_cast<uint32_t*>(base + L.rec);
-  int2* totals = reinterpret_cast<int2*>(base + L.totals);
-  int2* bases = reinterpret_cast<int2*>(base + L.bases);
+    return arg_fail(fn, "scratch must be 16-byte aligned and hold cotr_tsdf_mesh_scratch_bytes(Nx, Ny, Nz) bytes");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int total = Nx * Ny * Nz;
   hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, 1, info_out);
   const int nrun = (total + MS_THREADS - 1) / MS_THREADS;
-  hipLaunchKernelGGL(ms_classify_kernel, dim3((unsigned)std::min(nrun, MS_GRID)), dim3(MS_THREADS), 0, s, tsdf, weight, g, nrun, code);
-  hipLaunchKernelGGL(ms_count_kernel, dim3((unsigned)std::min(L.nblk, MS_GRID)), dim3(MS_THREADS), 0, s, code, g, found, L.nblk, rec, totals, info_out);
-  hipLaunchKernelGGL(ms_scan_kernel, dim3(1), dim3(MS_SCAN_THREADS), 0, s, totals, L.nblk, bases, info_out);
+  hipLaunchKernelGGL(ms_classify_kernel, dim3((unsigned)std::min(nrun, MS_GRID)), dim3(MS_THREADS), 0, s, tsdf, weight, g, nrun, L.code);
+  hipLaunchKernelGGL(ms_count_kernel, dim3((unsigned)std::min(L.nblk, MS_GRID)), dim3(MS_THREADS), 0, s, L.code, g, found, L.nblk, L.rec, L.totals, info_out);
+  hipLaunchKernelGGL(ms_scan_kernel, dim3(1), dim3(MS_SCAN_THREADS), 0, s, L.totals, L.nblk, L.bases, info_out);
   if (cap_verts > 0 || cap_tris > 0)   // the blocks with a surface are few and heavy: a workgroup each, so that they spread over the CUs
-    hipLaunchKernelGGL(ms_emit_kernel, dim3((unsigned)L.nblk), dim3(MS_THREADS), 0, s, tsdf, weight, g, code, rec, L.nblk, totals, bases, verts_out,
+    hipLaunchKernelGGL(ms_emit_kernel, dim3((unsigned)L.nblk), dim3(MS_THREADS), 0, s, tsdf, weight, g, L.code, L.rec, L.nblk, L.totals, L.bases, verts_out,
                        cap_verts > 0 ? normals_out : nullptr, cap_verts, tris_out, cap_tris);
   if (cap_tris > 0)
     hipLaunchKernelGGL(ms_pad_kernel, dim3((unsigned)(((size_t)cap_tris * 3 + MS_THREADS - 1) / MS_THREADS)), dim3(MS_THREADS), 0, s, tris_out, cap_tris,

@@ -77,7 +77,7 @@ def _looking_away(c):
     return c._replace(c2w=c.c2w @ np.diag([-1.0, 1.0, -1.0, 1.0]))
 
 
-@pytest.mark.parametrize('shape', [(1, 1), (2, 3), (255, 257), (256, 256), (480, 640), (1200, 1600)])
+@pytest.mark.parametrize('shape', [(1, 1), (2, 3), (255, 257), (256, 256), (257, 256), (480, 640), (1200, 1600)])
 def test_depth_corrs_shapes(shape):
     q, n = synth_captures(shape[0] + shape[1], *shape)
     rows, counts = _run([q, n], [n, q])

@@ -66,7 +66,7 @@ def test_square_corners_in_every_index_order(order):
 
 
 # ---- lane and wavefront edges; a point that keeps more triangles than the staging holds -------------------------------------
-@pytest.mark.parametrize('n', [63, 64, 65, 129, 257])
+@pytest.mark.parametrize('n', [63, 64, 65, 129, 256, 257, 513])   # 256: the width of the scan's chunks
 def test_random_points_around_the_wavefront_width(n):
     check(np.random.default_rng(n).uniform(0, 1, (n, 2)).astype(np.float32))
 

@@ -107,6 +107,14 @@ def test_ten_thousand_points_grid_and_delaunay():
     check(v, grid_attrs(v, 4), tri.simplices, 768, 1024)
 
 
+def test_more_block_totals_than_the_scan_takes_in_one_chunk():
+    # a workgroup of the setup pass holds 256 triangles and the scan of their totals walks chunks of 256: one chunk plus three
+    verts, tris = ro.jittered_grid(182, 182, 0.45, seed=14)
+    assert len(tris) == 66248 and (len(tris) + 255) // 256 > 256
+    out, mask = check(verts, grid_attrs(verts, 5), tris, 256, 512)
+    assert mask.all()
+
+
 @pytest.mark.parametrize('H,W', [(7, 13), (768, 1024)])
 def test_scipy_meshes_with_vertices_on_pixel_centres(H, W):
     spatial = pytest.importorskip('scipy.spatial')
