@@ -206,8 +206,10 @@ int compact(const uint64_t* ptrs, const int32_t* shapes, const double* cams, int
   if (cap < 0 || (size_t)n * cap > ((size_t)1 << 31)) return handleless_fail(COTR_ERR_ARG, "cap must be >= 0 and n * cap <= 2^31");
   if (!ptrs || !shapes || (!VALID && !cams) || !counts || (cap > 0 && !out))
     return handleless_fail(COTR_ERR_ARG, "the item tables, counts and the output must not be NULL");
-  if (!aligned(ptrs, 8) || !aligned(cams, 8) || !aligned(out, 16) || !aligned(scratch, 16))
-    return handleless_fail(COTR_ERR_ARG, "ptrs and cams must be 8-byte, the output and scratch 16-byte aligned");
+  // rows are written as double2 pairs, indices one int32 at a time: each is asked for what its store needs
+  if (!aligned(ptrs, 8) || !aligned(cams, 8) || !aligned(shapes, 4) || !aligned(counts, 4) || !aligned(out, VALID ? 4 : 16) || !aligned(scratch, 16))
+    return handleless_fail(COTR_ERR_ARG, VALID ? "cotr_depth_valid: ptrs must be 8-byte, shapes, indices and counts 4-byte and scratch 16-byte aligned"
+                                               : "cotr_depth_corrs: ptrs and cams must be 8-byte, shapes and counts 4-byte, rows and scratch 16-byte aligned");
   if (!scratch || scratch_bytes < scratch_for(n, max_src))
     return handleless_fail(COTR_ERR_ARG, "scratch is NULL or smaller than cotr_depth_corrs_scratch(n, max_src)");
   const int nb = nb_for(max_src);

@@ -915,7 +915,9 @@ int cotr_warp_perspective(const uint8_t* src, int Hs, int Ws, int C, const doubl
  *   item's n_src is clamped to it).  The compaction is a scan (wave ballots, block totals, their scan, scatter): two runs
  *   return the same bytes.
  * cotr_depth_valid: the same compaction with the predicate from_depth > 0 (to_depth and cams are not read) ->
- *   indices [n][cap] int32 = y * Wf + x of the valid pixels in source order, counts [n].
+ *   indices [n][cap] int32 (4-byte aligned: written one index at a time) = y * Wf + x of the valid pixels in source order,
+ *   counts [n].
+ *   ptrs and cams 8-byte, shapes and counts 4-byte aligned.
  *   scratch for both: DEVICE, 16-byte aligned, at least cotr_depth_corrs_scratch(n, max_src) bytes (0 for arguments out of range).
  * cotr_crop_depth_nearest: for each of n items crop the box boxes[i] = (x, y, size) (int32 [n][3], DEVICE, inside the map) of the
  *   float32 depth map srcs[i] (uint64 [n] DEVICE addresses) of shapes[i] = (H, W) (int32 [n][2], DEVICE) and resize it to
