@@ -34,6 +34,12 @@
 //                               is the scanned base of the edge's voxel + the live bits below the edge's code.
 //   6. ms_pad_kernel            (cap_tris above 0) -1 into the triangle rows past the count.
 // Every position comes from the scan, none from an atomic.
+// The colour volume, float32 [Nz][Ny][Nx][4] = (r, g, b, colour weight), 2 launches each:
+//   cotr_tsdf_color_integrate   ts_begin_kernel, then ts_color_integrate_kernel: ts_integrate_kernel's mapping and counters, a voxel
+//                               one 16-byte load and, where a capture coloured it, one 16-byte store.
+//   cotr_tsdf_color_points      ts_begin_kernel, then ts_color_points_kernel: one thread per point (no second launch without points).
+//   cotr_tsdf_color_map         ts_begin_kernel, then ts_color_map_kernel: one thread per pixel on the raycast's tiles.
+//                               Both blend the coloured corners of the point's cell through ts_color_at.
 // Integer atomics only: the same input gives the same bits.  No host waits, no allocation: capturable.  Compiled with
 // -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -51,6 +57,7 @@ using namespace cotr_detail;
 #define TS_MAX_CAPS 32
 #define TS_MAX_VOXELS (1 << 28)
 #define TS_MAX_STEPS 65536
+#define TS_MAX_POINTS (1 << 28)
 #define TS_ROWS 4              // runs of 256 voxels a workgroup of ts_integrate_kernel walks
 
 struct TsGrid {
@@ -72,6 +79,24 @@ __global__ __launch_bounds__(64) void ts_begin_kernel(const int32_t* __restrict_
 }
 
 // ---- integration ----------------------------------------------------------------------------------------------------------
+// The voxel centre P seen by capture c (pose m, camera cam): false unless Y_z > 0, the pixel (rint u, rint v) of its projection
+// lies inside the map and the depth z there is finite and > 0; then *pix is that pixel's index in depths ([n][H][W]) and
+// *sdf = z - Y_z.  The one statement of the projection: both integrate kernels call it.
+__device__ __forceinline__ bool ts_project(const double* __restrict__ m, const EsCam& cam, double Px, double Py, double Pz,
+                                           const float* __restrict__ depths, int c, int H, int W, size_t* pix, double* sdf) {
+  const double dx = Px - m[3], dy = Py - m[7], dz = Pz - m[11];
+  const double Yx = (m[0] * dx + m[4] * dy) + m[8] * dz, Yy = (m[1] * dx + m[5] * dy) + m[9] * dz, Yz = (m[2] * dx + m[6] * dy) + m[10] * dz;
+  if (!(Yz > 0.0)) return false;   // NaN too
+  const double xn = Yx / Yz, yn = Yy / Yz;
+  const double u = rint((cam.fx * xn + cam.s * yn) + cam.cx), v = rint(cam.fy * yn + cam.cy);
+  if (!(u >= 0.0 && u < (double)W && v >= 0.0 && v < (double)H)) return false;
+  *pix = ((size_t)c * H + (size_t)(int)v) * W + (size_t)(int)u;
+  const double z = (double)depths[*pix];
+  if (!(z > 0.0 && z < INFINITY)) return false;
+  *sdf = z - Yz;
+  return true;
+}
+
 __global__ __launch_bounds__(256) void ts_integrate_kernel(float* __restrict__ tsdf, float* __restrict__ weight, TsGrid g, double trunc,
                                                            const float* __restrict__ depths, int n, int H, int W, TsCaps caps,
                                                            const double* __restrict__ c2w, const int32_t* __restrict__ found,
@@ -91,30 +116,17 @@ __global__ __launch_bounds__(256) void ts_integrate_kernel(float* __restrict__ t
     bool touched = false;
     for (int c = 0; c < n; ++c) {
       if (found && found[c] == 0) continue;   // uniform
-      const double* __restrict__ m = c2w + c * 16;
-      const EsCam& cam = caps.k[c];
       bool valid = false, updated = false;
-      if (in) {
-        const double dx = Px - m[3], dy = Py - m[7], dz = Pz - m[11];
-        const double Yx = (m[0] * dx + m[4] * dy) + m[8] * dz, Yy = (m[1] * dx + m[5] * dy) + m[9] * dz,
-                     Yz = (m[2] * dx + m[6] * dy) + m[10] * dz;
-        if (Yz > 0.0) {   // false for NaN
-          const double xn = Yx / Yz, yn = Yy / Yz;
-          const double u = rint((cam.fx * xn + cam.s * yn) + cam.cx), v = rint(cam.fy * yn + cam.cy);
-          if (u >= 0.0 && u < (double)W && v >= 0.0 && v < (double)H) {
-            const double z = (double)depths[((size_t)c * H + (size_t)(int)v) * W + (size_t)(int)u];
-            if (z > 0.0 && z < INFINITY) {
-              valid = true;
-              const double sdf = z - Yz;
-              if (!(sdf < -trunc)) {
-                const double d = fmin(1.0, sdf / trunc), w = caps.w[c];
-                const double Td = (double)T, Wd = (double)Wt;
-                T = (float)((Td * Wd + d * w) / (Wd + w));
-                Wt = (float)fmin(Wd + w, max_weight);
-                updated = true;
-              }
-            }
-          }
+      size_t pix;
+      double sdf;
+      if (in && ts_project(c2w + c * 16, caps.k[c], Px, Py, Pz, depths, c, H, W, &pix, &sdf)) {
+        valid = true;
+        if (!(sdf < -trunc)) {
+          const double d = fmin(1.0, sdf / trunc), w = caps.w[c];
+          const double Td = (double)T, Wd = (double)Wt;
+          T = (float)((Td * Wd + d * w) / (Wd + w));
+          Wt = (float)fmin(Wd + w, max_weight);
+          updated = true;
         }
       }
       touched = touched || updated;
@@ -125,6 +137,59 @@ __global__ __launch_bounds__(256) void ts_integrate_kernel(float* __restrict__ t
       }
     }
     if (touched) tsdf[idx] = T, weight[idx] = Wt;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * n) {
+    const int v = (&cnt[0][0])[threadIdx.x];
+    if (v > 0) atomicAdd(&info[(threadIdx.x >> 1) * 4 + 1 + (threadIdx.x & 1)], v);
+  }
+}
+
+// The colour volume: ts_integrate_kernel's mapping and counters on float4 voxels (r, g, b, colour weight).  A
+// voxel is one 16-byte load, and one 16-byte store only where a capture coloured it: where its pixel holds a valid depth and
+// sdf lies in [-trunc, trunc].  tsdf and weight are not read.
+__global__ __launch_bounds__(256) void ts_color_integrate_kernel(float4* __restrict__ color, TsGrid g, double trunc, const float* __restrict__ depths,
+                                                                 const uint8_t* __restrict__ images, int n, int H, int W, TsCaps caps,
+                                                                 const double* __restrict__ c2w, const int32_t* __restrict__ found,
+                                                                 double max_weight, int32_t* __restrict__ info) {
+  __shared__ int cnt[TS_MAX_CAPS][2];   // voxels coloured, voxels whose pixel held a valid depth
+  if (threadIdx.x < 2 * TS_MAX_CAPS) (&cnt[0][0])[threadIdx.x] = 0;
+  __syncthreads();
+  const int total = g.Nx * g.Ny * g.Nz;
+  const bool first_lane = (threadIdx.x & 63) == 0;
+  for (int r = 0; r < TS_ROWS; ++r) {
+    const int idx = (blockIdx.x * TS_ROWS + r) * 256 + threadIdx.x;
+    const bool in = idx < total;
+    const int row = idx / g.Nx, i = idx - row * g.Nx, k = row / g.Ny, j = row - k * g.Ny;
+    const double Px = g.ox + g.voxel * (double)i, Py = g.oy + g.voxel * (double)j, Pz = g.oz + g.voxel * (double)k;
+    float4 C = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (in) C = color[idx];
+    bool touched = false;
+    for (int c = 0; c < n; ++c) {
+      if (found && found[c] == 0) continue;   // uniform
+      bool valid = false, coloured = false;
+      size_t pix;
+      double sdf;
+      if (in && ts_project(c2w + c * 16, caps.k[c], Px, Py, Pz, depths, c, H, W, &pix, &sdf)) {
+        valid = true;
+        if (!(sdf < -trunc) && !(sdf > trunc)) {
+          const uint8_t* __restrict__ p = images + pix * 3;
+          const double w = caps.w[c], Wd = (double)C.w, sum = Wd + w;
+          C.x = (float)(((double)C.x * Wd + (double)p[0] * w) / sum);
+          C.y = (float)(((double)C.y * Wd + (double)p[1] * w) / sum);
+          C.z = (float)(((double)C.z * Wd + (double)p[2] * w) / sum);
+          C.w = (float)fmin(sum, max_weight);
+          coloured = true;
+        }
+      }
+      touched = touched || coloured;
+      const int nv = __popcll(__ballot(valid)), nc = __popcll(__ballot(coloured));
+      if (first_lane) {
+        if (nc > 0) atomicAdd(&cnt[c][0], nc);
+        if (nv > 0) atomicAdd(&cnt[c][1], nv);
+      }
+    }
+    if (touched) color[idx] = C;
   }
   __syncthreads();
   if (threadIdx.x < 2 * n) {
@@ -249,6 +314,77 @@ __global__ __launch_bounds__(256) void ts_raycast_kernel(const float* __restrict
   if (lane == 0) {
     if (nh > 0) atomicAdd(&info[1], nh);
     if (nb > 0) atomicAdd(&info[2], nb);
+  }
+}
+
+// ---- the colour of points and of a depth map ---------------------------------------------------------------
+// The colour of the world point p as three bytes in bits 0-7, 8-15 and 16-23, and bit 24 set; 0 unless p lies in the box (faces
+// included, wider than ts_in_box: a mesh vertex on the last voxel layer has a colour) and a corner of its cell is coloured.  The
+// blend is renormalised over the coloured corners, walked with dx fastest, then dy, then dz.
+__device__ __forceinline__ unsigned ts_color_at(const float4* __restrict__ color, const TsGrid& g, double px, double py, double pz) {
+  const double qx = (px - g.ox) / g.voxel, qy = (py - g.oy) / g.voxel, qz = (pz - g.oz) / g.voxel;
+  if (!(qx >= 0.0 && qx <= (double)(g.Nx - 1) && qy >= 0.0 && qy <= (double)(g.Ny - 1) && qz >= 0.0 && qz <= (double)(g.Nz - 1))) return 0u;   // NaN too
+  const double bx = fmin(floor(qx), (double)(g.Nx - 2)), by = fmin(floor(qy), (double)(g.Ny - 2)), bz = fmin(floor(qz), (double)(g.Nz - 2));
+  const double rx = qx - bx, ry = qy - by, rz = qz - bz;
+  const int b = ((int)bz * g.Ny + (int)by) * g.Nx + (int)bx, sy = g.Nx, sz = g.Nx * g.Ny;
+  double S = 0.0, Cr = 0.0, Cg = 0.0, Cb = 0.0;
+#pragma unroll
+  for (int d = 0; d < 8; ++d) {
+    const double beta = (((d & 1) ? rx : 1.0 - rx) * ((d & 2) ? ry : 1.0 - ry)) * ((d & 4) ? rz : 1.0 - rz);
+    const float4 c = color[b + (d & 1) + ((d >> 1) & 1) * sy + (d >> 2) * sz];
+    if (c.w > 0.0f) S += beta, Cr += beta * (double)c.x, Cg += beta * (double)c.y, Cb += beta * (double)c.z;
+  }
+  if (!(S > 0.0)) return 0u;
+  const double r8 = fmin(fmax(rint(Cr / S), 0.0), 255.0), g8 = fmin(fmax(rint(Cg / S), 0.0), 255.0), b8 = fmin(fmax(rint(Cb / S), 0.0), 255.0);
+  return (unsigned)r8 | (unsigned)g8 << 8 | (unsigned)b8 << 16 | 1u << 24;
+}
+
+__global__ __launch_bounds__(256) void ts_color_points_kernel(const float4* __restrict__ color, TsGrid g, const double* __restrict__ points, int n,
+                                                              const int32_t* __restrict__ found, uint8_t* __restrict__ rgb_out,
+                                                              uint8_t* __restrict__ valid_out, int32_t* __restrict__ info) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const bool on = found ? found[0] != 0 : true;   // uniform
+  unsigned c = 0u;
+  if (p < n && on) c = ts_color_at(color, g, points[(size_t)p * 3], points[(size_t)p * 3 + 1], points[(size_t)p * 3 + 2]);
+  if (p < n) {
+    rgb_out[(size_t)p * 3] = (uint8_t)(c & 255u), rgb_out[(size_t)p * 3 + 1] = (uint8_t)((c >> 8) & 255u), rgb_out[(size_t)p * 3 + 2] = (uint8_t)((c >> 16) & 255u);
+    valid_out[p] = (uint8_t)(c >> 24);
+  }
+  const int nv = __popcll(__ballot((c >> 24) != 0u));
+  if ((threadIdx.x & 63) == 0 && nv > 0) atomicAdd(&info[1], nv);
+}
+
+// pixels tiled as in ts_raycast_kernel: the 8-corner gathers of neighbouring pixels share lines
+__global__ __launch_bounds__(256) void ts_color_map_kernel(const float4* __restrict__ color, TsGrid g, const float* __restrict__ depth, EsCam cam, int H,
+                                                           int W, const double* __restrict__ c2w, const int32_t* __restrict__ found,
+                                                           uint8_t* __restrict__ rgb_out, int32_t* __restrict__ info) {
+  const int tiles_x = (W + 15) >> 4;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int x = tx * 16 + (wave & 1) * 8 + (lane & 7), y = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
+  const bool in = x < W && y < H;
+  const bool on = found ? found[0] != 0 : true;   // uniform
+  unsigned c = 0u;
+  bool has = false;
+  if (in && on) {
+    const double z = (double)depth[(size_t)y * W + x];
+    if (z > 0.0 && z < INFINITY) {   // false for NaN
+      has = true;
+      const double yn = ((double)y - cam.cy) / cam.fy;
+      const double xn = ((double)x - cam.cx - cam.s * yn) / cam.fx;
+      const double Yx = xn * z, Yy = yn * z;
+      c = ts_color_at(color, g, ((c2w[0] * Yx + c2w[1] * Yy) + c2w[2] * z) + c2w[3], ((c2w[4] * Yx + c2w[5] * Yy) + c2w[6] * z) + c2w[7],
+                      ((c2w[8] * Yx + c2w[9] * Yy) + c2w[10] * z) + c2w[11]);
+    }
+  }
+  if (in) {
+    uint8_t* __restrict__ o = rgb_out + ((size_t)y * W + x) * 3;
+    o[0] = (uint8_t)(c & 255u), o[1] = (uint8_t)((c >> 8) & 255u), o[2] = (uint8_t)((c >> 16) & 255u);
+  }
+  const int nc = __popcll(__ballot((c >> 24) != 0u)), nd = __popcll(__ballot(has));
+  if (lane == 0) {
+    if (nc > 0) atomicAdd(&info[1], nc);
+    if (nd > 0) atomicAdd(&info[2], nd);
   }
 }
 
@@ -522,14 +658,45 @@ namespace {
 
 bool ts_finite(double v) { return fabs(v) < INFINITY; }   // false for NaN
 
-// the volume's arguments -> g; the message of the first rule broken, or NULL
-const char* ts_check_volume(const float* tsdf, const float* weight, int Nx, int Ny, int Nz, const double* origin, double voxel, TsGrid* g) {
+const char* ts_check_dims(int Nx, int Ny, int Nz, double voxel) {
   if (Nx < 2 || Ny < 2 || Nz < 2 || (long long)Nx * Ny * Nz > TS_MAX_VOXELS) return "Nx, Ny and Nz must be >= 2 with at most 2^28 voxels";
   if (!(voxel > 0.0) || !ts_finite(voxel)) return "voxel must be finite and > 0";
+  return nullptr;
+}
+
+// the volume's arguments -> g; the message of the first rule broken, or NULL
+const char* ts_check_volume(const float* tsdf, const float* weight, int Nx, int Ny, int Nz, const double* origin, double voxel, TsGrid* g) {
+  if (const char* msg = ts_check_dims(Nx, Ny, Nz, voxel)) return msg;
   if (!tsdf || !weight || !origin) return "tsdf, weight and origin must not be NULL";
   if (!ts_finite(origin[0]) || !ts_finite(origin[1]) || !ts_finite(origin[2])) return "origin must be finite";
   if (!aligned(tsdf, 4) || !aligned(weight, 4)) return "floats and int32 must be 4-byte and doubles 8-byte aligned";
   *g = {Nx, Ny, Nz, origin[0], origin[1], origin[2], voxel};
+  return nullptr;
+}
+
+// the same for the colour volume, which is read and written 16 bytes at a time
+const char* ts_check_color(const float* color, int Nx, int Ny, int Nz, const double* origin, double voxel, TsGrid* g) {
+  if (const char* msg = ts_check_dims(Nx, Ny, Nz, voxel)) return msg;
+  if (!color || !origin) return "color and origin must not be NULL";
+  if (!ts_finite(origin[0]) || !ts_finite(origin[1]) || !ts_finite(origin[2])) return "origin must be finite";
+  if (!aligned(color, 16)) return "color must be 16-byte aligned";
+  *g = {Nx, Ny, Nz, origin[0], origin[1], origin[2], voxel};
+  return nullptr;
+}
+
+// Ks and obs_weight of a call -> caps; the message of the first rule broken, or NULL
+const char* ts_captures(const double* Ks, const double* obs_weight, int n, TsCaps* caps) {
+  for (int c = 0; c < TS_MAX_CAPS; ++c) {
+    caps->k[c] = {1.0, 1.0, 0.0, 0.0, 0.0};
+    caps->w[c] = 1.0;
+  }
+  for (int c = 0; c < n; ++c) {
+    if (!es_camera(Ks + c * 9, &caps->k[c])) return "the camera matrices must be finite with focal lengths that are not 0";
+    if (obs_weight) {
+      if (!(obs_weight[c] > 0.0) || !ts_finite(obs_weight[c])) return "every obs_weight must be finite and > 0";
+      caps->w[c] = obs_weight[c];
+    }
+  }
   return nullptr;
 }
 
@@ -549,17 +716,7 @@ int cotr_tsdf_integrate(float* tsdf, float* weight, int Nx, int Ny, int Nz, cons
   if (!(max_weight > 0.0)) return arg_fail(fn, "max_weight must be > 0");
   if (!depths || !Ks || !c2w || !info_out) return arg_fail(fn, "depths, Ks, c2w and info_out must not be NULL");
   TsCaps caps;
-  for (int c = 0; c < TS_MAX_CAPS; ++c) {
-    caps.k[c] = {1.0, 1.0, 0.0, 0.0, 0.0};
-    caps.w[c] = 1.0;
-  }
-  for (int c = 0; c < n; ++c) {
-    if (!es_camera(Ks + c * 9, &caps.k[c])) return arg_fail(fn, "the camera matrices must be finite with focal lengths that are not 0");
-    if (obs_weight) {
-      if (!(obs_weight[c] > 0.0) || !ts_finite(obs_weight[c])) return arg_fail(fn, "every obs_weight must be finite and > 0");
-      caps.w[c] = obs_weight[c];
-    }
-  }
+  if (const char* msg = ts_captures(Ks, obs_weight, n, &caps)) return arg_fail(fn, msg);
   if (!aligned(depths, 4) || !aligned(c2w, 8) || !aligned(found, 4) || !aligned(info_out, 4))
     return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -592,6 +749,66 @@ int cotr_tsdf_raycast(const float* tsdf, const float* weight, int Nx, int Ny, in
   const unsigned tiles = (unsigned)((W + 15) / 16) * (unsigned)((H + 15) / 16);
   hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, 1, info_out);
   hipLaunchKernelGGL(ts_raycast_kernel, dim3(tiles), dim3(256), 0, s, tsdf, weight, g, ray, c2w, found, depth_out, normal_out, info_out);
+  return launched();
+}
+
+int cotr_tsdf_color_integrate(float* color, int Nx, int Ny, int Nz, const double* origin, double voxel, double trunc, const float* depths,
+                              const uint8_t* images, int n, int H, int W, const double* Ks, const double* c2w, const int32_t* found,
+                              const double* obs_weight, double max_weight, int32_t* info_out, cotr_stream stream) {
+  static const char* fn = "cotr_tsdf_color_integrate";
+  TsGrid g;
+  if (const char* msg = ts_check_color(color, Nx, Ny, Nz, origin, voxel, &g)) return arg_fail(fn, msg);
+  if (!(trunc > 0.0) || !ts_finite(trunc)) return arg_fail(fn, "trunc must be finite and > 0");
+  if (n < 1 || n > TS_MAX_CAPS) return arg_fail(fn, "n must be in [1, 32]");
+  if (H < 1 || W < 1 || (long long)H * W > MAX_PIXELS) return arg_fail(fn, "H and W must be >= 1 with at most 2^28 pixels");
+  if (!(max_weight > 0.0)) return arg_fail(fn, "max_weight must be > 0");
+  if (!depths || !images || !Ks || !c2w || !info_out) return arg_fail(fn, "depths, images, Ks, c2w and info_out must not be NULL");
+  TsCaps caps;
+  if (const char* msg = ts_captures(Ks, obs_weight, n, &caps)) return arg_fail(fn, msg);
+  if (!aligned(depths, 4) || !aligned(c2w, 8) || !aligned(found, 4) || !aligned(info_out, 4))
+    return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int total = Nx * Ny * Nz, per_group = 256 * TS_ROWS;
+  hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, n, info_out);
+  hipLaunchKernelGGL(ts_color_integrate_kernel, dim3((unsigned)((total + per_group - 1) / per_group)), dim3(256), 0, s, reinterpret_cast<float4*>(color), g,
+                     trunc, depths, images, n, H, W, caps, c2w, found, max_weight, info_out);
+  return launched();
+}
+
+int cotr_tsdf_color_points(const float* color, int Nx, int Ny, int Nz, const double* origin, double voxel, const double* points, int n,
+                           const int32_t* found, uint8_t* rgb_out, uint8_t* valid_out, int32_t* info_out, cotr_stream stream) {
+  static const char* fn = "cotr_tsdf_color_points";
+  TsGrid g;
+  if (const char* msg = ts_check_color(color, Nx, Ny, Nz, origin, voxel, &g)) return arg_fail(fn, msg);
+  if (n < 0 || n > TS_MAX_POINTS) return arg_fail(fn, "n must be in [0, 2^28]");
+  if ((n > 0 && (!points || !rgb_out || !valid_out)) || !info_out)
+    return arg_fail(fn, "points, rgb_out, valid_out (with n above 0) and info_out must not be NULL");
+  if (!aligned(points, 8) || !aligned(found, 4) || !aligned(info_out, 4))
+    return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, 1, info_out);
+  if (n > 0)
+    hipLaunchKernelGGL(ts_color_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(color), g, points, n, found,
+                       rgb_out, valid_out, info_out);
+  return launched();
+}
+
+int cotr_tsdf_color_map(const float* color, int Nx, int Ny, int Nz, const double* origin, double voxel, const float* depth, int H, int W,
+                        const double* K, const double* c2w, const int32_t* found, uint8_t* rgb_out, int32_t* info_out, cotr_stream stream) {
+  static const char* fn = "cotr_tsdf_color_map";
+  TsGrid g;
+  if (const char* msg = ts_check_color(color, Nx, Ny, Nz, origin, voxel, &g)) return arg_fail(fn, msg);
+  if (H < 1 || W < 1 || (long long)H * W > MAX_PIXELS) return arg_fail(fn, "H and W must be >= 1 with at most 2^28 pixels");
+  if (!depth || !K || !c2w || !rgb_out || !info_out) return arg_fail(fn, "depth, K, c2w, rgb_out and info_out must not be NULL");
+  EsCam cam;
+  if (!es_camera(K, &cam)) return arg_fail(fn, "the camera matrix must be finite with focal lengths that are not 0");
+  if (!aligned(depth, 4) || !aligned(c2w, 8) || !aligned(found, 4) || !aligned(info_out, 4))
+    return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned tiles = (unsigned)((W + 15) / 16) * (unsigned)((H + 15) / 16);
+  hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, 1, info_out);
+  hipLaunchKernelGGL(ts_color_map_kernel, dim3(tiles), dim3(256), 0, s, reinterpret_cast<const float4*>(color), g, depth, cam, H, W, c2w, found, rgb_out,
+                     info_out);
   return launched();
 }
 

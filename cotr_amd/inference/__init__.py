@@ -44,7 +44,8 @@ from .pnp import lift_pixels, localize, ransac_pnp, rodrigues, solve_pnp_ransac
 from .rigid3d import ransac_rigid3d, register_captures, register_captures_tensors, register_points
 from .structure import reconstruct_tensors, stack_views, triangulate_points, triangulate_points_tensors, triangulate_views
 from .triangulate import delaunay, triangulate_corr
-from .tsdf import TsdfVolume, extract_mesh, fuse_captures, integrate_depths, raycast_volume, track_capture, write_ply
+from .tsdf import (TsdfVolume, color_depth_map, extract_mesh, fuse_captures, integrate_colors, integrate_depths, raycast_volume, sample_colors,
+                   track_capture, write_ply)
 from .warp import get_perspective_transform, paste_by_corners, warp_by_corr, warp_by_map, warp_perspective
 from .zoom_engine import FasterSparseEngine, RefineResult, SparseEngine, ZoomEngine, patch_boxes
 
@@ -58,4 +59,5 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'bundle_adjust', 'bundle_adjust_tensors',
            'ransac_rigid3d', 'register_points', 'register_captures', 'register_captures_tensors',
            'icp_depth', 'refine_registration',
-           'TsdfVolume', 'integrate_depths', 'fuse_captures', 'raycast_volume', 'track_capture', 'extract_mesh', 'write_ply']
+           'TsdfVolume', 'integrate_depths', 'fuse_captures', 'raycast_volume', 'track_capture', 'extract_mesh', 'write_ply',
+           'integrate_colors', 'sample_colors', 'color_depth_map']

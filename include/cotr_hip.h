@@ -749,6 +749,54 @@ int cotr_tsdf_raycast(const float* tsdf, const float* weight, int Nx, int Ny, in
                       const double* K, const double* c2w, const int32_t* found, int H, int W, double near, double far,
                       double step, float* depth_out, double* normal_out, int32_t* info_out, cotr_stream stream);
 
+/* ---- the colour of a TSDF volume: fuse images, colour points and depth maps (cotr_amd/csrc/tsdf.hip) ------
+ * A third array beside tsdf and weight that averages the captures' 8-bit images near the surface, and its colour at points
+ * (the vertices of cotr_tsdf_mesh) and at the pixels of a depth map (the map of cotr_tsdf_raycast).  The rules are the
+ * library's own.
+ *
+ * The colour volume: color float32 [Nz][Ny][Nx][4] DEVICE = (r, g, b, colour weight), x fastest, owned by the caller, 16-byte
+ *   aligned, all 0 when fresh; colours on the images' scale 0 .. 255.  Nx, Ny, Nz, origin, voxel: those of
+ *   cotr_tsdf_integrate.  Storage is float32; every intermediate below is float64, and no product is contracted into an FMA.
+ * cotr_tsdf_color_integrate: depths, n, H, W, Ks, c2w, found, obs_weight, trunc, max_weight as in cotr_tsdf_integrate; images
+ *   uint8 [n][H][W][3] DEVICE.  tsdf and weight are neither read nor written: the depth call and the colour call may come in
+ *   either order.  Voxel (i, j, k), capture c: Y, (u, v), the pixel (rint u, rint v) and its depth z by the expressions of
+ *   cotr_tsdf_integrate in their order; skipped where that call skips before sdf.  sdf = z - Y_z; skipped when sdf < -trunc or
+ *   sdf > trunc: only the band around the surface takes a colour, not the free space in front of it.  p: the three bytes of
+ *   that pixel as doubles, Wc the stored colour weight:
+ *   each channel <- float32((double(channel) double(Wc) + p w) / (double(Wc) + w)), then
+ *   Wc <- float32(min(double(Wc) + w, max_weight)).
+ *   One thread owns a voxel and takes the captures in the order 0 .. n-1: the same bits as n calls of one capture each.
+ *   -> info_out int32 [n][4] = {integrated (0 when found skipped it), voxels coloured, voxels whose pixel held a valid
+ *   depth (the third column of cotr_tsdf_integrate for the same capture), 0}.
+ * The colour at a world point p: q_a = (p_a - origin_a) / voxel; p is in the box iff 0 <= q_a <= N_a - 1 on each axis (false
+ *   for NaN; the faces belong to it, unlike a raycast sample, so that a mesh vertex on the last voxel layer has a colour).
+ *   b_a = min(floor(q_a), N_a - 2), r_a = q_a - b_a; the corner b + (dx, dy, dz) has beta = (wx wy) wz with w = r for d = 1
+ *   and 1 - r for d = 0, and counts iff its colour weight is > 0.  Over the corners that count, dx fastest, then dy, then dz,
+ *   S and C_ch are the running sums of beta and beta c_ch from 0.  The point is valid iff it is in the box and S > 0; its
+ *   channel is rint(C_ch / S) (ties to even) clamped to 0 .. 255: renormalised over the coloured corners, so that colour
+ *   reaches the rim of what the cameras saw.
+ * cotr_tsdf_color_points: points float64 [n][3] DEVICE in the world frame, 0 <= n <= 2^28 (points, rgb_out and valid_out may
+ *   be NULL with n = 0); found int32 DEVICE [1] or NULL: found[0] == 0: every output is 0.  -> rgb_out uint8 [n][3] ((0, 0,
+ *   0) at an invalid point), valid_out uint8 [n], info_out int32 [4] = {ok (found), valid points, 0, 0}.
+ * cotr_tsdf_color_map: depth float32 [H][W] DEVICE (as cotr_tsdf_raycast writes it), K HOST, c2w [16] float64 DEVICE, found
+ *   as above; 1 <= H, W and H W <= 2^28.  Pixel (x, y) with a depth z that is finite and > 0: yn = (y - cy) / fy, xn = (x - cx -
+ *   skew yn) / fx (the raycast's ray), Y = (xn z, yn z, z), p_a = ((R_a0 Y_x + R_a1 Y_y) + R_a2 Y_z) + t_a, and the colour at
+ *   p by the rule above.  -> rgb_out uint8 [H][W][3], (0, 0, 0) at every other pixel and where p is not valid; info_out int32
+ *   [4] = {ok (found), pixels coloured, pixels with a depth, 0}.
+ * Stream-ordered, 2 launches each whatever the data (1 for cotr_tsdf_color_points with n = 0), no scratch, no host waits and
+ * no allocation (capturable); integer atomics only, and only for info_out: the same input gives the same bits.  Bad
+ * arguments are checked before any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_tsdf_color_integrate(float* color, int Nx, int Ny, int Nz, const double* origin, double voxel, double trunc,
+                              const float* depths, const uint8_t* images, int n, int H, int W, const double* Ks,
+                              const double* c2w, const int32_t* found, const double* obs_weight, double max_weight,
+                              int32_t* info_out, cotr_stream stream);
+int cotr_tsdf_color_points(const float* color, int Nx, int Ny, int Nz, const double* origin, double voxel,
+                           const double* points, int n, const int32_t* found, uint8_t* rgb_out, uint8_t* valid_out,
+                           int32_t* info_out, cotr_stream stream);
+int cotr_tsdf_color_map(const float* color, int Nx, int Ny, int Nz, const double* origin, double voxel, const float* depth,
+                        int H, int W, const double* K, const double* c2w, const int32_t* found, uint8_t* rgb_out,
+                        int32_t* info_out, cotr_stream stream);
+
 /* ---- the surface of a TSDF volume as an indexed triangle mesh (cotr_amd/csrc/tsdf.hip; rules in DESIGN.md 3h-12) ----------
  * Marching tetrahedra on the Kuhn split of every cell: no case table to trust, no ambiguous face, closed and consistently
  * oriented meshes by construction, about twice the triangles of marching cubes.  The rule is the library's own.
