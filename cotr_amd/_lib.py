@@ -164,6 +164,11 @@ _PROTOS = {
     'cotr_icp_depth': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_int,
                                       ctypes.c_int, ctypes.POINTER(ctypes.c_double)] + [ctypes.c_void_p] * 5 + [ctypes.c_double] * 4 +
                        [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 9 + [ctypes.c_size_t, ctypes.c_void_p]),
+    'cotr_icp_maps': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_double,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'cotr_icp_multiview': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p] +
+                           [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 8),
     'cotr_tsdf_integrate': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                            ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),

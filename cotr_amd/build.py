@@ -28,21 +28,21 @@ GEN_DIR = os.path.join(CSRC, 'experimental', 'gen')
 # generated name -> (product source, patch)
 GENERATED = {**{f: (f, f + '.patch') for f in FORKED}, 'common_exp.h': ('common.h', 'common_exp.h.patch')}
 SOURCES = ['gemm.hip', 'gemm_big.hip', 'gemm_wp.hip', 'bottleneck.hip', 'attention.hip', 'pointwise.hip', 'ln_reduce1.hip', 'stem_pool.hip', 'crop_resize.hip',
-           'dense_post.hip', 'ffn.hip', 'ffn_pipe.hip', 'ffn_rows.hip', 'att_rows.hip', 'conv23.hip', 'conv23m.hip', 'expand.hip', 'train.hip', 'attention_train.hip', 'pairs.hip', 'handleless.hip', 'triangulate.hip', 'delaunay.hip', 'guided.hip', 'homography.hip', 'essential.hip', 'pnp.hip', 'rigid3d.hip', 'icp.hip', 'tsdf.hip', 'structure.hip', 'bundle.hip', 'warp.hip', 'reproject.hip', 'overlap.hip', 'rotate.hip', 'api.hip']
+           'dense_post.hip', 'ffn.hip', 'ffn_pipe.hip', 'ffn_rows.hip', 'att_rows.hip', 'conv23.hip', 'conv23m.hip', 'expand.hip', 'train.hip', 'attention_train.hip', 'pairs.hip', 'handleless.hip', 'triangulate.hip', 'delaunay.hip', 'guided.hip', 'homography.hip', 'essential.hip', 'pnp.hip', 'rigid3d.hip', 'icp.hip', 'icp_multi.hip', 'tsdf.hip', 'structure.hip', 'bundle.hip', 'warp.hip', 'reproject.hip', 'overlap.hip', 'rotate.hip', 'api.hip']
 EXP_SOURCES = [os.path.join('experimental', 'head.hip'), os.path.join('experimental', 'gemm_ln.hip'), os.path.join('experimental', 'gemm_pp.hip'),
                os.path.join('experimental', 'gemm_h2.hip'), os.path.join('experimental', 'attention_h2.hip'), os.path.join('experimental', 'gemm_h2r.hip'),
                os.path.join('experimental', 'linear_rows.hip')]
 # Pillow-exact resamples and the torch-CPU-exact cycle map (8-bit, float and double code whose products must not be contracted into
 # FMAs behind the source's back; the FMAs that belong there are explicit)
 EXTRA_FLAGS = {'crop_resize.hip': ['-ffp-contract=off'], 'dense_post.hip': ['-ffp-contract=off'],
-               'triangulate.hip': ['-ffp-contract=off'], 'delaunay.hip': ['-ffp-contract=off'], 'guided.hip': ['-ffp-contract=off'], 'homography.hip': ['-ffp-contract=off'], 'essential.hip': ['-ffp-contract=off'], 'pnp.hip': ['-ffp-contract=off'], 'rigid3d.hip': ['-ffp-contract=off'], 'icp.hip': ['-ffp-contract=off'], 'tsdf.hip': ['-ffp-contract=off'], 'structure.hip': ['-ffp-contract=off'], 'bundle.hip': ['-ffp-contract=off'], 'warp.hip': ['-ffp-contract=off'],
+               'triangulate.hip': ['-ffp-contract=off'], 'delaunay.hip': ['-ffp-contract=off'], 'guided.hip': ['-ffp-contract=off'], 'homography.hip': ['-ffp-contract=off'], 'essential.hip': ['-ffp-contract=off'], 'pnp.hip': ['-ffp-contract=off'], 'rigid3d.hip': ['-ffp-contract=off'], 'icp.hip': ['-ffp-contract=off'], 'icp_multi.hip': ['-ffp-contract=off'], 'tsdf.hip': ['-ffp-contract=off'], 'structure.hip': ['-ffp-contract=off'], 'bundle.hip': ['-ffp-contract=off'], 'warp.hip': ['-ffp-contract=off'],
                'reproject.hip': ['-ffp-contract=off'], 'overlap.hip': ['-ffp-contract=off'], 'rotate.hip': ['-ffp-contract=off'],
                # att_rows.hip: matrix-instruction results in VGPRs, not AccVGPRs - its softmax VALU sits between the matrix instructions of ONE
                # wavefront per SIMD, and any AccVGPR access (v_accvgpr_read / write) waits for the matrix instruction in flight: with the scores in
                # AccVGPRs the softmax of a key block ran entirely BEHIND its 64 matrix instructions (K/V phase 205 k cycles against 131 k of matrix
                # work, whatever the interleaving; profiles/r5_att_rows_probe.txt)
                'att_rows.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}
-HEADERS = ['common.h', 'train.h', 'pillow_taps.h', 'warp_taps.h', 'camera.h', 'handleless.h', 'pinhole.h', 'ransac.h', 'refit.h', 'rodrigues.h', 'scan.h', 'view_table.h', 'gemm_tuned.inc', 'enc_split.inc', os.path.join('..', '..', 'include', 'cotr_hip.h')]
+HEADERS = ['common.h', 'train.h', 'pillow_taps.h', 'warp_taps.h', 'camera.h', 'handleless.h', 'pinhole.h', 'icp_maps.h', 'ransac.h', 'refit.h', 'rodrigues.h', 'scan.h', 'view_table.h', 'gemm_tuned.inc', 'enc_split.inc', os.path.join('..', '..', 'include', 'cotr_hip.h')]
 EXP_HEADERS = [os.path.join('experimental', f) for f in ['coop_tail.h', 'experimental.h', 'api_exp.inc', 'gemm_h2.h']] + \
               [os.path.join('experimental', 'patches', pt) for _, pt in GENERATED.values()]
 # code-object v5: loadable by the ROCm 7.0 runtime torch bundles as well as by ROCm 7.2's

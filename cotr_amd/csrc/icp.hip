@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "handleless.h"
+#include "icp_maps.h"
 #include "pinhole.h"
 #include "ransac.h"
 #include "refit.h"
@@ -57,17 +58,7 @@ struct IcPoints {
   double max_d2, normal_cos;
 };
 
-// ---- the maps -------------------------------------------------------------------------------------------------------------
-// the vertex of the pixel centre (x, y): cotr_lift_pixels' rule without c2w; false where the depth is not finite and > 0
-__device__ __forceinline__ bool ic_vertex(const float* __restrict__ depth, int W, const EsCam& k, int x, int y, double* v) {
-  const double z = (double)depth[(size_t)y * W + x];
-  if (!(z > 0.0 && z < INFINITY)) return false;
-  const double yn = ((double)y - k.cy) / k.fy;
-  const double xn = ((double)x - k.cx - k.s * yn) / k.fx;
-  v[0] = xn * z, v[1] = yn * z, v[2] = z;
-  return true;
-}
-
+// ---- the maps (the pixel rule: icp_maps.h) --------------------------------------------------------------------------------
 // One thread per pixel -> V[H W][3], N[H W][3] (NaN where invalid; the same to maps_out[H W][6] when given), the count of
 // valid normals.  which = 1 (B): only the source pixels are counted, those with x % stride == 0 and y % stride == 0 that
 // src_mask admits; source pixel j gets smask[j] = counted and assoc[j] = -1.
@@ -80,31 +71,8 @@ __global__ __launch_bounds__(256) void ic_map_kernel(const float* __restrict__ d
   bool counted = false;
   if (in) {
     const int y = p / W, x = p - y * W;
-    double v[3], n[3] = {NAN, NAN, NAN};
-    bool ok = ic_vertex(depth, W, k, x, y, v);
-    if (!ok) v[0] = v[1] = v[2] = NAN;
-    if (ok && x > 0 && x < W - 1 && y > 0 && y < H - 1) {
-      double l[3], r[3], u[3], d[3];
-      ok = ic_vertex(depth, W, k, x - 1, y, l) && ic_vertex(depth, W, k, x + 1, y, r) && ic_vertex(depth, W, k, x, y - 1, u) &&
-           ic_vertex(depth, W, k, x, y + 1, d);
-      if (ok) {
-        const double lim = edge * v[2];
-        ok = fabs(l[2] - v[2]) <= lim && fabs(r[2] - v[2]) <= lim && fabs(u[2] - v[2]) <= lim && fabs(d[2] - v[2]) <= lim;
-      }
-      if (ok) {
-        const double ax = r[0] - l[0], ay = r[1] - l[1], az = r[2] - l[2];
-        const double bx = d[0] - u[0], by = d[1] - u[1], bz = d[2] - u[2];
-        const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
-        const double norm = sqrt((cx * cx + cy * cy) + cz * cz);
-        ok = norm > 0.0;   // false for NaN
-        if (ok) {
-          n[0] = cx / norm, n[1] = cy / norm, n[2] = cz / norm;
-          if ((n[0] * v[0] + n[1] * v[1]) + n[2] * v[2] > 0.0) n[0] = -n[0], n[1] = -n[1], n[2] = -n[2];
-        }
-      }
-    } else {
-      ok = false;
-    }
+    double v[3], n[3];
+    const bool ok = ic_pixel(depth, H, W, k, edge, x, y, v, n);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       V[(size_t)p * 3 + c] = v[c];

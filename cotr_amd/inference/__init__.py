@@ -30,7 +30,9 @@ orientation of 3D-3D correspondences (3-point RANSAC on Horn's closed form, a cl
 ``with_scale=True``), ``ransac_rigid3d`` the same with device tensors, and ``register_captures`` / ``ZoomEngine.register`` the
 metric pose of one RGB-D capture against another from both depth maps.  ``icp_depth`` refines a rigid motion on every pixel of two
 depth maps (projective association, point-to-plane Gauss-Newton), ``refine_registration`` the same on two captures, and
-``register_captures(..., icp_iters=10)`` runs it behind the sparse registration.  ``TsdfVolume`` is a truncated signed distance volume on
+``register_captures(..., icp_iters=10)`` runs it behind the sparse registration.  ``icp_multiview`` refines the poses of 2 to 32 depth maps
+together on every pixel of every overlapping ordered pair (multi-way ICP, one normal system per step), ``vertex_normal_maps`` makes the
+maps it reads, ``refine_poses`` is the same on captures, and ``ZoomEngine.fuse(..., joint_iters=4)`` runs it before the fusion.  ``TsdfVolume`` is a truncated signed distance volume on
 the device, ``integrate_depths`` averages posed depth maps into it and ``fuse_captures`` posed captures, ``raycast_volume`` is the depth
 map (and normals) of its surface seen from a pose, ``track_capture`` ``icp_depth`` against such a map (frame-to-model tracking),
 ``extract_mesh`` its surface as an indexed triangle mesh (``write_ply`` puts it into a file), and ``ZoomEngine.fuse`` registers a list
@@ -40,6 +42,7 @@ from .essential import find_essential_mat, ransac_essential, recover_pose, refin
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .homography import find_homography, paste_by_homography, ransac_homography
 from .icp import icp_depth, refine_registration
+from .icp_multi import icp_multiview, refine_poses, vertex_normal_maps
 from .pnp import lift_pixels, localize, ransac_pnp, rodrigues, solve_pnp_ransac
 from .rigid3d import ransac_rigid3d, register_captures, register_captures_tensors, register_points
 from .structure import reconstruct_tensors, stack_views, triangulate_points, triangulate_points_tensors, triangulate_views
@@ -58,6 +61,6 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'triangulate_views', 'triangulate_points', 'triangulate_points_tensors', 'stack_views', 'reconstruct_tensors',
            'bundle_adjust', 'bundle_adjust_tensors',
            'ransac_rigid3d', 'register_points', 'register_captures', 'register_captures_tensors',
-           'icp_depth', 'refine_registration',
+           'icp_depth', 'refine_registration', 'vertex_normal_maps', 'icp_multiview', 'refine_poses',
            'TsdfVolume', 'integrate_depths', 'fuse_captures', 'raycast_volume', 'track_capture', 'extract_mesh', 'write_ply',
            'integrate_colors', 'sample_colors', 'color_depth_map']

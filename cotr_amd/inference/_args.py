@@ -1,5 +1,5 @@
 """The argument rules and allocations every geometry wrapper of this package shares (guided, homography, essential, pnp,
-structure, bundle, rigid3d, icp; triangulate and warp for the scratch query and the CPU-tensor refusal): each rule is stated
+structure, bundle, rigid3d, icp, icp_multi, tsdf; triangulate and warp for the scratch query and the CPU-tensor refusal): each rule is stated
 here once, and a caller passes the words its own message differs by, so every message reads as that wrapper's.
 
 The import rule (tests/test_wrapper_imports_cpu.py): a module of this package imports names that start with an underscore
@@ -139,6 +139,28 @@ def pose_matrix(c2w):
 def pose_on(m, device):
     """what ``pose_matrix`` returned -> the [16] device tensor the kernels read"""
     return None if m is None else on(m.reshape(16), device)
+
+
+def c2w_rows(c2ws, n):
+    """[n,4,4] camera-to-world: a device tensor as it is, anything else through ``pose_matrix`` -> float64 [n,16], where it was"""
+    if torch.is_tensor(c2ws) and c2ws.is_cuda:
+        if c2ws.dtype != F64 or c2ws.numel() != n * 16:
+            raise ValueError(f'c2ws on the device must be float64 [{n}, 4, 4], got {c2ws.dtype} {list(c2ws.shape)}')
+        return c2ws.reshape(n, 16)
+    if len(c2ws) != n:
+        raise ValueError(f'c2ws must hold one [4, 4] matrix for each of the {n} depth maps, got {len(c2ws)}')
+    return torch.from_numpy(np.stack([pose_matrix(m) for m in c2ws]).reshape(n, 16))
+
+
+def cameras(Ks, n):
+    """[n,3,3] camera matrices, or one [3,3] for every map -> (one ``camera`` per map, the [n][9] host doubles a call takes)"""
+    k = np.asarray(Ks.cpu() if torch.is_tensor(Ks) else Ks, dtype=np.float64)
+    if k.shape == (3, 3):
+        k = np.broadcast_to(k, (n, 3, 3))
+    if k.shape != (n, 3, 3):
+        raise ValueError(f'Ks must be [{n}, 3, 3] or [3, 3], got shape {k.shape}')
+    ks = [camera(m, 'Ks') for m in k]
+    return ks, (ctypes.c_double * (9 * n))(*[v for m in ks for v in m])
 
 
 def check_depth(depth):

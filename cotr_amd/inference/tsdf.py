@@ -92,17 +92,6 @@ def _check_color_volume(volume):
         raise ValueError('volume holds no colour: make it with TsdfVolume(..., color=True)')
 
 
-def _pose_rows(c2ws, n):
-    """[n,4,4] camera-to-world: a device tensor as it is, anything else through ``_args.pose_matrix`` -> float64 [n,16], where it was"""
-    if torch.is_tensor(c2ws) and c2ws.is_cuda:
-        if c2ws.dtype != F64 or c2ws.numel() != n * 16:
-            raise ValueError(f'c2ws on the device must be float64 [{n}, 4, 4], got {c2ws.dtype} {list(c2ws.shape)}')
-        return c2ws.reshape(n, 16)
-    if len(c2ws) != n:
-        raise ValueError(f'c2ws must hold one [4, 4] matrix for each of the {n} depth maps, got {len(c2ws)}')
-    return torch.from_numpy(np.stack([_args.pose_matrix(m) for m in c2ws]).reshape(n, 16))
-
-
 def _capture_args(volume, depths, Ks, c2ws, found, weights, images=None):
     """the argument rules of ``integrate_depths`` (and of ``integrate_colors``, with ``images``) -> (depths, the cameras, the pose
     rows, found, weights[, images]) with every tensor on the volume's device"""
@@ -118,7 +107,7 @@ def _capture_args(volume, depths, Ks, c2ws, found, weights, images=None):
     if k.shape != (n, 3, 3):
         raise ValueError(f'Ks must be [{n}, 3, 3] or [3, 3], got shape {k.shape}')
     ks = [_args.camera(m, 'Ks') for m in k]
-    rows = _pose_rows(c2ws, n)
+    rows = _args.c2w_rows(c2ws, n)
     if weights is not None:
         weights = [float(v) for v in np.asarray(weights, dtype=np.float64).reshape(-1)]
         if len(weights) != n:

@@ -754,15 +754,27 @@ class ZoomEngine:
         c2w_b, mask = register_captures(corrs[:, :2], corrs[:, 2:], cap_a, cap_b, **ransac_kw)
         return c2w_b, corrs, mask
 
-    def fuse(self, caps, volume, icp_iters=10, **register_kw):
+    def fuse(self, caps, volume, icp_iters=10, joint_iters=0, **register_kw):
         """A small reconstruction: the RGB-D captures ``caps[1:]`` (``cotr_amd.data.Capture``; their c2w is not read) are placed
         against the posed capture ``caps[0]`` by ``register`` (``register_kw``, with the dense refinement of ``icp_iters`` steps),
         and every capture that was placed is averaged into the ``TsdfVolume`` ``volume`` by ``fuse_captures``, in list order ->
-        (volume, poses: one c2w float64 [4,4] per capture, None where none was found, found: one bool per capture)."""
+        (volume, poses: one c2w float64 [4,4] per capture, None where none was found, found: one bool per capture).
+        ``joint_iters`` > 0: before the fusion the placed captures are refined together by ``refine_poses`` (that many steps
+        of multi-way ICP over every ordered pair, ``caps[0]`` fixed, ``max_dist`` = ``icp_max_dist`` or the threshold of
+        ``register_kw``); the captures must then share one depth-map size (ValueError).  0: no joint step, and no launch of it."""
         from .tsdf import fuse_captures
         caps = list(caps)
+        if joint_iters and len({tuple(cap.depth.shape) for cap in caps}) != 1:
+            raise ValueError(f'joint_iters needs captures of one depth-map size, got {sorted({tuple(cap.depth.shape) for cap in caps})}')
         poses = [np.asarray(caps[0].c2w, dtype=np.float64)] + [self.register(caps[0], cap, icp_iters=icp_iters, **register_kw)[0] for cap in caps[1:]]
         found = [p is not None for p in poses]
+        placed = [i for i, p in enumerate(poses) if p is not None]
+        if joint_iters and len(placed) >= 2:
+            from .icp_multi import refine_poses
+            max_dist = register_kw.get('icp_max_dist') or register_kw.get('threshold', 0.05)
+            joint, _ = refine_poses([caps[i] for i in placed], [poses[i] for i in placed], fixed=(0,), max_dist=max_dist, iters=joint_iters)
+            for i, p in zip(placed, joint):
+                poses[i] = p
         fuse_captures([cap._replace(c2w=p) for cap, p in zip(caps, poses) if p is not None], volume)
         return volume, poses, found
 

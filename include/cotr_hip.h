@@ -702,6 +702,68 @@ int cotr_icp_depth(const float* depth_a, int Ha, int Wa, const double* K_a, cons
                    int32_t* assoc_out, double* maps_a_out, double* maps_b_out, void* scratch, size_t scratch_bytes,
                    cotr_stream stream);
 
+/* ---- joint registration of n depth maps: multi-way point-to-plane ICP (cotr_amd/csrc/icp_multi.hip) -------
+ * All free camera-to-world poses of n depth maps of one size are refined together, on every ordered pair (edge) of a graph of
+ * views, with one normal system per step.  The rules are the library's own.  Neither call takes a scratch: all device state
+ * lives in the outputs below.
+ *
+ * cotr_icp_maps: depths [n][H][W] float32 DEVICE; Ks HOST [n][9], each as K in cotr_lift_pixels; edge as in cotr_icp_depth.
+ *   -> maps_out [n][H][W][6] float64 DEVICE: the vertex, then the normal, of every pixel by the rule of cotr_icp_depth (its
+ *   maps_a_out, bit for bit), NaN where there is none; info_out [n][4] int32 = {pixels with a vertex, pixels with a normal,
+ *   0, 0}.  1 <= n <= 32, 3 <= H, W, n H W <= 2^28, edge > 0 finite.  2 launches: a prologue, one thread a pixel.
+ *
+ * cotr_icp_multiview: maps [n][H][W][6] float64 DEVICE, what cotr_icp_maps writes; Ks HOST [n][9]; c2w0 [n][16] float64
+ *   DEVICE, the start, row-major [R | t] camera-to-world (c2w_out may be c2w0); edges [E][2] int32 DEVICE = (a, b): A = view a
+ *   is the target, B = view b the source; fixed_mask: bit v set, view v does not move; centre HOST [3], the point c the
+ *   twists turn about (the mean of the camera centres keeps the system well scaled); found int32 DEVICE [n] or NULL.
+ *   An edge is dead when an index is outside [0, n), a == b, found is 0 for either view, or an earlier edge names the same
+ *   ordered pair.  A dead edge has no pairs, its rows of edge_out are 0 and its rows of assoc_out -1.
+ *   One evaluation of a live edge at the working poses: R_ab[i][j] = (R_a[0][i] R_b[0][j] + R_a[1][i] R_b[1][j]) + R_a[2][i]
+ *   R_b[2][j], d = t_b - t_a, t_ab[i] = (R_a[0][i] d[0] + R_a[1][i] d[1]) + R_a[2][i] d[2]; then the gates of cotr_icp_depth
+ *   at R = R_ab, t = t_ab, in its order and with its arithmetic, through K_a, over the source pixels x % stride == 0 and y %
+ *   stride == 0 of B in row-major order (usable: B has a normal there), and its residual r = n_a . (Y - V_a).  A pose is
+ *   perturbed by a world-frame twist about c: R <- exp([w]x) R, t <- exp([w]x) (t - c) + c + dt.  With N[i] = (R_a[i][0]
+ *   n_x + R_a[i][1] n_y) + R_a[i][2] n_z and Yc[i] = (((R_a[i][0] Y_x + R_a[i][1] Y_y) + R_a[i][2] Y_z) + t_a[i]) - c[i], the
+ *   Jacobian row of r over (w, dt) of view b is J = (Yc x N, N) = (Yc_1 N_2 - Yc_2 N_1, Yc_2 N_0 - Yc_0 N_2, Yc_0 N_1 - Yc_1
+ *   N_0, N), and over those of view a it is -J.  29 sums as in cotr_icp_depth: the upper triangle of J^T J row-major (21),
+ *   J^T r (6), sum r^2, the pairs.
+ *   The source rows are cut into 8 bands, band s = rows [floor(s Hs / 8), floor((s + 1) Hs / 8)) of the Hs = ceil(H / stride)
+ *   source rows; one workgroup per (edge, band) adds its band's terms in a fixed order (per thread in row-major order, per
+ *   wavefront, across wavefronts) -> edge_out[e][s][0..28], [29] = the band's usable source pixels, [30], [31] = 0.
+ *   The step: a sum of an edge is that of its 8 bands in band order.  An edge with fewer than 6 pairs is dropped for the
+ *   step; the others are kept.  A view is free when it is not in fixed_mask, is found and has a kept edge; the free views
+ *   take slots in index order, 6 unknowns (w, dt) each.  The system: block (v, v) = the sum of J^T J over the kept edges that
+ *   touch v, the other view w ascending and (v, w) before (w, v); block (a, b) = -(J^T J of (lo, hi) + J^T J of (hi, lo)), lo
+ *   < hi the two views; the gradient of v: over w ascending, - J^T r of (v, w), then + J^T r of (w, v).  Cholesky by columns
+ *   on the packed lower triangle (at most 186 unknowns) fails when a pivot is not finite or <= pivot_tol times that entry's
+ *   original diagonal value; x solves system x = gradient, and every free view takes the twist (w, dt) = -x of its slot.
+ *   The chain stops, and the poses stay, with stop reason 1: no free view or fewer than 6 pairs over the kept edges; 3: sum
+ *   r^2 or an entry of the assembled system is not finite; 2: Cholesky failed.  The pivot rule detects a structurally
+ *   singular system only (a component of views tied to each other and to no fixed view: ratio <= 2e-16); a geometric slide,
+ *   such as views of two planes alone, passes it: the pairwise call has the eigenvalue test for that, and the per-edge sums of
+ *   edge_out are there so that a caller can examine an edge's normal matrix.  Otherwise every step is taken.  iters steps at
+ *   most, iters + 1 evaluations; the last only evaluates.
+ *   -> c2w_out [n][16] float64: the working poses, returned; info_out [8] int32 = {ok: ran all its evaluations, steps taken,
+ *   pairs over the kept edges at the returned poses, stop reason (0: ran all), live edges, edges kept at the last
+ *   evaluation, free views, 0}; view_info_out [n][4] int32 = {free, pairs over its kept edges, kept edges, 0}; stats_out [2]
+ *   float64 = {sum r^2 over the kept edges in edge order, sqrt(sum r^2 / pairs)}; edge_out [E][8][32] float64 (above), of
+ *   the evaluation at the returned poses.  Optional DEVICE outputs (NULL: not written): hist_out [iters + 1][4] float64 =
+ *   {sum r^2, pairs, smallest pivot over its original diagonal value (0 where no step was solved for), 0} of every
+ *   evaluation, rows after a stop 0; assoc_out [E][n_src] int32, n_src = ceil(H / stride) ceil(W / stride): for the
+ *   evaluation at the returned poses, the pixel of A paired with each source pixel, or -1.
+ *   2 <= n <= 32, 3 <= H, W, n H W <= 2^28, 1 <= E <= n (n - 1), fixed_mask with a bit below n, 0 <= iters <= 64, 1 <= stride
+ *   <= 64, max_dist > 0 finite, -1 <= normal_cos <= 1, 0 < pivot_tol < 1, centre finite.
+ * Stream-ordered, 1 + 2 (iters + 1) launches whatever the data (a prologue, iters + 1 pairs of edge and solve kernel), no host
+ * waits and no allocation (capturable); integer atomics only, sums in a fixed order: the same input gives the same bits.
+ * Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_icp_maps(const float* depths, int n, int H, int W, const double* Ks, double edge, double* maps_out,
+                  int32_t* info_out, cotr_stream stream);
+int cotr_icp_multiview(const double* maps, int n, int H, int W, const double* Ks, const double* c2w0, const int32_t* edges,
+                       int E, uint32_t fixed_mask, const double* centre, const int32_t* found, double max_dist,
+                       double normal_cos, double pivot_tol, int iters, int stride, double* c2w_out, int32_t* info_out,
+                       int32_t* view_info_out, double* stats_out, double* edge_out, double* hist_out, int32_t* assoc_out,
+                       cotr_stream stream);
+
 /* ---- a fused model of posed depth maps: TSDF integration and raycast (cotr_amd/csrc/tsdf.hip; rules in DESIGN.md 3h-11) ---
  * A truncated signed distance volume that averages registered depth maps, and the depth map of its zero crossing seen from
  * a pose: the map cotr_icp_depth tracks the next capture against.  The rules are the library's own.
