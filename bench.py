@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Headline benchmark: query-correspondences/sec of the COTR forward path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|batch256|dense|train] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|batch256|dense|train] [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs and nothing else: set up, warm up, time the K steps, write the outputs if asked,
+print the line (``roofline`` from the HIP events of the timed steps themselves, ``traffic`` from the committed profile).  ``--full``
+(headline workload, N == 1) adds every measurement that takes runs of its own - ``roofline.traffic`` measured in rocprofv3 child
+passes, ``roofline.stages`` / ``kernels`` / ``dominant_kernel`` / ``by_batch`` / ``batched_frac``, ``also_measured``, ``cpu_baseline``
+(``--research``: the split-f16 entry too) - after the timed steps and the dump; ``--no-extras`` / ``--no-cpu-baseline`` take their part
+out of a ``--full`` run again.  About half a minute of extra wall time; the timed steps and the headline value are the same either way.
 
 ``--dump-outputs DIR`` writes what the last timed step computed - pred_corrs (all pairs / queries of the job); for train the
 loss, pred_corrs and a seeded sample of the updated weights - as DIR/<name>.npy.  Inputs, weights and dropout seeds are
@@ -30,10 +37,10 @@ with a stand-in model (tests/test_bench_cpu.py): the only use of a non-HIP model
 Prints ONE JSON line on rank 0.  ``roofline`` is for the whole forward launch sequence (one "launch" = one cotr_forward =
 the ~100 kernels of one step): achieved = FLOP(B,Q) / mean step time measured with HIP events on the launch stream, against
 the fp32 MFMA peak (parity forces fp32 operands).  ``roofline.traffic`` = bytes crossing L2 <-> fabric per forward, measured
-by this run itself (two rocprofv3 --pmc passes of a child process: FETCH_SIZE x2 on gfx950 + WRITE_SIZE) when rocprofv3 is
-on the box, else taken from the committed profile - ``traffic_source`` says which.  ``cpu_baseline`` is the CPU oracle (a
-torch-CPU restatement of the reference, kind "port"; the reference itself, kind "reference", where /root/reference is
-importable) timed on this box's host cores on a bounded number of the same forward calls - rank 0, N == 1 only.
+by a ``--full`` run itself (two rocprofv3 --pmc passes of a child process: FETCH_SIZE x2 on gfx950 + WRITE_SIZE) where rocprofv3 is
+installed, else taken from the committed profile - ``traffic_source`` says which.  ``cpu_baseline`` (``--full``) is the CPU oracle (a
+torch-CPU restatement of the reference, kind "port"; the reference itself, kind "reference", where oracle.ref_import finds it)
+timed on the host cores on a bounded number of the same forward calls - rank 0, N == 1 only.
 """
 import argparse
 import csv
@@ -678,14 +685,17 @@ def main():
                     help='--workload train: per-weight gradient reductions + autograd accumulation instead of the GradSink')
     ap.add_argument('--graphed-train', action='store_true',
                     help='--workload train: the step as ONE captured HIP graph (training.GraphedTrainStep) instead of eager train_batch')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='only the timed steps (for rocprofv3 runs)')
+    ap.add_argument('--full', action='store_true',
+                    help='headline workload, N == 1: after the timed steps also measure what takes runs of its own (traffic under rocprofv3, '
+                         'stages, kernels, dominant kernel, other regimes and batch sizes, the CPU baseline); off by default')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='--full without the extra GPU measurements')
     ap.add_argument('--traffic', choices=['auto', 'measure', 'committed', 'none'], default='auto',
-                    help='roofline.traffic: measured by a rocprofv3 --pmc child of this run (auto: when available, N == 1, extras '
-                         'on), or the committed profile')
+                    help='roofline.traffic: measured by a rocprofv3 --pmc child of this run (auto: in a --full run, when available, '
+                         'N == 1, extras on), or the committed profile')
     ap.add_argument('--traffic-child', type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument('--research', action='store_true',
-                    help='also time the RESEARCH path (knob split_f16 of libcotr_hip_exp.so) in a child process and report it as a named secondary entry')
+                    help='--full: also time the RESEARCH path (knob split_f16 of libcotr_hip_exp.so) in a child process and report it as a named secondary entry')
     ap.add_argument('--research-child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--backend', choices=['nccl', 'gloo'], default='nccl', help='torch.distributed backend (nccl = RCCL; gloo with --dry-run)')
     ap.add_argument('--dry-queries', type=int, default=1031, help='--dry-run --workload dense: queries of the stand-in pair (131072 = the real grid)')
@@ -875,7 +885,8 @@ def main():
                                                      'fp32-MFMA path but not bit-identical to it; "roofline" below divides fp32-EQUIVALENT work by the fp32-MFMA '
                                                      'peak and is not a fraction of any roofline of the kernels that ran')
             line['roofline']['bound'] = 'none (research path)'
-        extras = world == 1 and not args.no_extras and not batch256 and not dense and not research
+        # everything below that measures anything (runs of its own, after the timed steps and the dump) belongs to --full
+        extras = args.full and world == 1 and not args.no_extras and not batch256 and not dense and not research
         if dumped:
             line['dumped_outputs'] = dumped
         line.update(ident)
@@ -908,7 +919,7 @@ def main():
             roof['by_batch'] = line['also_measured'].pop('by_batch')
             if args.research:   # opt-in: the driver's run times the product only
                 line['also_measured']['RESEARCH_split_f16_opt_in_not_the_product_path'] = research_split_f16()
-        if world == 1 and not args.no_cpu_baseline and not batch256 and not dense:
+        if args.full and world == 1 and not args.no_cpu_baseline and not batch256 and not dense:
             line['cpu_baseline'] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -90,6 +90,16 @@ def test_dump_outputs_writes_the_last_step_and_is_the_same_from_run_to_run(tmp_p
     assert np.array_equal(dumps[0], dumps[1])
 
 
+def test_full_is_an_option_and_off_by_default():
+    """--full (everything beyond the headline's own steps) exists, is off unless given, and leaves the plumbing and its line alone."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=600, env=_clean_env())
+    assert r.returncode == 0 and '--full' in r.stdout and 'off by default' in ' '.join(r.stdout.split())
+    plain = _run(['--dry-run', '--backend', 'gloo', '--steps', '2', '--warmup', '1'], _clean_env())
+    full = _run(['--dry-run', '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--full'], _clean_env())
+    assert set(plain) == set(full) and full['steps'] == 2 and full['warmup'] == 1 and full['gathered_rows'] == 1
+
+
 def test_steps_below_one_are_refused():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-run', '--backend', 'gloo', '--steps', '0'], cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=_clean_env())

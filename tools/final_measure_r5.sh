@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 if [ "$part" = all ] || [ "$part" = a ]; then
   python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" | tail -3 > $o/pytest_gpu.txt
   python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $o/smoke.txt 2>&1
-  python bench.py > $o/bench.json 2> $o/bench.err
+  python bench.py --full > $o/bench.json 2> $o/bench.err
   python bench.py --workload batch256 --steps 3 --warmup 1 --no-cpu-baseline --traffic none > $o/bench_batch256.json 2> $o/bench_batch256.err
   python bench.py --workload dense > $o/bench_dense.json 2> $o/bench_dense.err
   python tools/time_configs.py > $o/time_configs_batched.txt 2>&1
