@@ -65,17 +65,10 @@ __device__ __forceinline__ TvProj tv_project(const double* w, const TvPixel& q, 
   return r;
 }
 
-// ---- the table itself: a thread per view: camera, pose, centre c = -R^T t and the view's validity -> tab; info[0] = found,
-// info[1..7] = 0.  One workgroup of 64 threads.  File-local (static) on purpose: every translation unit that includes this header
-// gets its own copy, which is what lets the kernel live here, launched by structure.hip and bundle.hip alike, while structure.hip
-// keeps the instructions it had when the kernel was defined there.
-static __global__ __launch_bounds__(64) void tv_prepare_kernel(const double* __restrict__ cams, const double* __restrict__ poses, int V,
-                                                        const int32_t* __restrict__ found, double* __restrict__ tab,
-                                                        int32_t* __restrict__ info) {
-  const int v = threadIdx.x;
-  if (v < 8) info[v] = v == 0 ? (found ? (found[0] != 0) : 1) : 0;
-  if (v >= V) return;
-  double* w = tab + v * TV_ROW;
+// ---- the table itself ----------------------------------------------------------------------------------------------------------
+// Row v of the table (the Prepare rule of DESIGN.md 3h-6): camera, pose, centre c = -R^T t and the view's validity -> w.  The one
+// statement of the rule: tv_prepare_kernel writes the rows to global memory, mvdepth.hip builds them in LDS.
+__device__ __forceinline__ void tv_view_row(const double* __restrict__ cams, const double* __restrict__ poses, int v, double* w) {
   const double* k = cams + v * 5;
   const double* P = poses + v * 12;
   bool ok = true;
@@ -102,3 +95,18 @@ static __global__ __launch_bounds__(64) void tv_prepare_kernel(const double* __r
   w[TV_OK] = ok ? 1.0 : 0.0;
   w[21] = w[22] = w[23] = 0.0;
 }
+
+// A thread per view: its row -> tab; info[0] = found, info[1..7] = 0.  One workgroup of 64 threads.  File-local (static) on purpose:
+// every translation unit that includes this header gets its own copy, which is what lets the kernel live here, launched by structure.hip
+// and bundle.hip alike, while structure.hip keeps the instructions it had when the kernel was defined there.  A translation unit that
+// keeps no table in global memory (mvdepth.hip) defines TV_NO_PREPARE_KERNEL before the include and gets no copy.
+#ifndef TV_NO_PREPARE_KERNEL
+static __global__ __launch_bounds__(64) void tv_prepare_kernel(const double* __restrict__ cams, const double* __restrict__ poses, int V,
+                                                        const int32_t* __restrict__ found, double* __restrict__ tab,
+                                                        int32_t* __restrict__ info) {
+  const int v = threadIdx.x;
+  if (v < 8) info[v] = v == 0 ? (found ? (found[0] != 0) : 1) : 0;
+  if (v >= V) return;
+  tv_view_row(cams, poses, v, tab + v * TV_ROW);
+}
+#endif

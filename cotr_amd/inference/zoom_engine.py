@@ -778,6 +778,78 @@ class ZoomEngine:
         fuse_captures([cap._replace(c2w=p) for cap, p in zip(caps, poses) if p is not None], volume)
         return volume, poses, found
 
+    def depth_map(self, img_ref, imgs, K_ref, Ks, c2w_ref, c2ws, dense='flow', max_cycle=THRESHOLD_SPARSE, zoom_ins=np.linspace(0.5, 0.0625, 4),
+                  converge_iters=1, max_corrs=1000, **kw):
+        """The depth map of the posed image ``img_ref`` (camera ``K_ref``, camera-to-world ``c2w_ref``) from its correspondences
+        into the posed images ``imgs`` (``Ks``, ``c2ws``; 1 to 31 of them) by ``depth_from_corr``.  ``dense='flow'``: one ``flow``
+        call per neighbour, its map taken to pixels by ``flow_to_corr`` and valid where the cycle error is at most ``max_cycle``
+        (maps sampled at integer pixels: centres 0.0).  ``dense='sparse'``: one ``cotr_corr_multiscale`` (``zoom_ins``,
+        ``converge_iters``, ``max_corrs``) and one ``triangulate_corr(simplices='device', as_tensor=True)`` per neighbour, valid
+        where its triangles cover the pixel (maps sampled at pixel centres: centres 0.5).  ``kw``: the other arguments of
+        ``depth_from_corr``.  -> its dict, with corr float32 [K,H,W,2] and valid bool [K,H,W], the maps it was called on."""
+        from .depth import depth_from_corr, flow_to_corr
+        if dense not in ('flow', 'sparse'):
+            raise ValueError(f"dense must be 'flow' or 'sparse', got {dense!r}")
+        imgs = list(imgs)
+        if not imgs:
+            raise ValueError('depth_map needs at least one neighbour image')
+        img_ref = np.ascontiguousarray(img_ref)
+        maps, valid = [], []
+        for img in imgs:
+            img = np.ascontiguousarray(img)
+            if dense == 'flow':
+                corr, con = self.flow(img_ref, img, resample=False)[:2]
+                px, ok = flow_to_corr(corr, con, img.shape, max_cycle)
+                px, ok = torch.from_numpy(px), torch.from_numpy(ok)
+            else:
+                from .triangulate import triangulate_corr
+                corrs = self.cotr_corr_multiscale(img_ref, img, zoom_ins, converge_iters, max_corrs=max_corrs)
+                px, ok = triangulate_corr(np.asarray(corrs), img_ref.shape, img.shape, simplices='device', return_mask=True, as_tensor=True)
+                px = px.float()
+            maps.append(px)
+            valid.append(ok)
+        device = next(self.model.parameters()).device
+        corr, valid = torch.stack(maps).to(device), torch.stack(valid).to(device)
+        kw.setdefault('centres', 0.0 if dense == 'flow' else 0.5)
+        kw.setdefault('device', device)
+        out = depth_from_corr(corr, K_ref, c2w_ref, Ks, c2ws, valid=valid, **kw)
+        out['corr'], out['valid'] = corr, valid
+        return out
+
+    def fuse_images(self, imgs, Ks, c2ws, volume, neighbours=2, filter_kw=None, **kw):
+        """A reconstruction from posed photographs: every image of ``imgs`` (one size; ``Ks`` [n,3,3] or one [3,3], ``c2ws`` [n,4,4]
+        camera-to-world, host) gets a depth map by ``depth_map`` (``kw``) from the ``neighbours`` images whose camera centres are
+        nearest its own (the lower index first among equals), the maps are checked against each other by ``filter_depths``
+        (``filter_kw``: pairs, px_thresh, rel_thresh, min_views, max_violations), and the captures (image, filtered depth, the
+        camera ``depth_map`` returned, pose) are averaged into ``volume`` by ``fuse_captures``, with the images where the volume
+        holds colour -> (volume, depths float32 [n,H,W] on the device: what was fused, info: dict(depth: one int32 [8] of
+        ``depth_from_corr`` per image, filter: int32 [n,4] of ``filter_depths``, fused: the list of ``fuse_captures``))."""
+        from ..data import Capture
+        from . import _args
+        from .depth import filter_depths
+        from .tsdf import fuse_captures
+        imgs = [np.ascontiguousarray(img) for img in imgs]
+        n = len(imgs)
+        if n < 2:
+            raise ValueError(f'fuse_images needs at least two images, got {n}')
+        if len({img.shape[:2] for img in imgs}) != 1:
+            raise ValueError(f'the images must share one size, got {sorted({img.shape[:2] for img in imgs})}')
+        _args.check_int_range('neighbours', neighbours, 1, min(n - 1, 31))
+        ks = np.asarray(Ks, dtype=np.float64)
+        ks = np.broadcast_to(ks, (n, 3, 3)) if ks.shape == (3, 3) else ks
+        poses = _args.c2w_rows(c2ws, n).numpy().reshape(n, 4, 4)
+        centres = poses[:, :3, 3]
+        results = []
+        for i in range(n):
+            d = np.linalg.norm(centres - centres[i], axis=1)
+            d[i] = np.inf
+            near = [int(j) for j in np.argsort(d, kind='stable')[:int(neighbours)]]
+            results.append(self.depth_map(imgs[i], [imgs[j] for j in near], ks[i], ks[near], poses[i], poses[near], **kw))
+        kept = filter_depths(torch.stack([r['depth'] for r in results]), np.stack([r['K'] for r in results]), poses, **(filter_kw or {}))
+        caps = [Capture(imgs[i], kept['depth'][i], results[i]['K'], poses[i]) for i in range(n)]
+        _, fused = fuse_captures(caps, volume)
+        return volume, kept['depth'], dict(depth=[r['info'] for r in results], filter=kept['info'], fused=fused)
+
     def reconstruct(self, img_a, img_b, K_a, K_b, c2w_a=None, c2w_b=None, queries_a=None, zoom_ins=np.linspace(0.5, 0.0625, 4),
                     converge_iters=1, max_corrs=1000, rule='rays', pose_kw=None, bundle_rounds=0, **structure_kw):
         """demo_reconstruction.py up to its viewer: ``cotr_corr_multiscale`` from A into B (from ``queries_a`` [N, 2] with

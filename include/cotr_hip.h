@@ -981,6 +981,74 @@ int cotr_bundle_adjust(const double* points, const uint8_t* visible, const doubl
                        uint8_t* used_out, double* stats_out, int32_t* info_out, void* scratch, size_t scratch_bytes,
                        cotr_stream stream);
 
+/* ---- multi-view depth maps: a depth map from correspondence maps, and the cross-check of depth maps (cotr_amd/csrc/mvdepth.hip;
+ *      rules in DESIGN.md 3h-16) ----
+ * The step between dense correspondences and the TSDF stack: the correspondence maps of a reference view into its posed
+ * neighbours become the reference's depth map, and a set of depth maps is checked against each other before it is fused.  The
+ * rules are the library's own.  Neither call takes a scratch.  Every intermediate is float64, evaluated as bracketed below, and
+ * no product is contracted into an FMA.
+ *
+ * cotr_corr_depth: V = K + 1 views, view 0 the reference, views 1 .. K its neighbours.  DEVICE pointers: corr [K][H][W][2]
+ *   float32, 8-byte aligned: (u, v) = corr[k][y][x], the position in pixels of view k + 1 of what reference pixel (x, y) shows;
+ *   valid [K][H][W] uint8 or NULL (every entry counts); cams [V][5] and poses [V][12] float64 as in cotr_triangulate_views
+ *   (world-to-camera); found int32 [1] or NULL.
+ *   Views: a view is valid, and has the centre c_j = -R^T t, by the rule of cotr_triangulate_views.  When the reference view is
+ *   not valid or found[0] is 0, every output is empty: depth 0, views 0, err NaN, every counter 0.
+ *   Reference ray of pixel (x, y): (xn, yn) by the rule of cotr_ransac_essential in view 0, r_i = (R_0i xn + R_1i yn) + R_2i, not
+ *   normalised; X(s)_i = c_0i + s r_i, and the depth of X(s) in the reference camera is s itself.
+ *   Candidate views: neighbour j sees the pixel when it is valid, its entry of valid is not 0 and both its coordinates are
+ *   finite.  r_j: its ray, formed the same way from (u, v).  a = r.r, b = r.r_j, e = r_j.r_j, w = c_j - c_0 (every dot product
+ *   (p_0 q_0 + p_1 q_1) + p_2 q_2).  j has parallax iff b / sqrt(a e) <= max_cos; its candidate is
+ *   s_j = ((r.w) e - b (r_j.w)) / (a e - b b), degenerate when the denominator is 0 or not finite or s_j is not finite or <= 0.
+ *   P: the views that see the pixel and have parallax; the others take no part.  No view of P with a candidate that is not
+ *   degenerate: the pixel has no candidate.
+ *   Vote: the candidates of P that are not degenerate, ascending in j; each counts the views of P in which X(s_j) has depth z > 0
+ *   and float(squared reprojection error) <= float(threshold^2), by the projection of cotr_triangulate_views.  A candidate takes
+ *   over only with a strictly larger count: the first with the largest count gives s and U, its inlier views.  |U| < min_views:
+ *   the pixel has too few views.
+ *   Refit: up to refine_iters scalar Gauss-Newton steps on E(s) = sum over U of the squared reprojection errors e_j, ascending
+ *   in j.  With q = R_j r (q_i = (R_i0 r_0 + R_i1 r_1) + R_i2 r_2), (xn_j, yn_j, z) the projection of X(s) and (du, dv) its
+ *   residual: a_j = (q_0 - xn_j q_2) / z, b_j = (q_1 - yn_j q_2) / z, ju = fx a_j + skew b_j, jv = fy b_j, A += ju ju + jv jv,
+ *   g += ju du + jv dv; the proposal is s - g / A.  A step is kept only if A is finite and > 0, the new s is > 0, every view of U
+ *   keeps z > 0 and E falls; the first step not kept ends the refit.
+ *   Filters: the pixel is dropped by depth unless 0 < s < distance_thresh, and (depth passed) by error unless float(e_j) <=
+ *   float(threshold^2) for every view of U at the final s.
+ *   -> depth_out [H][W] float32 = float32(s), 0 where there is none; views_out [H][W] uint8 = |U|, 0 where there is no depth;
+ *   err_out [H][W] float32 = float32(E / |U|), NaN where there is no depth; info_out [8] int32 = {found, pixels with a depth,
+ *   pixels with too few views, without a candidate, dropped by depth, dropped by error, 0, steps kept in total}.
+ *   2 <= V <= 32, 1 <= H, W and H W <= 2^28, threshold > 0 finite with a squared float32 that is finite and not 0, -1 <= max_cos
+ *   <= 1, distance_thresh > 0 finite, 1 <= min_views <= 31, 0 <= refine_iters <= 64.
+ *
+ * cotr_depth_consistency: depths [n][H][W] float32 DEVICE, 2 <= n <= 32, 1 <= H, W and n H W <= 2^28; Ks HOST [n][9], each as K
+ *   in cotr_lift_pixels; c2w [n][16] float64 DEVICE, row-major camera-to-world; found int32 DEVICE [n] or NULL, as in
+ *   cotr_tsdf_integrate: a view whose entry is 0 is checked against nothing (its outputs and its row of info_out are 0) and no
+ *   view is checked against it; pairs [n][n] uint8 DEVICE or NULL (everything): view i is checked against view j only where
+ *   pairs[i][j] is not 0; the diagonal is not read.
+ *   Pixel (x, y) of view i is valid when its depth z is finite and > 0.  Its vertex Y = (xn z, yn z, z) by cotr_lift_pixels'
+ *   rule at the pixel centre, its world point P_a = ((R_a0 Y_x + R_a1 Y_y) + R_a2 Y_z) + t_a through c2w_i.  For every allowed
+ *   j != i, ascending: P in view j, its depth Y_z and its pixel by the expressions of cotr_tsdf_integrate in their order; j is
+ *   skipped unless Y_z > 0 and the pixel (rint u, rint v) (ties to even) lies inside the map and holds a valid depth d_j.  That
+ *   pixel of j is lifted at d_j through c2w_j and projected into view i the same way (not rounded): (u', v') with depth z'.
+ *   j is consistent iff z' > 0, (u' - x)^2 + (v' - y)^2 <= px_thresh^2 and |z' - z| <= rel_thresh z.  j is a violation iff it is
+ *   not consistent and d_j > Y_z (1 + rel_thresh): view j sees through the point.  The pixel is kept iff consistent >= min_views
+ *   and (max_violations < 0 or violations <= max_violations).
+ *   -> depth_out [n][H][W] float32: a kept pixel float32((z + sum z') / (1 + consistent)), summed over the consistent views
+ *   ascending, every other pixel 0; count_out [n][H][W] uint8 = consistent (0 at a pixel that is not valid); info_out [n][4]
+ *   int32 = {evaluated (found), valid pixels in, pixels kept, pixels with enough consistent views dropped by violations}.
+ *   px_thresh > 0 finite with a finite square, 0 < rel_thresh < 1, 0 <= min_views <= 31, -1 <= max_violations <= 31.
+ * Both: no output may share a byte with another output or with an input (depth_out is not depths): COTR_ERR_ARG.
+ * Stream-ordered, 2 launches each whatever the data (a prologue that sets info_out, then a thread a pixel), no scratch, no host
+ * waits and no allocation (capturable); integer atomics only, and only for info_out; no floating-point sum crosses a thread:
+ * the same input gives the same bits.  Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the message in
+ * cotr_raster_last_error(). */
+int cotr_corr_depth(const float* corr, const uint8_t* valid, const double* cams, const double* poses, int V, int H, int W,
+                    const int32_t* found, double threshold, double max_cos, double distance_thresh, int min_views,
+                    int refine_iters, float* depth_out, uint8_t* views_out, float* err_out, int32_t* info_out,
+                    cotr_stream stream);
+int cotr_depth_consistency(const float* depths, int n, int H, int W, const double* Ks, const double* c2w, const int32_t* found,
+                           const uint8_t* pairs, double px_thresh, double rel_thresh, int min_views, int max_violations,
+                           float* depth_out, uint8_t* count_out, int32_t* info_out, cotr_stream stream);
+
 /* ---- warps of 8-bit images: cv2.remap / cv2.warpPerspective, INTER_LINEAR, BORDER_CONSTANT 0 (cotr_amd/csrc/warp.hip) ----
  * The last host step of demo_single_pair.py:43 (image B warped by triangulate_corr's dense map) and of
  * demo_homography.py:46-49 (a picture pasted through four corners).  Rule in DESIGN.md 3i: OpenCV's 8-bit bilinear remap.
