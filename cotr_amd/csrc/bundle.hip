@@ -12,7 +12,7 @@
 //     per iteration:
 //       ba_points_kernel  a thread per point: V_p, g_p, the damped inverse and V_p*^-1 g_p -> 9 doubles per point
 //       ba_pairs_kernel   (view pair v <= w) x (chunk): the sums of W_v V*^-1 W_w^T, on the diagonal also U_v and b_v, per chunk
-//       ba_solve_kernel   one workgroup: the chunks in order, S and b assembled in LDS, Cholesky, both solves, the candidate poses
+//       ba_solve_kernel   one workgroup: the chunks in order, S and b assembled in LDS, Cholesky and both solves (chol.h), the candidate poses
 //       ba_update_kernel  a thread per point: the candidate X, its squared error and depth flag over the set, per workgroup
 //       ba_decide_kernel  one wavefront sums the cost, then one thread keeps or rejects the candidate (the current-buffer index flips), lambda, the counters
 //   ba_finish_kernel   the outputs
@@ -20,6 +20,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "chol.h"
 #include "handleless.h"
 #include "ransac.h"
 #include "rodrigues.h"
@@ -436,9 +437,6 @@ __global__ __launch_bounds__(BA_THREADS) void ba_pairs_kernel(const double* __re
   }
 }
 
-// the packed lower triangle with one more row: row i, column j <= i
-__device__ __forceinline__ int ba_tri(int i, int j) { return i * (i + 1) / 2 + j; }
-
 __global__ __launch_bounds__(BA_THREADS) void ba_solve_kernel(int V, int chunks, BaState* __restrict__ st, double* __restrict__ tabs,
                                                               const double* __restrict__ parts, double* __restrict__ dc) {
   // rows 0 .. m-1: S (lower triangle), row m: b; 187 * 188 / 2 doubles
@@ -467,48 +465,22 @@ __global__ __launch_bounds__(BA_THREADS) void ba_solve_kernel(int V, int chunks,
         const int t = BA_U + c * 6 - c * (c - 1) / 2 + (r - c);
         double u = 0.0;
         for (int k = 0; k < chunks; ++k) u = u + src[(size_t)k * BA_SUMS + t];
-        L[ba_tri(6 * a + r, 6 * a + c)] = (r == c ? u * damp : u) - y;
+        L[ch_tri(6 * a + r, 6 * a + c)] = (r == c ? u * damp : u) - y;
       } else {
-        L[ba_tri(6 * b + c, 6 * a + r)] = -y;
+        L[ch_tri(6 * b + c, 6 * a + r)] = -y;
       }
     } else if (v == w && i >= BA_B && i < BA_NSUMS) {
       double s = 0.0;
       for (int k = 0; k < chunks; ++k) s = s + src[(size_t)k * BA_SUMS + i];
-      L[ba_tri(m, 6 * a + (i - BA_B))] = s;
+      L[ch_tri(m, 6 * a + (i - BA_B))] = s;
     }
   }
-  // Cholesky by columns, the right-hand side carried as row m: every entry is updated by one thread, column after column
-  bool bad = false;
-  for (int k = 0; k < m; ++k) {
-    __syncthreads();
-    const double pivot = L[ba_tri(k, k)];
-    if (!(pivot > 0.0) || !isfinite(pivot)) {   // uniform
-      bad = true;
-      break;
-    }
-    const double d = sqrt(pivot);
-    __syncthreads();
-    for (int i = k + tid; i <= m; i += BA_THREADS) L[ba_tri(i, k)] = i == k ? d : L[ba_tri(i, k)] / d;
-    __syncthreads();
-    // the trailing update on a 16 x 16 grid of threads: rows k+1 .. m (row m: the right-hand side), columns k+1 .. min(row, m-1)
-    for (int i = k + 1 + (tid >> 4); i <= m; i += 16) {
-      const double lik = L[ba_tri(i, k)];
-      const int last = i < m ? i : m - 1;
-      for (int j = k + 1 + (tid & 15); j <= last; j += 16) L[ba_tri(i, j)] -= lik * L[ba_tri(j, k)];
-    }
-  }
-  __syncthreads();
-  // L^T x = y, y in row m
-  if (!bad) {
-    for (int k = m - 1; k >= 0; --k) {
-      const double x = L[ba_tri(m, k)] / L[ba_tri(k, k)];
-      if (tid == 0) xs[k] = x;
-      for (int i = tid; i < k; i += BA_THREADS) L[ba_tri(m, i)] -= L[ba_tri(k, i)] * x;
-      __syncthreads();
-    }
-  } else {
+  // Cholesky and both solves (chol.h); a pivot must be positive and finite
+  const bool bad = !ch_factor<BA_THREADS>(L, m, [](int, double pivot) { return pivot > 0.0 && isfinite(pivot); });
+  if (bad)
     for (int i = tid; i < m; i += BA_THREADS) xs[i] = 0.0;
-  }
+  else
+    ch_back<BA_THREADS>(L, m, xs);
   __syncthreads();
   for (int i = tid; i < m; i += BA_THREADS) dc[i] = xs[i];
   if (tid == 0) st->bad = bad ? 1 : 0;

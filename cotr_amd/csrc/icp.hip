@@ -24,7 +24,6 @@
 
 #include "handleless.h"
 #include "icp_maps.h"
-#include "pinhole.h"
 #include "ransac.h"
 #include "refit.h"
 
@@ -109,33 +108,30 @@ struct IcTerms {
     const double X[3] = {pts.Vb[b * 3], pts.Vb[b * 3 + 1], pts.Vb[b * 3 + 2]};
     const double Px = (R[0] * X[0] + R[1] * X[1]) + R[2] * X[2], Py = (R[3] * X[0] + R[4] * X[1]) + R[5] * X[2],
                  Pz = (R[6] * X[0] + R[7] * X[1]) + R[8] * X[2];
-    const double Yx = Px + st->t[0], Yy = Py + st->t[1], Yz = Pz + st->t[2];
-    int a = -1;
-    if (Yz > 0.0) {   // false for NaN
-      const double xn = Yx / Yz, yn = Yy / Yz;
-      const double u = rint((pts.ka.fx * xn + pts.ka.s * yn) + pts.ka.cx), v = rint(pts.ka.fy * yn + pts.ka.cy);
-      if (u >= 0.0 && u < (double)pts.Wa && v >= 0.0 && v < (double)pts.Ha) {
-        const size_t q = (size_t)(int)v * pts.Wa + (int)u;
-        const double nx = pts.Na[q * 3], ny = pts.Na[q * 3 + 1], nz = pts.Na[q * 3 + 2];
-        if (nx == nx) {   // A has a valid normal there
-          const double dx = Yx - pts.Va[q * 3], dy = Yy - pts.Va[q * 3 + 1], dz = Yz - pts.Va[q * 3 + 2];
-          if ((dx * dx + dy * dy) + dz * dz <= pts.max_d2) {
-            const double mx = pts.Nb[b * 3], my = pts.Nb[b * 3 + 1], mz = pts.Nb[b * 3 + 2];
-            const double Rx = (R[0] * mx + R[1] * my) + R[2] * mz, Ry = (R[3] * mx + R[4] * my) + R[5] * mz,
-                         Rz = (R[6] * mx + R[7] * my) + R[8] * mz;
-            if ((Rx * nx + Ry * ny) + Rz * nz >= pts.normal_cos) {
-              a = (int)q;
-              const double r = (nx * dx + ny * dy) + nz * dz;
-              const double J[6] = {Py * nz - Pz * ny, Pz * nx - Px * nz, Px * ny - Py * nx, nx, ny, nz};
+    const double Y[3] = {Px + st->t[0], Py + st->t[1], Pz + st->t[2]};
+    double u, v;
+    int a = -1, ax, ay;
+    if (es_project(pts.ka, Y, &u, &v) && es_nearest(u, v, pts.Ha, pts.Wa, &ax, &ay)) {   // pinhole.h: Y_z > 0, a pixel of A
+      const size_t q = (size_t)ay * pts.Wa + ax;
+      const double nx = pts.Na[q * 3], ny = pts.Na[q * 3 + 1], nz = pts.Na[q * 3 + 2];
+      if (nx == nx) {   // A has a valid normal there
+        const double dx = Y[0] - pts.Va[q * 3], dy = Y[1] - pts.Va[q * 3 + 1], dz = Y[2] - pts.Va[q * 3 + 2];
+        if ((dx * dx + dy * dy) + dz * dz <= pts.max_d2) {
+          const double mx = pts.Nb[b * 3], my = pts.Nb[b * 3 + 1], mz = pts.Nb[b * 3 + 2];
+          const double Rx = (R[0] * mx + R[1] * my) + R[2] * mz, Ry = (R[3] * mx + R[4] * my) + R[5] * mz,
+                       Rz = (R[6] * mx + R[7] * my) + R[8] * mz;
+          if ((Rx * nx + Ry * ny) + Rz * nz >= pts.normal_cos) {
+            a = (int)q;
+            const double r = (nx * dx + ny * dy) + nz * dz;
+            const double J[6] = {Py * nz - Pz * ny, Pz * nx - Px * nz, Px * ny - Py * nx, nx, ny, nz};
 #pragma unroll
-              for (int i = 0; i < 6; ++i) {
+            for (int i = 0; i < 6; ++i) {
 #pragma unroll
-                for (int j = i; j < 6; ++j) acc[rf_tri<6>(i, j)] += J[i] * J[j];
-                acc[21 + i] += J[i] * r;
-              }
-              acc[27] += r * r;
-              acc[28] += 1.0;
+              for (int j = i; j < 6; ++j) acc[rf_tri<6>(i, j)] += J[i] * J[j];
+              acc[21 + i] += J[i] * r;
             }
+            acc[27] += r * r;
+            acc[28] += 1.0;
           }
         }
       }
@@ -335,7 +331,7 @@ int cotr_icp_depth(const float* depth_a, int Ha, int Wa, const double* K_a, cons
   if (!depth_a || !depth_b || !K_a || !K_b || !R0 || !t0 || !R_out || !t_out || !info_out || !stats_out || !scratch)
     return ic_fail("depth_a, depth_b, K_a, K_b, R0, t0, R_out, t_out, info_out, stats_out and scratch must not be NULL");
   EsCam ka, kb;
-  if (!es_camera(K_a, &ka) || !es_camera(K_b, &kb)) return ic_fail("the camera matrices must be finite with focal lengths that are not 0");
+  if (!es_camera(K_a, &ka) || !es_camera(K_b, &kb)) return ic_fail(ES_CAMERAS_WHAT);
   if (!aligned(depth_a, 4) || !aligned(depth_b, 4) || !aligned(R0, 8) || !aligned(t0, 8) || !aligned(c2w_a, 8) || !aligned(found, 4) ||
       !aligned(R_out, 8) || !aligned(t_out, 8) || !aligned(info_out, 4) || !aligned(stats_out, 8) || !aligned(hist_out, 8) ||
       !aligned(assoc_out, 4) || !aligned(maps_a_out, 8) || !aligned(maps_b_out, 8) || !aligned(scratch, 16))

@@ -1,33 +1,23 @@
 // The pixel rule of the vertex and normal maps (icp.hip: cotr_icp_depth, icp_multi.hip: cotr_icp_maps), stated once.  Rules in
-// DESIGN.md 3h-9.  Included by translation units compiled with -ffp-contract=off.
+// DESIGN.md 3h-9; the vertex is pinhole.h's.  Included by translation units compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "pinhole.h"
 
-// the vertex of the pixel centre (x, y): cotr_lift_pixels' rule without c2w; false where the depth is not finite and > 0
-__device__ __forceinline__ bool ic_vertex(const float* __restrict__ depth, int W, const EsCam& k, int x, int y, double* v) {
-  const double z = (double)depth[(size_t)y * W + x];
-  if (!(z > 0.0 && z < INFINITY)) return false;
-  const double yn = ((double)y - k.cy) / k.fy;
-  const double xn = ((double)x - k.cx - k.s * yn) / k.fx;
-  v[0] = xn * z, v[1] = yn * z, v[2] = z;
-  return true;
-}
-
-// Pixel (x, y) of a H x W map -> its vertex v and its normal n, NaN where there is none; true when it has a normal: an
+// Pixel (x, y) of a H x W map -> its vertex v (es_vertex) and its normal n, NaN where there is none; true when it has a normal: an
 // interior pixel whose five depths are valid, whose four neighbours lie within edge z of its depth, and whose central
 // differences have a cross product that is not 0.  The normal is turned towards the camera.
 __device__ __forceinline__ bool ic_pixel(const float* __restrict__ depth, int H, int W, const EsCam& k, double edge, int x, int y, double* v,
                                          double* n) {
   n[0] = n[1] = n[2] = NAN;
-  bool ok = ic_vertex(depth, W, k, x, y, v);
+  bool ok = es_vertex(depth, W, k, x, y, v);
   if (!ok) v[0] = v[1] = v[2] = NAN;
   if (ok && x > 0 && x < W - 1 && y > 0 && y < H - 1) {
     double l[3], r[3], u[3], d[3];
-    ok = ic_vertex(depth, W, k, x - 1, y, l) && ic_vertex(depth, W, k, x + 1, y, r) && ic_vertex(depth, W, k, x, y - 1, u) &&
-         ic_vertex(depth, W, k, x, y + 1, d);
+    ok = es_vertex(depth, W, k, x - 1, y, l) && es_vertex(depth, W, k, x + 1, y, r) && es_vertex(depth, W, k, x, y - 1, u) &&
+         es_vertex(depth, W, k, x, y + 1, d);
     if (ok) {
       const double lim = edge * v[2];
       ok = fabs(l[2] - v[2]) <= lim && fabs(r[2] - v[2]) <= lim && fabs(u[2] - v[2]) <= lim && fabs(d[2] - v[2]) <= lim;

@@ -13,7 +13,7 @@
 //                               order, every wavefront in a fixed butterfly, the 4 wavefronts in order -> edge_out[e][band]
 //      im_solve_kernel          one workgroup: the bands of every edge in band order, the edge gate, the free views, the packed
 //                               lower triangle of the 6F x 6F system with its right-hand side in LDS (every entry added up by one
-//                               thread in a fixed order), Cholesky by columns, both solves, the twist of every free view
+//                               thread in a fixed order), Cholesky by columns and both solves (chol.h), the twist of every free view
 //      The last pair only evaluates.  The stop reason in info_out idles the chain after a stop; its length never depends on the
 //      data.
 // All device state lives in the documented outputs (c2w_out, edge_out, info_out): there is no scratch.  Integer atomics only:
@@ -24,9 +24,9 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "chol.h"
 #include "handleless.h"
 #include "icp_maps.h"
-#include "pinhole.h"
 #include "ransac.h"
 #include "refit.h"
 #include "rodrigues.h"
@@ -45,10 +45,6 @@ using namespace cotr_detail;
 #define IM_MAX_DIM (6 * (TV_MAX_VIEWS - 1))   // 186 unknowns: at least one view is fixed
 #define IM_TAB (TV_MAX_VIEWS * TV_MAX_VIEWS)
 
-struct ImCams {
-  EsCam k[TV_MAX_VIEWS];
-};
-
 struct ImGrid {
   int n, H, W, stride, ws, hs;   // ws, hs: source pixels in a row, source rows
   double max_d2, normal_cos;
@@ -61,7 +57,7 @@ __global__ __launch_bounds__(64) void im_maps_begin_kernel(int n, int32_t* __res
 }
 
 // grid (pixels / 256, n): maps_out[c][H W][6] = vertex, normal (NaN where there is none); info[c] = {vertices, normals, 0, 0}
-__global__ __launch_bounds__(256) void im_map_kernel(const float* __restrict__ depths, int H, int W, ImCams cams, double edge,
+__global__ __launch_bounds__(256) void im_map_kernel(const float* __restrict__ depths, int H, int W, EsCams cams, double edge,
                                                      double* __restrict__ maps_out, int32_t* __restrict__ info) {
   const int c = blockIdx.y;
   const int p = blockIdx.x * 256 + threadIdx.x;
@@ -116,7 +112,7 @@ __global__ __launch_bounds__(IM_THREADS) void im_begin_kernel(int n, int E, cons
 }
 
 // grid (IM_BANDS, E).  Edge e = (a, b): A = view a is the target, B = view b the source.
-__global__ __launch_bounds__(IM_THREADS) void im_edge_kernel(const double* __restrict__ maps, ImCams cams, ImGrid g, const int32_t* __restrict__ edges,
+__global__ __launch_bounds__(IM_THREADS) void im_edge_kernel(const double* __restrict__ maps, EsCams cams, ImGrid g, const int32_t* __restrict__ edges,
                                                               const int32_t* __restrict__ found, const double* __restrict__ poses,
                                                               const int32_t* __restrict__ info, double* __restrict__ edge_out,
                                                               int32_t* __restrict__ assoc) {
@@ -232,9 +228,6 @@ __global__ __launch_bounds__(IM_THREADS) void im_edge_kernel(const double* __res
   }
 }
 
-// the packed lower triangle with one more row: row i, column j <= i
-__device__ __forceinline__ int im_tri(int i, int j) { return i * (i + 1) / 2 + j; }
-
 // entry i of edge e: its bands in band order
 __device__ __forceinline__ double im_band_sum(const double* __restrict__ edge_out, int e, int i) {
   const double* p = edge_out + (size_t)e * IM_EDGE + i;
@@ -335,7 +328,7 @@ __global__ __launch_bounds__(IM_THREADS) void im_solve_kernel(int n, int E, cons
           if (e2 >= 0) x = x + im_band_sum(edge_out, e2, t);
           val = -x;
         }
-        L[im_tri(6 * p + r, 6 * q + c)] = val;
+        L[ch_tri(6 * p + r, 6 * q + c)] = val;
       } else {
         const int i = it - nblk * 36, p = i / 6, r = i - p * 6, v = view_of[p];
         for (int u = 0; u < n; ++u) {
@@ -343,49 +336,27 @@ __global__ __launch_bounds__(IM_THREADS) void im_solve_kernel(int n, int E, cons
           if (e1 >= 0) val = val - im_band_sum(edge_out, e1, 21 + r);   // v is the target
           if (e2 >= 0) val = val + im_band_sum(edge_out, e2, 21 + r);   // v is the source
         }
-        L[im_tri(m, i)] = val;
+        L[ch_tri(m, i)] = val;
       }
       if (!(fabs(val) < INFINITY)) bad = 1;   // also for NaN
     }
     if (__syncthreads_or(bad)) {
       reason = 3;
     } else {
-      // Cholesky by columns, the right-hand side carried as row m: every entry is updated by one thread, column after column
-      bool fail = false;
+      // Cholesky and both solves (chol.h); a pivot must be positive, finite and above pivot_tol of its entry before the elimination
       min_ratio = INFINITY;
-      for (int col = 0; col < m; ++col) {
-        __syncthreads();
-        const double pivot = L[im_tri(col, col)], d0 = diag0[col];
-        if (!(fabs(pivot) < INFINITY) || !(pivot > 0.0) || !(pivot > pivot_tol * d0)) {   // uniform
-          fail = true;
-          break;
-        }
+      const bool fail = !ch_factor<IM_THREADS>(L, m, [&](int col, double pivot) {
+        const double d0 = diag0[col];
+        if (!(fabs(pivot) < INFINITY) || !(pivot > 0.0) || !(pivot > pivot_tol * d0)) return false;
         const double ratio = pivot / d0;
         if (ratio < min_ratio) min_ratio = ratio;
-        const double d = sqrt(pivot);
-        __syncthreads();
-        for (int i = col + tid; i <= m; i += IM_THREADS) L[im_tri(i, col)] = i == col ? d : L[im_tri(i, col)] / d;
-        __syncthreads();
-        // the trailing update on a 16 x 16 grid of threads: rows col+1 .. m, columns col+1 .. min(row, m-1)
-        for (int i = col + 1 + (tid >> 4); i <= m; i += 16) {
-          const double lik = L[im_tri(i, col)];
-          const int end = i < m ? i : m - 1;
-          for (int j = col + 1 + (tid & 15); j <= end; j += 16) L[im_tri(i, j)] -= lik * L[im_tri(j, col)];
-        }
-      }
-      __syncthreads();
+        return true;
+      });
       if (fail) {
         reason = 2;
         min_ratio = 0.0;
       } else {
-        // L^T x = y, y in row m
-        for (int col = m - 1; col >= 0; --col) {
-          const double x = L[im_tri(m, col)] / L[im_tri(col, col)];
-          if (tid == 0) xs[col] = x;
-          __syncthreads();
-          for (int i = tid; i < col; i += IM_THREADS) L[im_tri(m, i)] -= L[im_tri(col, i)] * x;
-          __syncthreads();
-        }
+        ch_back<IM_THREADS>(L, m, xs);
         stepped = true;
         // the twist -x of every free view: R <- exp([w]x) R, t <- exp([w]x) (t - c) + c + dt
         if (tid < n && slot[tid] >= 0) {
@@ -429,13 +400,6 @@ const char* im_shape(int n, int lo, int H, int W) {
   return nullptr;
 }
 
-bool im_cameras(const double* Ks, int n, ImCams* cams) {
-  for (int i = 0; i < TV_MAX_VIEWS; ++i) cams->k[i] = EsCam{1.0, 1.0, 0.0, 0.0, 0.0};
-  for (int i = 0; i < n; ++i)
-    if (!es_camera(Ks + 9 * i, &cams->k[i])) return false;
-  return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -445,8 +409,8 @@ int cotr_icp_maps(const float* depths, int n, int H, int W, const double* Ks, do
   if (const char* what = im_shape(n, 1, H, W)) return arg_fail(FN, what);
   if (!(edge > 0.0) || !(edge < INFINITY)) return arg_fail(FN, "edge must be finite and > 0");
   if (!depths || !Ks || !maps_out || !info_out) return arg_fail(FN, "depths, Ks, maps_out and info_out must not be NULL");
-  ImCams cams;
-  if (!im_cameras(Ks, n, &cams)) return arg_fail(FN, "the camera matrices must be finite with focal lengths that are not 0");
+  EsCams cams;
+  if (const char* what = es_cameras(Ks, n, &cams)) return arg_fail(FN, what);
   if (!aligned(depths, 4) || !aligned(maps_out, 8) || !aligned(info_out, 4)) return arg_fail(FN, "floats and int32 must be 4-byte and doubles 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(im_maps_begin_kernel, dim3(1), dim3(64), 0, s, n, info_out);
@@ -469,8 +433,8 @@ int cotr_icp_multiview(const double* maps, int n, int H, int W, const double* Ks
   if (!(pivot_tol > 0.0) || !(pivot_tol < 1.0)) return arg_fail(FN, "pivot_tol must be in (0, 1)");
   if (!maps || !Ks || !c2w0 || !edges || !centre || !c2w_out || !info_out || !view_info_out || !stats_out || !edge_out)
     return arg_fail(FN, "maps, Ks, c2w0, edges, centre, c2w_out, info_out, view_info_out, stats_out and edge_out must not be NULL");
-  ImCams cams;
-  if (!im_cameras(Ks, n, &cams)) return arg_fail(FN, "the camera matrices must be finite with focal lengths that are not 0");
+  EsCams cams;
+  if (const char* what = es_cameras(Ks, n, &cams)) return arg_fail(FN, what);
   if (!isfinite(centre[0]) || !isfinite(centre[1]) || !isfinite(centre[2])) return arg_fail(FN, "centre must be finite");
   if (!aligned(maps, 8) || !aligned(c2w0, 8) || !aligned(edges, 4) || !aligned(found, 4) || !aligned(c2w_out, 8) || !aligned(info_out, 4) ||
       !aligned(view_info_out, 4) || !aligned(stats_out, 8) || !aligned(edge_out, 8) || !aligned(hist_out, 8) || !aligned(assoc_out, 4))

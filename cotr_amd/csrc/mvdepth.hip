@@ -4,13 +4,13 @@
 // same input gives the same bits.  Compiled with -ffp-contract=off.
 //
 // cotr_corr_depth
-//   1. md_begin_kernel        info = {found, 0, ...}
+//   1. hl_begin_kernel        (handleless.h) info = {found, 0, ...}
 //   2. md_depth_kernel        a thread per pixel.  Every workgroup rebuilds the view table (tv_view_row of view_table.h: the Prepare rule of
 //                             cotr_triangulate_views, at most 32 x 24 doubles) in LDS with a thread per view and reads it at uniform
 //                             addresses; the 8 bytes of a neighbour's correspondence are read coalesced whenever a loop needs them
 //                             (nothing per view lives in registers: the sets of views are 32-bit masks)
 // cotr_depth_consistency
-//   1. md_begin_kernel        info[i] = {found[i], 0, 0, 0}
+//   1. hl_begin_kernel        info[i] = {found[i], 0, 0, 0}
 //   2. md_consistency_kernel  grid (blocks of pixels, n): the reference view is blockIdx.y, so its camera and pose are wave-uniform;
 //                             the depth of view j at the projected pixel is the only gather
 // The counters of both are wave ballots, summed per workgroup in LDS, one integer atomic a counter and workgroup.
@@ -19,7 +19,6 @@
 #include <stdint.h>
 
 #include "handleless.h"
-#include "icp_maps.h"
 #define TV_NO_PREPARE_KERNEL   // the table is built in LDS by every workgroup: tv_view_row alone
 #include "view_table.h"
 
@@ -28,15 +27,7 @@ using namespace cotr_detail;
 #define MD_THREADS 256
 #define MD_WAVES (MD_THREADS / 64)
 #define MD_MAX_REFINE 64
-#define MD_MAX_MAPS 32
-
-// rows of n x 4 (or one row of 8) counters: column 0 = found, the rest 0
-__global__ __launch_bounds__(64) void md_begin_kernel(const int32_t* __restrict__ found, int n, int cols, int32_t* __restrict__ info) {
-  const int c = threadIdx.x;
-  if (c >= n) return;
-  info[c * cols] = found ? (found[c] != 0 ? 1 : 0) : 1;
-  for (int i = 1; i < cols; ++i) info[c * cols + i] = 0;
-}
+#define MD_MAX_MAPS ES_MAX_CAMS
 
 // per-wavefront counts -> part[wave][col]; then, after a barrier, one atomic a column whose sum is not 0: column i goes to dst[i],
 // from column `gap` on to dst[i + 1]
@@ -54,15 +45,6 @@ __device__ __forceinline__ void md_flush(int (*part)[COLS], const int* mine, int
 }
 
 // ---- cotr_corr_depth --------------------------------------------------------------------------------------------------------
-// r = R^T (xn, yn, 1), not normalised, (xn, yn) the normalised pixel
-__device__ __forceinline__ void md_ray(const double* w, double u, double v, double* r) {
-  const EsCam k = {w[0], w[1], w[2], w[3], w[4]};
-  double x, y;
-  es_normalise(k, u, v, &x, &y);
-  const double* R = w + TV_R;
-  r[0] = (R[0] * x + R[3] * y) + R[6], r[1] = (R[1] * x + R[4] * y) + R[7], r[2] = (R[2] * x + R[5] * y) + R[8];
-}
-
 struct MdPixel {
   const double* tab;                 // the view table in LDS
   const float* __restrict__ corr;
@@ -91,7 +73,7 @@ struct MdCand {
 __device__ __forceinline__ MdCand md_candidate(const MdPixel& c, int j, const TvPixel& q, double max_cos) {
   const double* w = c.tab + j * TV_ROW;
   double rk[3];
-  md_ray(w, q.u, q.v, rk);
+  tv_view_ray(w, q.u, q.v, rk);
   const double* r = c.r;
   const double a = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
   const double b = (r[0] * rk[0] + r[1] * rk[1]) + r[2] * rk[2];
@@ -154,7 +136,7 @@ __global__ __launch_bounds__(MD_THREADS) void md_depth_kernel(const float* __res
   float depth = 0.0f, mean = __builtin_nanf("");
   if (in) {
     MdPixel c = {tab, corr, HW, p, V, {0.0, 0.0, 0.0}};
-    md_ray(tab, (double)(int)(p % (size_t)W), (double)(int)(p / (size_t)W), c.r);
+    tv_view_ray(tab, (double)(int)(p % (size_t)W), (double)(int)(p / (size_t)W), c.r);
 
     // P: the neighbours that see the pixel and have parallax; whether one of them gives a candidate
     uint32_t P = 0;
@@ -234,30 +216,8 @@ __global__ __launch_bounds__(MD_THREADS) void md_depth_kernel(const float* __res
 }
 
 // ---- cotr_depth_consistency -------------------------------------------------------------------------------------------------
-// the cameras of a call: kernel arguments, read at a uniform index
-struct MdCams {
-  EsCam k[MD_MAX_MAPS];
-};
-
-// camera point Y of view m (row-major [R | t] camera-to-world) -> world
-__device__ __forceinline__ void md_to_world(const double* __restrict__ m, const double* Y, double* P) {
-  P[0] = ((m[0] * Y[0] + m[1] * Y[1]) + m[2] * Y[2]) + m[3];
-  P[1] = ((m[4] * Y[0] + m[5] * Y[1]) + m[6] * Y[2]) + m[7];
-  P[2] = ((m[8] * Y[0] + m[9] * Y[1]) + m[10] * Y[2]) + m[11];
-}
-
-// world P in view m: Y = R^T (P - t), and where Y_z > 0 its pixel (u, v), not rounded; cotr_tsdf_integrate's expressions
-__device__ __forceinline__ bool md_to_pixel(const double* __restrict__ m, const EsCam& cam, const double* P, double* Yz, double* u, double* v) {
-  const double dx = P[0] - m[3], dy = P[1] - m[7], dz = P[2] - m[11];
-  const double Yx = (m[0] * dx + m[4] * dy) + m[8] * dz, Yy = (m[1] * dx + m[5] * dy) + m[9] * dz;
-  *Yz = (m[2] * dx + m[6] * dy) + m[10] * dz;
-  if (!(*Yz > 0.0)) return false;   // NaN too
-  const double xn = Yx / *Yz, yn = Yy / *Yz;
-  *u = (cam.fx * xn + cam.s * yn) + cam.cx, *v = cam.fy * yn + cam.cy;
-  return true;
-}
-
-__global__ __launch_bounds__(MD_THREADS) void md_consistency_kernel(const float* __restrict__ depths, int n, int H, int W, MdCams cams,
+// the camera and pose rules are pinhole.h's: es_vertex, es_to_world, es_to_camera, es_project, es_nearest
+__global__ __launch_bounds__(MD_THREADS) void md_consistency_kernel(const float* __restrict__ depths, int n, int H, int W, EsCams cams,
                                                                     const double* __restrict__ c2w, const int32_t* __restrict__ found,
                                                                     const uint8_t* __restrict__ pairs, double px2, double rel, int min_views,
                                                                     int max_violations, float* __restrict__ depth_out,
@@ -275,8 +235,8 @@ __global__ __launch_bounds__(MD_THREADS) void md_consistency_kernel(const float*
   const double* mi = c2w + i * 16;
   const int x = (int)(p % (size_t)W), y = (int)(p / (size_t)W);
   double Y[3], P[3] = {0.0, 0.0, 0.0};
-  const bool ok = in && ic_vertex(depths + (size_t)i * HW, W, ki, x, y, Y);
-  if (ok) md_to_world(mi, Y, P);
+  const bool ok = in && es_vertex(depths + (size_t)i * HW, W, ki, x, y, Y);
+  if (ok) es_to_world(mi, Y, P);
   const double z = ok ? Y[2] : 0.0;
   int consistent = 0, violations = 0;
   double sum = z;
@@ -285,22 +245,22 @@ __global__ __launch_bounds__(MD_THREADS) void md_consistency_kernel(const float*
     if (!ok) continue;
     const EsCam kj = cams.k[j];
     const double* mj = c2w + j * 16;
-    double Yz, u, v;
-    if (!md_to_pixel(mj, kj, P, &Yz, &u, &v)) continue;
-    u = rint(u), v = rint(v);
-    if (!(u >= 0.0 && u < (double)W && v >= 0.0 && v < (double)H)) continue;
-    double Yj[3], Q[3];
-    if (!ic_vertex(depths + (size_t)j * HW, W, kj, (int)u, (int)v, Yj)) continue;
-    md_to_world(mj, Yj, Q);
-    double z2, u2, v2;
-    bool good = md_to_pixel(mi, ki, Q, &z2, &u2, &v2);
+    double Pj[3], u, v;   // P in view j
+    es_to_camera(mj, P, Pj);
+    int xj, yj;
+    if (!es_project(kj, Pj, &u, &v) || !es_nearest(u, v, H, W, &xj, &yj)) continue;
+    double Yj[3], Q[3], Qi[3];   // the vertex of j there, in the world, back in view i
+    if (!es_vertex(depths + (size_t)j * HW, W, kj, xj, yj, Yj)) continue;
+    es_to_world(mj, Yj, Q);
+    es_to_camera(mi, Q, Qi);
+    bool good = es_project(ki, Qi, &u, &v);
     if (good) {
-      const double du = u2 - (double)x, dv = v2 - (double)y;
-      good = du * du + dv * dv <= px2 && fabs(z2 - z) <= rel * z;
+      const double du = u - (double)x, dv = v - (double)y;
+      good = du * du + dv * dv <= px2 && fabs(Qi[2] - z) <= rel * z;
     }
     if (good)
-      ++consistent, sum += z2;
-    else if (Yj[2] > Yz * (1.0 + rel))
+      ++consistent, sum += Qi[2];
+    else if (Yj[2] > Pj[2] * (1.0 + rel))
       ++violations;
   }
   const bool enough = ok && consistent >= min_views;
@@ -366,7 +326,7 @@ int cotr_corr_depth(const float* corr, const uint8_t* valid, const double* cams,
                        {cams, (size_t)V * 40}, {poses, (size_t)V * 96}, {found, 4}};
   if (md_alias(r, 9, 4)) return arg_fail(fn, "an output must not overlap another output or an input");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(md_begin_kernel, dim3(1), dim3(64), 0, s, found, 1, 8, info_out);
+  hipLaunchKernelGGL(hl_begin_kernel<>, dim3(1), dim3(64), 0, s, found, 1, 8, info_out);
   hipLaunchKernelGGL(md_depth_kernel, dim3((unsigned)((HW + MD_THREADS - 1) / MD_THREADS)), dim3(MD_THREADS), 0, s, corr, valid, cams, poses, V, H, W,
                      found, thr, max_cos, distance_thresh, min_views, refine_iters, depth_out, views_out, err_out, info_out);
   return launched();
@@ -384,10 +344,8 @@ int cotr_depth_consistency(const float* depths, int n, int H, int W, const doubl
   if (max_violations < -1 || max_violations > MD_MAX_MAPS - 1) return arg_fail(fn, "max_violations must be in [-1, 31]");
   if (!depths || !Ks || !c2w || !depth_out || !count_out || !info_out)
     return arg_fail(fn, "depths, Ks, c2w, depth_out, count_out and info_out must not be NULL");
-  MdCams cams;
-  for (int c = 0; c < MD_MAX_MAPS; ++c) cams.k[c] = {1.0, 1.0, 0.0, 0.0, 0.0};
-  for (int c = 0; c < n; ++c)
-    if (!es_camera(Ks + c * 9, &cams.k[c])) return arg_fail(fn, "the camera matrices must be finite with focal lengths that are not 0");
+  EsCams cams;
+  if (const char* what = es_cameras(Ks, n, &cams)) return arg_fail(fn, what);
   if (!aligned(depths, 4) || !aligned(c2w, 8) || !aligned(found, 4) || !aligned(depth_out, 4) || !aligned(info_out, 4))
     return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
   const size_t HW = (size_t)H * W, all = (size_t)n * HW;
@@ -395,7 +353,7 @@ int cotr_depth_consistency(const float* depths, int n, int H, int W, const doubl
                        {found, (size_t)n * 4}, {pairs, (size_t)n * n}};
   if (md_alias(r, 7, 3)) return arg_fail(fn, "an output must not overlap another output or an input (depth_out is not depths)");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(md_begin_kernel, dim3(1), dim3(64), 0, s, found, n, 4, info_out);
+  hipLaunchKernelGGL(hl_begin_kernel<>, dim3(1), dim3(64), 0, s, found, n, 4, info_out);
   hipLaunchKernelGGL(md_consistency_kernel, dim3((unsigned)((HW + MD_THREADS - 1) / MD_THREADS), n), dim3(MD_THREADS), 0, s, depths, n, H, W, cams, c2w,
                      found, pairs, px_thresh * px_thresh, rel_thresh, min_views, max_violations, depth_out, count_out, info_out);
   return launched();

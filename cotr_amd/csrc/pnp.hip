@@ -25,7 +25,6 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "camera.h"
 #include "handleless.h"
 #include "pinhole.h"
 #include "ransac.h"
@@ -389,29 +388,28 @@ __global__ __launch_bounds__(64) void pn_finish_kernel(int chunks, const double*
 }
 
 // ---- the lift -------------------------------------------------------------------------------------------------------------
-// One thread per point: the depth at the pixel the point falls in (ties to even), X = z K^-1 (x, y, 1) with the point as
-// it is, then c2w (rows as in camera.h) when given; three NaN outside the map or without a finite depth > 0.
+// One thread per point: the depth at the pixel the point falls in (es_nearest), X = z K^-1 (x, y, 1) with the point as
+// it is (es_ray), then c2w (es_to_world) when given; three NaN outside the map or without a finite depth > 0.
 __global__ __launch_bounds__(256) void pn_lift_kernel(const float* __restrict__ depth, int H, int W, EsCam k, const double* __restrict__ c2w,
                                                       const double* __restrict__ pts, int n, double* __restrict__ out) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   const double x = pts[(size_t)p * 2], y = pts[(size_t)p * 2 + 1];
-  const double rx = rint(x), ry = rint(y);
-  double X = NAN, Y = NAN, Z = NAN;
-  if (rx >= 0.0 && rx < (double)W && ry >= 0.0 && ry < (double)H) {   // false for NaN
-    const double z = (double)depth[(size_t)(int)ry * W + (int)rx];
+  int px, py;
+  double X[3] = {NAN, NAN, NAN};
+  if (es_nearest(x, y, H, W, &px, &py)) {
+    const double z = (double)depth[(size_t)py * W + px];
     if (z > 0.0 && z < INFINITY) {
-      const double yn = (y - k.cy) / k.fy;
-      const double xn = (x - k.cx - k.s * yn) / k.fx;
-      const double cx = xn * z, cy = yn * z;
-      if (c2w) {
-        X = row4(c2w, cx, cy, z), Y = row4(c2w + 4, cx, cy, z), Z = row4(c2w + 8, cx, cy, z);
-      } else {
-        X = cx, Y = cy, Z = z;
-      }
+      double xn, yn;
+      es_ray(k, x, y, &xn, &yn);
+      const double c[3] = {xn * z, yn * z, z};
+      if (c2w)
+        es_to_world(c2w, c, X);
+      else
+        X[0] = c[0], X[1] = c[1], X[2] = c[2];
     }
   }
-  out[(size_t)p * 3] = X, out[(size_t)p * 3 + 1] = Y, out[(size_t)p * 3 + 2] = Z;
+  out[(size_t)p * 3] = X[0], out[(size_t)p * 3 + 1] = X[1], out[(size_t)p * 3 + 2] = X[2];
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------

@@ -19,16 +19,13 @@ using namespace cotr_detail;
 #define TV_MAX_REFINE 64
 #define TV_THREADS 64
 
-// ---- per-view arithmetic (w: the view's row of the table; the pixel, the projection and the solve are in view_table.h) -----
-// d = R^T (x, y, 1) / |R^T (x, y, 1)| with (x, y) the normalised pixel
+// ---- per-view arithmetic (w: the view's row of the table; the pixel, its ray, the projection and the solve are in view_table.h) -----
+// d = tv_view_ray, normalised
 __device__ __forceinline__ void tv_ray(const double* w, const TvPixel& q, double* d) {
-  const EsCam k = {w[0], w[1], w[2], w[3], w[4]};
-  double x, y;
-  es_normalise(k, q.u, q.v, &x, &y);
-  const double* R = w + TV_R;
-  const double r0 = (R[0] * x + R[3] * y) + R[6], r1 = (R[1] * x + R[4] * y) + R[7], r2 = (R[2] * x + R[5] * y) + R[8];
-  const double len = sqrt((r0 * r0 + r1 * r1) + r2 * r2);
-  d[0] = r0 / len, d[1] = r1 / len, d[2] = r2 / len;
+  double r[3];
+  tv_view_ray(w, q.u, q.v, r);
+  const double len = sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+  d[0] = r[0] / len, d[1] = r[1] / len, d[2] = r[2] / len;
 }
 
 // acc[0..5] += I - d d^T (00 01 02 11 12 22), acc[6..8] += (I - d d^T) c = c - d (d . c)

@@ -3,14 +3,14 @@
 // every intermediate is float64.
 //
 // cotr_tsdf_integrate: 2 launches on the caller's stream, whatever the data:
-//   1. ts_begin_kernel          one thread per capture: its info row = {found, 0, 0, 0}
+//   1. hl_begin_kernel          (handleless.h) one thread per capture: its info row = {found, 0, 0, 0}
 //   2. ts_integrate_kernel      one thread per voxel, consecutive lanes on consecutive x; a workgroup walks TS_ROWS runs of 256
 //                               voxels and every thread its captures in order, so the volume is read once and written once
 //                               (where a capture updated it) whatever n is.  The counts of a capture: a ballot per wavefront,
 //                               one integer add of it into the workgroup's LDS counters, and one integer atomic per
 //                               workgroup, capture and counter into info at the end.
 // cotr_tsdf_raycast: 2 launches:
-//   1. ts_begin_kernel          info = {found, 0, 0, 0}
+//   1. hl_begin_kernel          info = {found, 0, 0, 0}
 //   2. ts_raycast_kernel        one thread per pixel, a wavefront on an 8 x 8 pixel tile (a workgroup on 16 x 16), so the 8-corner
 //                               gathers of neighbouring rays share cache lines.  Samples outside the volume's box are skipped
 //                               without a gather, and a ray that has left the box ends: along a ray the coordinates are
@@ -19,7 +19,7 @@
 //                               sample after it is invalid by the rule itself.  The hit and back-face counts: a ballot and one
 //                               integer atomic per wavefront.
 // cotr_tsdf_mesh (marching tetrahedra on the Kuhn split of every cell): 4 launches to count, 1 or 2 more to write:
-//   1. ts_begin_kernel          info = {found, 0, 0, 0}
+//   1. hl_begin_kernel          info = {found, 0, 0, 0}
 //   2. ms_classify_kernel       one thread per voxel: the cell above it is valid, and the inside bits of its 8 corners (2 B a voxel
 //                               of scratch).  A lane reads its column of 4 voxels and takes the column at x + 1 from the next lane.
 //   3. ms_count_kernel          one thread per voxel, blocks of 512 voxels: the 7 live bits of the voxel's edges from the codes of the
@@ -35,13 +35,13 @@
 //   6. ms_pad_kernel            (cap_tris above 0) -1 into the triangle rows past the count.
 // Every position comes from the scan, none from an atomic.
 // The colour volume, float32 [Nz][Ny][Nx][4] = (r, g, b, colour weight), 2 launches each:
-//   cotr_tsdf_color_integrate   ts_begin_kernel, then ts_color_integrate_kernel: ts_integrate_kernel's mapping and counters, a voxel
+//   cotr_tsdf_color_integrate   hl_begin_kernel, then ts_color_integrate_kernel: ts_integrate_kernel's mapping and counters, a voxel
 //                               one 16-byte load and, where a capture coloured it, one 16-byte store.
-//   cotr_tsdf_color_points      ts_begin_kernel, then ts_color_points_kernel: one thread per point (no second launch without points).
-//   cotr_tsdf_color_map         ts_begin_kernel, then ts_color_map_kernel: one thread per pixel on the raycast's tiles.
+//   cotr_tsdf_color_points      hl_begin_kernel, then ts_color_points_kernel: one thread per point (no second launch without points).
+//   cotr_tsdf_color_map         hl_begin_kernel, then ts_color_map_kernel: one thread per pixel on the raycast's tiles.
 //                               Both blend the coloured corners of the point's cell through ts_color_at.
-// Integer atomics only: the same input gives the same bits.  No host waits, no allocation: capturable.  Compiled with
-// -ffp-contract=off.
+// The camera and pose arithmetic is pinhole.h's.  Integer atomics only: the same input gives the same bits.  No host waits, no
+// allocation: capturable.  Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -54,7 +54,7 @@
 
 using namespace cotr_detail;
 
-#define TS_MAX_CAPS 32
+#define TS_MAX_CAPS ES_MAX_CAMS
 #define TS_MAX_VOXELS (1 << 28)
 #define TS_MAX_STEPS 65536
 #define TS_MAX_POINTS (1 << 28)
@@ -67,33 +67,24 @@ struct TsGrid {
 
 // the cameras and observation weights of a call: kernel arguments, read at a uniform index
 struct TsCaps {
-  EsCam k[TS_MAX_CAPS];
+  EsCams cams;
   double w[TS_MAX_CAPS];
 };
-
-__global__ __launch_bounds__(64) void ts_begin_kernel(const int32_t* __restrict__ found, int n, int32_t* __restrict__ info) {
-  const int c = threadIdx.x;
-  if (c >= n) return;
-  info[c * 4] = found ? (found[c] != 0 ? 1 : 0) : 1;
-  info[c * 4 + 1] = info[c * 4 + 2] = info[c * 4 + 3] = 0;
-}
 
 // ---- integration ----------------------------------------------------------------------------------------------------------
 // The voxel centre P seen by capture c (pose m, camera cam): false unless Y_z > 0, the pixel (rint u, rint v) of its projection
 // lies inside the map and the depth z there is finite and > 0; then *pix is that pixel's index in depths ([n][H][W]) and
-// *sdf = z - Y_z.  The one statement of the projection: both integrate kernels call it.
-__device__ __forceinline__ bool ts_project(const double* __restrict__ m, const EsCam& cam, double Px, double Py, double Pz,
-                                           const float* __restrict__ depths, int c, int H, int W, size_t* pix, double* sdf) {
-  const double dx = Px - m[3], dy = Py - m[7], dz = Pz - m[11];
-  const double Yx = (m[0] * dx + m[4] * dy) + m[8] * dz, Yy = (m[1] * dx + m[5] * dy) + m[9] * dz, Yz = (m[2] * dx + m[6] * dy) + m[10] * dz;
-  if (!(Yz > 0.0)) return false;   // NaN too
-  const double xn = Yx / Yz, yn = Yy / Yz;
-  const double u = rint((cam.fx * xn + cam.s * yn) + cam.cx), v = rint(cam.fy * yn + cam.cy);
-  if (!(u >= 0.0 && u < (double)W && v >= 0.0 && v < (double)H)) return false;
-  *pix = ((size_t)c * H + (size_t)(int)v) * W + (size_t)(int)u;
+// *sdf = z - Y_z.  Both integrate kernels call it; the arithmetic is pinhole.h's.
+__device__ __forceinline__ bool ts_project(const double* __restrict__ m, const EsCam& cam, const double* P, const float* __restrict__ depths, int c,
+                                           int H, int W, size_t* pix, double* sdf) {
+  double Y[3], u, v;
+  es_to_camera(m, P, Y);
+  int x, y;
+  if (!es_project(cam, Y, &u, &v) || !es_nearest(u, v, H, W, &x, &y)) return false;
+  *pix = (size_t)c * H * W + (size_t)(y * W + x);
   const double z = (double)depths[*pix];
   if (!(z > 0.0 && z < INFINITY)) return false;
-  *sdf = z - Yz;
+  *sdf = z - Y[2];
   return true;
 }
 
@@ -110,7 +101,7 @@ __global__ __launch_bounds__(256) void ts_integrate_kernel(float* __restrict__ t
     const int idx = (blockIdx.x * TS_ROWS + r) * 256 + threadIdx.x;
     const bool in = idx < total;
     const int row = idx / g.Nx, i = idx - row * g.Nx, k = row / g.Ny, j = row - k * g.Ny;
-    const double Px = g.ox + g.voxel * (double)i, Py = g.oy + g.voxel * (double)j, Pz = g.oz + g.voxel * (double)k;
+    const double P[3] = {g.ox + g.voxel * (double)i, g.oy + g.voxel * (double)j, g.oz + g.voxel * (double)k};
     float T = 0.0f, Wt = 0.0f;
     if (in) T = tsdf[idx], Wt = weight[idx];
     bool touched = false;
@@ -119,7 +110,7 @@ __global__ __launch_bounds__(256) void ts_integrate_kernel(float* __restrict__ t
       bool valid = false, updated = false;
       size_t pix;
       double sdf;
-      if (in && ts_project(c2w + c * 16, caps.k[c], Px, Py, Pz, depths, c, H, W, &pix, &sdf)) {
+      if (in && ts_project(c2w + c * 16, caps.cams.k[c], P, depths, c, H, W, &pix, &sdf)) {
         valid = true;
         if (!(sdf < -trunc)) {
           const double d = fmin(1.0, sdf / trunc), w = caps.w[c];
@@ -161,7 +152,7 @@ __global__ __launch_bounds__(256) void ts_color_integrate_kernel(float4* __restr
     const int idx = (blockIdx.x * TS_ROWS + r) * 256 + threadIdx.x;
     const bool in = idx < total;
     const int row = idx / g.Nx, i = idx - row * g.Nx, k = row / g.Ny, j = row - k * g.Ny;
-    const double Px = g.ox + g.voxel * (double)i, Py = g.oy + g.voxel * (double)j, Pz = g.oz + g.voxel * (double)k;
+    const double P[3] = {g.ox + g.voxel * (double)i, g.oy + g.voxel * (double)j, g.oz + g.voxel * (double)k};
     float4 C = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (in) C = color[idx];
     bool touched = false;
@@ -170,7 +161,7 @@ __global__ __launch_bounds__(256) void ts_color_integrate_kernel(float4* __restr
       bool valid = false, coloured = false;
       size_t pix;
       double sdf;
-      if (in && ts_project(c2w + c * 16, caps.k[c], Px, Py, Pz, depths, c, H, W, &pix, &sdf)) {
+      if (in && ts_project(c2w + c * 16, caps.cams.k[c], P, depths, c, H, W, &pix, &sdf)) {
         valid = true;
         if (!(sdf < -trunc) && !(sdf > trunc)) {
           const uint8_t* __restrict__ p = images + pix * 3;
@@ -251,13 +242,12 @@ __global__ __launch_bounds__(256) void ts_raycast_kernel(const float* __restrict
   int state = 0;               // 1: a hit, 2: ended at a back face
   double s_hit = 0.0, dcz = 0.0, dw[3] = {0.0, 0.0, 0.0};
   if (in && on) {
-    const double yn = ((double)y - ray.k.cy) / ray.k.fy;
-    const double xn = ((double)x - ray.k.cx - ray.k.s * yn) / ray.k.fx;
+    double xn, yn;
+    es_ray(ray.k, (double)x, (double)y, &xn, &yn);
     const double norm = sqrt((xn * xn + yn * yn) + 1.0);
-    const double dcx = xn / norm, dcy = yn / norm;
     dcz = 1.0 / norm;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) dw[a] = (c2w[a * 4] * dcx + c2w[a * 4 + 1] * dcy) + c2w[a * 4 + 2] * dcz;
+    const double dc[3] = {xn / norm, yn / norm, dcz};
+    es_rotate(c2w, dc, dw);
     const double t0 = c2w[3], t1 = c2w[7], t2 = c2w[11];
     bool prev_ok = false, was_in = false;
     double prev_f = 0.0;
@@ -299,11 +289,11 @@ __global__ __launch_bounds__(256) void ts_raycast_kernel(const float* __restrict
         ok = ok && ts_sample(tsdf, weight, g, px, py + g.voxel, pz, &fp[1]) && ts_sample(tsdf, weight, g, px, py - g.voxel, pz, &fm[1]);
         ok = ok && ts_sample(tsdf, weight, g, px, py, pz + g.voxel, &fp[2]) && ts_sample(tsdf, weight, g, px, py, pz - g.voxel, &fm[2]);
         if (ok) {
-          const double gx = fp[0] - fm[0], gy = fp[1] - fm[1], gz = fp[2] - fm[2];
-          const double len = sqrt((gx * gx + gy * gy) + gz * gz);
+          const double gr[3] = {fp[0] - fm[0], fp[1] - fm[1], fp[2] - fm[2]};
+          const double len = sqrt((gr[0] * gr[0] + gr[1] * gr[1]) + gr[2] * gr[2]);
           if (len > 0.0) {     // false for NaN
-#pragma unroll
-            for (int a = 0; a < 3; ++a) nrm[a] = ((c2w[a] * gx + c2w[4 + a] * gy) + c2w[8 + a] * gz) / len;
+            es_unrotate(c2w, gr, nrm);
+            nrm[0] = nrm[0] / len, nrm[1] = nrm[1] / len, nrm[2] = nrm[2] / len;
           }
         }
       }
@@ -367,14 +357,11 @@ __global__ __launch_bounds__(256) void ts_color_map_kernel(const float4* __restr
   unsigned c = 0u;
   bool has = false;
   if (in && on) {
-    const double z = (double)depth[(size_t)y * W + x];
-    if (z > 0.0 && z < INFINITY) {   // false for NaN
-      has = true;
-      const double yn = ((double)y - cam.cy) / cam.fy;
-      const double xn = ((double)x - cam.cx - cam.s * yn) / cam.fx;
-      const double Yx = xn * z, Yy = yn * z;
-      c = ts_color_at(color, g, ((c2w[0] * Yx + c2w[1] * Yy) + c2w[2] * z) + c2w[3], ((c2w[4] * Yx + c2w[5] * Yy) + c2w[6] * z) + c2w[7],
-                      ((c2w[8] * Yx + c2w[9] * Yy) + c2w[10] * z) + c2w[11]);
+    double Y[3], P[3];
+    has = es_vertex(depth, W, cam, x, y, Y);
+    if (has) {
+      es_to_world(c2w, Y, P);
+      c = ts_color_at(color, g, P[0], P[1], P[2]);
     }
   }
   if (in) {
@@ -686,12 +673,10 @@ const char* ts_check_color(const float* color, int Nx, int Ny, int Nz, const dou
 
 // Ks and obs_weight of a call -> caps; the message of the first rule broken, or NULL
 const char* ts_captures(const double* Ks, const double* obs_weight, int n, TsCaps* caps) {
-  for (int c = 0; c < TS_MAX_CAPS; ++c) {
-    caps->k[c] = {1.0, 1.0, 0.0, 0.0, 0.0};
-    caps->w[c] = 1.0;
-  }
+  for (int c = 0; c < TS_MAX_CAPS; ++c) caps->w[c] = 1.0;
+  es_cameras(Ks, 0, &caps->cams);   // every row at its default; a row's camera and weight are then checked together, in row order
   for (int c = 0; c < n; ++c) {
-    if (!es_camera(Ks + c * 9, &caps->k[c])) return "the camera matrices must be finite with focal lengths that are not 0";
+    if (!es_camera(Ks + c * 9, &caps->cams.k[c])) return ES_CAMERAS_WHAT;
     if (obs_weight) {
       if (!(obs_weight[c] > 0.0) || !ts_finite(obs_weight[c])) return "every obs_weight must be finite and > 0";
       caps->w[c] = obs_weight[c];
@@ -721,7 +706,7 @@ int cotr_tsdf_integrate(float* tsdf, float* weight, int Nx, int Ny, int Nz, cons
     return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int total = Nx * Ny * Nz, per_group = 256 * TS_ROWS;
-  hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, n, info_out);
+  hipLaunchKernelGGL(hl_begin_kernel<>, dim3(1), dim3(64), 0, s, found, n, 4, info_out);
   hipLaunchKernelGGL(ts_integrate_kernel, dim3((unsigned)((total + per_group - 1) / per_group)), dim3(256), 0, s, tsdf, weight, g, trunc, depths, n, H,
                      W, caps, c2w, found, max_weight, info_out);
   return launched();
@@ -747,7 +732,7 @@ int cotr_tsdf_raycast(const float* tsdf, const float* weight, int Nx, int Ny, in
   ray.H = H, ray.W = W, ray.steps = (int)steps, ray.near = near, ray.step = step;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned tiles = (unsigned)((W + 15) / 16) * (unsigned)((H + 15) / 16);
-  hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, 1, info_out);
+  hipLaunchKernelGGL(hl_begin_kernel<>, dim3(1), dim3(64), 0, s, found, 1, 4, info_out);
   hipLaunchKernelGGL(ts_raycast_kernel, dim3(tiles), dim3(256), 0, s, tsdf, weight, g, ray, c2w, found, depth_out, normal_out, info_out);
   return launched();
 }
@@ -769,7 +754,7 @@ int cotr_tsdf_color_integrate(float* color, int Nx, int Ny, int Nz, const double
     return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int total = Nx * Ny * Nz, per_group = 256 * TS_ROWS;
-  hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, n, info_out);
+  hipLaunchKernelGGL(hl_begin_kernel<>, dim3(1), dim3(64), 0, s, found, n, 4, info_out);
   hipLaunchKernelGGL(ts_color_integrate_kernel, dim3((unsigned)((total + per_group - 1) / per_group)), dim3(256), 0, s, reinterpret_cast<float4*>(color), g,
                      trunc, depths, images, n, H, W, caps, c2w, found, max_weight, info_out);
   return launched();
@@ -786,7 +771,7 @@ int cotr_tsdf_color_points(const float* color, int Nx, int Ny, int Nz, const dou
   if (!aligned(points, 8) || !aligned(found, 4) || !aligned(info_out, 4))
     return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, 1, info_out);
+  hipLaunchKernelGGL(hl_begin_kernel<>, dim3(1), dim3(64), 0, s, found, 1, 4, info_out);
   if (n > 0)
     hipLaunchKernelGGL(ts_color_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(color), g, points, n, found,
                        rgb_out, valid_out, info_out);
@@ -806,7 +791,7 @@ int cotr_tsdf_color_map(const float* color, int Nx, int Ny, int Nz, const double
     return arg_fail(fn, "floats and int32 must be 4-byte and doubles 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned tiles = (unsigned)((W + 15) / 16) * (unsigned)((H + 15) / 16);
-  hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, 1, info_out);
+  hipLaunchKernelGGL(hl_begin_kernel<>, dim3(1), dim3(64), 0, s, found, 1, 4, info_out);
   hipLaunchKernelGGL(ts_color_map_kernel, dim3(tiles), dim3(256), 0, s, reinterpret_cast<const float4*>(color), g, depth, cam, H, W, c2w, found, rgb_out,
                      info_out);
   return launched();
@@ -874,7 +859,7 @@ int cotr_tsdf_mesh(const float* tsdf, const float* weight, int Nx, int Ny, int N
     return arg_fail(fn, "scratch must be 16-byte aligned and hold cotr_tsdf_mesh_scratch_bytes(Nx, Ny, Nz) bytes");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int total = Nx * Ny * Nz;
-  hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, s, found, 1, info_out);
+  hipLaunchKernelGGL(hl_begin_kernel<>, dim3(1), dim3(64), 0, s, found, 1, 4, info_out);
   const int nrun = (total + MS_THREADS - 1) / MS_THREADS;
   hipLaunchKernelGGL(ms_classify_kernel, dim3((unsigned)std::min(nrun, MS_GRID)), dim3(MS_THREADS), 0, s, tsdf, weight, g, nrun, L.code);
   hipLaunchKernelGGL(ms_count_kernel, dim3((unsigned)std::min(L.nblk, MS_GRID)), dim3(MS_THREADS), 0, s, L.code, g, found, L.nblk, L.rec, L.totals, info_out);

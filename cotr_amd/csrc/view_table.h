@@ -1,6 +1,6 @@
 // The view table of the structure estimators (structure.hip: triangulation with known cameras, bundle.hip: bundle adjustment)
-// and the arithmetic both share: a view's validity, a point's pixel, the projection of a world point and the symmetric 3 x 3
-// solve by cofactors.  Rules in DESIGN.md 3h-6.  Include only from files compiled with -ffp-contract=off.
+// and the arithmetic they share with mvdepth.hip: a view's validity, a point's pixel, a pixel's ray, the projection of a world
+// point and the symmetric 3 x 3 solve by cofactors.  Rules in DESIGN.md 3h-6.  Include only from files compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -26,6 +26,15 @@ __device__ __forceinline__ TvPixel tv_pixel(const double* __restrict__ points, s
   const double2 q = *reinterpret_cast<const double2*>(points + ((size_t)v * N + p) * 2);
   const float uf = (float)q.x, vf = (float)q.y;
   return {(double)uf, (double)vf, isfinite(uf) && isfinite(vf)};
+}
+
+// the ray of pixel (u, v) through the view's centre, in the world and not normalised: R^T (xn, yn, 1), (xn, yn) by es_normalise
+__device__ __forceinline__ void tv_view_ray(const double* w, double u, double v, double* r) {
+  const EsCam k = {w[0], w[1], w[2], w[3], w[4]};
+  double x, y;
+  es_normalise(k, u, v, &x, &y);
+  const double* R = w + TV_R;
+  r[0] = (R[0] * x + R[3] * y) + R[6], r[1] = (R[1] * x + R[4] * y) + R[7], r[2] = (R[2] * x + R[5] * y) + R[8];
 }
 
 // Cofactors c (00 01 02 11 12 22) of the symmetric 3 x 3 matrix m (00 01 02 11 12 22); returns its determinant.
