@@ -1,5 +1,5 @@
 // Host plumbing of the entry points that take no cotr_handle (triangulate.hip, delaunay.hip, warp.hip, reproject.hip, overlap.hip,
-// rotate.hip, tsdf.hip, icp.hip, icp_multi.hip, mvdepth.hip, structure.hip, bundle.hip, and through ransac.h guided.hip,
+// rotate.hip, tsdf.hip, icp.hip, icp_multi.hip, mvdepth.hip, photodepth.hip, structure.hip, bundle.hip, and through ransac.h guided.hip,
 // homography.hip, essential.hip, pnp.hip, rigid3d.hip): a failure is reported through a per-thread message that
 // cotr_raster_last_error() returns (handleless.hip), the scratch of a call is cut into its regions by one Carver,
 // and the calls that count into info_out begin with one kernel (below).
@@ -49,7 +49,7 @@ constexpr int MAX_PIXELS = 1 << 28;
 
 }  // namespace cotr_detail
 
-// The first launch of the calls that count into info_out (tsdf.hip, mvdepth.hip), one workgroup of 64: a thread per row of n <= 64
+// The first launch of the calls that count into info_out (tsdf.hip, mvdepth.hip, photodepth.hip), one workgroup of 64: a thread per row of n <= 64
 // rows of `cols` counters, column 0 = found[row] != 0 (1 without found), the rest 0.  A template (launched as hl_begin_kernel<>)
 // so that only a file that launches it gets a copy: an unused static kernel would be emitted in every file that includes this.
 template <int = 0>

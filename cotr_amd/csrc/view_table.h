@@ -1,5 +1,5 @@
 // The view table of the structure estimators (structure.hip: triangulation with known cameras, bundle.hip: bundle adjustment)
-// and the arithmetic they share with mvdepth.hip: a view's validity, a point's pixel, a pixel's ray, the projection of a world
+// and the arithmetic they share with mvdepth.hip and photodepth.hip: a view's validity, a point's pixel, a pixel's ray, the projection of a world
 // point and the symmetric 3 x 3 solve by cofactors.  Rules in DESIGN.md 3h-6.  Include only from files compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -76,7 +76,7 @@ __device__ __forceinline__ TvProj tv_project(const double* w, const TvPixel& q, 
 
 // ---- the table itself ----------------------------------------------------------------------------------------------------------
 // Row v of the table (the Prepare rule of DESIGN.md 3h-6): camera, pose, centre c = -R^T t and the view's validity -> w.  The one
-// statement of the rule: tv_prepare_kernel writes the rows to global memory, mvdepth.hip builds them in LDS.
+// statement of the rule: tv_prepare_kernel writes the rows to global memory, mvdepth.hip and photodepth.hip build them in LDS.
 __device__ __forceinline__ void tv_view_row(const double* __restrict__ cams, const double* __restrict__ poses, int v, double* w) {
   const double* k = cams + v * 5;
   const double* P = poses + v * 12;
@@ -108,7 +108,7 @@ __device__ __forceinline__ void tv_view_row(const double* __restrict__ cams, con
 // A thread per view: its row -> tab; info[0] = found, info[1..7] = 0.  One workgroup of 64 threads.  File-local (static) on purpose:
 // every translation unit that includes this header gets its own copy, which is what lets the kernel live here, launched by structure.hip
 // and bundle.hip alike, while structure.hip keeps the instructions it had when the kernel was defined there.  A translation unit that
-// keeps no table in global memory (mvdepth.hip) defines TV_NO_PREPARE_KERNEL before the include and gets no copy.
+// keeps no table in global memory (mvdepth.hip, photodepth.hip) defines TV_NO_PREPARE_KERNEL before the include and gets no copy.
 #ifndef TV_NO_PREPARE_KERNEL
 static __global__ __launch_bounds__(64) void tv_prepare_kernel(const double* __restrict__ cams, const double* __restrict__ poses, int V,
                                                         const int32_t* __restrict__ found, double* __restrict__ tab,

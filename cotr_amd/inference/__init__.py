@@ -39,9 +39,11 @@ map (and normals) of its surface seen from a pose, ``track_capture`` ``icp_depth
 of captures against the first and fuses those it placed.  ``depth_from_corr`` turns the correspondence maps of a posed reference view into 1 to 31 posed
 neighbours into its depth map (a depth per pixel voted on over the neighbours and refitted on the reprojection error), ``flow_to_corr`` takes
 ``ZoomEngine.flow``'s map to the pixels it reads, ``filter_depths`` checks 2 to 32 depth maps against each other (``filter_captures`` on captures),
-and ``ZoomEngine.depth_map`` / ``ZoomEngine.fuse_images`` run them from posed photographs to a fused volume."""
+and ``ZoomEngine.depth_map`` / ``ZoomEngine.fuse_images`` run them from posed photographs to a fused volume.  ``refine_depth_photo``
+checks such a depth map against the pixels it describes (a photometric plane sweep around each pixel's depth over the posed neighbour images,
+``to_grey`` of them; ``refine_captures_photo`` on captures), and ``depth_map(..., photo_sweeps=2)`` runs it behind ``depth_from_corr``."""
 from .bundle import bundle_adjust, bundle_adjust_tensors
-from .depth import depth_from_corr, filter_captures, filter_depths, flow_to_corr
+from .depth import depth_from_corr, filter_captures, filter_depths, flow_to_corr, refine_captures_photo, refine_depth_photo, to_grey
 from .essential import find_essential_mat, ransac_essential, recover_pose, refine_pose_tensors, refine_relative_pose, relative_pose
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .homography import find_homography, paste_by_homography, ransac_homography
@@ -67,4 +69,5 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'ransac_rigid3d', 'register_points', 'register_captures', 'register_captures_tensors',
            'icp_depth', 'refine_registration', 'vertex_normal_maps', 'icp_multiview', 'refine_poses',
            'TsdfVolume', 'integrate_depths', 'fuse_captures', 'raycast_volume', 'track_capture', 'extract_mesh', 'write_ply',
-           'integrate_colors', 'sample_colors', 'color_depth_map', 'depth_from_corr', 'flow_to_corr', 'filter_depths', 'filter_captures']
+           'integrate_colors', 'sample_colors', 'color_depth_map', 'depth_from_corr', 'flow_to_corr', 'filter_depths', 'filter_captures',
+           'to_grey', 'refine_depth_photo', 'refine_captures_photo']

@@ -6,7 +6,10 @@ depth map - per pixel one scalar along a known ray, voted on over the neighbours
 ``filter_depths`` is one ``cotr_depth_consistency`` call: 2 to 32 depth maps of one size are checked against each other (the
 geometric-consistency step of multi-view stereo), ``filter_captures`` the same on ``cotr_amd.data.Capture``.
 ``ZoomEngine.depth_map`` and ``ZoomEngine.fuse_images`` run them behind the engine's correspondences and in front of
-``fuse_captures``.  The rules are the library's own.  No CPU fallback."""
+``fuse_captures``.  ``refine_depth_photo`` is one ``cotr_photo_depth`` call of cotr_amd/csrc/photodepth.hip: a depth map is
+checked against the pixels it describes - a few depth hypotheses around each pixel's depth, the one kept at which the patches of
+the posed neighbour images (``to_grey``) look most like the reference's; ``refine_captures_photo`` the same on captures.  The
+rules are the library's own.  No CPU fallback."""
 import numpy as np
 import torch
 
@@ -18,6 +21,7 @@ from ._args import I32, U8
 MAX_VIEWS = _args.MAX_VIEWS
 MAX_PIXELS = 1 << 28
 MAX_REFINE = 64
+MAX_RADIUS, MAX_STEPS, MAX_SWEEPS = 4, 16, 8
 F32 = torch.float32
 
 
@@ -231,3 +235,136 @@ def filter_captures(caps, pairs=None, min_overlap=None, **kw):
     Ks = np.stack([np.asarray(cap.K.cpu() if torch.is_tensor(cap.K) else cap.K, dtype=np.float64) for cap in caps])
     r = filter_depths(depths, Ks, [cap.c2w for cap in caps], pairs=pairs, device=device, **kw)
     return [cap._replace(depth=r['depth'][i]) for i, cap in enumerate(caps)], r
+
+
+# ---- the photometric refinement -------------------------------------------------------------------------------------------------
+def to_grey(images):
+    """uint8 [..., H, W, 3] (RGB) or uint8 [..., H, W] (grey already: passed through), array or device tensor -> uint8 device tensor
+    [..., H, W] by the integer rule (77 R + 150 G + 29 B + 128) >> 8.  A last axis of 3 behind at least two others is the colour."""
+    if not torch.is_tensor(images):
+        images = np.asarray(images)
+    if images.dtype not in (torch.uint8, np.uint8):
+        raise ValueError(f'images must be uint8, got {images.dtype}')
+    if len(images.shape) < 2:
+        raise ValueError(f'images must be [..., H, W, 3] or [..., H, W], got shape {tuple(images.shape)}')
+    _args.no_cpu_tensors('the depth maps run', images)
+    t = on(images, _args.device(images.device if torch.is_tensor(images) else None))
+    return grey_rule(t) if t.dim() >= 3 and t.shape[-1] == 3 else t
+
+
+def grey_rule(rgb):
+    """uint8 tensor [..., 3] -> uint8 [...]: (77 R + 150 G + 29 B + 128) >> 8, where the tensor is"""
+    c = rgb.to(I32)
+    return ((77 * c[..., 0] + 150 * c[..., 1] + 29 * c[..., 2] + 128) >> 8).to(U8)
+
+
+def _check_photo_args(radius, steps, sweeps, rel_step, min_var, min_score, min_views, distance_thresh, K):
+    _args.check_int_range('radius', radius, 1, MAX_RADIUS)
+    _args.check_int_range('steps', steps, 1, MAX_STEPS)
+    _args.check_int_range('sweeps', sweeps, 1, MAX_SWEEPS)
+    _args.check_positive('rel_step', rel_step)
+    if not int(steps) * float(rel_step) < 1:
+        raise ValueError(f'steps * rel_step must be < 1, got {steps} * {rel_step}')
+    _args.check_positive('min_var', min_var)
+    if not -1 <= min_score <= 1:
+        raise ValueError(f'min_score must be in [-1, 1], got {min_score}')
+    _args.check_int_range('min_views', min_views, 1, K)
+    _args.check_distance(distance_thresh)
+
+
+def _enqueue_photo_depth(lib, grey, depth, cams, poses, found, radius, steps, sweeps, rel_step, min_var, min_score, min_views, distance_thresh,
+                         keep_input):
+    """every tensor on the device of ``grey`` already, every argument checked -> the dict of ``refine_depth_photo``"""
+    V, H, W = (int(v) for v in grey.shape)
+    out, score, views, info = _args.empty(grey.device, ((H, W), F32), ((H, W), F32), ((H, W), U8), (8, I32))
+    check_op(lib.cotr_photo_depth(ptr(grey), ptr(depth), ptr(cams), ptr(poses), V, H, W, ptr(found), int(radius), int(steps), int(sweeps),
+                                  float(rel_step), float(min_var), float(min_score), int(min_views), float(distance_thresh),
+                                  1 if keep_input else 0, ptr(out), ptr(score), ptr(views), ptr(info), _lib.current_stream_ptr()),
+             'cotr_photo_depth')
+    return dict(depth=out, score=score, views=views, mask=views > 0, info=info)
+
+
+def refine_depth_photo(depth, img_ref, imgs, K_ref, c2w_ref, Ks, c2ws, radius=2, steps=4, sweeps=3, rel_step=0.004, min_var=4.0,
+                       min_score=0.5, min_views=1, distance_thresh=50.0, keep_input=True, found=None, device=None):
+    """One ``cotr_photo_depth`` call on the current stream: the depth map ``depth`` float32 [H,W] of a reference view (image
+    ``img_ref``, camera ``K_ref`` [3,3] under which depth[y, x] sits at the integer pixel (x, y) - the K that ``depth_from_corr``
+    returns - and pose ``c2w_ref`` [4,4] camera-to-world, both host) refined on the images ``imgs`` of 1 to 31 posed neighbours
+    (``Ks`` [K,3,3] or one [3,3], ``c2ws`` [K,4,4], host).  The images, uint8 [H,W,3] or grey [H,W] of the depth map's size, go
+    through ``to_grey``; arrays or device tensors.  Per pixel with a depth, ``sweeps`` sweeps of 2 ``steps`` + 1 depths around the
+    current one, ``rel_step`` (relative) apart in the first sweep and half as far in each one after: at each depth the
+    (2 ``radius`` + 1)^2 patch, fronto-parallel at that depth, is sampled in every neighbour and scored by its zero-mean
+    normalised cross-correlation with the reference's; the depth with the best mean score over the neighbours that see the whole
+    patch (at least ``min_views`` of them, each with a patch variance of at least ``min_var``) wins, moved by a parabola through
+    its two neighbours.  The result is kept when the last sweep's score is at least ``min_score`` and the depth lies in (0,
+    ``distance_thresh``).  Pixels on the image's rim of ``radius`` pixels, pixels whose own patch has a variance below ``min_var``
+    and pixels not kept hold the depth they came with (``keep_input``) or 0.  ``found`` int [1]: 0 empties the result.
+    -> dict of device tensors: depth float32 [H,W], score float32 [H,W] (NaN: not refined), views uint8 [H,W] (scoring
+    neighbours, 0: not refined), mask bool [H,W] (refined), info int32 [8] = (found, refined, without an input depth, rim, flat,
+    nothing scored, below min_score, dropped by range)."""
+    if not torch.is_tensor(depth):
+        depth = np.asarray(depth)
+    _args.check_depth(depth)
+    H, W = (int(v) for v in depth.shape)
+    imgs = list(imgs)
+    K = len(imgs)
+    if not 1 <= K <= MAX_VIEWS - 1:
+        raise ValueError(f'between 1 and {MAX_VIEWS - 1} neighbour images, got {K}')
+    for name, img in [('img_ref', img_ref)] + [(f'imgs[{k}]', img) for k, img in enumerate(imgs)]:
+        shape = tuple(img.shape) if hasattr(img, 'shape') else np.shape(img)
+        if shape not in ((H, W), (H, W, 3)):
+            raise ValueError(f'{name} must be [{H}, {W}, 3] or [{H}, {W}], the size of the depth map, got shape {shape}')
+        if getattr(img, 'dtype', None) not in (torch.uint8, np.uint8):
+            raise ValueError(f'{name} must be uint8, got {getattr(img, "dtype", type(img))}')
+    k_ref = reference_camera(K_ref)
+    ks, _ = _args.cameras(Ks, K)
+    ref = _args.pose_matrix(c2w_ref)
+    if ref is None:
+        raise ValueError('c2w_ref must be a finite [4, 4] matrix, got None')
+    rows = _args.c2w_rows(c2ws.cpu() if torch.is_tensor(c2ws) else c2ws, K).numpy().reshape(K, 4, 4)
+    _check_photo_args(radius, steps, sweeps, rel_step, min_var, min_score, min_views, distance_thresh, K)
+    if found is not None and int(np.prod(tuple(np.shape(found) if not torch.is_tensor(found) else found.shape))) != 1:
+        raise ValueError('found must be [1]')
+    _args.no_cpu_tensors('the depth maps run', depth, img_ref, found, *imgs)
+    all_k = np.stack([k_ref] + [np.array(k, dtype=np.float64).reshape(3, 3) for k in ks])
+    cams = np.stack([all_k[:, 0, 0], all_k[:, 1, 1], all_k[:, 0, 2], all_k[:, 1, 2], all_k[:, 0, 1]], axis=1)
+    poses = _w2c_rows(np.concatenate([ref[None], rows]))
+    device = _args.device(device)
+    with torch.cuda.device(device):
+        grey = torch.stack([to_grey(on(img, device)) for img in [img_ref] + imgs])
+        return _enqueue_photo_depth(_lib.load_library(), grey, on(_args.tensor(depth, np.float32), device), on(cams, device), on(poses, device),
+                                    _args.found_i32(found, device), radius, steps, sweeps, rel_step, min_var, min_score, min_views,
+                                    distance_thresh, keep_input)
+
+
+def nearest_views(c2ws, i, neighbours):
+    """the ``neighbours`` views whose camera centres are nearest that of view i, the nearer first (the lower index among equals)"""
+    centres = np.asarray(c2ws, dtype=np.float64)[:, :3, 3]
+    d = np.linalg.norm(centres - centres[i], axis=1)
+    d[i] = np.inf
+    return [int(j) for j in np.argsort(d, kind='stable')[:int(neighbours)]]
+
+
+def refine_captures_photo(caps, neighbours=2, **kw):
+    """``refine_depth_photo`` on every one of the posed captures ``caps`` (``cotr_amd.data.Capture`` of one size, each with an
+    image) against the ``neighbours`` captures whose camera centres are nearest its own, the choice of ``ZoomEngine.fuse_images``
+    -> (the captures with their depth replaced by the refined map, a device tensor; the list of ``refine_depth_photo``'s dicts).
+    ``kw``: the other arguments of ``refine_depth_photo``."""
+    caps = list(caps)
+    n = len(caps)
+    if n < 2:
+        raise ValueError(f'refine_captures_photo needs at least two captures, got {n}')
+    _args.check_int_range('neighbours', neighbours, 1, min(n - 1, MAX_VIEWS - 1))
+    if any(cap.image is None for cap in caps):
+        raise ValueError('every capture needs an image')
+    shapes = {tuple(cap.depth.shape) for cap in caps}
+    if len(shapes) != 1:
+        raise ValueError(f'the captures must share one depth-map size, got {sorted(shapes)}')
+    if any(cap.c2w is None for cap in caps):
+        raise ValueError('c2w must be a finite [4, 4] matrix, got None')
+    poses = np.stack([_args.pose_matrix(cap.c2w) for cap in caps])
+    results = []
+    for i, cap in enumerate(caps):
+        near = nearest_views(poses, i, neighbours)
+        results.append(refine_depth_photo(cap.depth, cap.image, [caps[j].image for j in near], cap.K, poses[i], np.stack([np.asarray(
+            caps[j].K.cpu() if torch.is_tensor(caps[j].K) else caps[j].K, dtype=np.float64) for j in near]), poses[near], **kw))
+    return [cap._replace(depth=r['depth']) for cap, r in zip(caps, results)], results

@@ -779,15 +779,18 @@ class ZoomEngine:
         return volume, poses, found
 
     def depth_map(self, img_ref, imgs, K_ref, Ks, c2w_ref, c2ws, dense='flow', max_cycle=THRESHOLD_SPARSE, zoom_ins=np.linspace(0.5, 0.0625, 4),
-                  converge_iters=1, max_corrs=1000, **kw):
+                  converge_iters=1, max_corrs=1000, photo_sweeps=0, photo_kw=None, **kw):
         """The depth map of the posed image ``img_ref`` (camera ``K_ref``, camera-to-world ``c2w_ref``) from its correspondences
         into the posed images ``imgs`` (``Ks``, ``c2ws``; 1 to 31 of them) by ``depth_from_corr``.  ``dense='flow'``: one ``flow``
         call per neighbour, its map taken to pixels by ``flow_to_corr`` and valid where the cycle error is at most ``max_cycle``
         (maps sampled at integer pixels: centres 0.0).  ``dense='sparse'``: one ``cotr_corr_multiscale`` (``zoom_ins``,
         ``converge_iters``, ``max_corrs``) and one ``triangulate_corr(simplices='device', as_tensor=True)`` per neighbour, valid
         where its triangles cover the pixel (maps sampled at pixel centres: centres 0.5).  ``kw``: the other arguments of
-        ``depth_from_corr``.  -> its dict, with corr float32 [K,H,W,2] and valid bool [K,H,W], the maps it was called on."""
-        from .depth import depth_from_corr, flow_to_corr
+        ``depth_from_corr``.  -> its dict, with corr float32 [K,H,W,2] and valid bool [K,H,W], the maps it was called on.
+        ``photo_sweeps`` > 0: ``refine_depth_photo`` with that many sweeps (``photo_kw``: its other arguments) runs on the depth map
+        and the images, which must then share one size, under the cameras the maps were sampled at; depth and mask are the refined
+        ones, ``photo`` is its dict and ``depth_corr`` the map it started from.  0: no such call is made."""
+        from .depth import depth_from_corr, flow_to_corr, reference_camera, refine_depth_photo
         if dense not in ('flow', 'sparse'):
             raise ValueError(f"dense must be 'flow' or 'sparse', got {dense!r}")
         imgs = list(imgs)
@@ -814,6 +817,11 @@ class ZoomEngine:
         kw.setdefault('device', device)
         out = depth_from_corr(corr, K_ref, c2w_ref, Ks, c2ws, valid=valid, **kw)
         out['corr'], out['valid'] = corr, valid
+        if photo_sweeps:
+            ks = np.broadcast_to(np.asarray(Ks, dtype=np.float64), (len(imgs), 3, 3))
+            photo = refine_depth_photo(out['depth'], img_ref, imgs, out['K'], c2w_ref, np.stack([reference_camera(k, kw['centres']) for k in ks]), c2ws,
+                                       sweeps=photo_sweeps, device=kw['device'], **(photo_kw or {}))
+            out.update(depth_corr=out['depth'], depth=photo['depth'], mask=photo['mask'], photo=photo)
         return out
 
     def fuse_images(self, imgs, Ks, c2ws, volume, neighbours=2, filter_kw=None, **kw):
@@ -821,12 +829,13 @@ class ZoomEngine:
         camera-to-world, host) gets a depth map by ``depth_map`` (``kw``) from the ``neighbours`` images whose camera centres are
         nearest its own (the lower index first among equals), the maps are checked against each other by ``filter_depths``
         (``filter_kw``: pairs, px_thresh, rel_thresh, min_views, max_violations), and the captures (image, filtered depth, the
-        camera ``depth_map`` returned, pose) are averaged into ``volume`` by ``fuse_captures``, with the images where the volume
+        camera ``depth_map`` returned, pose; with ``photo_sweeps`` in ``kw`` the maps are refined on the images first) are averaged into
+        ``volume`` by ``fuse_captures``, with the images where the volume
         holds colour -> (volume, depths float32 [n,H,W] on the device: what was fused, info: dict(depth: one int32 [8] of
         ``depth_from_corr`` per image, filter: int32 [n,4] of ``filter_depths``, fused: the list of ``fuse_captures``))."""
         from ..data import Capture
         from . import _args
-        from .depth import filter_depths
+        from .depth import filter_depths, nearest_views
         from .tsdf import fuse_captures
         imgs = [np.ascontiguousarray(img) for img in imgs]
         n = len(imgs)
@@ -838,12 +847,9 @@ class ZoomEngine:
         ks = np.asarray(Ks, dtype=np.float64)
         ks = np.broadcast_to(ks, (n, 3, 3)) if ks.shape == (3, 3) else ks
         poses = _args.c2w_rows(c2ws, n).numpy().reshape(n, 4, 4)
-        centres = poses[:, :3, 3]
         results = []
         for i in range(n):
-            d = np.linalg.norm(centres - centres[i], axis=1)
-            d[i] = np.inf
-            near = [int(j) for j in np.argsort(d, kind='stable')[:int(neighbours)]]
+            near = nearest_views(poses, i, neighbours)
             results.append(self.depth_map(imgs[i], [imgs[j] for j in near], ks[i], ks[near], poses[i], poses[near], **kw))
         kept = filter_depths(torch.stack([r['depth'] for r in results]), np.stack([r['K'] for r in results]), poses, **(filter_kw or {}))
         caps = [Capture(imgs[i], kept['depth'][i], results[i]['K'], poses[i]) for i in range(n)]

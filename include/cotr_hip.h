@@ -1049,6 +1049,51 @@ int cotr_depth_consistency(const float* depths, int n, int H, int W, const doubl
                            const uint8_t* pairs, double px_thresh, double rel_thresh, int min_views, int max_violations,
                            float* depth_out, uint8_t* count_out, int32_t* info_out, cotr_stream stream);
 
+/* ---- photometric refinement of a depth map: a plane sweep around the depth each pixel came with (cotr_amd/csrc/photodepth.hip;
+ *      rules in DESIGN.md 3h-18) ----
+ * The step behind cotr_corr_depth: the depth of a reference pixel is moved to where the patches of the posed neighbour images look
+ * most like the reference's.  The rule is the library's own.  No scratch.  Every intermediate is float64, evaluated as bracketed
+ * below, and no product is contracted into an FMA.
+ *
+ * cotr_photo_depth: V = K + 1 views, view 0 the reference, views 1 .. K its neighbours.  DEVICE pointers: grey [V][H][W] uint8, the
+ *   views' images, all of one size; depth_in [H][W] float32, the reference's depth (a pixel whose entry is not finite and > 0 has
+ *   none); cams [V][5] and poses [V][12] float64 and found int32 [1] or NULL as in cotr_corr_depth.
+ *   Views: validity, centre c_0 and the ray r(x, y) of a reference pixel as in cotr_corr_depth.  When the reference view is not
+ *   valid or found[0] is 0, every output is empty: depth 0, score NaN, views 0, every counter 0.
+ *   Patch of pixel (x, y): the N = (2 R + 1)^2 taps (x + dx, y + dy), dy outer and dx inner, each ascending from -R to R; a_t the
+ *   image of view 0 there.  Sa = sum a_t, Saa = sum a_t a_t in that order (every sum below likewise, starting from 0).  A pixel
+ *   with a tap outside the image is rim; a pixel with Saa - Sa Sa / N < min_var N is flat (rim is tested first).
+ *   Score of a valid neighbour j at the depth s: tap t is the world point X_i = c_0i + s r_i(x + dx, y + dy), whose depth in the
+ *   reference camera is s: the patch is fronto-parallel.  (z, u, v): its depth and pixel in view j by the projection of
+ *   cotr_triangulate_views (u = (fx xn + skew yn) + cx, v = fy yn + cy).  j scores only if every tap has z > 0, 0 <= u <= W - 1
+ *   and 0 <= v <= H - 1.  b_t, the bilinear sample: x0 = max(min(floor u, W - 2), 0), x1 = min(x0 + 1, W - 1), au = u - x0, y0, y1,
+ *   av likewise, g the image of view j; b_t = (1 - av) ((1 - au) g[y0][x0] + au g[y0][x1]) + av ((1 - au) g[y1][x0] + au g[y1][x1]).
+ *   Sb = sum b_t, Sbb = sum b_t b_t, Sab = sum a_t b_t; j scores only if Sbb - Sb Sb / N >= min_var N, and its score is
+ *   (Sab - Sa Sb / N) / sqrt((Saa - Sa Sa / N) (Sbb - Sb Sb / N)).
+ *   f(s): the sum of the scores of the scoring neighbours, ascending in j, over their number n; it exists when n >= min_views.
+ *   Sweep i = 0 .. sweeps - 1 around the centre c_i (c_0 = depth_in): h_i = rel_step / 2^i; the hypotheses s_k = c_i (1 + k h_i),
+ *   k = -steps .. steps.  The winner k* is the k with the largest f that exists; among equal f the smallest |k|, then the
+ *   negative one.  d = 0; when |k*| < steps, f- = f(s_(k*-1)) and f+ = f(s_(k*+1)) both exist and den = (f- - 2 f(s_k*)) + f+ < 0:
+ *   d = 0.5 (f- - f+) / den, clipped to [-0.5, 0.5].  c_(i+1) = c_i (1 + (k* + d) h_i); a sweep in which no f exists leaves the
+ *   centre where it is.
+ *   Finish: a pixel with an input depth that is neither rim nor flat is refined iff an f existed in the last sweep, that sweep's
+ *   f(s_k*) >= min_score and float32(c_sweeps) lies in (0, distance_thresh): depth_out = float32(c_sweeps), score_out =
+ *   float32(f(s_k*)), views_out = n there.  Every other pixel: score NaN, views 0, and depth_out = depth_in when keep_input is 1
+ *   and the pixel has an input depth, else 0.
+ *   -> depth_out, score_out [H][W] float32, views_out [H][W] uint8, info_out [8] int32 = {found, pixels refined, without an input
+ *   depth, rim, flat, without an f in the last sweep, below min_score, dropped by range} (each pixel in the first that applies).
+ *   2 <= V <= 32, 1 <= H, W and H W <= 2^28, 1 <= radius <= 4, 1 <= steps <= 16, 1 <= sweeps <= 8, rel_step > 0 finite with
+ *   steps rel_step < 1, min_var > 0 finite, -1 <= min_score <= 1, 1 <= min_views <= V - 1, distance_thresh > 0 finite, keep_input
+ *   0 or 1.  No output may share a byte with another output or with an input (depth_out is not depth_in): COTR_ERR_ARG.
+ * Stream-ordered, 2 launches whatever the data (a prologue that sets info_out, then a thread a pixel that runs every sweep), no
+ * scratch, no host waits and no allocation (capturable); integer atomics only, and only for info_out; no floating-point sum
+ * crosses a thread: the same input gives the same bits.  Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the
+ * message in cotr_raster_last_error(). */
+int cotr_photo_depth(const uint8_t* grey, const float* depth_in, const double* cams, const double* poses, int V, int H, int W,
+                     const int32_t* found, int radius, int steps, int sweeps, double rel_step, double min_var, double min_score,
+                     int min_views, double distance_thresh, int keep_input, float* depth_out, float* score_out, uint8_t* views_out,
+                     int32_t* info_out, cotr_stream stream);
+
 /* ---- warps of 8-bit images: cv2.remap / cv2.warpPerspective, INTER_LINEAR, BORDER_CONSTANT 0 (cotr_amd/csrc/warp.hip) ----
  * The last host step of demo_single_pair.py:43 (image B warped by triangulate_corr's dense map) and of
  * demo_homography.py:46-49 (a picture pasted through four corners).  Rule in DESIGN.md 3i: OpenCV's 8-bit bilinear remap.
