@@ -205,6 +205,10 @@ _PROTOS = {
     'cotr_bundle_adjust': (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 6 +
                            [ctypes.c_size_t, ctypes.c_void_p]),
+    'cotr_average_rotations': (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_double] * 3 + [ctypes.c_void_p] * 6),
+    'cotr_solve_positions_work_doubles': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'cotr_solve_positions': (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 8),
     'cotr_warp_map': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4),
     'cotr_warp_perspective': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                              ctypes.c_int] + [ctypes.c_void_p] * 4),

@@ -11,6 +11,7 @@ __device__ __forceinline__ int ch_tri(int i, int j) { return i * (i + 1) / 2 + j
 
 // L <- its Cholesky factor, row m <- the forward solve L y = b.  admit(col, pivot), called uniformly with every column's pivot before
 // its square root is taken, says whether to go on; false at the first pivot it refuses (L is then half done).  Ends with a barrier.
+// (global_pose.hip solves one factor for many right-hand sides: ch_forward below puts a fresh one through the same forward solve.)
 template <int THREADS, class Admit>
 __device__ __forceinline__ bool ch_factor(double* L, int m, Admit admit) {
   static_assert(THREADS == 256, "the trailing update runs on a 16 x 16 grid of threads");
@@ -36,6 +37,22 @@ __device__ __forceinline__ bool ch_factor(double* L, int m, Admit admit) {
   }
   __syncthreads();
   return ok;
+}
+
+// A fresh right-hand side b in row m of a factor ch_factor returned true for: row m <- the forward solve L y = b, by the operations
+// ch_factor applies to that row (the division by the column's diagonal entry, then one update per entry by one thread), so the same b
+// gives the bits ch_factor would have left.  Begins and ends with a barrier.
+template <int THREADS>
+__device__ __forceinline__ void ch_forward(double* L, int m) {
+  const int tid = threadIdx.x;
+  for (int col = 0; col < m; ++col) {
+    __syncthreads();
+    const double y = L[ch_tri(m, col)] / L[ch_tri(col, col)];
+    __syncthreads();
+    if (tid == 0) L[ch_tri(m, col)] = y;
+    for (int j = col + 1 + tid; j < m; j += THREADS) L[ch_tri(m, j)] -= y * L[ch_tri(j, col)];
+  }
+  __syncthreads();
 }
 
 // L^T x = y, y in row m -> xs[0 .. m-1] (complete for every thread on return), after ch_factor returned true.  One barrier a column

@@ -41,17 +41,23 @@ neighbours into its depth map (a depth per pixel voted on over the neighbours an
 ``ZoomEngine.flow``'s map to the pixels it reads, ``filter_depths`` checks 2 to 32 depth maps against each other (``filter_captures`` on captures),
 and ``ZoomEngine.depth_map`` / ``ZoomEngine.fuse_images`` run them from posed photographs to a fused volume.  ``refine_depth_photo``
 checks such a depth map against the pixels it describes (a photometric plane sweep around each pixel's depth over the posed neighbour images,
-``to_grey`` of them; ``refine_captures_photo`` on captures), and ``depth_map(..., photo_sweeps=2)`` runs it behind ``depth_from_corr``."""
+``to_grey`` of them; ``refine_captures_photo`` on captures), and ``depth_map(..., photo_sweeps=2)`` runs it behind ``depth_from_corr``.
+``average_rotations`` turns relative rotations over a graph of view pairs into the rotations of 2 to 32 views (a greedy tree, then
+annealed robust steps on the graph; every edge comes back with its residual and inlier flag), ``solve_positions`` places the camera
+centres and the points on the tracks with those rotations (the points eliminated, the smallest eigenvector of the reduced matrix),
+``reconstruct_views_tensors`` chains the two-view poses, both, the triangulation and the bundle adjustment as one device sequence,
+and ``ZoomEngine.reconstruct_views`` runs it from photographs and intrinsics to the poses ``fuse_images`` takes."""
 from .bundle import bundle_adjust, bundle_adjust_tensors
 from .depth import depth_from_corr, filter_captures, filter_depths, flow_to_corr, refine_captures_photo, refine_depth_photo, to_grey
 from .essential import find_essential_mat, ransac_essential, recover_pose, refine_pose_tensors, refine_relative_pose, relative_pose
+from .global_pose import average_rotations, average_rotations_host, solve_positions, solve_positions_host
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .homography import find_homography, paste_by_homography, ransac_homography
 from .icp import icp_depth, refine_registration
 from .icp_multi import icp_multiview, refine_poses, vertex_normal_maps
 from .pnp import lift_pixels, localize, ransac_pnp, rodrigues, solve_pnp_ransac
 from .rigid3d import ransac_rigid3d, register_captures, register_captures_tensors, register_points
-from .structure import reconstruct_tensors, stack_views, triangulate_points, triangulate_points_tensors, triangulate_views
+from .structure import reconstruct_tensors, reconstruct_views_tensors, stack_views, triangulate_points, triangulate_points_tensors, triangulate_views
 from .triangulate import delaunay, triangulate_corr
 from .tsdf import (TsdfVolume, color_depth_map, extract_mesh, fuse_captures, integrate_colors, integrate_depths, raycast_volume, sample_colors,
                    track_capture, write_ply)
@@ -65,7 +71,8 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'refine_pose_tensors', 'refine_relative_pose',
            'lift_pixels', 'ransac_pnp', 'solve_pnp_ransac', 'rodrigues', 'localize',
            'triangulate_views', 'triangulate_points', 'triangulate_points_tensors', 'stack_views', 'reconstruct_tensors',
-           'bundle_adjust', 'bundle_adjust_tensors',
+           'bundle_adjust', 'bundle_adjust_tensors', 'average_rotations', 'average_rotations_host', 'solve_positions', 'solve_positions_host',
+           'reconstruct_views_tensors',
            'ransac_rigid3d', 'register_points', 'register_captures', 'register_captures_tensors',
            'icp_depth', 'refine_registration', 'vertex_normal_maps', 'icp_multiview', 'refine_poses',
            'TsdfVolume', 'integrate_depths', 'fuse_captures', 'raycast_volume', 'track_capture', 'extract_mesh', 'write_ply',

@@ -207,3 +207,105 @@ def reconstruct_tensors(corrs, img_a, img_b, K_a, K_b, c2w_a=None, c2w_b=None, r
         r['mask'] = r['mask'] & inside
     r['corrs'] = c
     return r
+
+
+def _k3(row):
+    """a camera row (fx, fy, cx, cy, skew) -> the [3,3] camera matrix"""
+    fx, fy, cx, cy, s = (float(v) for v in row)
+    return np.array([[fx, s, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+
+
+def _check_blocks(blocks, V):
+    """-> [(anchor, neighbours, points tensor [1 + k, Q, 2] where it was)], every index checked, and the points as they were given"""
+    out, given = [], []
+    if not len(blocks):
+        raise ValueError('reconstruct_views needs at least one block')
+    for block in blocks:
+        if not isinstance(block, (tuple, list)) or len(block) != 3 or not hasattr(block[1], '__len__'):
+            raise ValueError('a block must be (anchor, neighbours, points [1 + neighbours, Q, 2])')
+        a, nbrs, pts = block
+        given.append(pts)
+        nbrs = [int(b) for b in nbrs]
+        t = _args.tensor(pts)
+        if t.dim() != 3 or t.shape[2] != 2 or t.shape[0] != 1 + len(nbrs) or not nbrs:
+            raise ValueError(f'the points of a block must be [1 + neighbours, Q, 2], got shape {tuple(t.shape)} with {len(nbrs)} neighbours')
+        if t.shape[1] < 5:
+            raise ValueError(f'a block needs at least 5 queries, got {t.shape[1]}')
+        if not 0 <= int(a) < V or any(not 0 <= b < V or b == int(a) for b in nbrs) or len(set(nbrs)) != len(nbrs):
+            raise ValueError(f'a block names its anchor and distinct other views in [0, {V}), got anchor {a} and neighbours {nbrs}')
+        out.append((int(a), nbrs, t.to(dtype=torch.float64)))
+    if sum(len(n) for _, n, _ in out) > V * (V - 1):
+        raise ValueError(f'at most V (V - 1) = {V * (V - 1)} view pairs, got {sum(len(n) for _, n, _ in out)}')
+    return out, given
+
+
+def reconstruct_views_tensors(blocks, cameras, V, root=0, pose_kw=None, rotation_kw=None, position_kw=None, bundle_rounds=2, device=None,
+                              **kw):
+    """The poses of ``V`` views (2 to 32) and the points they see from matched query sets alone, as one device sequence with
+    no host wait.  ``blocks``: a list of (anchor view a, neighbour views b_1 .. b_k, points [1 + k, Q, 2] in
+    the layout of ``stack_views``: the anchor's queries, then what each neighbour sees of them); ``cameras`` [V,3,3], one [3,3]
+    or [V,5] rows, host.  Per (anchor, neighbour) ``relative_pose_tensors`` (``pose_kw``; refine_rounds 4 unless given) gives the
+    edge (a, b) its rotation, its inlier count as weight and its found flag; ``average_rotations`` (``rotation_kw``) turns the
+    edges into rotations, ``solve_positions`` (``position_kw``) places the centres on the tracks - a block's queries are the
+    tracks, visible where the two-view inlier masks say - ``triangulate_views`` (``kw``: threshold, min_angle,
+    distance_thresh, refine_iters, robust) fits the points on the resulting poses, and with ``bundle_rounds`` > 0
+    ``bundle_adjust_tensors(rounds=bundle_rounds, fixed_views=(root,))`` refines both.  Every found flag is chained on the
+    device.  -> dict of device tensors: poses float64 [V,3,4] world-to-camera (the root at [I | 0]; NaN translation for a view
+    that was not placed), c2w float64 [V,4,4] (what ``fuse_images`` takes), X float64 [N,3] and mask bool [N] over the N = sum Q
+    tracks in block order, located int32 [V], points float64 [V,N,2] and visible bool [V,N] (the tracks as they were solved),
+    edges int32 [E,2], and the dicts of the steps: pairs (one per edge), rotations, positions, triangulation, bundle."""
+    from .bundle import bundle_adjust_tensors
+    from .essential import relative_pose_tensors
+    from .global_pose import average_rotations, solve_positions
+    _args.check_int_range('V', V, 2, MAX_VIEWS)
+    blocks, given = _check_blocks(blocks, V)
+    rows = _args.cam_rows(cameras, V)
+    if rows.is_cuda:
+        raise ValueError('cameras must be host arrays (the two-view estimators read them on the host)')
+    if int(bundle_rounds) != bundle_rounds or bundle_rounds < 0:
+        raise ValueError(f'bundle_rounds must be an integer >= 0, got {bundle_rounds}')
+    _args.check_int_range('root', root, 0, V - 1)
+    _args.no_cpu_tensors(_SUBJECT, *given)
+    rows = rows.numpy()
+    Ks = [_k3(r) for r in rows]
+    device = _args.device(device)
+    N = sum(int(p.shape[1]) for _, _, p in blocks)
+    points = torch.full((V, N, 2), float('nan'), dtype=torch.float64, device=device)
+    visible = torch.zeros((V, N), dtype=torch.bool, device=device)
+    edges, pairs, at = [], [], 0
+    with torch.cuda.device(device):
+        for a, nbrs, pts in blocks:
+            pts = pts.to(device)
+            Q = int(pts.shape[1])
+            points[a, at:at + Q] = pts[0]
+            for i, b in enumerate(nbrs):
+                pose = relative_pose_tensors(pts[0].contiguous(), pts[1 + i].contiguous(), Ks[a], Ks[b], device=device,
+                                             **dict(dict(refine_rounds=4), **(pose_kw or {})))
+                points[b, at:at + Q] = pts[1 + i]
+                visible[b, at:at + Q] = pose['mask']
+                visible[a, at:at + Q] |= pose['mask']
+                edges.append((a, b))
+                pairs.append(pose)
+            at += Q
+        e = torch.tensor(edges, dtype=torch.int32, device=device)
+        R_rel = torch.stack([p['R'] for p in pairs])
+        weights = torch.stack([p['mask'].sum() for p in pairs]).to(torch.float64)
+        found = torch.stack([p['info'][0] for p in pairs])
+        rot = average_rotations(R_rel, e, V, weights=weights, found=found, root=root, device=device, **(rotation_kw or {}))
+        pos = solve_positions(points, rows, rot['R'], visible=visible, located=rot['located'], found=rot['info'], root=root, device=device,
+                              **(position_kw or {}))
+        tri = triangulate_views(points, rows, pos['poses'], visible=pos['used'], found=pos['info'], device=device, **kw)
+        r = dict(poses=pos['poses'], X=tri['X'], mask=tri['mask'], located=rot['located'], points=points, visible=visible, edges=e, pairs=pairs,
+                 rotations=rot, positions=pos, triangulation=tri)
+        if bundle_rounds > 0:
+            ba = bundle_adjust_tensors(points, rows, pos['poses'], tri['X'], visible=tri['used'] & tri['mask'][None], fixed_views=(root,),
+                                       rounds=int(bundle_rounds), found=tri['info'], device=device,
+                                       **{k: v for k, v in kw.items() if k in ('threshold', 'distance_thresh')})
+            r['poses'], r['X'], r['bundle'] = ba['poses'], ba['X'], ba
+        Rt = r['poses'][:, :, :3].transpose(1, 2)
+        c2w = torch.zeros((V, 4, 4), dtype=torch.float64, device=device)
+        c2w[:, :3, :3] = Rt
+        c2w[:, :3, 3] = -(Rt @ r['poses'][:, :, 3:])[:, :, 0]
+        c2w[:, 3, 3] = 1.0
+        r['c2w'] = c2w
+    return r

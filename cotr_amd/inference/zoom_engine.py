@@ -878,6 +878,43 @@ class ZoomEngine:
             structure_kw = dict(structure_kw, bundle_rounds=bundle_rounds)
         return reconstruct_tensors(np.asarray(corrs), img_a, img_b, K_a, K_b, c2w_a, c2w_b, rule=rule, pose_kw=pose_kw, **structure_kw)
 
+    def reconstruct_views(self, imgs, Ks, span=2, anchors=None, queries=None, grid=16, zoom_ins=np.linspace(0.5, 0.0625, 4), converge_iters=1,
+                          **kw):
+        """From photographs and their intrinsics to poses: every anchor view (``anchors``; None: every view) has its queries
+        (``queries`` [Q,2], or a list with one set per anchor; None: a ``grid`` x ``grid`` lattice over the anchor image, built here
+        because force=True needs explicit queries - it is not the grid ``cotr_corr_multiscale`` would draw for itself) matched into the views within ``span`` of its index by ``cotr_corr_multiscale(..., queries_a=q, force=True)``, one
+        row per query, and ``reconstruct_views_tensors`` (``kw``) turns the blocks into poses and points: the
+        rotations averaged over the graph of view pairs, the centres solved on the tracks, the points triangulated and both
+        bundle-adjusted.  ``Ks`` [V,3,3] or one [3,3].  -> its dict; ``c2w`` is what ``fuse_images`` takes as ``c2ws``."""
+        from .structure import reconstruct_views_tensors, stack_views
+        V = len(imgs)
+        if not 2 <= V <= 32:
+            raise ValueError(f'between 2 and 32 images, got {V}')
+        if int(span) != span or span < 1:
+            raise ValueError(f'span must be an integer >= 1, got {span}')
+        anchors = list(range(V)) if anchors is None else [int(a) for a in anchors]
+        if not anchors or any(not 0 <= a < V for a in anchors):
+            raise ValueError(f'anchors must name views in [0, {V}), got {anchors}')
+        if queries is not None and not isinstance(queries, (list, tuple)):
+            queries = [queries] * len(anchors)
+        if queries is not None and len(queries) != len(anchors):
+            raise ValueError(f'queries must hold one set per anchor ({len(anchors)}), got {len(queries)}')
+        blocks = []
+        for i, a in enumerate(anchors):
+            nbrs = [b for b in range(max(0, a - int(span)), min(V, a + int(span) + 1)) if b != a]
+            if queries is None:
+                H, W = imgs[a].shape[:2]
+                gx, gy = np.meshgrid((np.arange(grid) + 0.5) * W / grid, (np.arange(grid) + 0.5) * H / grid)
+                q = np.stack([gx.reshape(-1), gy.reshape(-1)], axis=1)
+            else:
+                q = np.asarray(queries[i], dtype=np.float64)
+            corrs = [np.asarray(self.cotr_corr_multiscale(imgs[a], imgs[b], zoom_ins, converge_iters, max_corrs=q.shape[0], queries_a=q,
+                                                          force=True)) for b in nbrs]
+            if any(c.shape != (q.shape[0], 4) for c in corrs):
+                raise ValueError(f'anchor {a}: cotr_corr_multiscale must return one row per query ({q.shape[0]}), got {[c.shape for c in corrs]}')
+            blocks.append((a, nbrs, stack_views(corrs)))
+        return reconstruct_views_tensors(blocks, Ks, V, **kw)
+
     @staticmethod
     def _task_objects(shape_a, shape_b, loc_from, loc_to, ident, area_a, area_b, zoom_ins, converge_iters, results, executed,
                       with_ident):

@@ -981,6 +981,82 @@ int cotr_bundle_adjust(const double* points, const uint8_t* visible, const doubl
                        uint8_t* used_out, double* stats_out, int32_t* info_out, void* scratch, size_t scratch_bytes,
                        cotr_stream stream);
 
+/* ---- the poses of N views from pairwise results: rotation averaging and the position solve (cotr_amd/csrc/global_pose.hip;
+ *      rules in DESIGN.md 3h-19) ----
+ * The global step between the two-view poses and the bundle adjustment.  Poses are world-to-camera [R | t], the centre is
+ * C = -R^T t.  The rules are the library's own.  Neither call takes a scratch.  Every intermediate is float64 and no product is
+ * contracted into an FMA.
+ *
+ * cotr_average_rotations: DEVICE pointers: R_rel [E][9] float64 row-major, edges [E][2] int32 = (i, j): x_j ~ R_ij x_i + t_ij, so
+ *   R_j = R_ij R_i (what cotr_recover_pose returns with i as view 1); weights [E] float64 or NULL (every edge 1); found [E] int32
+ *   or NULL.  Repeated and reversed pairs are allowed and each counts.
+ *   Dead edge: an index outside [0, n), i = j, found[e] = 0, a weight that is <= 0 or not finite, a matrix entry that is not
+ *   finite.  The others are live.
+ *   Start: R_root = I, located in round 0.  In round k = 1 .. n - 1 every view not yet located takes R_j = R_ij R_i (through an
+ *   edge (j, i): R_j = R_ji^T R_i) from the live edge of largest weight that joins it to a view located before round k, the
+ *   lowest edge index among equals.  A view never reached is not located: its rotation is NaN and its edges take no part.
+ *   Step k = 0 .. iters - 1, sigma_k = max(sigma_end, sigma0 2^-k): per live edge between located views r_e = log(R_j^T (R_ij R_i))
+ *   and w_e = weight_e / (1 + (|r_e| / sigma_k)^2)^2; log(M): a = the vector of (M - M^T) / 2, s = |a|, c = (trace - 1) / 2,
+ *   theta = atan2(s, c), r = a theta / s where s > 1e-8, r = a below that with c > 0, else theta times the unit vector along the
+ *   column of M + I with the largest diagonal entry.  The step minimises sum w_e |r_e + x_i - x_j|^2 over the located views
+ *   other than the root (the root's x is 0) as ONE system of 3 F <= 93 unknowns, F the located views other than the root in
+ *   index order: the weighted graph Laplacian (x) I_3, right-hand side -w_e r_e at i and +w_e r_e at j, each view's sums over its
+ *   edges in ascending edge index by one thread; Cholesky by columns.  A pivot that is not finite, <= 0 or <= 1e-9 times its
+ *   diagonal entry before the elimination (the relative rule of cotr_icp_multiview) stops the chain: stop reason 2, the
+ *   rotations stay.  No located view other than the root: stop reason 1.  Then R_v <- R_v exp([x_v]x) by the Rodrigues rule of
+ *   cotr_ransac_pnp.
+ *   -> R_out [n][9] float64; edge_out [E][4] float64 = {|r_e| at the output (NaN for an edge that takes no part), w_e of the last
+ *   step taken (weight_e when none was, 0 for an edge that takes no part), live, inlier: takes part and |r_e| <= edge_thresh};
+ *   view_info_out [n][4] int32 = {located, the round it was located in (-1: never), its live edges, its inlier edges};
+ *   info_out [8] int32 = {ok: at least two views located and no pivot refused, located views, live edges, inlier edges, steps
+ *   taken, stop reason (0 ran all, 1, 2), 0, 0}; stats_out [2] float64 = {sum w_e |r_e|^2 at the output in edge order, the
+ *   largest |r_e| over the inliers}.
+ *   2 <= n <= 32, 1 <= E <= n (n - 1), 0 <= root < n, 0 <= iters <= 64, 0 < sigma_end <= sigma0 finite, edge_thresh > 0 finite
+ *   (radians).  One launch of one workgroup whatever the data; all state in LDS.
+ *
+ * cotr_solve_positions: DEVICE pointers: points [V][n][2] float64 (16-byte aligned), visible [V][n] uint8 or NULL, cams [V][5] as
+ *   for cotr_triangulate_views, with its pixel rounding and its ray; R [V][9] float64 (e.g. R_out above); located [V] int32 or
+ *   NULL (every view); found int32 [1] or NULL.  A view is valid when its camera row is finite with focal lengths that are not
+ *   0, its rotation is finite and its entry of located is not 0.  found[0] = 0, or a root that is not valid: every output is 0.
+ *   Ray of observation (v, p): d = R_v^T r / |r|, r the ray of cotr_triangulate_views with R_v.  P = I - d d^T.  Model:
+ *   P_vp (X_p - C_v) = 0 for every observation of the set, C_root = 0.
+ *   The set of round 1: the observations of the valid views that visible admits and whose rounded coordinates are finite; of a
+ *   later round: those of them with depth d . (X_p - C_v) > 0 and atan2(|d x (X_p - C_v)|, depth) <= threshold / sqrt(|fx fy|)
+ *   at the previous round's X and C (a view not placed then has no centre and stays out).  A view other than the root with
+ *   fewer than min_obs observations so counted leaves the set for the round; then a point with fewer than two views, or whose
+ *   A_p = sum_v P_vp (views ascending, one thread) has a determinant that is 0 or not finite (the cofactor rule of
+ *   cotr_triangulate_views), leaves it too.
+ *   Reduced matrix over the placed views other than the root, in index order: S_vw = [v = w] sum_p P_vp - sum_p P_vp A_p^-1 P_wp,
+ *   summed per thread, wavefront and chunk of 2048 points in the fixed order of cotr_bundle_adjust.  mu = 1e-12 times the largest
+ *   diagonal entry of S; Cholesky of S + mu I (a pivot <= 0 or not finite: the call fails, ok = 0, C, the translations and X
+ *   are NaN, the later rounds do nothing).  power_iters steps of inverse iteration x <- y / |y|, y = (S + mu I)^-1 x, from
+ *   x_i = 1 + (i mod 3) / 2 + (i div 3) / 8, normalised; lambda0 = 1 / (x . y) - mu at the last step.  A second run from
+ *   x_i = 1 + ((5 i) mod 7) / 4 - (i div 3) / 16, the start and every y deflated by the first run's vector, gives lambda1.
+ *   X_p = A_p^-1 sum_v P_vp C_v.  Sign: turned round when more observations of the set have negative depth than positive.
+ *   Scale: the root-mean-square distance of the other placed centres from the root is 1.
+ *   -> C_out [V][3] float64 (NaN for a view not placed), poses_out [V][12] = [R | -R C], X_out [n][3] (NaN for a point that
+ *   left the set), used_out [V][n] uint8 (the last round's set), stats_out [4] float64 = {lambda0, lambda1, the cost
+ *   sum |P (X - C)|^2 of the last set at the output scale, 0}, info_out [8] int32 = {ok, observations in the last set, views
+ *   placed (the root included), valid views dropped, points solved, positive depths, negative depths, rounds run}.
+ *   The caller judges ambiguity from lambda1: tracks that do not tie a group of views to the root leave that group free to
+ *   shift and scale, which shows as lambda1 ~ lambda0 ~ 0 while ok stays 1.  With V = 2 the solution is the baseline direction.
+ *   work_out: DEVICE, at least cotr_solve_positions_work_doubles(V, n) float64, 8-byte aligned, an output whose content is the
+ *   call's own: the view rows, the state and counters, the raw centres, A_p^-1 [n][6], the cost per 256 points and the block
+ *   sums [V (V + 1) / 2][chunks][16].
+ *   2 <= V <= 32, 1 <= n <= 2^20, 0 <= root < V, threshold > 0 finite (pixels), 1 <= rounds <= 8, min_obs >= 1,
+ *   1 <= power_iters <= 64.  1 + 6 rounds launches whatever the data.
+ * Both: stream-ordered, no host waits and no allocation (capturable); integer atomics only, every floating-point sum in a fixed
+ * order: the same input gives the same bits.  Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the message in
+ * cotr_raster_last_error(). */
+int cotr_average_rotations(const double* R_rel, const int32_t* edges, const double* weights, const int32_t* found, int n, int E,
+                           int root, int iters, double sigma0, double sigma_end, double edge_thresh, double* R_out,
+                           double* edge_out, int32_t* view_info_out, int32_t* info_out, double* stats_out, cotr_stream stream);
+int cotr_solve_positions_work_doubles(int V, int n, size_t* doubles);
+int cotr_solve_positions(const double* points, const uint8_t* visible, const double* cams, const double* R,
+                         const int32_t* located, int V, int n, const int32_t* found, int root, double threshold, int rounds,
+                         int min_obs, int power_iters, double* C_out, double* poses_out, double* X_out, uint8_t* used_out,
+                         double* stats_out, int32_t* info_out, double* work_out, cotr_stream stream);
+
 /* ---- multi-view depth maps: a depth map from correspondence maps, and the cross-check of depth maps (cotr_amd/csrc/mvdepth.hip;
  *      rules in DESIGN.md 3h-16) ----
  * The step between dense correspondences and the TSDF stack: the correspondence maps of a reference view into its posed
