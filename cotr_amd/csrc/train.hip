@@ -756,19 +756,22 @@ int train_add_drop_ln_fwd(const float* x, const float* a, const float* w, const 
   return LAUNCH_OK();
 }
 
-int train_ln_bwd_parts(int rows) {
-  int per = (rows + 511) / 512;
-  per = (per + 3) / 4 * 4;
-  return (rows + per - 1) / per;
-}
+// Rows a workgroup of the kernels that leave per-workgroup partials (a wavefront takes every 4th row: a multiple of 4), and the
+// number of workgroups = partials.  The size query and the launcher of an op read the same pair, so they cannot drift apart
+// (DESIGN.md 3h-20); rows <= 0: no partials (the queries used to divide by zero there).
+static int rows_per_wg4(int rows, int max_wg) { return ((rows + max_wg - 1) / max_wg + 3) / 4 * 4; }
+static int ln_bwd_rows_per_wg(int rows) { return rows_per_wg4(rows, 512); }
+static int head_bwd_rows_per_wg(int rows) { return rows_per_wg4(rows, 256); }
+static int colsum_rows_per_wg(int M) { return (M + 255) / 256; }
+static int parts_of(int rows, int per) { return rows > 0 ? (rows + per - 1) / per : 0; }
+
+int train_ln_bwd_parts(int rows) { return parts_of(rows, ln_bwd_rows_per_wg(rows)); }
 
 // ds (and da = ds * mask / (1 - p) when da != nullptr); dwb [512] = dgamma | dbeta; part holds train_ln_bwd_parts(rows) * 512
 int train_ln_bwd(const float* dy, const float* s_in, const float* stats, const float* w, float* ds, float* da, float* part,
                  float* dwb, int rows, float p, uint32_t seed, hipStream_t s) {
   if (rows <= 0) return 0;
-  int per = (rows + 511) / 512;
-  per = (per + 3) / 4 * 4;
-  const int nwg = (rows + per - 1) / per;
+  const int per = ln_bwd_rows_per_wg(rows), nwg = train_ln_bwd_parts(rows);
   hipLaunchKernelGGL(ln_bwd_kernel, dim3(nwg), dim3(256), 0, s, dy, s_in, stats, w, ds, da, part, rows, per, train_thresh(p),
                      p > 0.f ? 1.f / (1.f - p) : 1.f, seed, train_salt_ptr());
   if (hipGetLastError() != hipSuccess) return -2;
@@ -865,16 +868,12 @@ int train_relu_drop_bwd(const float* dy, const float* y, float* dx, size_t n, fl
   return LAUNCH_OK();
 }
 
-int train_colsum_parts(int M) {
-  const int per = (M + 255) / 256;
-  return (M + per - 1) / per;
-}
+int train_colsum_parts(int M) { return parts_of(M, colsum_rows_per_wg(M)); }
 
 int train_colsum(const float* x, float* part, float* out, int M, int N, hipStream_t s) {
   if (M <= 0 || N <= 0) return 0;
   if (N % 4 || N > 4096) return -1;
-  const int per = (M + 255) / 256;
-  const int nwg = (M + per - 1) / per;
+  const int per = colsum_rows_per_wg(M), nwg = train_colsum_parts(M);
   hipLaunchKernelGGL(colsum_kernel, dim3(nwg), dim3(256), 0, s, x, part, M, N, per);
   if (hipGetLastError() != hipSuccess) return -2;
   return train_sum_parts(part, nwg, (size_t)N, out, s);
@@ -931,6 +930,18 @@ static bool gemm_tn_use_big(int M, int N, int K) {
   return N % 128 == 0 && K % 128 == 0 && (size_t)N * K >= (size_t)512 * 256 && M >= 2048;
 }
 
+// Rows a split (a multiple of the 32-row step of both kernels) and the number of partials WRITTEN for M > 0 rows: at most
+// train_gemm_tn_splits(M, N, K), which sizes `part`, and fewer where the rounding of `per` makes the last splits empty (M = 4100,
+// N = K = 256: 26 of 32).  train_gemm_tn_parts and train_conv_wgrad_parts launch from this one plan and return its count.
+struct GemmTnPlan {
+  int per, nsplit;
+};
+static GemmTnPlan gemm_tn_plan(int M, int N, int K) {
+  const int splits = train_gemm_tn_splits(M, N, K);
+  const int per = ((M + splits - 1) / splits + 31) / 32 * 32;
+  return GemmTnPlan{per, (M + per - 1) / per};
+}
+
 int train_gemm_tn_splits(int M, int N, int K) {
   if (gemm_tn_use_big(M, N, K)) {
     const int tiles = (N / 128) * (K / 128);
@@ -966,10 +977,8 @@ int train_gemm_tn(const float* A, const float* B, float* part, float* out, float
 int train_gemm_tn_parts(const float* A, const float* B, float* part, int M, int N, int K, int with_colsum, hipStream_t s) {
   if (N % 64 || K % 64 || M < 0) return -1;
   if (M == 0) return 0;
-  const int splits = train_gemm_tn_splits(M, N, K);
-  int per = (M + splits - 1) / splits;
-  per = (per + 31) / 32 * 32;
-  const int nsplit = (M + per - 1) / per;
+  const GemmTnPlan plan = gemm_tn_plan(M, N, K);
+  const int per = plan.per, nsplit = plan.nsplit;
   if (gemm_tn_use_big(M, N, K)) {
     const float* zeros = gemm_zero_buffer();
     if (zeros == nullptr) return -2;
@@ -1000,10 +1009,8 @@ int train_conv_wgrad_parts(const float* dz, const float* x, float* part, int B, 
   const ConvGeo g = conv_geo(B, Hin, Win, Cin, ksize, stride);
   const int M = B * g.Hout * 2 * g.Wout, N = Cout, K = ksize * ksize * Cin;
   if (!gemm_tn_use_big(M, N, K)) return -1;
-  const int splits = train_gemm_tn_splits(M, N, K);
-  int per = (M + splits - 1) / splits;
-  per = (per + 31) / 32 * 32;
-  const int nsplit = (M + per - 1) / per;
+  const GemmTnPlan plan = gemm_tn_plan(M, N, K);
+  const int per = plan.per, nsplit = plan.nsplit;
   const float* zeros = gemm_zero_buffer();
   if (zeros == nullptr) return -2;
   static PerDeviceFlag attr_set;
@@ -1019,18 +1026,12 @@ int train_conv_wgrad_parts(const float* dz, const float* x, float* part, int B, 
   return nsplit;
 }
 
-int train_head_bwd_parts(int rows) {
-  int per = (rows + 255) / 256;
-  per = (per + 3) / 4 * 4;
-  return (rows + per - 1) / per;
-}
+int train_head_bwd_parts(int rows) { return parts_of(rows, head_bwd_rows_per_wg(rows)); }
 
 // dh [rows][256]; dw2 [2][256] and db2 [2] contiguous in `dwb` (514 floats)
 int train_head_bwd(const float* dy, const float* h, const float* w2, float* dh, float* part, float* dwb, int rows, hipStream_t s) {
   if (rows <= 0) return 0;
-  int per = (rows + 255) / 256;
-  per = (per + 3) / 4 * 4;
-  const int nwg = (rows + per - 1) / per;
+  const int per = head_bwd_rows_per_wg(rows), nwg = train_head_bwd_parts(rows);
   hipLaunchKernelGGL(head_bwd_kernel, dim3(nwg), dim3(256), 0, s, dy, h, w2, dh, part, rows, per);
   if (hipGetLastError() != hipSuccess) return -2;
   if (dwb == nullptr) return 0;                          // deferred (train_reduce_jobs)

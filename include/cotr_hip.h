@@ -249,17 +249,24 @@ int cotr_op_posenc(const float* pts, float* y, int n, cotr_stream stream);
  * with dropout active.  All device pointers, fp32, rows of 256 channels unless stated.  Dropout is counter-based
  * (keep = hash(seed, element index) >= p * 2^32): backward kernels recompute the mask from (seed, index), nothing is stored;
  * p == 0 makes every kernel exact (what the gradient goldens pin).  Reductions across workgroups go through `part` scratch and
- * are summed in a fixed order (no atomics: a step is bit-repeatable).  cotr_train_*_parts / _splits give the scratch sizes. */
+ * are summed in a fixed order (no atomics: a step is bit-repeatable).  cotr_train_*_parts / _splits give the scratch sizes.
+ * Alignment: a pointer the kernels access as float4 must be 16-byte aligned (with rows of 256 floats, or a row stride that is a
+ * multiple of 4, every row then is); a pointer they access by scalar needs the 4-byte alignment of a float.  The "alignment of"
+ * line under each prototype says which is which; tests/test_train_guard_gpu.py places every buffer at exactly that and no better.
+ * No entry point checks it: a misaligned float4 pointer is undefined behaviour, not COTR_ERR_ARG. */
 /* y[m] = x[m] + x2[m % mod] (mod == 0: row m): src + pos (transformer.py:147), tgt + query_pos (:192) */
 int cotr_train_add_rowmod(const float* x, const float* x2, int mod, float* y, int rows, cotr_stream stream);
+/* alignment of cotr_train_add_rowmod: x, x2, y 16-byte aligned */
 /* y = LayerNorm(s), s = x + dropout(a) (x may be NULL); s_out (may be NULL) and stats [rows][2] = (mean, rstd) for the backward:
  * transformer.py:154-155,157-158 (encoder), :196-198,200-201 (decoder), :110-111 (decoder.norm with x NULL, p 0) */
 int cotr_train_add_drop_ln_fwd(const float* x, const float* a, const float* w, const float* b, float* s_out, float* y, float* stats,
                                int rows, float p, uint32_t seed, cotr_stream stream);
-int cotr_train_ln_bwd_parts(int rows);
+/* alignment of cotr_train_add_drop_ln_fwd: x, a, w, b, s_out, y 16-byte aligned; stats 4-byte aligned */
+int cotr_train_ln_bwd_parts(int rows);   /* like cotr_train_colsum_parts and cotr_train_head_bwd_parts: 0 for rows <= 0 */
 /* ds = d loss / d s (= dx), da = ds * mask / (1-p) (may be NULL), dwb [512] = dgamma | dbeta; part: parts * 512 floats */
 int cotr_train_ln_bwd(const float* dy, const float* s_in, const float* stats, const float* w, float* ds, float* da, float* part,
                       float* dwb, int rows, float p, uint32_t seed, cotr_stream stream);
+/* alignment of cotr_train_ln_bwd: dy, s_in, w, ds, da 16-byte aligned; stats, part, dwb 4-byte aligned */
 /* Captured (hipGraph) training steps: the seed argument of a dropout launch is baked into the graph, so every training kernel that
  * draws a mask XORs its seed with the word at `salt` (device memory, read at kernel start); the captured step advances that word
  * itself (any device-side add), so each replay draws fresh masks and forward / backward of one step agree.  NULL (default) = the
@@ -270,12 +277,16 @@ int cotr_train_set_dropout_salt(const unsigned int* salt);
 int cotr_train_clear_dropout_salt(const unsigned int* salt);
 /* in place x *= mask / (1-p) (n % 4 == 0); backward of y = dropout(relu(h)): dx = y > 0 ? dy / (1-p) : 0 (p == 0: relu backward) */
 int cotr_train_dropout_fwd(float* x, size_t n, float p, uint32_t seed, cotr_stream stream);
+/* alignment of cotr_train_dropout_fwd: x 16-byte aligned */
 int cotr_train_relu_drop_bwd(const float* dy, const float* y, float* dx, size_t n, float p, cotr_stream stream);
+/* alignment of cotr_train_relu_drop_bwd: dy, y, dx 16-byte aligned */
 /* out[N] = column sums of x [M][N] (bias gradients); part: parts(M) * N floats */
 int cotr_train_colsum_parts(int M);
 int cotr_train_colsum(const float* x, float* part, float* out, int M, int N, cotr_stream stream);
+/* alignment of cotr_train_colsum: x, part 16-byte aligned (N % 4 == 0 keeps every row so); out 4-byte aligned */
 /* dst [C][R] = src [R][C]^T (W^T once per optimiser step, for dX = dY . W on the GEMM kernels) */
 int cotr_train_transpose(const float* src, float* dst, int R, int C, cotr_stream stream);
+/* alignment of cotr_train_transpose: src, dst 4-byte aligned */
 /* Convolution backward of the trainable backbone stages (layer2 / layer3, backbone.py:66-69) by explicit im2col over the NHWC
  * side-by-side activations [B][Hin][2*Win][Cin] (each half padded on its own, like the forward kernels):
  *   col [B*Hout*2*Wout][k*k*Cin] = im2col(x);  wgrad dW [Cout][k*k*Cin] = dz^T . col (cotr_train_gemm_tn);
@@ -283,17 +294,23 @@ int cotr_train_transpose(const float* src, float* dst, int R, int C, cotr_stream
  * cotr_train_scale_rows: out[r][:] = w[r][:] * scale[r] (FrozenBN folded into the weights / unfolded from their gradient);
  * cotr_train_transpose_batched: per batch element dst[C][R] = src[R][C]^T (torch's [Cout][Cin][k*k] <-> packed [Cout][k*k][Cin]) */
 int cotr_train_im2col(const float* x, float* col, int B, int Hin, int Win, int Cin, int ksize, int stride, cotr_stream stream);
+/* alignment of cotr_train_im2col: x, col 16-byte aligned (Cin % 4 == 0) */
 int cotr_train_col2im(const float* dcol, float* dx, int B, int Hin, int Win, int Cin, int ksize, int stride, cotr_stream stream);
+/* alignment of cotr_train_col2im: dcol, dx 16-byte aligned (Cin % 4 == 0) */
 int cotr_train_scale_rows(const float* w, const float* scale, float* out, int rows, int cols, cotr_stream stream);
+/* alignment of cotr_train_scale_rows: w, out 16-byte aligned (cols % 4 == 0); scale 4-byte aligned */
 int cotr_train_transpose_batched(const float* src, float* dst, int batch, int R, int C, cotr_stream stream);
+/* alignment of cotr_train_transpose_batched: src, dst 4-byte aligned */
 /* out [N][K] = A [M][N]^T . B [M][K] (dW = dY^T . X, both row-major, no transposed copies); N, K multiples of 64.
  * colsum != NULL: also colsum [N] = column sums of A (db) from the same pass over dY; it must be out + N*K (one buffer
  * [N*K + N]) so that one launch finishes both.  part: splits(M, N, K) * (N * K + N) floats */
 int cotr_train_gemm_tn_splits(int M, int N, int K);
 int cotr_train_gemm_tn(const float* A, const float* B, float* part, float* out, float* colsum, int M, int N, int K,
                        cotr_stream stream);
+/* alignment of cotr_train_gemm_tn: A, B 16-byte aligned; part, out, colsum 4-byte aligned */
 /* The partials of cotr_train_gemm_tn alone (part [splits][N*K (+ N with with_colsum)]): -> number of partials written (0 for
- * M == 0), < 0 = error.  cotr_train_ln_bwd / cotr_train_head_bwd with dwb == NULL likewise leave their partials unsummed.
+ * M == 0), < 0 = error.  The count can be SMALLER than cotr_train_gemm_tn_splits(M, N, K) - the rows of a split are rounded up to a
+ * multiple of 32 (M = 4100, N = K = 256: 26 of 32) - and the partials past it are not written: sum only the count returned.  cotr_train_ln_bwd / cotr_train_head_bwd with dwb == NULL likewise leave their partials unsummed.
  * cotr_train_reduce_jobs finishes ALL partials of a backward pass in one launch and accumulates them into the gradient buffers
  * (cotr_amd/train_ops.py: GradSink - replaces one reduction launch per weight plus autograd's add_ into .grad):
  *   for each job, each source in order:  dst[perm(e)] += scale[e / row_len] * sum_{p < nparts, in order} part[p * pstride + e]
@@ -312,6 +329,7 @@ typedef struct cotr_reduce_job {
   unsigned row_len, cin, taps, vec;
 } cotr_reduce_job;
 int cotr_train_gemm_tn_parts(const float* A, const float* B, float* part, int M, int N, int K, int with_colsum, cotr_stream stream);
+/* alignment of cotr_train_gemm_tn_parts: A, B 16-byte aligned; part 4-byte aligned */
 /* The same partials for the weight gradient of a convolution WITHOUT its im2col image (round 6): A = dz [B*Hout*2*Wout][Cout], the
  * second operand is gathered from x [B][Hin][2*Win][Cin] by the kernel (zeros where a tap leaves the half) - the bits of
  * cotr_train_im2col + cotr_train_gemm_tn_parts(dz, col, ..., 0).  part as for cotr_train_gemm_tn_parts with M = B*Hout*2*Wout,
@@ -319,10 +337,14 @@ int cotr_train_gemm_tn_parts(const float* A, const float* B, float* part, int M,
  * shapes): form the image and call cotr_train_gemm_tn_parts. */
 int cotr_train_conv_wgrad_parts(const float* dz, const float* x, float* part, int B, int Hin, int Win, int Cin, int Cout, int ksize,
                                 int stride, cotr_stream stream);
+/* alignment of cotr_train_conv_wgrad_parts: dz, x 16-byte aligned; part 4-byte aligned */
 /* out[i] = part[0][i] + part[1][i] + ... in split order (i < n; part [nparts][n]): what cotr_train_gemm_tn does after its partials */
 int cotr_train_sum_parts(const float* part, int nparts, size_t n, float* out, cotr_stream stream);
+/* alignment of cotr_train_sum_parts: part, out 4-byte aligned */
 int cotr_train_reduce_jobs(const cotr_reduce_job* jobs, const cotr_reduce_src* srcs, const unsigned* chunk_job, int njobs, int nchunks,
                            cotr_stream stream);
+/* alignment of cotr_train_reduce_jobs: jobs, srcs 8-byte aligned (they hold pointers), chunk_job 4-byte aligned; inside a job with vec = 1
+ * dst and every part 16-byte aligned and numel, pstride, row_len, cin multiples of 4, with vec = 0 4-byte aligned; scale 4-byte aligned */
 /* torch.optim.Adam's update (train_cotr.py:49-57: betas (0.9, 0.999), eps 1e-8, no weight decay / amsgrad) over EVERY trainable
  * parameter in one launch, on flat gradient / exp_avg / exp_avg_sq buffers of one layout (cotr_amd/training.py: FusedAdam on the
  * GradSink's buffer):  m += (g - m)(1 - b1);  v = v b2 + (1 - b2) g g;  p -= lr[group] / bc1 * m / (sqrt(v) / bc2_sqrt + eps).
@@ -338,6 +360,8 @@ typedef struct cotr_adam_job {
 int cotr_train_adam(const cotr_adam_job* jobs, const unsigned* chunk_job, int nchunks, const float* g, float* m, float* v, const float* lr,
                     int ngroups, double beta1, double beta2, double eps, double bias_correction1, double bias_correction2_sqrt,
                     const float* step, cotr_stream stream);
+/* alignment of cotr_train_adam: jobs 8-byte aligned, chunk_job and step 4-byte aligned, lr a host array; a job with vec = 1 needs p, g + off,
+ * m + off, v + off 16-byte aligned (g, m, v 16-byte aligned and off a multiple of 4), with vec = 0 everything 4-byte aligned */
 /* Every weight-shaped operand of a training step re-derived from the parameters in ONE launch (after the optimiser step): the W^T
  * slices of the dX GEMMs, the packed [Cout][k][k][Cin] convolution weights, the FrozenBN-scaled transposed convolution weights (one
  * fp32 multiply per element, as cotr_train_scale_rows makes).  A job is a batched strided transpose of 32 x 32 tiles:
@@ -352,15 +376,19 @@ typedef struct cotr_perm_job {
   unsigned tile0, tiles_r, tiles_c, pad;
 } cotr_perm_job;
 int cotr_train_perm_jobs(const cotr_perm_job* jobs, const unsigned* tile_job, int njobs, int ntiles, cotr_stream stream);
+/* alignment of cotr_train_perm_jobs: jobs 8-byte aligned, tile_job 4-byte aligned; src, dst, scale inside a job 4-byte aligned */
 /* last corr_embed layer 256 -> 2 (position_encoding.py:23-26): y [nb][nq][2]; backward: dh [rows][256], dwb [514] = dW2 | db2 */
 int cotr_train_head_fwd(const float* x, const float* w, const float* b, float* y, int nb, int nq, cotr_stream stream);
+/* alignment of cotr_train_head_fwd: x, w 16-byte aligned; b, y 4-byte aligned */
 int cotr_train_head_bwd_parts(int rows);
 int cotr_train_head_bwd(const float* dy, const float* h, const float* w2, float* dh, float* part, float* dwb, int rows,
                         cotr_stream stream);
+/* alignment of cotr_train_head_bwd: h, w2, dh 16-byte aligned; dy, part, dwb 4-byte aligned */
 /* o = dropout(softmax(q k^T * qscale)) v per head (8 x 32; q [nb*nq][ldq], k [nb*512][ldk], v [nb*512][ldv]); lse [nb*nq][8]
  * (log2-domain log-sum-exp) for the backward */
 int cotr_train_attention_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo, float* lse,
                              int nb, int nq, float qscale, float p, uint32_t seed, cotr_stream stream);
+/* alignment of cotr_train_attention_fwd: q, k, v, o 16-byte aligned and every ld a multiple of 4; lse 4-byte aligned */
 /* dq [nb*nq][lddq], dk [nb*512][lddk], dv [nb*512][lddv]; delta: nb*nq*8 floats of scratch; o / d_o share ldo.
  * scratch: cotr_train_attention_bwd_scratch(nb, nq) floats or NULL - room for the dQ partials of the one-pass backward when the keys
  * of a head are split over several workgroups (few pairs); without it that shape takes the two-kernel form */
@@ -368,6 +396,8 @@ int cotr_train_attention_bwd(const float* q, int ldq, const float* k, int ldk, c
                              const float* d_o, int ldo, const float* lse, float* delta, float* dq, int lddq, float* dk, int lddk,
                              float* dv, int lddv, int nb, int nq, float qscale, float p, uint32_t seed, float* scratch,
                              cotr_stream stream);
+/* alignment of cotr_train_attention_bwd: q, k, v, o, d_o, dq, dk, dv, scratch 16-byte aligned and every ld a multiple of 4; lse, delta
+ * 4-byte aligned */
 size_t cotr_train_attention_bwd_scratch(int nb, int nq);
 
 /* ---- engine-side input construction (one launch per zoom level) -------------

@@ -23,12 +23,14 @@ import functools
 
 import numpy as np
 
-from tests.guard_arena import Arena
+from tests.guard_arena import Arena, is_fill
 
 In = collections.namedtuple('In', 'name array kind', defaults=(None,))
 Out = collections.namedtuple('Out', 'name dtype shape kind', defaults=(None,))
 Aux = collections.namedtuple('Aux', 'name array kind', defaults=(None,))  # an input a Table points to: placed, not passed
+AuxOut = collections.namedtuple('AuxOut', 'name dtype shape kind', defaults=(None,))  # an output a Table points to: placed, not passed
 Table = collections.namedtuple('Table', 'name dtype shape make kind')      # make(addr) with addr(name) -> int: the array
+Ref = collections.namedtuple('Ref', 'name offset', defaults=(0,))          # the address of a buffer placed by another argument, + offset bytes
 NULL, SCRATCH, SCRATCH_BYTES, STREAM = 'NULL', 'SCRATCH', 'SCRATCH_BYTES', 'STREAM'
 
 Call = collections.namedtuple('Call', 'args expect')
@@ -51,16 +53,18 @@ def size_by_pointer(fn_name, dims):
     return query
 
 
-def place(call, nbytes, device, fill, early_rear_band=0, scratch_shift=0, scratch_bytes=None):
-    """-> (arena, argv, outs): the call's buffers in a fresh arena and the ctypes arguments; outs: name -> (dtype, shape)"""
+def place(call, nbytes, device, fill, early_rear_band=0, scratch_shift=0, scratch_bytes=None, early_outputs=None):
+    """-> (arena, argv, outs): the call's buffers in a fresh arena and the ctypes arguments; outs: name -> (dtype, shape);
+    early_outputs: {output name: bytes by which its rear band starts early} (the control on a buffer that is not ``scratch``)"""
     arena, outs = Arena(device, fill), {}
+    early_outputs = early_outputs or {}
     for a in call.args:
         if isinstance(a, (In, Aux)):
             arena.add_input(a.name, a.array, a.kind)
         elif isinstance(a, Table):
             arena.add_input(a.name, np.zeros(a.shape, a.dtype), a.kind)
-        elif isinstance(a, Out):
-            arena.add_output(a.name, a.dtype, a.shape, kind=a.kind)
+        elif isinstance(a, (Out, AuxOut)):
+            arena.add_output(a.name, a.dtype, a.shape, early_outputs.get(a.name, 0), kind=a.kind)
             outs[a.name] = (np.dtype(a.dtype), tuple(a.shape))
     arena.add('scratch', nbytes, 'scratch', early_rear_band)
     arena.build()
@@ -69,10 +73,12 @@ def place(call, nbytes, device, fill, early_rear_band=0, scratch_shift=0, scratc
             arena.set_input(a.name, np.asarray(a.make(arena.addr), dtype=a.dtype).reshape(a.shape))
     argv = []
     for a in call.args:
-        if isinstance(a, Aux):
+        if isinstance(a, (Aux, AuxOut)):
             continue
         if isinstance(a, (In, Out, Table)):
             argv.append(arena.ptr(a.name))
+        elif isinstance(a, Ref):
+            argv.append(ctypes.c_void_p(arena.addr(a.name) + a.offset))
         elif a is NULL or a is STREAM:
             argv.append(None)
         elif a is SCRATCH:
@@ -91,6 +97,15 @@ def read_outputs(arena, outs):
 def filled(a, fill):
     """every byte of the array is the fill"""
     return bool((np.ascontiguousarray(a).reshape(-1).view(np.uint8) == fill).all())
+
+
+def same_written_bytes(a, fill_a, b, fill_b, what):
+    """two runs' copies of one output: wherever either run wrote (an element that is not its run's fill) the bytes are equal"""
+    both_fill = is_fill(a, fill_a) & is_fill(b, fill_b)
+    ra = np.ascontiguousarray(a).reshape(-1).view(np.uint8).reshape(a.size, a.dtype.itemsize)
+    rb = np.ascontiguousarray(b).reshape(-1).view(np.uint8).reshape(b.size, b.dtype.itemsize)
+    differ = (ra != rb).any(axis=1) & ~both_fill.reshape(-1)
+    assert not differ.any(), f'{what}: {int(differ.sum())} elements differ between fill 0x{fill_a:02X} and 0x{fill_b:02X}, first at {int(np.flatnonzero(differ)[0])}'
 
 
 def opt(present, out):

@@ -16,13 +16,12 @@ int), from fresh arenas, and asserts
 Two controls show that the check sees what it should: with the scratch's rear band moved 256 bytes into the scratch (the library
 is still told the true size, and the whole scratch stays inside the arena) a kernel that writes the end of its last region
 trips the check; and one byte written into a band with a torch index assignment is found and named."""
-import numpy as np
 import pytest
 import torch
 
 from cotr_amd import _lib
 from tests import scratch_guard_cases as sg
-from tests.guard_arena import BAND, GuardError, is_fill
+from tests.guard_arena import BAND, GuardError
 
 pytestmark = pytest.mark.gpu
 
@@ -56,13 +55,7 @@ def run(entry, params, fill):
     return call, arena, sg.read_outputs(arena, outs)
 
 
-def same_written_bytes(a, fill_a, b, fill_b, what):
-    """two runs' copies of one output: wherever either run wrote (an element that is not its run's fill) the bytes are equal"""
-    both_fill = is_fill(a, fill_a) & is_fill(b, fill_b)
-    ra = np.ascontiguousarray(a).reshape(-1).view(np.uint8).reshape(a.size, a.dtype.itemsize)
-    rb = np.ascontiguousarray(b).reshape(-1).view(np.uint8).reshape(b.size, b.dtype.itemsize)
-    differ = (ra != rb).any(axis=1) & ~both_fill.reshape(-1)
-    assert not differ.any(), f'{what}: {int(differ.sum())} elements differ between fill 0x{fill_a:02X} and 0x{fill_b:02X}, first at {int(np.flatnonzero(differ)[0])}'
+same_written_bytes = sg.same_written_bytes
 
 
 @pytest.mark.parametrize('ec', CASES, ids=_id)
