@@ -28,7 +28,7 @@ GEN_DIR = os.path.join(CSRC, 'experimental', 'gen')
 # generated name -> (product source, patch)
 GENERATED = {**{f: (f, f + '.patch') for f in FORKED}, 'common_exp.h': ('common.h', 'common_exp.h.patch')}
 SOURCES = ['gemm.hip', 'gemm_big.hip', 'gemm_wp.hip', 'bottleneck.hip', 'attention.hip', 'pointwise.hip', 'ln_reduce1.hip', 'stem_pool.hip', 'crop_resize.hip',
-           'dense_post.hip', 'ffn.hip', 'ffn_pipe.hip', 'ffn_rows.hip', 'att_rows.hip', 'conv23.hip', 'conv23m.hip', 'expand.hip', 'train.hip', 'attention_train.hip', 'pairs.hip', 'handleless.hip', 'triangulate.hip', 'delaunay.hip', 'guided.hip', 'homography.hip', 'essential.hip', 'pnp.hip', 'rigid3d.hip', 'icp.hip', 'icp_multi.hip', 'tsdf.hip', 'mvdepth.hip', 'photodepth.hip', 'structure.hip', 'bundle.hip', 'global_pose.hip', 'warp.hip', 'reproject.hip', 'overlap.hip', 'rotate.hip', 'api.hip']
+           'dense_post.hip', 'ffn.hip', 'ffn_pipe.hip', 'ffn_rows.hip', 'att_rows.hip', 'conv23.hip', 'conv23m.hip', 'expand.hip', 'train.hip', 'attention_train.hip', 'pairs.hip', 'handleless.hip', 'triangulate.hip', 'delaunay.hip', 'guided.hip', 'homography.hip', 'essential.hip', 'pnp.hip', 'rigid3d.hip', 'icp.hip', 'icp_multi.hip', 'tsdf.hip', 'mvdepth.hip', 'photodepth.hip', 'structure.hip', 'bundle.hip', 'global_pose.hip', 'tracks.hip', 'warp.hip', 'reproject.hip', 'overlap.hip', 'rotate.hip', 'api.hip']
 EXP_SOURCES = [os.path.join('experimental', 'head.hip'), os.path.join('experimental', 'gemm_ln.hip'), os.path.join('experimental', 'gemm_pp.hip'),
                os.path.join('experimental', 'gemm_h2.hip'), os.path.join('experimental', 'attention_h2.hip'), os.path.join('experimental', 'gemm_h2r.hip'),
                os.path.join('experimental', 'linear_rows.hip')]

@@ -46,7 +46,11 @@ checks such a depth map against the pixels it describes (a photometric plane swe
 annealed robust steps on the graph; every edge comes back with its residual and inlier flag), ``solve_positions`` places the camera
 centres and the points on the tracks with those rotations (the points eliminated, the smallest eigenvector of the reduced matrix),
 ``reconstruct_views_tensors`` chains the two-view poses, both, the triangulation and the bundle adjustment as one device sequence,
-and ``ZoomEngine.reconstruct_views`` runs it from photographs and intrinsics to the poses ``fuse_images`` takes."""
+and ``ZoomEngine.reconstruct_views`` runs it from photographs and intrinsics to the poses ``fuse_images`` takes.
+``build_tracks_tensors`` turns the keypoint index pairs of ``mutual_matches`` over many view pairs into multi-view tracks (the
+connected components of the match graph, a view seen twice in conflict; ``build_tracks`` with host arrays),
+``reconstruct_tracks_tensors`` chains the two-view poses, their inlier masks, the tracks and the same tail, and
+``ZoomEngine.reconstruct_keypoints`` runs it from photographs, intrinsics and keypoints."""
 from .bundle import bundle_adjust, bundle_adjust_tensors
 from .depth import depth_from_corr, filter_captures, filter_depths, flow_to_corr, refine_captures_photo, refine_depth_photo, to_grey
 from .essential import find_essential_mat, ransac_essential, recover_pose, refine_pose_tensors, refine_relative_pose, relative_pose
@@ -58,6 +62,7 @@ from .icp_multi import icp_multiview, refine_poses, vertex_normal_maps
 from .pnp import lift_pixels, localize, ransac_pnp, rodrigues, solve_pnp_ransac
 from .rigid3d import ransac_rigid3d, register_captures, register_captures_tensors, register_points
 from .structure import reconstruct_tensors, reconstruct_views_tensors, stack_views, triangulate_points, triangulate_points_tensors, triangulate_views
+from .tracks import build_tracks, build_tracks_tensors, reconstruct_tracks_tensors
 from .triangulate import delaunay, triangulate_corr
 from .tsdf import (TsdfVolume, color_depth_map, extract_mesh, fuse_captures, integrate_colors, integrate_depths, raycast_volume, sample_colors,
                    track_capture, write_ply)
@@ -72,7 +77,7 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'lift_pixels', 'ransac_pnp', 'solve_pnp_ransac', 'rodrigues', 'localize',
            'triangulate_views', 'triangulate_points', 'triangulate_points_tensors', 'stack_views', 'reconstruct_tensors',
            'bundle_adjust', 'bundle_adjust_tensors', 'average_rotations', 'average_rotations_host', 'solve_positions', 'solve_positions_host',
-           'reconstruct_views_tensors',
+           'reconstruct_views_tensors', 'build_tracks', 'build_tracks_tensors', 'reconstruct_tracks_tensors',
            'ransac_rigid3d', 'register_points', 'register_captures', 'register_captures_tensors',
            'icp_depth', 'refine_registration', 'vertex_normal_maps', 'icp_multiview', 'refine_poses',
            'TsdfVolume', 'integrate_depths', 'fuse_captures', 'raycast_volume', 'track_capture', 'extract_mesh', 'write_ply',

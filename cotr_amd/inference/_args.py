@@ -1,5 +1,5 @@
 """The argument rules and allocations every geometry wrapper of this package shares (guided, homography, essential, pnp,
-structure, bundle, rigid3d, icp, icp_multi, tsdf, depth; triangulate and warp for the scratch query and the CPU-tensor refusal): each rule is stated
+structure, bundle, rigid3d, icp, icp_multi, tsdf, depth, tracks; triangulate and warp for the scratch query and the CPU-tensor refusal): each rule is stated
 here once, and a caller passes the words its own message differs by, so every message reads as that wrapper's.
 
 The import rule (tests/test_wrapper_imports_cpu.py): a module of this package imports names that start with an underscore

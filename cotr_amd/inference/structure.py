@@ -254,9 +254,7 @@ def reconstruct_views_tensors(blocks, cameras, V, root=0, pose_kw=None, rotation
     that was not placed), c2w float64 [V,4,4] (what ``fuse_images`` takes), X float64 [N,3] and mask bool [N] over the N = sum Q
     tracks in block order, located int32 [V], points float64 [V,N,2] and visible bool [V,N] (the tracks as they were solved),
     edges int32 [E,2], and the dicts of the steps: pairs (one per edge), rotations, positions, triangulation, bundle."""
-    from .bundle import bundle_adjust_tensors
     from .essential import relative_pose_tensors
-    from .global_pose import average_rotations, solve_positions
     _args.check_int_range('V', V, 2, MAX_VIEWS)
     blocks, given = _check_blocks(blocks, V)
     rows = _args.cam_rows(cameras, V)
@@ -287,25 +285,35 @@ def reconstruct_views_tensors(blocks, cameras, V, root=0, pose_kw=None, rotation
                 edges.append((a, b))
                 pairs.append(pose)
             at += Q
-        e = torch.tensor(edges, dtype=torch.int32, device=device)
-        R_rel = torch.stack([p['R'] for p in pairs])
-        weights = torch.stack([p['mask'].sum() for p in pairs]).to(torch.float64)
-        found = torch.stack([p['info'][0] for p in pairs])
-        rot = average_rotations(R_rel, e, V, weights=weights, found=found, root=root, device=device, **(rotation_kw or {}))
-        pos = solve_positions(points, rows, rot['R'], visible=visible, located=rot['located'], found=rot['info'], root=root, device=device,
-                              **(position_kw or {}))
-        tri = triangulate_views(points, rows, pos['poses'], visible=pos['used'], found=pos['info'], device=device, **kw)
-        r = dict(poses=pos['poses'], X=tri['X'], mask=tri['mask'], located=rot['located'], points=points, visible=visible, edges=e, pairs=pairs,
-                 rotations=rot, positions=pos, triangulation=tri)
-        if bundle_rounds > 0:
-            ba = bundle_adjust_tensors(points, rows, pos['poses'], tri['X'], visible=tri['used'] & tri['mask'][None], fixed_views=(root,),
-                                       rounds=int(bundle_rounds), found=tri['info'], device=device,
-                                       **{k: v for k, v in kw.items() if k in ('threshold', 'distance_thresh')})
-            r['poses'], r['X'], r['bundle'] = ba['poses'], ba['X'], ba
-        Rt = r['poses'][:, :, :3].transpose(1, 2)
-        c2w = torch.zeros((V, 4, 4), dtype=torch.float64, device=device)
-        c2w[:, :3, :3] = Rt
-        c2w[:, :3, 3] = -(Rt @ r['poses'][:, :, 3:])[:, :, 0]
-        c2w[:, 3, 3] = 1.0
-        r['c2w'] = c2w
+        return _enqueue_view_poses(points, visible, rows, edges, pairs, V, root, rotation_kw, position_kw, bundle_rounds, kw, device)
+
+
+def _enqueue_view_poses(points, visible, rows, edges, pairs, V, root, rotation_kw, position_kw, bundle_rounds, kw, device):
+    """What follows the two-view poses, whoever made the tracks (``reconstruct_views_tensors``, ``tracks.reconstruct_tracks_tensors``):
+    points [V,N,2] and visible bool [V,N] on ``device``, ``rows`` the host camera rows, ``edges`` the (i, j) of ``pairs`` (the dicts
+    of ``relative_pose_tensors``), every argument checked, inside ``torch.cuda.device(device)`` -> the dict of
+    ``reconstruct_views_tensors``"""
+    from .bundle import bundle_adjust_tensors
+    from .global_pose import average_rotations, solve_positions
+    e = torch.tensor(edges, dtype=torch.int32, device=device)
+    R_rel = torch.stack([p['R'] for p in pairs])
+    weights = torch.stack([p['mask'].sum() for p in pairs]).to(torch.float64)
+    found = torch.stack([p['info'][0] for p in pairs])
+    rot = average_rotations(R_rel, e, V, weights=weights, found=found, root=root, device=device, **(rotation_kw or {}))
+    pos = solve_positions(points, rows, rot['R'], visible=visible, located=rot['located'], found=rot['info'], root=root, device=device,
+                          **(position_kw or {}))
+    tri = triangulate_views(points, rows, pos['poses'], visible=pos['used'], found=pos['info'], device=device, **kw)
+    r = dict(poses=pos['poses'], X=tri['X'], mask=tri['mask'], located=rot['located'], points=points, visible=visible, edges=e, pairs=pairs,
+             rotations=rot, positions=pos, triangulation=tri)
+    if bundle_rounds > 0:
+        ba = bundle_adjust_tensors(points, rows, pos['poses'], tri['X'], visible=tri['used'] & tri['mask'][None], fixed_views=(root,),
+                                   rounds=int(bundle_rounds), found=tri['info'], device=device,
+                                   **{k: v for k, v in kw.items() if k in ('threshold', 'distance_thresh')})
+        r['poses'], r['X'], r['bundle'] = ba['poses'], ba['X'], ba
+    Rt = r['poses'][:, :, :3].transpose(1, 2)
+    c2w = torch.zeros((V, 4, 4), dtype=torch.float64, device=device)
+    c2w[:, :3, :3] = Rt
+    c2w[:, :3, 3] = -(Rt @ r['poses'][:, :, 3:])[:, :, 0]
+    c2w[:, 3, 3] = 1.0
+    r['c2w'] = c2w
     return r

@@ -915,6 +915,36 @@ class ZoomEngine:
             blocks.append((a, nbrs, stack_views(corrs)))
         return reconstruct_views_tensors(blocks, Ks, V, **kw)
 
+    def reconstruct_keypoints(self, imgs, Ks, keypoints, pairs=None, span=2, zoom_ins=np.linspace(0.5, 0.0625, 4), converge_iters=1, **kw):
+        """From photographs, their intrinsics and a keypoint set [k_v, 2] per view to poses: every view pair (``pairs``, a list
+        of (i, j); None: every i < j <= i + ``span``) takes the two ``cotr_corr_multiscale`` calls of ``guided_match`` (every
+        keypoint of i into j and every keypoint of j into i, force=True) and ``mutual_matches``, whose index pairs
+        ``reconstruct_tracks_tensors`` (``kw``) turns into tracks over all views, poses and points: a keypoint
+        matched from view 0 to 1 and from 1 to 2 is one point seen three times.  ``Ks`` [V,3,3] or one [3,3].  -> its dict."""
+        from .guided import mutual_matches
+        from .tracks import reconstruct_tracks_tensors
+        V = len(imgs)
+        if not 2 <= V <= 32:
+            raise ValueError(f'between 2 and 32 images, got {V}')
+        if len(keypoints) != V:
+            raise ValueError(f'keypoints must hold one set per image ({V}), got {len(keypoints)}')
+        if int(span) != span or span < 1:
+            raise ValueError(f'span must be an integer >= 1, got {span}')
+        if pairs is None:
+            pairs = [(i, j) for i in range(V) for j in range(i + 1, min(V, i + int(span) + 1))]
+        pairs = [(int(i), int(j)) for i, j in pairs]
+        if not pairs or any(not 0 <= i < V or not 0 <= j < V or i == j for i, j in pairs) or len(set(pairs)) != len(pairs):
+            raise ValueError(f'pairs must name distinct pairs of two different views in [0, {V}), got {pairs}')
+        kps = [np.asarray(k, dtype=np.float64) for k in keypoints]
+        pair_matches = {}
+        for i, j in pairs:
+            corrs_i_j = self.cotr_corr_multiscale(imgs[i], imgs[j], zoom_ins, converge_iters, max_corrs=kps[i].shape[0], queries_a=kps[i],
+                                                  force=True)
+            corrs_j_i = self.cotr_corr_multiscale(imgs[j], imgs[i], zoom_ins, converge_iters, max_corrs=kps[j].shape[0], queries_a=kps[j],
+                                                  force=True)
+            pair_matches[(i, j)] = mutual_matches(corrs_i_j, corrs_j_i, kps[i], kps[j])
+        return reconstruct_tracks_tensors(kps, pair_matches, Ks, **kw)
+
     @staticmethod
     def _task_objects(shape_a, shape_b, loc_from, loc_to, ident, area_a, area_b, zoom_ins, converge_iters, results, executed,
                       with_ident):

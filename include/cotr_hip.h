@@ -1087,6 +1087,48 @@ int cotr_solve_positions(const double* points, const uint8_t* visible, const dou
                          int min_obs, int power_iters, double* C_out, double* poses_out, double* X_out, uint8_t* used_out,
                          double* stats_out, int32_t* info_out, double* work_out, cotr_stream stream);
 
+/* ---- multi-view tracks from pairwise keypoint matches (cotr_amd/csrc/tracks.hip; rules in DESIGN.md 3h-21) ----
+ * The step between the keypoint index pairs of cotr_nearest_mutual and the N-view calls above, which consume tracks: points
+ * [V][n][2] and visible [V][n].  All arithmetic is on integers.  The call takes no scratch.
+ *
+ * cotr_build_tracks: a node is one keypoint of one view; nodes are numbered view by view: node g belongs to view v when
+ *   offsets[v] <= g < offsets[v + 1], K = offsets[V].  DEVICE pointers: offsets [V + 1] int32, non-decreasing from 0 (a view
+ *   may have no keypoints); matches [M][2] int32, global node ids; keep [M] uint8 or NULL (all ones; e.g. the two-view inlier
+ *   masks); keypoints [K][2] float64 or NULL.
+ *   Dead match: an id outside [0, K), both ids in one view (a = b included), or keep[m] = 0.  Repeated and reversed matches are
+ *   allowed.  A node with at least one live match is touched; the others belong to nothing.
+ *   Component: a connected component of the live matches over the touched nodes; its label is its smallest node id.
+ *   Conflict: view v is in conflict in a component that holds two different nodes of v.  conflict = 0 ("drop"): a component
+ *   with any view in conflict is not a track.  conflict = 1 ("views"): the views in conflict are taken out of it and the rest
+ *   goes on.
+ *   Track: a component that survives the conflict rule and has at least min_views views left.  Tracks are numbered in
+ *   ascending label; track t < cap is written, tracks from cap on are only counted.
+ *   -> track_of_node [K] int32: the track of each observation written (-1 for an untouched node, a node of a view in conflict,
+ *   a node of a component that is no track, or a track >= cap); node_out [V][cap] int32: the keypoint index local to its view,
+ *   or -1; visible_out [V][cap] uint8; points_out [V][cap][2] float64, NULL exactly when keypoints is NULL: the keypoint, or
+ *   NaN where not visible; info_out [8] int32 = {tracks found (the cap not applied), tracks written, observations written,
+ *   live matches, components, components with a view in conflict, components that survive the conflict rule but keep fewer
+ *   than min_views views, views of the longest written track}.  Under conflict = 1 a component can count in both [5] and [6].
+ *   Columns info[1] .. cap - 1 are written as empty (-1, 0, NaN), so a later call can take all cap columns at a fixed shape
+ *   with no host wait.  With cap = 0 the three [V][cap] outputs are not touched and may be NULL, as may matches with M = 0.
+ *   offsets cannot be checked on the host.  The view of node g is found by a binary search over entries 1 .. V - 1 that stays
+ *   in [0, V) whatever the table holds: it is the largest v with offsets[v] <= g when the table is non-decreasing, and some
+ *   view in range, the same on every call, when it is not.  Every rule above then holds with that assignment, every write
+ *   stays inside the outputs, and node_out = g - offsets[view] is only meaningful for a table that is non-decreasing from 0.
+ *   work_out: DEVICE, at least cotr_build_tracks_work_ints(K, M) int32, 4-byte aligned, an output whose content is the call's
+ *   own, each region on its own 256 bytes from the start: the parents [K] (at the end the position of a root's track within
+ *   its 256 nodes, or -1), the labels [K], the seen and the conflict masks [K] each, the touched flags [K] uint8, the block
+ *   sums [ceil(K / 256)], 8 counters.
+ *   2 <= V <= 32, 1 <= K <= 2^21, 0 <= M <= 2^24, 2 <= min_views <= V, 0 <= cap <= K / 2.  M = 0 is legal and yields no tracks.
+ *   int32 pointers 4-byte, float64 pointers 8-byte aligned.
+ * Stream-ordered, 7 launches whatever the data, no cooperative launch, no host waits and no allocation (capturable); integer
+ * atomics only: the same input gives the same bits, whatever the order of the matches.  Bad arguments are checked before any
+ * HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_build_tracks_work_ints(int K, int M, size_t* ints);
+int cotr_build_tracks(const int32_t* offsets, const int32_t* matches, const uint8_t* keep, const double* keypoints, int V, int K,
+                      int M, int min_views, int conflict, int cap, int32_t* track_of_node, int32_t* node_out,
+                      uint8_t* visible_out, double* points_out, int32_t* info_out, int32_t* work_out, cotr_stream stream);
+
 /* ---- multi-view depth maps: a depth map from correspondence maps, and the cross-check of depth maps (cotr_amd/csrc/mvdepth.hip;
  *      rules in DESIGN.md 3h-16) ----
  * The step between dense correspondences and the TSDF stack: the correspondence maps of a reference view into its posed
