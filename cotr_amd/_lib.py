@@ -211,6 +211,8 @@ _PROTOS = {
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 8),
     'cotr_build_tracks_work_ints': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     'cotr_build_tracks': (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 7),
+    'cotr_detect_keypoints_work_bytes': (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_size_t)]),
+    'cotr_detect_keypoints': (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 7 + [ctypes.c_double] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 6),
     'cotr_warp_map': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4),
     'cotr_warp_perspective': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                              ctypes.c_int] + [ctypes.c_void_p] * 4),

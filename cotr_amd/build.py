@@ -28,14 +28,14 @@ GEN_DIR = os.path.join(CSRC, 'experimental', 'gen')
 # generated name -> (product source, patch)
 GENERATED = {**{f: (f, f + '.patch') for f in FORKED}, 'common_exp.h': ('common.h', 'common_exp.h.patch')}
 SOURCES = ['gemm.hip', 'gemm_big.hip', 'gemm_wp.hip', 'bottleneck.hip', 'attention.hip', 'pointwise.hip', 'ln_reduce1.hip', 'stem_pool.hip', 'crop_resize.hip',
-           'dense_post.hip', 'ffn.hip', 'ffn_pipe.hip', 'ffn_rows.hip', 'att_rows.hip', 'conv23.hip', 'conv23m.hip', 'expand.hip', 'train.hip', 'attention_train.hip', 'pairs.hip', 'handleless.hip', 'triangulate.hip', 'delaunay.hip', 'guided.hip', 'homography.hip', 'essential.hip', 'pnp.hip', 'rigid3d.hip', 'icp.hip', 'icp_multi.hip', 'tsdf.hip', 'mvdepth.hip', 'photodepth.hip', 'structure.hip', 'bundle.hip', 'global_pose.hip', 'tracks.hip', 'warp.hip', 'reproject.hip', 'overlap.hip', 'rotate.hip', 'api.hip']
+           'dense_post.hip', 'ffn.hip', 'ffn_pipe.hip', 'ffn_rows.hip', 'att_rows.hip', 'conv23.hip', 'conv23m.hip', 'expand.hip', 'train.hip', 'attention_train.hip', 'pairs.hip', 'handleless.hip', 'triangulate.hip', 'delaunay.hip', 'guided.hip', 'homography.hip', 'essential.hip', 'pnp.hip', 'rigid3d.hip', 'icp.hip', 'icp_multi.hip', 'tsdf.hip', 'mvdepth.hip', 'photodepth.hip', 'structure.hip', 'bundle.hip', 'global_pose.hip', 'tracks.hip', 'keypoints.hip', 'warp.hip', 'reproject.hip', 'overlap.hip', 'rotate.hip', 'api.hip']
 EXP_SOURCES = [os.path.join('experimental', 'head.hip'), os.path.join('experimental', 'gemm_ln.hip'), os.path.join('experimental', 'gemm_pp.hip'),
                os.path.join('experimental', 'gemm_h2.hip'), os.path.join('experimental', 'attention_h2.hip'), os.path.join('experimental', 'gemm_h2r.hip'),
                os.path.join('experimental', 'linear_rows.hip')]
 # Pillow-exact resamples and the torch-CPU-exact cycle map (8-bit, float and double code whose products must not be contracted into
 # FMAs behind the source's back; the FMAs that belong there are explicit)
 EXTRA_FLAGS = {'crop_resize.hip': ['-ffp-contract=off'], 'dense_post.hip': ['-ffp-contract=off'],
-               'triangulate.hip': ['-ffp-contract=off'], 'delaunay.hip': ['-ffp-contract=off'], 'guided.hip': ['-ffp-contract=off'], 'homography.hip': ['-ffp-contract=off'], 'essential.hip': ['-ffp-contract=off'], 'pnp.hip': ['-ffp-contract=off'], 'rigid3d.hip': ['-ffp-contract=off'], 'icp.hip': ['-ffp-contract=off'], 'icp_multi.hip': ['-ffp-contract=off'], 'tsdf.hip': ['-ffp-contract=off'], 'mvdepth.hip': ['-ffp-contract=off'], 'photodepth.hip': ['-ffp-contract=off'], 'structure.hip': ['-ffp-contract=off'], 'bundle.hip': ['-ffp-contract=off'], 'global_pose.hip': ['-ffp-contract=off'], 'warp.hip': ['-ffp-contract=off'],
+               'triangulate.hip': ['-ffp-contract=off'], 'delaunay.hip': ['-ffp-contract=off'], 'guided.hip': ['-ffp-contract=off'], 'homography.hip': ['-ffp-contract=off'], 'essential.hip': ['-ffp-contract=off'], 'pnp.hip': ['-ffp-contract=off'], 'rigid3d.hip': ['-ffp-contract=off'], 'icp.hip': ['-ffp-contract=off'], 'icp_multi.hip': ['-ffp-contract=off'], 'tsdf.hip': ['-ffp-contract=off'], 'mvdepth.hip': ['-ffp-contract=off'], 'photodepth.hip': ['-ffp-contract=off'], 'structure.hip': ['-ffp-contract=off'], 'bundle.hip': ['-ffp-contract=off'], 'global_pose.hip': ['-ffp-contract=off'], 'keypoints.hip': ['-ffp-contract=off'], 'warp.hip': ['-ffp-contract=off'],
                'reproject.hip': ['-ffp-contract=off'], 'overlap.hip': ['-ffp-contract=off'], 'rotate.hip': ['-ffp-contract=off'],
                # att_rows.hip: matrix-instruction results in VGPRs, not AccVGPRs - its softmax VALU sits between the matrix instructions of ONE
                # wavefront per SIMD, and any AccVGPR access (v_accvgpr_read / write) waits for the matrix instruction in flight: with the scores in

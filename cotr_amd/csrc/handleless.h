@@ -1,5 +1,5 @@
 // Host plumbing of the entry points that take no cotr_handle (triangulate.hip, delaunay.hip, warp.hip, reproject.hip, overlap.hip,
-// rotate.hip, tsdf.hip, icp.hip, icp_multi.hip, mvdepth.hip, photodepth.hip, structure.hip, bundle.hip, tracks.hip, and through ransac.h guided.hip,
+// rotate.hip, tsdf.hip, icp.hip, icp_multi.hip, mvdepth.hip, photodepth.hip, structure.hip, bundle.hip, tracks.hip, keypoints.hip, and through ransac.h guided.hip,
 // homography.hip, essential.hip, pnp.hip, rigid3d.hip): a failure is reported through a per-thread message that
 // cotr_raster_last_error() returns (handleless.hip), the scratch of a call is cut into its regions by one Carver,
 // and the calls that count into info_out begin with one kernel (below).

@@ -50,13 +50,17 @@ and ``ZoomEngine.reconstruct_views`` runs it from photographs and intrinsics to 
 ``build_tracks_tensors`` turns the keypoint index pairs of ``mutual_matches`` over many view pairs into multi-view tracks (the
 connected components of the match graph, a view seen twice in conflict; ``build_tracks`` with host arrays),
 ``reconstruct_tracks_tensors`` chains the two-view poses, their inlier masks, the tracks and the same tail, and
-``ZoomEngine.reconstruct_keypoints`` runs it from photographs, intrinsics and keypoints."""
+``ZoomEngine.reconstruct_keypoints`` runs it from photographs, intrinsics and keypoints.  ``detect_keypoints_tensors`` makes those
+keypoints (a corner score on the integer structure tensor of 8-bit images, non-maximum suppression and the best K under a total
+order, sub-pixel positions; defined exactly), ``detect_keypoints`` is its host form, and ``ZoomEngine.detect_keypoints`` the
+same on the engine: ``guided_match`` and ``reconstruct_keypoints`` call it when they are given no keypoints."""
 from .bundle import bundle_adjust, bundle_adjust_tensors
 from .depth import depth_from_corr, filter_captures, filter_depths, flow_to_corr, refine_captures_photo, refine_depth_photo, to_grey
 from .essential import find_essential_mat, ransac_essential, recover_pose, refine_pose_tensors, refine_relative_pose, relative_pose
 from .global_pose import average_rotations, average_rotations_host, solve_positions, solve_positions_host
 from .guided import filter_guided_matches, find_fundamental_mat, mutual_matches
 from .homography import find_homography, paste_by_homography, ransac_homography
+from .keypoints import detect_keypoints, detect_keypoints_tensors
 from .icp import icp_depth, refine_registration
 from .icp_multi import icp_multiview, refine_poses, vertex_normal_maps
 from .pnp import lift_pixels, localize, ransac_pnp, rodrigues, solve_pnp_ransac
@@ -82,4 +86,4 @@ __all__ = ['ZoomEngine', 'SparseEngine', 'FasterSparseEngine', 'patch_boxes', 'R
            'icp_depth', 'refine_registration', 'vertex_normal_maps', 'icp_multiview', 'refine_poses',
            'TsdfVolume', 'integrate_depths', 'fuse_captures', 'raycast_volume', 'track_capture', 'extract_mesh', 'write_ply',
            'integrate_colors', 'sample_colors', 'color_depth_map', 'depth_from_corr', 'flow_to_corr', 'filter_depths', 'filter_captures',
-           'to_grey', 'refine_depth_photo', 'refine_captures_photo']
+           'to_grey', 'refine_depth_photo', 'refine_captures_photo', 'detect_keypoints', 'detect_keypoints_tensors']

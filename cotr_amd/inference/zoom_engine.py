@@ -663,12 +663,23 @@ class ZoomEngine:
             idx = np.array([None if i < 0 else int(i) for i in idx], dtype=object)
         return (corrs, idx) if return_idx else corrs
 
-    def guided_match(self, img_a, img_b, kp_a, kp_b, zoom_ins=np.linspace(0.5, 0.0625, 4), converge_iters=1, **filter_kw):
+    def detect_keypoints(self, imgs, **kw):
+        """``detect_keypoints`` on one image or a list of them: one float64 [k, 2] array of (x, y) per image, the
+        queries ``cotr_corr_multiscale`` takes and the keypoints of ``guided_match`` and ``reconstruct_keypoints``."""
+        from . import keypoints as detector
+        return detector.detect_keypoints(imgs, **kw)
+
+    def guided_match(self, img_a, img_b, kp_a=None, kp_b=None, zoom_ins=np.linspace(0.5, 0.0625, 4), converge_iters=1, detect_kw=None, **filter_kw):
         """demo_guided_matching.py:44-65 on this engine: ``cotr_corr_multiscale`` from every keypoint of A into B and from
         every keypoint of B into A (max_corrs = number of keypoints, force=True), then ``filter_guided_matches``: the mutual
-        nearest keypoints that the fundamental-matrix RANSAC keeps, rows (x_a, y_a, x_b, y_b).  ``filter_kw``:
-        ransac_threshold (5), confidence (0.999999), seed (0)."""
+        nearest keypoints that the fundamental-matrix RANSAC keeps, rows (x_a, y_a, x_b, y_b).  A keypoint set that is None is
+        detected here (``detect_keypoints`` with ``detect_kw``).  ``filter_kw``: ransac_threshold (5), confidence (0.999999),
+        seed (0)."""
         from .guided import filter_guided_matches
+        missing = [i for i, k in enumerate((kp_a, kp_b)) if k is None]
+        if missing:
+            found = self.detect_keypoints([(img_a, img_b)[i] for i in missing], **(detect_kw or {}))
+            kp_a, kp_b = (found[missing.index(i)] if i in missing else k for i, k in enumerate((kp_a, kp_b)))
         kp_a, kp_b = np.asarray(kp_a), np.asarray(kp_b)
         corrs_a_b = self.cotr_corr_multiscale(img_a, img_b, zoom_ins, converge_iters, max_corrs=kp_a.shape[0], queries_a=kp_a,
                                               force=True)
@@ -915,8 +926,10 @@ class ZoomEngine:
             blocks.append((a, nbrs, stack_views(corrs)))
         return reconstruct_views_tensors(blocks, Ks, V, **kw)
 
-    def reconstruct_keypoints(self, imgs, Ks, keypoints, pairs=None, span=2, zoom_ins=np.linspace(0.5, 0.0625, 4), converge_iters=1, **kw):
-        """From photographs, their intrinsics and a keypoint set [k_v, 2] per view to poses: every view pair (``pairs``, a list
+    def reconstruct_keypoints(self, imgs, Ks, keypoints=None, pairs=None, span=2, zoom_ins=np.linspace(0.5, 0.0625, 4), converge_iters=1,
+                              detect_kw=None, **kw):
+        """From photographs, their intrinsics and a keypoint set [k_v, 2] per view (None: ``detect_keypoints`` of the photographs
+        with ``detect_kw``) to poses: every view pair (``pairs``, a list
         of (i, j); None: every i < j <= i + ``span``) takes the two ``cotr_corr_multiscale`` calls of ``guided_match`` (every
         keypoint of i into j and every keypoint of j into i, force=True) and ``mutual_matches``, whose index pairs
         ``reconstruct_tracks_tensors`` (``kw``) turns into tracks over all views, poses and points: a keypoint
@@ -926,6 +939,8 @@ class ZoomEngine:
         V = len(imgs)
         if not 2 <= V <= 32:
             raise ValueError(f'between 2 and 32 images, got {V}')
+        if keypoints is None:
+            keypoints = self.detect_keypoints(list(imgs), **(detect_kw or {}))
         if len(keypoints) != V:
             raise ValueError(f'keypoints must hold one set per image ({V}), got {len(keypoints)}')
         if int(span) != span or span < 1:

@@ -1129,6 +1129,48 @@ int cotr_build_tracks(const int32_t* offsets, const int32_t* matches, const uint
                       int M, int min_views, int conflict, int cap, int32_t* track_of_node, int32_t* node_out,
                       uint8_t* visible_out, double* points_out, int32_t* info_out, int32_t* work_out, cotr_stream stream);
 
+/* ---- keypoints of 8-bit grey images (cotr_amd/csrc/keypoints.hip; rules in DESIGN.md 3h-22) ----
+ * The first link of the chain: what cotr_nearest_mutual, cotr_build_tracks and the engine's queries take as keypoints.  On an
+ * 8-bit image the structure tensor is integer arithmetic and the selection a total order on (key, pixel index), so the result
+ * is defined exactly, whatever order the workgroups run in.
+ *
+ * cotr_detect_keypoints: DEVICE pointers: images [n][H][W] uint8, grey; mask [n][H][W] uint8 or NULL (all ones).
+ *   Gradients: Ix, Iy are the 3x3 Sobel responses with weights 1-2-1 (right minus left, below minus above), integers;
+ *   a, b, c the sums of Ix Ix, Ix Iy, Iy Iy over the (2r+1)^2 box around the pixel, r = window_radius, in int64.  For r <= 4,
+ *   a, c <= 81 * 1020^2, so every integer below fits int64.
+ *   Key of a pixel, an int64 that orders pixels.  score = 1 (harris): key = 64 (a c - b b) - 3 (a + c)^2 (k = 3/64), and the
+ *   score is S = (double)key.  score = 0 (min_eig): S = (double)(a + c) - sqrt((double)((a - c)^2 + 4 b b)), twice the smaller
+ *   eigenvalue, every operation IEEE round-to-nearest, and key = the bit pattern of S, which keeps the order of S > 0.  In both
+ *   S <= 0 gives key 0.  Key 0 also where the pixel is closer than max(border, r + 1) to an image edge (no support ever
+ *   leaves the image) and where mask is 0.  The score map of the sub-pixel step is S where key > 0, and 0 elsewhere.
+ *   Candidate: a pixel p with key(p) > 0, S(p) >= min_score, and for every other pixel q of the (2R+1)^2 window around it,
+ *   R = nms_radius, pixels outside the image taken as key 0: key(q) < key(p), or key(q) == key(p) and q has the larger raster
+ *   index y W + x.  No two candidates lie within Chebyshev distance R of each other, so an image has at most
+ *   cap = ceil(H / (R+1)) * ceil(W / (R+1)) of them.
+ *   Selection: Smax = the largest S among the image's candidates; a candidate survives when S >= quality * Smax (one double
+ *   multiply); survivors are ordered by key descending, then raster index ascending; the first K = max_keypoints are written
+ *   in that order, and rows from their count on as NaN / NaN / -1, so a later call can take all K rows at a fixed shape with
+ *   no host wait.
+ *   Sub-pixel position, per axis, from the score map at the pixel (S_0) and its two neighbours (S_m before, S_p behind):
+ *   den = (S_m - S_0) + (S_p - S_0); off = den < 0 ? 0.5 * (S_m - S_p) / den : 0, clamped to [-0.5, 0.5];
+ *   xy = (x + off_x, y + off_y).  Integer pixel indices are pixel coordinates, as for the engine's queries and cv2.
+ *   -> xy_out [n][K][2] float64; score_out [n][K] float64 (S); pixel_out [n][K] int32 (the raster index); info_out [n][4]
+ *   int32 = {candidates, survivors of the quality test, keypoints written, 0}.
+ *   work_out: DEVICE, at least cotr_detect_keypoints_work_bytes(n, H, W, nms_radius) bytes, 8-byte aligned, an output whose
+ *   content is the call's own and whose candidate order is not defined, each region on its own 256 bytes from the start:
+ *   the candidates' keys [n][cap] int64, their positions [n][cap][2] float64, their pixels [n][cap] int32, the candidates
+ *   per image [n] int32, the largest key per image [n] uint64.  The list cannot overflow.
+ *   1 <= n <= 64, 1 <= window_radius <= 4, 1 <= nms_radius <= 8, border >= 0, 2 max(border, r + 1) + 1 <= H, W,
+ *   H, W <= 2^20, n H W <= 2^28, 0 <= quality <= 1, min_score not NaN, 1 <= max_keypoints <= 65536.  float64 pointers 8-byte, int32
+ *   pointers 4-byte aligned.
+ * Stream-ordered, 3 launches whatever the data, no cooperative launch, no host waits and no allocation (capturable); integer
+ * atomics only (the length of the candidate list, a 64-bit maximum of keys, the counts of info): the same input gives the same
+ * bits.  Bad arguments are checked before any HIP call: COTR_ERR_ARG, with the message in cotr_raster_last_error(). */
+int cotr_detect_keypoints_work_bytes(int n, int H, int W, int nms_radius, size_t* bytes);
+int cotr_detect_keypoints(const uint8_t* images, const uint8_t* mask, int n, int H, int W, int score, int window_radius,
+                          int nms_radius, int border, double quality, double min_score, int max_keypoints, double* xy_out,
+                          double* score_out, int32_t* pixel_out, int32_t* info_out, void* work_out, cotr_stream stream);
+
 /* ---- multi-view depth maps: a depth map from correspondence maps, and the cross-check of depth maps (cotr_amd/csrc/mvdepth.hip;
  *      rules in DESIGN.md 3h-16) ----
  * The step between dense correspondences and the TSDF stack: the correspondence maps of a reference view into its posed
